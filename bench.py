@@ -2,7 +2,7 @@
 """Benchmark of the CMax loss hot path (BASELINE.json metric: Mevents/s through the CMax loss
 forward + backward, DSEC 480x640).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C4] [--dump-outputs DIR] [--full]
 
 A step = FocusLoss.calc(trajectories, times, batch) + backward to `trajectories` on one synthetic
 batch that is already resident in HBM.  With N > 1 (one process per GPU, launched by
@@ -10,9 +10,12 @@ torch.distributed.run) every rank processes its own shard of the batch (weak sca
 data-path collective) and the averaged network gradient (124 MB fp32, the reference UNet) is
 all-reduced over RCCL on a side stream, overlapped with the next step's loss.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
-`roofline` (dominant kernel, algorithmic bytes / HIP-event time / 8 TB/s) and `cpu_baseline`
-(the CPU oracle timed on the host cores on a bounded sample)."""
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly K steps in one block
+and prints the headline (`value`, `ms_per_step`, ...).  --dump-outputs DIR then writes what the last
+timed step computed as DIR/<name>.npy (dump_outputs).  --full adds everything else in the same line:
+two more blocks of K steps, `roofline` (dominant kernel, algorithmic bytes / HIP-event time / 8 TB/s),
+the cross-checks and variants of the step, the extra workloads and operators in `also`, and
+`cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample)."""
 import argparse
 import json
 import os
@@ -26,6 +29,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 measured copy)
+SETUP_SECONDS = 1.0     # least wall time of the set-up steps before the W warm-up steps
 
 WORKLOADS = {
     # name: (B per GPU, events per sample, num_bins, num_basis, smooth_type, smooth_weight, description)
@@ -378,6 +382,28 @@ def dry_run(args, rank, world):
         dist.destroy_process_group()
 
 
+DUMP_BYTES = 60_000_000     # --dump-outputs: all files together stay below this (+ a few bytes for the scalars)
+DUMP_SEED = 0
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: {name: CPU tensor} -> outdir/<name>.npy, float32 (the dtype of the timed path; float64 stays float64).
+    The arrays that are not scalars share DUMP_BYTES evenly; one larger than its share is written as the values at a fixed
+    seeded set of flat indices (sorted), outdir/<name>_sample.npy -- the same indices for the same shape, so two builds
+    run with the same arguments are compared value for value."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    share = DUMP_BYTES // max(1, sum(1 for a in arrays.values() if a.numel() > 1))
+    for name, a in arrays.items():
+        x = a.detach().cpu().numpy()
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32, copy=False)
+        fname, cap = name, max(1, share // x.itemsize)
+        if x.size > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, cap, replace=False))
+            x, fname = x.reshape(-1)[idx], name + '_sample'
+        np.save(os.path.join(outdir, fname + '.npy'), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -401,10 +427,20 @@ def main():
     ap.add_argument('--also', default='C2,C4,C4b6', help='extra workloads reported in the "also" field (N=1 only)')
     ap.add_argument('--no-nondefault', action='store_true', help='skip the timing of the non-default loss settings (profiling runs: '
                     'their kernels share names with the headline\'s)')
+    ap.add_argument('--full', action='store_true',
+                    help='measure and check everything beside the headline (the options above shape this part): repeated blocks, '
+                         'roofline and per-kernel times, HIP-graph and static-shape replays, the other event layout, the atomic-path '
+                         'cross-check, the all-reduce legs, the extra workloads and operators in "also", the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy '
+                         '(rank 0; arrays larger than their share of %d MB as a fixed seeded sample, DIR/<name>_sample.npy)'
+                         % (DUMP_BYTES // 1_000_000))
     args = ap.parse_args()
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if args.gpus > 1 and not _in_rank_env():
         launch_ranks(args, sys.argv[1:])          # does not return
     rank = int(os.environ.get('RANK', 0))
@@ -440,7 +476,7 @@ def main():
 
     from motionpriorcmax_amd import LossFactory, ops, dp
 
-    def run_workload(name, steps, warmup, with_comm, instrument=True, force_group=False, net_only=False):
+    def run_workload(name, steps, warmup, with_comm, instrument=True, force_group=False, net_only=False, capture=False):
         wl = WORKLOADS[name]
         L = LossFactory.get_loss_calculator('FOCUS', loss_config(wl))
         # The timed steps ROTATE over `args.batches` distinct resident batches (events + trajectories; C3: 4 x 101 MB), as a training
@@ -474,12 +510,15 @@ def main():
         if net_only:                      # (the same step with the network but without any exchange: what the exchange itself costs)
             producer = dp.OverlappedGradProducer(dp.GradAllReducer(device=comm_dev))
         counter = [0]
+        keep = {} if capture else None      # (--dump-outputs: what the latest step returned to its caller)
 
         def step(rotate=True):
             st_ = sets[counter[0] % nbat] if rotate else sets[0]
             counter[0] += 1
-            loss, _, _ = L.calc(st_['traj'], times_d, st_['batch'])
+            loss, log, misc = L.calc(st_['traj'], times_d, st_['batch'])
             loss.backward()
+            if keep is not None:
+                keep.update(loss=loss, log=log, misc=misc, grad=st_['traj'].grad)
             st_['traj'].grad = None
             if producer is not None:
                 producer.wait()      # the previous step's all-reduce must be done before "the optimizer" (and before the gradients are zeroed)
@@ -490,17 +529,24 @@ def main():
             return loss
 
         # set-up, not part of the W warm-up steps: bring the caching allocator to its steady state (the
-        # per-step workspaces are first hipMalloc'ed over several steps) and the device out of its idle clocks
-        for _ in range(8):
-            step()
-        torch.cuda.synchronize()
+        # per-step workspaces are first hipMalloc'ed over several steps) and the device out of its idle clocks -- rounds of
+        # 8 steps until SETUP_SECONDS have passed (8 steps alone left the first timed block 2-4 % slower than the next two
+        # in every recorded run); the ranks take one decision, so that they all run the same steps
+        t_setup = time.perf_counter()
+        while True:
+            for _ in range(8):
+                step()
+            torch.cuda.synchronize()
+            if dp.max_over_ranks(time.perf_counter() - t_setup, comm_dev) >= SETUP_SECONDS:
+                break
         for _ in range(warmup):
             step()
         # EXACTLY `steps` steps per timed block, each block bracketed by barrier + synchronize and reduced with
-        # MAX over ranks; three consecutive blocks, the MEDIAN one is reported (a fresh box showed one-off host
-        # stalls of ~15 ms that land in one block); all block times go into the JSON line
+        # MAX over ranks.  The first block is the headline; --full times two more blocks of the same steps right after it
+        # (a fresh box showed one-off host stalls of ~15 ms that land in one block) and all block times go into the JSON line
         blocks, own_blocks = [], []
-        for _ in range(3):
+        outputs = None
+        for blk in range(3 if args.full else 1):
             if world > 1:
                 dist.barrier()
             torch.cuda.synchronize()
@@ -518,11 +564,18 @@ def main():
             own = time.perf_counter() - t0
             own_blocks.append(own)
             blocks.append(dp.max_over_ranks(own, comm_dev))
-        dt = sorted(blocks)[1]
+            if blk == 0 and keep is not None:
+                # what the caller of the last timed step received (copied before any later step: a replayed plan reuses its buffers)
+                outputs = {'loss': keep['loss'].detach(), 'focus_loss': keep['log']['focus_loss'],
+                           'smoothness_loss': keep['log']['smoothness_loss'], 'iwes': keep['misc']['iwes'],
+                           'trajectories_grad': keep['grad']}
+                outputs = {k: v.cpu().clone() for k, v in outputs.items()}
+                keep.clear()
+        dt = blocks[0]
         total_valid = dp.sum_over_ranks(valid_local, comm_dev)
         # the same number of steps on ONE resident batch (what rounds 1-4 timed), beside the rotating figure
         single = None
-        if nbat > 1 and reducer is None and producer is None:
+        if args.full and nbat > 1 and reducer is None and producer is None:
             sb = []
             for _ in range(3):
                 torch.cuda.synchronize()
@@ -538,10 +591,10 @@ def main():
         # (the last timed step ran on batch (steps - 1) % nbat: the cross-checks below compare against that one)
         lastset = sets[(steps - 1) % nbat]
         trajd, batch, batch_time, evd = lastset['traj'], lastset['batch'], lastset['batch_time'], lastset['batch_time']['events']
-        # every rank's own time for the median block and its own event count (the headline uses the MAX over ranks)
+        # every rank's own time for the headline block and its own event count (the headline uses the MAX over ranks)
         per_rank = None
-        if world > 1:
-            mine = torch.tensor([sorted(own_blocks)[1], valid_local], dtype=torch.float64, device=comm_dev)
+        if args.full and world > 1:
+            mine = torch.tensor([own_blocks[0], valid_local], dtype=torch.float64, device=comm_dev)
             allr = [torch.zeros_like(mine) for _ in range(world)]
             dist.all_gather(allr, mine)
             per_rank = {'ms_per_step': [round(1e3 * float(a[0]) / steps, 4) for a in allr],
@@ -549,7 +602,7 @@ def main():
             per_rank['balance_min_over_max'] = round(min(per_rank['value']) / max(per_rank['value']), 4)
         # the exchange alone (no loss step beside it): achieved all-reduce rate against the xGMI bounds
         comm_alone = None
-        if reducer is not None and world > 1:
+        if args.full and reducer is not None and world > 1:
             for _ in range(2):
                 reducer.start(); reducer.wait()
             torch.cuda.synchronize(); dist.barrier()
@@ -695,11 +748,14 @@ def main():
                      'grad_rel_l2_vs_atomic_path': float((ta.grad - tb.grad).norm() / tb.grad.norm())}
         return dict(wl=wl, dt=dt, blocks=blocks, steps=steps, total_valid=total_valid, stages=stages, kernels=kernels, graph_ms=graph_ms,
                     loss=float(last.item()), n=traj.shape[2], check=check, ordered=ordered, static=static_ms, per_rank=per_rank,
-                    comm_alone=comm_alone, single=single, nbat=nbat)
+                    comm_alone=comm_alone, single=single, nbat=nbat, outputs=outputs)
 
-    r = run_workload(args.workload, args.steps, args.warmup, args.grad_allreduce)
+    r = run_workload(args.workload, args.steps, args.warmup, args.grad_allreduce, instrument=args.full,
+                     capture=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r['outputs'])
     r_comm = None
-    if world > 1 and not args.grad_allreduce:
+    if args.full and world > 1 and not args.grad_allreduce:
         # the data-parallel training step's one real exchange: the same steps with the averaged
         # network gradient (UNet-sized, 124 MB fp32) all-reduced over RCCL on a side stream, overlapping the next loss
         r_comm = run_workload(args.workload, args.steps, args.warmup, True, instrument=False)
@@ -795,21 +851,25 @@ def main():
     out = {
         'metric': 'Mevents/s through CMax loss fwd+bwd, DSEC 480x640',
         'value': round(value, 3), 'unit': 'Mevents/s', 'n_gpus': world, 'steps': args.steps,
-        'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4),
-        'blocks_ms_per_step': [round(1e3 * x / r['steps'], 4) for x in r['blocks']], 'higher_is_better': True,
+        'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
         'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
         'config': {'workload': f"{args.workload}: {wl['desc']}", 'batch_per_gpu': wl['B'], 'events_layout': args.events_layout,
                    'resident_batches_rotated': r.get('nbat', 1),
                    'global_batch': wl['B'] * world, 'events_per_sample': wl['M'], 'num_bins': wl['nb'],
                    'num_knn': KNN, 'image': [H, W], 'parallelism': f'dp{world}',
                    'grad_allreduce_MB': round(dp.UNET_GRAD_NUMEL * 4 / 1e6, 2) if (world > 1 and args.grad_allreduce) else 0},
-        'rccl_ranks': rccl_ranks, 'per_rank': r.get('per_rank'),
-        'loss': r['loss'], 'loss_check': r.get('check'),
-        'single_batch': r.get('single'),
-        'other_event_layout': r.get('ordered'),
-        'static_shapes': r.get('static'),
-        'roofline': roofline_of(r, args.workload),
+        'rccl_ranks': rccl_ranks, 'loss': r['loss'],
     }
+    if args.full:
+        out.update({
+            'blocks_ms_per_step': [round(1e3 * x / r['steps'], 4) for x in r['blocks']],
+            'per_rank': r.get('per_rank'),
+            'loss_check': r.get('check'),
+            'single_batch': r.get('single'),
+            'other_event_layout': r.get('ordered'),
+            'static_shapes': r.get('static'),
+            'roofline': roofline_of(r, args.workload),
+        })
     if isinstance(r.get('graph_ms'), float):
         out['hip_graph'] = {'ms_per_step': round(r['graph_ms'], 4), 'value': round(r['total_valid'] / (r['graph_ms'] * 1e-3) / 1e6, 3),
                             'unit': 'Mevents/s', 'note': 'calc + backward captured once (torch.cuda.CUDAGraph) and replayed'}
@@ -826,7 +886,7 @@ def main():
                     'side stream) the moment its last gradient is written, overlapping the rest of that backward and the next step\'s loss'}
         r_net = run_workload(args.workload, args.steps, args.warmup, False, instrument=False, net_only=True)
         out['dp_with_grad_allreduce']['same_steps_without_the_exchange_ms'] = round(1e3 * r_net['dt'] / r_net['steps'], 4)
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         also = {}
         # the data-parallel leg on ONE GPU: a process group of one rank, so that the bucketed all-reduce goes through the RCCL call path
         # (stream ordering, bucket events) beside a real gradient producer; what it measures here is the contention of the network's
@@ -853,7 +913,7 @@ def main():
             # each extra workload runs in a fresh child process: the caching allocator of this process
             # (sized by the main workload) otherwise frees/reallocates inside the child's timed steps
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), '--workload', name, '--steps', str(args.steps),
+            cmd = [sys.executable, os.path.abspath(__file__), '--full', '--workload', name, '--steps', str(args.steps),
                    '--warmup', str(args.warmup), '--no-cpu-baseline', '--no-realistic', '--no-nondefault', '--also', '', '--events-layout', args.events_layout,
                    '--batches', str(args.batches)]
             try:

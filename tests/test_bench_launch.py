@@ -1,10 +1,13 @@
 """`python bench.py --gpus N` launches its own ranks (reference: scripts/flow_training.py:125-128 fans out from one
 command with `devices=args.gpus`).  Checked here without a GPU through the dry-run mode (MPC_BENCH_DRYRUN=1: the same
-fan-out, process group, barriers and MAX/SUM reductions over gloo with an empty step)."""
+fan-out, process group, barriers and MAX/SUM reductions over gloo with an empty step).  Also the plain run's contract
+(headline only, exactly --steps timed steps) and what --dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -47,3 +50,42 @@ def test_failing_rank_fails_the_parent():
     import torch
     if not torch.cuda.is_available():
         assert r.returncode != 0
+
+
+def test_dump_outputs_is_seeded_and_bounded(tmp_path):
+    # --dump-outputs: scalars and small arrays as they are; an array larger than its share of the budget as the same seeded sample every time
+    import numpy as np
+    import torch
+    import bench
+    big = bench.DUMP_BYTES // 4 + 1000                           # float32 elements: more than one array's share of two
+    arrays = {'loss': torch.tensor(1.25), 'small': torch.arange(12.).reshape(3, 4), 'a': torch.randn(big), 'b': torch.randn(big)}
+    for d in ('x', 'y'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    names = sorted(os.listdir(tmp_path / 'x'))
+    assert names == ['a_sample.npy', 'b_sample.npy', 'loss.npy', 'small.npy']
+    assert sum(os.path.getsize(tmp_path / 'x' / n) for n in names) <= bench.DUMP_BYTES + 4096
+    for n in names:
+        x, y = np.load(tmp_path / 'x' / n), np.load(tmp_path / 'y' / n)
+        assert x.dtype == np.float32 and np.array_equal(x, y)
+    assert np.load(tmp_path / 'x' / 'loss.npy').shape == () and np.array_equal(np.load(tmp_path / 'x' / 'small.npy'), arrays['small'].numpy())
+    a = np.load(tmp_path / 'x' / 'a_sample.npy')
+    assert np.isin(a, arrays['a'].numpy()).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    # a plain run prints the headline only, times exactly --steps steps and writes what its last timed step returned
+    import numpy as np
+    r = _run(['--gpus', '1', '--steps', '3', '--warmup', '1', '--workload', 'C2', '--dump-outputs', str(tmp_path)], {}, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-1500:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0 and d['value'] > 0 and d['unit'] == 'Mevents/s' and d['dtype'] == 'f32'
+    assert not {'roofline', 'also', 'cpu_baseline', 'blocks_ms_per_step', 'loss_check'} & set(d)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ['focus_loss.npy', 'iwes.npy', 'loss.npy', 'smoothness_loss.npy', 'trajectories_grad.npy']
+    assert float(np.load(tmp_path / 'loss.npy')) == d['loss']
+    assert np.load(tmp_path / 'iwes.npy').shape == (1, 1, 2, 480, 640)
+    g = np.load(tmp_path / 'trajectories_grad.npy')
+    assert g.shape == (1, 16, 120 * 160, 2) and np.isfinite(g).all() and np.abs(g).max() > 0

@@ -112,7 +112,7 @@ def test_bench_two_ranks_control_flow_over_gloo():
     env = dict(os.environ, MPC_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     # plain `python bench.py --gpus 2`: the parent launches the two ranks itself and relays rank 0's line
     env = {k: v for k, v in env.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--workload', 'C2']
+    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--workload', 'C2', '--full']
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

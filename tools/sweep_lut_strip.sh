@@ -6,7 +6,7 @@ for v in "-DEV_LUT_THREADS_ORD=1024" "-DEV_LUT_THREADS_ORD=512" "-DEV_LUT_THREAD
   MPC_EXTRA_HIPCC_FLAGS="$v" python -m motionpriorcmax_amd.build > /dev/null 2>&1 || echo BUILD FAILED
   for kb in 48 24 16 12; do
     echo "== $v  MPC_EV_CSTRIP_KB=$kb"
-    MPC_EV_CSTRIP_KB=$kb python bench.py --also "" --no-cpu-baseline --no-hip-graph 2>/dev/null | python -c "
+    MPC_EV_CSTRIP_KB=$kb python bench.py --full --also "" --no-cpu-baseline --no-hip-graph 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['roofline']['kernels_us']
 print(d['ms_per_step'], {n:k[n]['us_per_launch'] for n in ('k_ev_bin','k_iwe_accum','k_lut_accum')})"

@@ -367,6 +367,34 @@ int mpc_curve_traj_fwd(const float *params, const float *basis, const float *pos
 int mpc_curve_traj_bwd(const float *grad_traj, const float *basis, float scale, float *grad_params,
                        int32_t B, int32_t d, int32_t T, int32_t n, void *stream);
 
+/* ---- row A3 of SURVEY.md 8(a): the network's coefficient grid -> `trajectories` for the loss, and back.
+ * Reference: src/modules/trajectory_net.py:57-119 (compute_basis, calculate_coords, calculate_trajectories_at_t: the reference's
+ * TrajectoryNet.step, :142-161), src/utils/trajectories.py:3-52 (tile mask, coeffs_grid_to_list), src/utils/basis.py:4-46.
+ *   grid   [B][S][2k][H][W]  channels 0..k-1: y coefficients, k..2k-1: x; the S scales are summed
+ *   tiles  (y, x) = (iy * tile + tile / 2, ix * tile + tile / 2), iy < hq = ceil((H - tile / 2) / tile), ix < wq likewise (the count of
+ *          get_optical_flow_tile_mask's mask[s::tile, s::tile] -- NOT ceil(H / tile) as the LUT cells of mpc_pe_tile_rows); tile
+ *          i = iy * wq + ix, n = hq * wq (the order of torch.nonzero)
+ *   dphi[t][j] = phi_j(times[t]) - phi_j(anchor_time), j = 1..k:  MPC_BASIS_POLY t^j,  MPC_BASIS_DCT sqrt(2) cos(pi/2 (2t + 1) j) --
+ *          evaluated by the kernels from the DEVICE array times [n_t] (never read by the host) -- or MPC_BASIS_MATRIX: the caller's
+ *          dphi [n_t][k] (a learned basis: net(times) - net(anchor)); `times` may be NULL then, `dphi` is ignored otherwise
+ *   traj   [B][n_t][n][2]  (out)  (y, x) = sum_j dphi[t][j] * (cy[j], cx[j]) (+ the tile centre if add_offsets)
+ *   rows   [B*n][2k] (out, or NULL)  the scale-summed coefficients of every tile (what the backward needs for grad_dphi)
+ * mpc_grid_traj_bwd: grad_grid [B][S][2k][H][W] (out) = the adjoint applied to grad_traj [B][n_t][n][2]: EVERY element is written (0 off
+ * the tile centres; nothing to pre-zero).  grad_dphi [n_t][k] (out, or NULL; MPC_BASIS_MATRIX only, needs rows of the forward and
+ * scratch of mpc_grid_traj_scratch_floats() floats) = sum over (b, i) of g.y * cy[j] + g.x * cx[j], summed in a fixed order.
+ * Limits: k <= 16, n_t * k * 4 <= 16 KB (else MPC_E_UNSUPPORTED).  B = 0 or no tile: the forward launches nothing; the backward
+ * still zero-fills a grid without tiles, and with B = 0 writes grad_dphi = 0 (if given); pointers to empty arrays may be NULL. */
+#define MPC_BASIS_POLY 0
+#define MPC_BASIS_DCT 1
+#define MPC_BASIS_MATRIX 2
+int64_t mpc_grid_traj_scratch_floats(int32_t B, int32_t k, int32_t H, int32_t W, int32_t tile, int32_t n_t);
+int mpc_grid_traj_fwd(const float *grid, const float *times, const float *dphi, int32_t basis, float anchor_time, int32_t add_offsets,
+                      float *traj, float *rows, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W, int32_t tile, int32_t n_t,
+                      void *stream);
+int mpc_grid_traj_bwd(const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time, const float *rows,
+                      float *grad_grid, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W,
+                      int32_t tile, int32_t n_t, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

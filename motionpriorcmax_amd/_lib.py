@@ -24,6 +24,7 @@ F_ATOMIC_PATH = 1 << 10
 F_NO_BWD_RECORDS = 1 << 11
 
 E_NULL, E_SHAPE, E_UNSUPPORTED = -1, -2, -4        # include/mpcmax.h
+BASIS_POLY, BASIS_DCT, BASIS_MATRIX = 0, 1, 2
 SCAL_LOSS, SCAL_FOCUS, SCAL_SMOOTH, SCAL_VAL, SCAL_GCOEF, SCAL_COUNT = 0, 1, 2, 3, 4, 8
 
 EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_knn_lut_fwd',
@@ -34,7 +35,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_event_lut_strips', 'mpc_event_order_workspace_bytes', 'mpc_event_bucket_order', 'mpc_event_splat_bwd_ordered',
            'mpc_profile_start', 'mpc_profile_stop', 'mpc_event_splat_fwd_fixed', 'mpc_iwe_from_fixed',
            'mpc_ingest_ordered_workspace_bytes', 'mpc_ingest_scatter_ordered', 'mpc_pool2_fwd', 'mpc_pool2_bwd_add', 'mpc_event_pos_grad', 'mpc_pe_warp', 'mpc_pe_grad', 'mpc_pe_grad_ordered', 'mpc_pe_grad_ordered_supported', 'mpc_bounds_check', 'mpc_curve_traj_fwd', 'mpc_curve_traj_bwd',
-           'mpc_pe_tile_rows', 'mpc_pe_tile_rows_bwd', 'mpc_pe_basis_field', 'mpc_pe_rows_grad_finish']
+           'mpc_pe_tile_rows', 'mpc_pe_tile_rows_bwd', 'mpc_pe_basis_field', 'mpc_pe_rows_grad_finish',
+           'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd']
 
 
 class Shape(ctypes.Structure):
@@ -146,6 +148,10 @@ def lib():
     L.mpc_pe_basis_field.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
     L.mpc_pe_rows_grad_finish.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mpc_profile_stop.argtypes = [ctypes.c_char_p, i32, ctypes.POINTER(f32), i32]
+    L.mpc_grid_traj_scratch_floats.argtypes = [i32] * 6
+    L.mpc_grid_traj_scratch_floats.restype = i64
+    L.mpc_grid_traj_fwd.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp] + [i32] * 7 + [vp]
+    L.mpc_grid_traj_bwd.argtypes = [vp, vp, vp, i32, f32, vp, vp, vp, vp] + [i32] * 7 + [vp]
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

@@ -1166,6 +1166,54 @@ class CurveTrajFn(torch.autograd.Function):
         return gp, None, None, None
 
 
+class GridTrajFn(torch.autograd.Function):
+    """The network's coefficient grid [B, S, 2k, H, W] -> `trajectories` [B, n_t, n, 2] (y, x) at the tile centres (row A3 of SURVEY.md
+    8(a): reference trajectory_net.py:57-119): one kernel forward, one backward (two when `dphi` needs a gradient), csrc/grid_traj.hip,
+    instead of the mask gather / compute_basis / permute chain of plain torch and its adjoints.  basis: C.BASIS_POLY or C.BASIS_DCT
+    (evaluated by the kernels from the device `times`: `dphi` is None) or C.BASIS_MATRIX (`dphi` [n_t, k] = net(times) - net(anchor),
+    differentiable).  No host synchronisation either way; `times` gets no gradient (the reference does not differentiate them)."""
+
+    @staticmethod
+    def forward(ctx, coeff_grid, times, dphi, basis: int, anchor: float, add_offsets: bool, tile: int):
+        _require_gpu(coeff_grid, 'coeff_grid')
+        B, S, c2, H, W = coeff_grid.shape
+        k, dev = c2 // 2, coeff_grid.device
+        cg = _f32c(coeff_grid.detach())
+        tm = None if times is None else _f32c(times.detach()).reshape(-1)
+        dp = None if dphi is None else _f32c(dphi.detach())
+        n_t = dp.shape[0] if dp is not None else tm.shape[0]
+        s = tile // 2
+        hq = (H - s + tile - 1) // tile if H > s else 0
+        wq = (W - s + tile - 1) // tile if W > s else 0
+        traj = torch.empty((B, n_t, hq * wq, 2), dtype=torch.float32, device=dev)
+        rows = None
+        if dp is not None and ctx.needs_input_grad[2]:        # (saved only when the basis itself is learned)
+            rows = torch.empty((B * hq * wq, c2), dtype=torch.float32, device=dev)
+        C.check(C.lib().mpc_grid_traj_fwd(_ptr(cg), _ptr(tm), _ptr(dp), int(basis), float(anchor), int(bool(add_offsets)), _ptr(traj),
+                                          _ptr(rows), B, S, k, H, W, int(tile), n_t, _stream(dev)), 'mpc_grid_traj_fwd')
+        ctx.save_for_backward(tm, dp, rows)
+        ctx.dims = (B, S, k, H, W, int(tile), n_t, int(basis), float(anchor))
+        return traj
+
+    @staticmethod
+    def backward(ctx, g):
+        tm, dp, rows = ctx.saved_tensors
+        B, S, k, H, W, tile, n_t, basis, anchor = ctx.dims
+        g = _f32c(g)
+        dev = g.device
+        gg = torch.empty((B, S, 2 * k, H, W), dtype=torch.float32, device=dev)          # (every element is written by the kernel)
+        gd = scratch = None
+        if rows is not None:
+            nsc = int(C.lib().mpc_grid_traj_scratch_floats(B, k, H, W, tile, n_t))
+            if nsc < 0:
+                C.check(nsc, 'mpc_grid_traj_scratch_floats')
+            gd = torch.empty((n_t, k), dtype=torch.float32, device=dev)
+            scratch = torch.empty(max(nsc, 1), dtype=torch.float32, device=dev)
+        C.check(C.lib().mpc_grid_traj_bwd(_ptr(g), _ptr(tm), _ptr(dp), basis, anchor, _ptr(rows), _ptr(gg), _ptr(gd), _ptr(scratch),
+                                          B, S, k, H, W, tile, n_t, _stream(dev)), 'mpc_grid_traj_bwd')
+        return gg, None, gd, None, None, None, None
+
+
 def knn_indices(cfg: PathConfig, trajectories):
     """Debug/test helper: the K neighbour indices [B, nb, Q, K] (ascending distance, index)."""
     _require_gpu(trajectories, 'trajectories')

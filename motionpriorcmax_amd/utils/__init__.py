@@ -4,3 +4,4 @@ from .event_image_converter import EventImageConverter  # noqa: F401
 from .voxel_grid import VoxelGrid, voxel_grids  # noqa: F401
 from .ingest import ingest_events  # noqa: F401
 from .flow import dense_flow_from_traj, calculate_flow_error, ErrorCalculatorFactory, OpticalFlowError  # noqa: F401
+from .grid_traj import trajectories_from_grid, flow_from_grid  # noqa: F401

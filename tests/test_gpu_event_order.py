@@ -111,6 +111,9 @@ def test_ordered_step_against_the_oracle():
     assert abs(lg.item() - lo.item()) <= 1e-5 * abs(lo.item())
     np.testing.assert_allclose(ig.cpu().numpy(), mo['iwes'].numpy(), rtol=0, atol=1e-5 * mo['iwes'].abs().max().item())
     assert (gg.cpu() - to.grad).norm() / to.grad.norm() < 1e-2
+    # the rows the device saw, in their bucket order (polarity blocks by row index are kept)
+    from grad_accounting import end_to_end_accounting
+    end_to_end_accounting(cfg, ordered['events'].cpu(), num_pos, traj, gg.cpu(), to.grad, blurred=mo['iwes'], label='bucket-ordered')
 
 
 def test_unit_weight_rows_and_empty_blocks():

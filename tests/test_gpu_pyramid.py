@@ -55,6 +55,14 @@ def test_pyramid_matches_its_definition(norm, smooth_type, levels):
     assert abs(log['focus_loss'].item() - fo.item()) <= 1e-5 * abs(fo.item())
     rel = float((tg.grad.cpu() - to.grad).norm() / to.grad.norm())
     assert rel < (1e-4 if norm == 'l2' else 2e-2), rel          # ('l1': sign() of near-zero Sobel responses)
+    # every level's near-zero responses, carried to the level-0 pixels under them
+    from oracle import focus_oracle as O
+    from grad_accounting import end_to_end_accounting, pyramid_near_zero_pixels
+    lut, _, idx = O.interpolate_flow(traj[:, :1], traj[:, 1:], cfg['image_shape'], 4, cfg['num_knn'], return_idx=True)
+    _, raw = O.make_iwes(ev, O.warp_events(ev, lut, 4), times[:1], cfg['image_shape'], True, True, True, num_pos)
+    aff = pyramid_near_zero_pixels(raw, levels) if norm == 'l1' else None
+    end_to_end_accounting(cfg, ev, num_pos, traj, tg.grad.cpu(), to.grad, lut=lut, idx=idx, affected=aff,
+                          label=f'pyramid {norm} {smooth_type} levels={levels}')
     assert misc['iwes'].shape == (2, 1, 2, 96, 128)
 
 

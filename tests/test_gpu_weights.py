@@ -60,3 +60,5 @@ def test_loss_with_a_weighted_valid_column():
     np.testing.assert_allclose(mg['iwes'].cpu().numpy(), mo['iwes'].numpy(), rtol=0, atol=1e-5 * mo['iwes'].abs().max().item())
     gn = (tg.grad.cpu() - to.grad).norm() / to.grad.norm()
     assert gn < 1e-2, gn
+    from grad_accounting import end_to_end_accounting
+    end_to_end_accounting(cfg, ev, num_pos, traj, tg.grad.cpu(), to.grad, blurred=mo['iwes'], label='weighted valid column')

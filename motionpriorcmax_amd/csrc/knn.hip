@@ -1067,28 +1067,47 @@ __global__ __launch_bounds__(256, NEXT ? KNN_BW_OCC_NEXT : (IWD ? KNN_BW_OCC_IWD
             lg = reinterpret_cast<float2 *>(s_dyn + ncell * 4);          // (ncell is even: 8-byte aligned)
         }
         int tie = 0;
-        for (int rr = tid >> 5; rr < RW; rr += 8) {
+        // 16 rows x 16 columns of cells per pass, and the loads of ALL three column groups of a pass (RP <= 48) in flight together --
+        // unconditional, at addresses clamped into the field, so that the compiler issues them before the first use.  Before: a
+        // load-use-store iteration per cell, 5-7 per thread, each a dependent round trip at seven workgroups per CU -- 5.6 of a
+        // workgroup's 11.3 us passed before its window loop (now 4.5 of 10.2, tools/bwd_stamp_probe.py; the kernel 118 -> 108 us at C3,
+        // SQ_WAIT_ANY 0.48 -> 0.39 of the wave cycles: profiles/knn_bwd_runs.md).  Two row groups per batch: no further gain.
+        constexpr int NCG = 3;
+        static_assert(16 * NCG >= KNN_BW_PITCH && 16 * NCG >= 16 + 2 * KNN_RQ_MAX, "three column groups cover a staged row");
+        for (int rr = tid >> 4; rr < RW; rr += 16) {
             const int yy = ry0 + rr;
-            for (int cc = tid & 31; cc < RP; cc += 32) {          // (columns RW..RP-1: padding, never a member)
-                const int xx = rx0 + cc;
-                float dk = -1.f, wn = 1.f; int ik = -1;
+            const bool yin = yy >= 0 && yy < p.hq;
+            const size_t qrow = (size_t)min(max(yy, 0), p.hq - 1) * p.wq;
+            float dkv[NCG], wnv[NCG]; int ikv[NCG]; float2 gv[NCG], gnv[NCG];
+#pragma unroll
+            for (int k = 0; k < NCG; ++k) {
+                const size_t qc = qrow + (size_t)min(max(rx0 + (tid & 15) + 16 * k, 0), p.wq - 1);
+                const size_t q = (size_t)bt * p.G + qc;
+                dkv[k] = knn_state[q];
+                ikv[k] = reinterpret_cast<const int *>(knn_state)[BQ + q];
+                wnv[k] = IWD ? knn_state[2 * BQ + q] : 1.f;
+                gv[k] = gl2[qc];
+                gnv[k] = has_next ? gn2[qc] : make_float2(0.f, 0.f);
+            }
+#pragma unroll
+            for (int k = 0; k < NCG; ++k) {
+                const int cc = (tid & 15) + 16 * k, xx = rx0 + cc;          // (columns RW..RP-1: padding, never a member)
+                float dk = -1.f; int ik = -1;
                 float2 g = make_float2(0.f, 0.f), gn = make_float2(0.f, 0.f);
-                if (cc < RW && yy >= 0 && yy < p.hq && xx >= 0 && xx < p.wq) {
-                    const size_t q = (size_t)bt * p.G + (size_t)yy * p.wq + xx;
-                    dk = knn_state[q];
-                    ik = reinterpret_cast<const int *>(knn_state)[BQ + q];
-                    if (IWD) wn = knn_state[2 * BQ + q];
-                    g = gl2[(size_t)yy * p.wq + xx];
-                    if (has_next) { gn = gn2[(size_t)yy * p.wq + xx]; if (gnext_scale != nullptr) gn = make_float2(gn.x * gns, gn.y * gns); }
+                if (cc < RW && yin && xx >= 0 && xx < p.wq) {
+                    dk = dkv[k]; ik = ikv[k]; g = gv[k];
+                    const float wn = wnv[k];
+                    if (has_next) { gn = gnv[k]; if (gnext_scale != nullptr) gn = make_float2(gn.x * gns, gn.y * gns); }
                     if (ik & KNN_FAR_FLAG) dk = -1.f;        // served by the fallback kernel: k_knn_bwd_far adds its gradient
                     else tie |= ik & KNN_TIE_FLAG;
                     // 'iwd': the query's normaliser goes into its staged gradient (a cell that is no member of anything holds 0: its
                     // weight is 0, and 0 x a non-finite quotient would not be)
                     if (IWD) g = (dk >= 0.f && wn > 0.f) ? make_float2(g.x / wn, g.y / wn) : make_float2(0.f, 0.f);
-                    ik &= KNN_IDX_MASK;
                 }
-                ldk[MPC_IDX(rr * RP + cc, ncell)] = dk; lg[MPC_IDX(rr * RP + cc, ncell)] = g;
-                if (NEXT) lgn[MPC_IDX(rr * RP + cc, ncell)] = gn;
+                if (cc < RP) {
+                    ldk[MPC_IDX(rr * RP + cc, ncell)] = dk; lg[MPC_IDX(rr * RP + cc, ncell)] = g;
+                    if (NEXT) lgn[MPC_IDX(rr * RP + cc, ncell)] = gn;
+                }
             }
         }
         if (tid < KNN_BW_WMAX) {                    // slack behind the last row: never a member

@@ -305,6 +305,36 @@ int64_t mpc_voxel_workspace_bytes(const mpc_vox_shape *s);
 int mpc_voxel_grid(const mpc_vox_shape *s, const float *xytp, const int32_t *counts, float *grid,
                    void *ws, void *stream);
 
+/* ---- centred voxel grid: the network input of the EVIMO2 and MultiFlow configurations, reference
+ * src/loader/utils/representation.py:26-111 (VoxelGrid.convert) and :9-18 (norm_voxel_grid) as called from
+ * src/loader/evimo2/datasubset.py:146-189 and src/loader/multiflow/sample.py:172-200, with the resize of datasubset.py:189
+ * (F.interpolate(size=(Ho, Wo), mode='bilinear', align_corners=False)) applied after the normalisation.
+ * x, y, pol [B][N] fp32 (pol in {0,1}; integer coordinates are exact in fp32), time [B][N] int64 (increasing within a sample;
+ * rows beyond counts[b] are ignored), counts [B] int32, centres [B][2] int64 = (t0_center, t1_center) per sample or NULL = the
+ * first and last valid timestamp of the sample (read on the device).  All pointers are device pointers.
+ * t_norm = float(time - c0) / float(c1 - c0) * float(C - 1); floor for every index; int_xy = 1: two taps per event at [t, y, x]
+ * (representation.py:85-94; an event outside the sensor or with a non-integer coordinate is DROPPED, where the reference's flat
+ * index wraps or raises), int_xy = 0: eight taps (:96-109).  c1 == c0 (also: a sample of one event with default centres) gives
+ * no time axis: such a sample's grid is zero.  norm = 1: mean / unbiased std over the non-zero entries, (v - mean) / std if
+ * std > 0 else v - mean, zeros stay.  grid [B][C][Ho or H][Wo or W] (out, every element written); a sample with counts[b] == 0
+ * is all zero.  Kernels only, on `stream`; no allocation, no host synchronisation: the call can be captured into a HIP graph.
+ * MPC_E_UNSUPPORTED: C < 2, H < 2 or W < 2 (the reference's asserts), or sizes the LDS strips cannot hold.
+ * ws: mpc_repr_workspace_bytes(s) bytes, sized for the worst case so that no event distribution can overflow it: record buckets of
+ * four times the mean fill (128 B per event row of [B][N]), per-sample spill regions that hold every record a sample can produce
+ * (64 B per row, 96 B with int_xy = 0) and their chunk lists (one 16-byte descriptor per binning workgroup and bucket it can
+ * overflow, up to 64 B per row): about 260 B x B x N, 2.3 GB at B = 6, N = 1 500 000.  It is scratch: nothing is kept between calls. */
+typedef struct mpc_repr_shape {
+    int32_t B, N, C, H, W, int_xy, norm, Ho, Wo;   /* Ho = Wo = 0: no resize */
+} mpc_repr_shape;
+int64_t mpc_repr_workspace_bytes(const mpc_repr_shape *s);
+int mpc_repr_grid(const mpc_repr_shape *s, const float *x, const float *y, const int64_t *time, const float *pol,
+                  const int32_t *counts, const int64_t *centres, float *grid, void *ws, void *stream);
+/* norm_voxel_grid (representation.py:9-18) of grids that already lie in device memory: grid [B][per_sample], each sample
+ * normalised in place over its non-zero entries.  ws: mpc_repr_norm_workspace_bytes(B) bytes.  No host synchronisation (the
+ * reference's `if std > 0` is one). */
+int64_t mpc_repr_norm_workspace_bytes(int32_t B);
+int mpc_repr_norm(float *grid, int32_t B, int64_t per_sample, void *ws, void *stream);
+
 /* ---- next row: event ingest, reference src/loader/dsec/loader.py:152-167 (time
  * normalisation, bin index, in-image filter, polarity split) + :360-415 (pad_events, sequence_collate_fn).
  * x, y, p [B][N] float32, t_us [B][N] int64 (increasing within a sample), counts [B] int32 (device).

@@ -36,7 +36,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_profile_start', 'mpc_profile_stop', 'mpc_event_splat_fwd_fixed', 'mpc_iwe_from_fixed',
            'mpc_ingest_ordered_workspace_bytes', 'mpc_ingest_scatter_ordered', 'mpc_pool2_fwd', 'mpc_pool2_bwd_add', 'mpc_event_pos_grad', 'mpc_pe_warp', 'mpc_pe_grad', 'mpc_pe_grad_ordered', 'mpc_pe_grad_ordered_supported', 'mpc_bounds_check', 'mpc_curve_traj_fwd', 'mpc_curve_traj_bwd',
            'mpc_pe_tile_rows', 'mpc_pe_tile_rows_bwd', 'mpc_pe_basis_field', 'mpc_pe_rows_grad_finish',
-           'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd']
+           'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd',
+           'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm']
 
 
 class Shape(ctypes.Structure):
@@ -54,6 +55,10 @@ class FocusBuffers(ctypes.Structure):
 
 class VoxShape(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ('B', 'N', 'C', 'H', 'W', 'norm')] + [('quantile', ctypes.c_float), ('keep', ctypes.c_float)]
+
+
+class ReprShape(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ('B', 'N', 'C', 'H', 'W', 'int_xy', 'norm', 'Ho', 'Wo')]
 
 
 class IngestShape(ctypes.Structure):
@@ -152,6 +157,12 @@ def lib():
     L.mpc_grid_traj_scratch_floats.restype = i64
     L.mpc_grid_traj_fwd.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp] + [i32] * 7 + [vp]
     L.mpc_grid_traj_bwd.argtypes = [vp, vp, vp, i32, f32, vp, vp, vp, vp] + [i32] * 7 + [vp]
+    L.mpc_repr_workspace_bytes.argtypes = [ctypes.POINTER(ReprShape)]
+    L.mpc_repr_workspace_bytes.restype = i64
+    L.mpc_repr_grid.argtypes = [ctypes.POINTER(ReprShape), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpc_repr_norm_workspace_bytes.argtypes = [i32]
+    L.mpc_repr_norm_workspace_bytes.restype = i64
+    L.mpc_repr_norm.argtypes = [vp, i32, i64, vp, vp]
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

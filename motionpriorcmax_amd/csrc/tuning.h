@@ -96,6 +96,13 @@
                               // 0.283 ms against 0.265 at the DSEC batch shape; 50 KB: the binning pass pays for the extra buckets)
 #endif
 
+// ---- repr.hip ------------------------------------------------------------------------------------------------------
+#ifndef REPR_STRIP_KB
+#define REPR_STRIP_KB 75      // LDS budget of a strip of the centred voxel grid (the input rows behind a range of output rows): the fastest of
+                              // 37 / 50 / 75 / 150 KB for the whole call at the C4 batch (6 x 65 x 480 x 640 -> 384 x 512; two workgroups per CU at 75,
+                              // one at 150): tools/repr_call_time.py under one build each, figures in DESIGN.md 7 f-2b
+#endif
+
 // ---- common.h ------------------------------------------------------------------------------------------------------
 #ifndef MPC_CT_H
 #define MPC_CT_H 32

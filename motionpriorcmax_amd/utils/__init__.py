@@ -5,3 +5,5 @@ from .voxel_grid import VoxelGrid, voxel_grids  # noqa: F401
 from .ingest import ingest_events  # noqa: F401
 from .flow import dense_flow_from_traj, calculate_flow_error, ErrorCalculatorFactory, OpticalFlowError  # noqa: F401
 from .grid_traj import trajectories_from_grid, flow_from_grid  # noqa: F401
+from . import representation  # noqa: F401  (representation.VoxelGrid is the EVIMO2 / MultiFlow class; VoxelGrid above is the DSEC one)
+from .representation import representation_grids  # noqa: F401

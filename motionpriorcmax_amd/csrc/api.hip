@@ -313,13 +313,17 @@ extern "C" int mpc_focus_fwd(const mpc_shape *s, const mpc_focus_buffers *io, vo
     int rc = mpc_knn_lut_fwd_ex(s, io->traj, io->flow_lut, io->flow_next, io->knn_state, nullptr, ws, stream, 1, rec_bwd ? io->events : nullptr, &done);
     if (rc) return rc;
     int s_nimg = 0, s_C = 0;
+    const float *field = nullptr;
+    bool fuse = false;       // the smoothness pass rides in the contrast launch (k_contrast_smooth_march) instead of running here
     if (io->smooth_weight > 0.f) {
         const bool on_next = (s->flags & MPC_F_WANT_NEXT) != 0;
-        const float *field = on_next ? io->flow_next : io->flow_lut;
+        field = on_next ? io->flow_next : io->flow_lut;
         s_nimg = on_next ? s->B * (s->nb - 1) : s->B * s->nb;
         s_C = on_next ? 2 : 2 * s->T;
         if (s_nimg > 0) {
-            if ((rc = mpc_lut_smooth(s, field, s_nimg, s_C, io->smooth_weight, io->smooth_grad, ws, stream))) return rc;
+            // (the condition under which mpc_contrast_fwd takes the marching kernel, on the tiled event path)
+            fuse = io->grad_iwe && !(s->flags & (MPC_F_OBJ_VARIANCE | MPC_F_ATOMIC_PATH)) && s->T == 1;
+            if (!fuse && (rc = mpc_lut_smooth(s, field, s_nimg, s_C, io->smooth_weight, io->smooth_grad, ws, stream))) return rc;
         } else s_C = 0;
     }
     // (the bucket counters were zeroed by the first kernel of the KNN forward, unless the event path is not the tiled one)
@@ -329,7 +333,9 @@ extern "C" int mpc_focus_fwd(const mpc_shape *s, const mpc_focus_buffers *io, vo
         if (io->event_offsets) sf.flags |= MPC_F_NO_BWD_RECORDS;
         if ((rc = mpc_event_splat_fwd_ex(&sf, io->events, io->flow_lut, io->t_ref, io->iwe_raw, ws, stream, done, io->event_offsets))) return rc;
     }
-    if ((rc = mpc_contrast_fwd(s, io->iwe_raw, io->iwe_blur, io->grad_iwe, ws, stream))) return rc;
+    if (fuse) rc = mpc_contrast_smooth_fwd(s, io->iwe_raw, io->iwe_blur, io->grad_iwe, field, s_nimg, s_C, io->smooth_weight, io->smooth_grad, ws, stream);
+    else rc = mpc_contrast_fwd(s, io->iwe_raw, io->iwe_blur, io->grad_iwe, ws, stream);
+    if (rc) return rc;
     return mpc_finalize_ex(s, s_nimg, s_C, io->smooth_weight, io->scal, io->scal_out, ws, stream);
 }
 

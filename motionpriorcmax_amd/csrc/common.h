@@ -119,6 +119,9 @@ int mpc_event_splat_fwd_ex(const mpc_shape *s, const float *events, const float 
 int mpc_validate_shape(const mpc_shape *s);
 int mpc_finalize_ex(const mpc_shape *s, int32_t smooth_nimg, int32_t smooth_C, float smooth_weight, float *scal, float *scal_out,
                     void *ws, void *stream);
+// contrast.hip: the marching contrast kernel and the smoothness kernel as one launch (mpc_focus_fwd)
+int mpc_contrast_smooth_fwd(const mpc_shape *s, const float *iwe_raw, float *iwe_blur, float *grad_iwe, const float *field,
+                            int32_t smooth_nimg, int32_t smooth_C, float smooth_weight, float *grad_field, void *ws, void *stream);
 // KNN (knn.hip): margin of the bucket grid; is the points' counting sort the global-memory one; does the forward keep a far list
 int mpc_knn_margin(const mpc_shape *s);
 int mpc_knn_tiles(const mpc_shape *s);          // 16 x 16 cell tiles of the bucket grid per (sample, bin)

@@ -133,14 +133,16 @@ __device__ __forceinline__ float lane_right(float v) {     // value of lane + 1 
 // TH rows per band: MPC_CT_H (32) for batches, 16 when that leaves the chip short of wavefronts (B = 1: 360 bands of 32
 // rows on 256 CUs; measured at C2 18.2 -> 12.0 us, neutral at C3); `nslots` entries of the partial-sum array exist and
 // the finalize kernel adds them all, so the bands of the coarser tiling clear the entries they do not use
+// (the body takes its block coordinates as arguments: bx, by, bz of a grid gx x gy x gz -- k_contrast_march hands it blockIdx /
+// gridDim, k_contrast_smooth_march below the coordinates it decomposes from a linear block id)
 template <bool L2N, int TH>
-__global__ __launch_bounds__(64) void k_contrast_march(const float *__restrict__ raw, float *__restrict__ blur,
-                                                       float *__restrict__ gimg, double *__restrict__ part, int H, int W,
-                                                       int nslots) {
+__device__ __forceinline__ void contrast_march_body(const float *__restrict__ raw, float *__restrict__ blur,
+                                                    float *__restrict__ gimg, double *__restrict__ part, int H, int W,
+                                                    int nslots, unsigned bx, unsigned by, unsigned bz, unsigned gx, unsigned gy, unsigned gz) {
     constexpr int TW = MPC_CF_TW;
     const int c = threadIdx.x;
-    const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
-    const size_t img_off = (size_t)blockIdx.z * H * W;
+    const int tx0 = bx * TW, ty0 = by * TH;
+    const size_t img_off = (size_t)bz * H * W;
     const float *src = raw + img_off;
     float ka, kc;
     blur_taps(ka, kc);
@@ -227,12 +229,19 @@ __global__ __launch_bounds__(64) void k_contrast_march(const float *__restrict__
     }
     acc = wave_sum_d(acc);
     if (c == 0) {
-        const size_t bid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-        const size_t nb_ = (size_t)gridDim.x * gridDim.y * gridDim.z;
+        const size_t bid = ((size_t)bz * gy + by) * gx + bx;
+        const size_t nb_ = (size_t)gx * gy * gz;
         part[2 * MPC_IDX(bid, nslots)] = acc;
         part[2 * bid + 1] = 0.0;
         for (size_t e = bid + nb_; e < (size_t)nslots; e += nb_) { part[2 * e] = 0.0; part[2 * e + 1] = 0.0; }
     }
+}
+
+template <bool L2N, int TH>
+__global__ __launch_bounds__(64) void k_contrast_march(const float *__restrict__ raw, float *__restrict__ blur,
+                                                       float *__restrict__ gimg, double *__restrict__ part, int H, int W,
+                                                       int nslots) {
+    contrast_march_body<L2N, TH>(raw, blur, gimg, part, H, W, nslots, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y, gridDim.z);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -387,13 +396,14 @@ __global__ void k_scale(const float *__restrict__ x, const float *__restrict__ a
 // ------------------------------------------------------------------------------------------
 // TH rows per band: MPC_SM_H (16), or half of it for small fields (smooth_band_rows below)
 template <int TH>
-__global__ __launch_bounds__(64) void k_lut_smooth_march(const float *__restrict__ field, float *__restrict__ gfield,
-                                                         double *__restrict__ part, int hq, int wq, int C, float gscale) {
+__device__ __forceinline__ void lut_smooth_march_body(const float *__restrict__ field, float *__restrict__ gfield,
+                                                      double *__restrict__ part, int hq, int wq, int C, float gscale,
+                                                      unsigned bx, unsigned by, unsigned bz, unsigned gx, unsigned gy) {
     constexpr int TW = MPC_SM_W;
     const int c = threadIdx.x;
     const int C2 = C >> 1;
-    const int img = blockIdx.z / C2, cp = blockIdx.z - img * C2;
-    const int x0 = blockIdx.x * TW, y0 = blockIdx.y * TH;
+    const int img = bz / C2, cp = bz - img * C2;
+    const int x0 = bx * TW, y0 = by * TH;
     const size_t base = (size_t)img * hq * wq * C2 + cp;        // in float2 units
     const float2 *f2 = reinterpret_cast<const float2 *>(field);
     float2 *g2 = reinterpret_cast<float2 *>(gfield);
@@ -458,9 +468,70 @@ __global__ __launch_bounds__(64) void k_lut_smooth_march(const float *__restrict
     }
     a0 = wave_sum_d(a0); a1 = wave_sum_d(a1);
     if (c == 0) {
-        const size_t bid = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const size_t bid = ((size_t)bz * gy + by) * gx + bx;
         part[2 * bid] = a0;
         part[2 * bid + 1] = a1;
+    }
+}
+
+template <int TH>
+__global__ __launch_bounds__(64) void k_lut_smooth_march(const float *__restrict__ field, float *__restrict__ gfield,
+                                                         double *__restrict__ part, int hq, int wq, int C, float gscale) {
+    lut_smooth_march_body<TH>(field, gfield, part, hq, wq, C, gscale, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, gridDim.y);
+}
+
+// ------------------------------------------------------------------------------------------
+// contrast + smoothness in ONE launch (mpc_focus_fwd): the two marching kernels above are independent of each other (the
+// smoothness reads the finished LUT, the contrast the raw IWE), both are 64-thread workgroups without LDS or barrier, and each
+// alone leaves wave slots empty and runs short of its issue and bandwidth limits.  A 1-D grid of n_c + n_s workgroups; a
+// wave-uniform branch on the linear block id picks the body and the id is decomposed into the (x, y, z) the body had in its own
+// launch -- same arithmetic, same partial-sum slots, so k_finalize adds the same numbers in the same order.
+// Order of the two kinds of workgroup in the grid: MPC_CS_ORDER (tuning.h has the measurements).
+//   0: the contrast workgroups first, 1: the smoothness workgroups first,
+//   2: interleaved in proportion to their counts -- `ng` groups of `ra` contrast and `rb` smoothness workgroups, the rest (of
+//      the larger kind, if the counts are not a multiple of each other) behind them, contrast first.
+// ------------------------------------------------------------------------------------------
+struct mpc_cs_grid {
+    unsigned cgx, cgy, cgz, sgx, sgy;     // the grids the two kernels have in launches of their own (smoothness z: what is left)
+    unsigned n_c, n_s;                    // workgroups of each kind
+    unsigned ra, rb, ng;                  // interleaved order: group shape and count
+};
+
+template <bool L2N, int CTH, int STH>
+__global__ __launch_bounds__(64) void k_contrast_smooth_march(const float *__restrict__ raw, float *__restrict__ blur,
+                                                              float *__restrict__ gimg, double *__restrict__ cpart, int H, int W,
+                                                              int nslots, const float *__restrict__ field, float *__restrict__ gfield,
+                                                              double *__restrict__ spart, int hq, int wq, int C, float gscale,
+                                                              const mpc_cs_grid g) {
+    const unsigned b = blockIdx.x;
+    bool smooth;
+    unsigned i;
+#if MPC_CS_ORDER == 0
+    smooth = b >= g.n_c;
+    i = smooth ? b - g.n_c : b;
+#elif MPC_CS_ORDER == 1
+    smooth = b < g.n_s;
+    i = smooth ? b : b - g.n_s;
+#else
+    const unsigned per = g.ra + g.rb, head = g.ng * per;
+    if (b < head) {
+        const unsigned grp = b / per, k = b - grp * per;
+        smooth = k >= g.ra;
+        i = smooth ? grp * g.rb + (k - g.ra) : grp * g.ra + k;
+    } else {
+        const unsigned t = b - head, rem_c = g.n_c - g.ng * g.ra;
+        smooth = t >= rem_c;
+        i = smooth ? g.ng * g.rb + (t - rem_c) : g.ng * g.ra + t;
+    }
+#endif
+    if (!smooth) {
+        const unsigned zy = i / g.cgx, bx = i - zy * g.cgx;
+        const unsigned bz = zy / g.cgy, by = zy - bz * g.cgy;
+        contrast_march_body<L2N, CTH>(raw, blur, gimg, cpart, H, W, nslots, bx, by, bz, g.cgx, g.cgy, g.cgz);
+    } else {
+        const unsigned zy = i / g.sgx, bx = i - zy * g.sgx;
+        const unsigned bz = zy / g.sgy, by = zy - bz * g.sgy;
+        lut_smooth_march_body<STH>(field, gfield, spart, hq, wq, C, gscale, bx, by, bz, g.sgx, g.sgy);
     }
 }
 
@@ -529,6 +600,53 @@ extern "C" int mpc_lut_smooth(const mpc_shape *s, const float *field, int32_t ni
     const float gscale = (float)((double)smooth_weight / (2.0 * count));
     if (band == MPC_SM_H) MPC_LAUNCH(k_lut_smooth_march<MPC_SM_H>, grid, dim3(64), 0, st, field, grad_field, spart, s->hq, s->wq, C, gscale);
     else MPC_LAUNCH(k_lut_smooth_march<MPC_SM_H / 2>, grid, dim3(64), 0, st, field, grad_field, spart, s->hq, s->wq, C, gscale);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+// mpc_focus_fwd: mpc_lut_smooth and the marching form of mpc_contrast_fwd as one launch (k_contrast_smooth_march).  The caller has
+// checked that mpc_contrast_fwd would take the marching kernel (grad_iwe given, not the variance objective); band heights,
+// grids and partial-sum slots are the ones the two entry points choose, so mpc_finalize reads what it reads after them.  Taken at every
+// size: the one launch measured faster than the two at C3, C2 and C4 (tuning.h: MPC_CS_ORDER).
+int mpc_contrast_smooth_fwd(const mpc_shape *s, const float *iwe_raw, float *iwe_blur, float *grad_iwe, const float *field,
+                            int32_t nimg, int32_t C, float smooth_weight, float *grad_field, void *ws, void *stream) {
+    MPC_CHECK_ARG(s && iwe_raw && iwe_blur && grad_iwe && field && ws, MPC_E_NULL, "null argument");
+    int rc = mpc_validate_shape(s);
+    if (rc) return rc;
+    const mpc_ws_layout L = mpc_layout(s);
+    MPC_CHECK_ARG(!(s->flags & MPC_F_OBJ_VARIANCE), MPC_E_SHAPE, "the variance objective has no marching kernel");
+    MPC_CHECK_ARG(nimg > 0 && C > 0 && (C % 2) == 0, MPC_E_SHAPE, "field must have an even number of channels");
+    hipStream_t st = (hipStream_t)stream;
+    // contrast grid: as mpc_contrast_fwd
+    dim3 cgrid(mpc_cdiv(s->W, MPC_CF_TW), mpc_cdiv(s->H, MPC_CT_H), L.nimg);
+    const bool chalf = (int64_t)cgrid.x * cgrid.y * cgrid.z < 1536;
+    if (chalf) cgrid.y = mpc_cdiv(s->H, MPC_CT_H / 2);
+    // smoothness grid: as mpc_lut_smooth
+    const int band = smooth_band_rows(s, nimg, C);
+    const dim3 sgrid(mpc_cdiv(s->wq, MPC_SM_W), mpc_cdiv(s->hq, band), nimg * (C / 2));
+    const int64_t n_c = (int64_t)cgrid.x * cgrid.y * cgrid.z, n_s = (int64_t)sgrid.x * sgrid.y * sgrid.z;
+    MPC_CHECK_ARG(n_s <= L.n_sblocks_max, MPC_E_SHAPE, "field larger than the LUT of this shape");
+    MPC_CHECK_ARG(n_c > 0 && n_c <= L.n_cblocks && n_c + n_s < ((int64_t)1 << 31), MPC_E_SHAPE, "grid out of range");
+    mpc_cs_grid g;
+    g.cgx = cgrid.x; g.cgy = cgrid.y; g.cgz = cgrid.z; g.sgx = sgrid.x; g.sgy = sgrid.y;
+    g.n_c = (unsigned)n_c; g.n_s = (unsigned)n_s;
+    if (n_c >= n_s) { g.rb = 1; g.ra = (unsigned)(n_c / n_s); }
+    else { g.ra = 1; g.rb = (unsigned)(n_s / n_c); }
+    g.ng = (unsigned)(n_c / g.ra < n_s / g.rb ? n_c / g.ra : n_s / g.rb);
+    double *cpart = (double *)((char *)ws + L.off_cpart), *spart = (double *)((char *)ws + L.off_spart);
+    const double count = (double)nimg * C * s->hq * s->wq;
+    const float gscale = (float)((double)smooth_weight / (2.0 * count));
+    const dim3 grid((unsigned)(n_c + n_s));
+    const bool l2 = (s->flags & MPC_F_NORM_L2) != 0, shalf = band != MPC_SM_H;
+#define MPC_CS_GO(L2N, CTH, STH)                                                                                                   \
+    MPC_LAUNCH((k_contrast_smooth_march<L2N, CTH, STH>), grid, dim3(64), 0, st, iwe_raw, iwe_blur, grad_iwe, cpart, s->H, s->W,  \
+               L.n_cblocks, field, grad_field, spart, s->hq, s->wq, C, gscale, g)
+#define MPC_CS_GO_S(L2N, CTH)                                                                                                     \
+    do { if (shalf) MPC_CS_GO(L2N, CTH, MPC_SM_H / 2); else MPC_CS_GO(L2N, CTH, MPC_SM_H); } while (0)
+    if (l2) { if (chalf) MPC_CS_GO_S(true, MPC_CT_H / 2); else MPC_CS_GO_S(true, MPC_CT_H); }
+    else { if (chalf) MPC_CS_GO_S(false, MPC_CT_H / 2); else MPC_CS_GO_S(false, MPC_CT_H); }
+#undef MPC_CS_GO_S
+#undef MPC_CS_GO
     MPC_CHECK_LAUNCH();
     return 0;
 }

@@ -11,6 +11,18 @@
 #define MPC_SM_PF 2
 #endif
 
+#ifndef MPC_CS_ORDER
+#define MPC_CS_ORDER 0    // k_contrast_smooth_march: order of the two kinds of workgroup in the 1-D grid.  0: contrast first, 1: smoothness
+                          // first, 2: interleaved in proportion to their counts.  Launch time in us (HIP events, inside the step, two
+                          // runs of 20 steps each) against k_contrast_march + k_lut_smooth_march in launches of their own:
+                          //          two launches    0             1             2             2, eight at a turn
+                          //   C3     33.6 + 23.6     46.7 / 47.1   46.6 / 46.8   54.1 / 54.1   53.2 / 53.7
+                          //   C2     11.7 +  8.1     12.0 / 12.1   12.7 / 12.9   13.2 / 13.1   12.7 / 13.0
+                          //   C4     11.6 + 10.4     12.4 / 12.3   14.2 / 14.1   13.8 / 14.2   13.8 / 13.8
+                          // Every order beats the two launches at all three sizes, so there is no size below which mpc_focus_fwd goes
+                          // back to them (profiles/contrast_smooth_runs.md)
+#endif
+
 // ---- events.hip ----------------------------------------------------------------------------------------------------
 #ifndef EV_PER_THREAD
 #define EV_PER_THREAD 2   // measured at C3: 2 -> 98.6 us, 4 -> 106.9, 8 -> 107.5 (whole forward splat)

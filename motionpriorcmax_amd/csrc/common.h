@@ -161,4 +161,44 @@ __device__ __forceinline__ double block_sum_d(double v, double *lds /* NT/64 dou
     __syncthreads();
     return r;
 }
+// Smallest / largest `v` over a workgroup of NT threads; result valid in thread 0 (exact in any order).
+template <int NT>
+__device__ __forceinline__ double block_min_d(double v, double *lds /* NT/64 doubles */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = INFINITY;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NT / 64; ++i) r = fmin(r, lds[i]);
+    }
+    __syncthreads();
+    return r;
+}
+template <int NT>
+__device__ __forceinline__ double block_max_d(double v, double *lds /* NT/64 doubles */) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = -INFINITY;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int i = 0; i < NT / 64; ++i) r = fmax(r, lds[i]);
+    }
+    __syncthreads();
+    return r;
+}
+
+// Q33.30 fixed point of the LDS accumulators (ds_add_u64: integer sums, any order, bitwise reproducible).  The format is part
+// of the ABI: mpc_iwe_from_fixed (events.hip) converts a caller's buffer of such sums.
+#define MPC_FIX_SHIFT 30
+__device__ __forceinline__ long long mpc_to_fixed(float v) {         // |v| < 2^31
+    const float hi = truncf(v);
+    return ((long long)(int)hi << MPC_FIX_SHIFT) + (long long)(int)((v - hi) * (float)(1 << MPC_FIX_SHIFT));
+}
+__device__ __forceinline__ float mpc_from_fixed(long long a) {
+    return (float)((double)a * (1.0 / (double)(1 << MPC_FIX_SHIFT)));
+}
 #endif

@@ -224,7 +224,6 @@ __global__ __launch_bounds__(256) void k_event_pos_grad(const mpc_shape s, const
 // than fp32 accumulation of the same taps, and integer sums are order independent, so the
 // image is bitwise reproducible from run to run.
 // ==========================================================================================
-#define EV_FIX_SHIFT 30
 #define EV_MARKER 0x6d706331   // 'mpc1': backward records of this workspace are valid
 
 struct BinLayout {
@@ -236,15 +235,8 @@ struct BinLayout {
 
 struct __attribute__((packed, aligned(4))) rec3 { float y, x, w; };       // forward record (one 12-byte store / load)
 
-__device__ __forceinline__ long long ev_to_fixed_small(float v) {   // |v| < 2
-    return (long long)(int)(v * (float)(1 << EV_FIX_SHIFT));
-}
-__device__ __forceinline__ long long ev_to_fixed(float v) {         // |v| < 2^31
-    const float hi = truncf(v);
-    return ((long long)(int)hi << EV_FIX_SHIFT) + (long long)(int)((v - hi) * (float)(1 << EV_FIX_SHIFT));
-}
-__device__ __forceinline__ float ev_from_fixed(long long a) {
-    return (float)((double)a * (1.0 / (double)(1 << EV_FIX_SHIFT)));
+__device__ __forceinline__ long long ev_to_fixed_small(float v) {   // |v| < 2; otherwise mpc_to_fixed (common.h)
+    return (long long)(int)(v * (float)(1 << MPC_FIX_SHIFT));
 }
 
 // Workgroups are dealt round-robin over the 8 XCDs (each with its own L2).  Map physical block p to
@@ -456,7 +448,7 @@ __global__ __launch_bounds__(1024) void k_iwe_accum(const BinLayout L, float *__
                 });
             else
                 record_taps(e[u].y, e[u].x, e[u].w, H, W, row0, row1, [&](int yy, int xx, float v) {
-                    atomicAdd(&s_acc[MPC_IDX((yy - row0) * W + xx, npix)], (unsigned long long)ev_to_fixed(v));
+                    atomicAdd(&s_acc[MPC_IDX((yy - row0) * W + xx, npix)], (unsigned long long)mpc_to_fixed(v));
                 });
         }
     }
@@ -466,12 +458,12 @@ __global__ __launch_bounds__(1024) void k_iwe_accum(const BinLayout L, float *__
         for (int i = tid; i < npix; i += 1024) dst[i] = (long long)s_acc[i];
     } else {
         float *dst = iwe + ((size_t)img * H + row0) * W;
-        for (int i = tid; i < npix; i += 1024) dst[i] = ev_from_fixed((long long)s_acc[i]);
+        for (int i = tid; i < npix; i += 1024) dst[i] = mpc_from_fixed((long long)s_acc[i]);
     }
 }
 
 __global__ __launch_bounds__(256) void k_iwe_from_fixed(const long long *__restrict__ src, float *__restrict__ dst, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = ev_from_fixed(src[i]);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = mpc_from_fixed(src[i]);
 }
 
 struct __attribute__((packed, aligned(4))) pair4 { float x, y; };
@@ -597,8 +589,8 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
         for (int u = 0; u < NIF; ++u) {
             if (r0 + u * NT < n && (!ORDERED || e[u].z != 0.f)) {
                 const int cell = (int)(__float_as_uint(e[u].w) & 0x7fffffffu);
-                atomicAdd(&s_acc[MPC_IDX(2 * cell, 2 * ncell)], (unsigned long long)ev_to_fixed(gy[u]));
-                atomicAdd(&s_acc[MPC_IDX(2 * cell + 1, 2 * ncell)], (unsigned long long)ev_to_fixed(gx[u]));
+                atomicAdd(&s_acc[MPC_IDX(2 * cell, 2 * ncell)], (unsigned long long)mpc_to_fixed(gy[u]));
+                atomicAdd(&s_acc[MPC_IDX(2 * cell + 1, 2 * ncell)], (unsigned long long)mpc_to_fixed(gx[u]));
             }
         }
     }
@@ -609,7 +601,7 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
     float2 *dst = reinterpret_cast<float2 *>(glut) + ((size_t)bt * p.hq + crow0) * p.wq;
     const float2 *add = add_term ? reinterpret_cast<const float2 *>(add_term) + ((size_t)bt * p.hq + crow0) * p.wq : nullptr;
     for (int i = tid; i < ncell; i += NT) {
-        float2 v = make_float2(coef * ev_from_fixed((long long)s_acc[2 * i]), coef * ev_from_fixed((long long)s_acc[2 * i + 1]));
+        float2 v = make_float2(coef * mpc_from_fixed((long long)s_acc[2 * i]), coef * mpc_from_fixed((long long)s_acc[2 * i + 1]));
         if (add) { const float2 o = add[i]; v.x += gout * o.x; v.y += gout * o.y; }
         dst[i] = v;
     }
@@ -970,15 +962,15 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
             unsigned long long *a = s_pacc + (size_t)lc * 2 * kk;
             for (int j = 0; j < kk; ++j) {
                 const float f = j < PE_KMAX ? ph[j] : phi[grow[u] * k + j];
-                atomicAdd(a + j, (unsigned long long)ev_to_fixed(f * gy[u]));
-                atomicAdd(a + kk + j, (unsigned long long)ev_to_fixed(f * gx[u]));
+                atomicAdd(a + j, (unsigned long long)mpc_to_fixed(f * gy[u]));
+                atomicAdd(a + kk + j, (unsigned long long)mpc_to_fixed(f * gx[u]));
             }
         }
     }
     __syncthreads();
     const float coef = scal[MPC_SCAL_GCOEF] * (grad_out ? grad_out[0] : 1.f);
     float *dst = gcoef + ((size_t)part * p.B * p.hq * p.wq + cell0) * 2 * kk;
-    for (int i = tid; i < ncell * 2 * kk; i += PE_NT) dst[i] = coef * ev_from_fixed((long long)s_pacc[i]);
+    for (int i = tid; i < ncell * 2 * kk; i += PE_NT) dst[i] = coef * mpc_from_fixed((long long)s_pacc[i]);
 }
 
 extern "C" int mpc_pe_warp(const mpc_shape *s, const float *events, const float *coef_rows, const float *phi, int32_t k,

@@ -3,8 +3,8 @@
 // called from src/loader/evimo2/datasubset.py:146-189 and src/loader/multiflow/sample.py:172-200), with the resize of
 // datasubset.py:189 (F.interpolate, bilinear, align_corners=False) fused into the write pass.
 //
-// Same machinery as voxel.hip: one binning pass appends 16-byte records to per-(sample, channel, row-strip) buckets (crowded
-// buckets spill in chunks to their sample's spill region), one workgroup per bucket accumulates its strip in LDS as Q33.30 fixed
+// Same machinery as voxel.hip: one binning pass appends 16-byte records to per-(sample, channel, row-strip) buckets
+// (strip_buckets.h, shared with it), one workgroup per bucket accumulates its strip in LDS as Q33.30 fixed
 // point (ds_add_u64: integer sums, any order, bitwise reproducible) and writes it with plain stores; with a normalisation the
 // strips are accumulated twice (statistics, then the write) so that the grid is written once and never read back.
 //
@@ -19,10 +19,8 @@
 //     recorded for both strips.  The statistics count every input row once, in the strip that owns it: rows [lo(s), lo(s + 1)).
 //     The write pass normalises the four source values as it reads them and stores Ho x Wo rows; the H x W grid never exists in
 //     HBM.  Without a resize the same code runs with lo / hi = the strip's own rows.
-#include "common.h"
-#include "bounds.h"
+#include "strip_buckets.h"
 
-#define REPR_FIX_SHIFT 30
 #define REPR_PER_THREAD 2
 #define REPR_SLOTS 6          // buckets one event can vote into: 2 channels x up to 3 strips (rows y0, y0 + 1 across a shared row)
 #define REPR_NORM_BLOCKS 256
@@ -35,12 +33,7 @@ struct ReprGeom {
     float sh, sw;         // float(H) / Ho, float(W) / Wo   (area_pixel_compute_scale)
 };
 
-struct ReprLayout {
-    int NBk, cap;
-    int spcap, chcap;     // spill records / chunk descriptors per sample
-    int *gcount;          // [NBk + 2 B]   fill of every bucket; then per sample: spilled records, chunks
-    float4 *rec, *ovf;    // rec [NBk][cap], ovf [B][spcap]
-    int4 *chunk;          // [B][chcap]  {bucket within the sample, first spill record, records, -}
+struct ReprLayout : StripBuckets {
     double *spart;        // [NBk][REPR_STAT]  partial statistics of the strips: count, sum, sum of squares, smallest, largest non-zero entry
     float *stat;          // [B][4]      mean, std (0: subtract only)
 };
@@ -69,33 +62,10 @@ __host__ __device__ __forceinline__ void repr_strip_rows(const ReprGeom &g, int 
     hi = b + 1 > own_hi ? b + 1 : own_hi;
 }
 
-__device__ __forceinline__ long long repr_to_fixed(float v) {         // |v| < 2^31
-    const float hi = truncf(v);
-    return ((long long)(int)hi << REPR_FIX_SHIFT) + (long long)(int)((v - hi) * (float)(1 << REPR_FIX_SHIFT));
-}
 // representation.py:14-17 for one non-zero entry: (v - mean) / std if std > 0 else v - mean
 __device__ __forceinline__ float repr_norm(float v, float mean, float sd) {
     const float d = v - mean;
     return sd > 0.f ? d / sd : d;
-}
-__device__ __forceinline__ float repr_from_fixed(long long a) {
-    return (float)((double)a * (1.0 / (double)(1 << REPR_FIX_SHIFT)));
-}
-
-// smallest `v` over a workgroup of NT threads; result valid in thread 0 (the shape of common.h: block_sum_d)
-template <int NT>
-__device__ __forceinline__ double block_min_d(double v, double *lds /* NT/64 doubles */) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, 64));
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double r = INFINITY;
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int i = 0; i < NT / 64; ++i) r = fmin(r, lds[i]);
-    }
-    __syncthreads();
-    return r;
 }
 
 // grid (chunks * B rounded up to 8), 256 threads, dynamic LDS = (3 C NS + 2 NS + 1) ints
@@ -105,13 +75,11 @@ __global__ __launch_bounds__(256) void k_repr_bin(const mpc_repr_shape s, const 
                                                   const int *__restrict__ counts, const long long *__restrict__ centres) {
     extern __shared__ int s_cnt[];
     const int chunks = (s.N + 256 * REPR_PER_THREAD - 1) / (256 * REPR_PER_THREAD);
-    const int per = (chunks * s.B + 7) >> 3;
-    const int lblk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);        // XCD-contiguous order
+    const int lblk = sb_bin_block(chunks * s.B);
     if (lblk >= chunks * s.B) return;
     const int tid = threadIdx.x, b = lblk / chunks, chunk = lblk - b * chunks;
     const int NS = G.NS, nloc = s.C * NS;
-    int *s_base = s_cnt + nloc;
-    int *s_spill = s_base + nloc;         // slot - s_spill[lb] = place in the sample's spill region, for the slots >= cap
+    int *s_base = s_cnt + nloc, *s_spill = s_base + nloc;
     int *s_lo = s_spill + nloc;           // [NS + 1]  first input row of every strip, then H
     int *s_hi = s_lo + NS + 1;            // [NS]      one past the last input row a strip holds
     for (int i = tid; i < nloc; i += 256) s_cnt[i] = 0;
@@ -183,38 +151,12 @@ __global__ __launch_bounds__(256) void k_repr_bin(const mpc_repr_shape s, const 
         }
     }
     __syncthreads();
-    for (int i = tid; i < nloc; i += 256) {
-        const int c = s_cnt[i];
-        const int base = c > 0 ? atomicAdd(&L.gcount[MPC_IDX(b * nloc + i, L.NBk)], c) : 0;
-        s_base[i] = base;
-        // the slots [max(base, cap), base + c) of this workgroup lie beyond the bucket: ONE run of the sample's spill region,
-        // named in the sample's chunk list (the bucket's own workgroup reads the list and then only its runs)
-        const int first = max(base, L.cap), nsp = base + c - first;
-        if (nsp > 0) {
-            const int sp0 = atomicAdd(&L.gcount[L.NBk + 2 * b], nsp);
-            const int ci = atomicAdd(&L.gcount[L.NBk + 2 * b + 1], 1);
-            MPC_EXPECT(ci < L.chcap);
-            if (ci < L.chcap) L.chunk[(size_t)b * L.chcap + MPC_IDX(ci, L.chcap)] = make_int4(i, sp0, nsp, 0);
-            s_spill[i] = first - sp0;
-        }
-    }
-    __syncthreads();
+    sb_reserve(L, b, nloc, s_cnt, s_base, s_spill);
 #pragma unroll
     for (int k = 0; k < REPR_PER_THREAD; ++k)
 #pragma unroll
-        for (int u = 0; u < REPR_SLOTS; ++u) {
-            const int lb = bk[k][u];
-            if (lb < 0) continue;
-            const int g = b * nloc + lb;
-            const int slot = s_base[MPC_IDX(lb, nloc)] + rk[k][u];
-            const float4 rec = make_float4(ry[k], rx[k], rw[k][u / 3], __int_as_float(g));
-            if (slot < L.cap) L.rec[MPC_IDX((size_t)g * L.cap + slot, (long long)L.NBk * L.cap)] = rec;
-            else {
-                const int q = slot - s_spill[MPC_IDX(lb, nloc)];
-                MPC_EXPECT(q >= 0 && q < L.spcap);
-                if (q >= 0 && q < L.spcap) L.ovf[(size_t)b * L.spcap + q] = rec;
-            }
-        }
+        for (int u = 0; u < REPR_SLOTS; ++u)
+            if (bk[k][u] >= 0) sb_store(L, b, nloc, bk[k][u], rk[k][u], ry[k], rx[k], rw[k][u / 3], s_base, s_spill);
 }
 
 // the taps of one record that fall into the rows [lo, hi) of a strip, added to its LDS accumulators
@@ -222,7 +164,7 @@ __device__ __forceinline__ void repr_vote(unsigned long long *s_acc, const float
     if (int_xy) {
         const int yy = (int)e.x, xx = (int)e.y;
         if (yy < lo || yy >= hi || xx < 0 || xx >= W) return;
-        atomicAdd(&s_acc[MPC_IDX((yy - lo) * W + xx, npix)], (unsigned long long)repr_to_fixed(e.z));
+        atomicAdd(&s_acc[MPC_IDX((yy - lo) * W + xx, npix)], (unsigned long long)mpc_to_fixed(e.z));
         return;
     }
     const int y0 = (int)floorf(fminf(fmaxf(e.x, -8.f), (float)H + 8.f)), x0 = (int)floorf(fminf(fmaxf(e.y, -8.f), (float)W + 8.f));
@@ -237,7 +179,7 @@ __device__ __forceinline__ void repr_vote(unsigned long long *s_acc, const float
             if (yy < lo || yy >= hi) continue;
             const float wy = 1.f - fabsf((float)yy - e.x);
             // value * wx * wy * wt left to right (representation.py:103); value = +-1 commutes exactly
-            atomicAdd(&s_acc[MPC_IDX((yy - lo) * W + xx, npix)], (unsigned long long)repr_to_fixed((wx * wy) * e.z));
+            atomicAdd(&s_acc[MPC_IDX((yy - lo) * W + xx, npix)], (unsigned long long)mpc_to_fixed((wx * wy) * e.z));
         }
     }
 }
@@ -269,27 +211,7 @@ __global__ __launch_bounds__(1024) void k_repr_accum(const ReprGeom G, const Rep
     }
     for (int i = tid; i < npix; i += 1024) s_acc[i] = 0ull;
     __syncthreads();
-    const int filled = L.gcount[MPC_IDX(g, L.NBk)], n = min(filled, L.cap);
-    const float4 *rec = L.rec + (size_t)g * L.cap;
-    for (int r = tid; r < n; r += 1024) repr_vote(s_acc, rec[r], int_xy, H, W, lo, hi, npix);
-    if (filled > L.cap) {                                 // (workgroup-uniform) this bucket spilled
-        const int nloc = C * G.NS, b = g / nloc, lb = g - b * nloc;
-        const int nch = min(L.gcount[L.NBk + 2 * b + 1], L.chcap);
-        const int4 *ch = L.chunk + (size_t)b * L.chcap;
-        const float4 *ovf = L.ovf + (size_t)b * L.spcap;
-        for (int c0 = 0; c0 < nch; c0 += 1024) {          // the chunk list, a descriptor per thread; a wavefront takes the runs its lanes found
-            int4 d = make_int4(-1, 0, 0, 0);
-            if (c0 + tid < nch) d = ch[MPC_IDX(c0 + tid, L.chcap)];
-            unsigned long long mm = __ballot(d.x == lb);
-            while (mm != 0ull) {
-                const int l = __ffsll((long long)mm) - 1;
-                mm &= mm - 1ull;
-                const int sp0 = __shfl(d.y, l, 64);
-                const int cnt = min(__shfl(d.z, l, 64), max(L.spcap - sp0, 0));
-                for (int r = (tid & 63); r < cnt; r += 64) repr_vote(s_acc, ovf[MPC_IDX(sp0 + r, L.spcap)], int_xy, H, W, lo, hi, npix);
-            }
-        }
-    }
+    sb_drain(L, g, C * G.NS, [&](const float4 e) { repr_vote(s_acc, e, int_xy, H, W, lo, hi, npix); });
     __syncthreads();
     if (MODE == 1) {
         // per-thread partials in fp32 (a thread sees ~10 entries), everything above them in fp64
@@ -297,14 +219,14 @@ __global__ __launch_bounds__(1024) void k_repr_accum(const ReprGeom G, const Rep
         int cnt = 0;
         float sum = 0.f, sq = 0.f, mn = INFINITY, mx = -INFINITY;
         for (int i = tid; i < nown; i += 1024) {
-            const float v = repr_from_fixed((long long)s_acc[MPC_IDX(i, npix)]);
+            const float v = mpc_from_fixed((long long)s_acc[MPC_IDX(i, npix)]);
             if (v != 0.f) { ++cnt; sum += v; sq = fmaf(v, v, sq); mn = fminf(mn, v); mx = fmaxf(mx, v); }
         }
         const double r0 = block_sum_d<1024>((double)cnt, s_red[0]);
         const double r1 = block_sum_d<1024>((double)sum, s_red[1]);
         const double r2 = block_sum_d<1024>((double)sq, s_red[2]);
         const double r3 = block_min_d<1024>((double)mn, s_red[0]);
-        const double r4 = -block_min_d<1024>(-(double)mx, s_red[1]);
+        const double r4 = block_max_d<1024>((double)mx, s_red[1]);
         if (tid == 0) {
             double *p = L.spart + (size_t)MPC_IDX(g, L.NBk) * REPR_STAT;
             p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r3; p[4] = r4; p[5] = 0.0;
@@ -314,7 +236,7 @@ __global__ __launch_bounds__(1024) void k_repr_accum(const ReprGeom G, const Rep
     float sub = 0.f, sd = 0.f;                               // the sample's mean and std (0: subtract only)
     if (MODE == 2) { const int b = img / C; sub = L.stat[b * 4 + 0]; sd = L.stat[b * 4 + 1]; }
     auto value = [&](int yy, int xx) -> float {              // entry (yy, xx) of the (normalised) full-size grid (representation.py:14-17)
-        float v = repr_from_fixed((long long)s_acc[MPC_IDX((yy - lo) * W + xx, npix)]);
+        float v = mpc_from_fixed((long long)s_acc[MPC_IDX((yy - lo) * W + xx, npix)]);
         if (MODE == 2 && v != 0.f) v = repr_norm(v, sub, sd);
         return v;
     };
@@ -322,7 +244,7 @@ __global__ __launch_bounds__(1024) void k_repr_accum(const ReprGeom G, const Rep
         float *dst = grid + ((size_t)img * H + lo) * W;
         const int nown = (own_hi - lo) * W;
         for (int i = tid; i < nown; i += 1024) {
-            float v = repr_from_fixed((long long)s_acc[MPC_IDX(i, npix)]);
+            float v = mpc_from_fixed((long long)s_acc[MPC_IDX(i, npix)]);
             if (MODE == 2 && v != 0.f) v = repr_norm(v, sub, sd);
             dst[i] = v;
         }
@@ -368,7 +290,7 @@ __global__ __launch_bounds__(256) void k_repr_finalize(const double *__restrict_
     const double s1 = block_sum_d<256>(sum, s_red[1]);
     const double s2 = block_sum_d<256>(sq, s_red[2]);
     const double lo = block_min_d<256>(mn, s_red[0]);
-    const double hi = -block_min_d<256>(-mx, s_red[1]);
+    const double hi = block_max_d<256>(mx, s_red[1]);
     if (threadIdx.x == 0) {
         float sub = 0.f, sd = 0.f;
         if (n > 0.0) {                                        // representation.py:11-17
@@ -395,7 +317,7 @@ __global__ __launch_bounds__(256) void k_repr_gstats(const float *__restrict__ g
     const double r1 = block_sum_d<256>(sum, s_red[1]);
     const double r2 = block_sum_d<256>(sq, s_red[2]);
     const double r3 = block_min_d<256>(mn, s_red[0]);
-    const double r4 = -block_min_d<256>(-mx, s_red[1]);
+    const double r4 = block_max_d<256>(mx, s_red[1]);
     if (threadIdx.x == 0) {
         double *p = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * REPR_STAT;
         p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r3; p[4] = r4; p[5] = 0.0;
@@ -413,7 +335,7 @@ __global__ __launch_bounds__(256) void k_repr_gnorm(float *__restrict__ grid, co
 }
 
 // ------------------------------------------------------------------------------------------
-struct ReprHostLayout { ReprGeom G; ReprLayout L; int lds_rows; int64_t off_count, off_rec, off_ovf, off_chunk, off_spart, off_stat, total; };
+struct ReprHostLayout { ReprGeom G; ReprLayout L; int lds_rows; int64_t total; };
 
 static int repr_max_rows(const ReprGeom &G) {
     int m = 0;
@@ -479,36 +401,11 @@ static ReprHostLayout repr_layout(const mpc_repr_shape *s, const ReprGeom &G, in
     h.G = G;
     h.lds_rows = rows;
     ReprLayout &L = h.L;
-    const int64_t B1 = s->B > 0 ? s->B : 1, nloc = (int64_t)s->C * G.NS;
-    L.NBk = (int)(s->B * nloc);
-    int64_t cap = 4 * ((2 * (int64_t)s->N + nloc - 1) / nloc);           // four times the mean fill (an event: two channels)
-    if (cap < 4096) cap = 4096;
-    if (cap > 2 * (int64_t)s->N) cap = 2 * (int64_t)s->N;
-    L.cap = (int)(cap > 0 ? cap : 1);
-    // spill region of a sample: every record it can produce; chunk list: one descriptor per (binning workgroup, bucket it
-    // overflowed) -- a binning workgroup holds 256 * REPR_PER_THREAD events in at most C * NS buckets
-    const int64_t per_event = s->int_xy ? 4 : REPR_SLOTS;
-    L.spcap = (int)(per_event * s->N > 0 ? per_event * s->N : 1);
-    {
-        const int64_t wgs = mpc_cdiv(s->N > 0 ? s->N : 1, 256 * REPR_PER_THREAD);
-        const int64_t per_wg = nloc < 256 * REPR_PER_THREAD * per_event ? nloc : 256 * REPR_PER_THREAD * per_event;
-        L.chcap = (int)(wgs * per_wg);
-    }
-    int64_t off = 0;
-    h.off_count = off; off += mpc_align((int64_t)(L.NBk + 2 * B1 + 8) * 4);
-    h.off_rec = off;   off += mpc_align((int64_t)L.NBk * L.cap * 16 + 16);
-    h.off_ovf = off;   off += mpc_align(B1 * L.spcap * 16 + 16);
-    h.off_chunk = off; off += mpc_align(B1 * L.chcap * 16 + 16);
-    h.off_spart = off; off += mpc_align((int64_t)(L.NBk > 0 ? L.NBk : 1) * REPR_STAT * 8);
-    h.off_stat = off;  off += mpc_align(B1 * 4 * 4);
+    // an event votes into two channels x up to three strips; an integer pixel has one row, in at most two strips
+    int64_t off = sb_layout(L, s->B, s->N, (int64_t)s->C * G.NS, s->int_xy ? 4 : REPR_SLOTS, 256 * REPR_PER_THREAD, ws);
+    L.spart = sb_take<double>(ws, off, (int64_t)(L.NBk > 0 ? L.NBk : 1) * REPR_STAT * 8);
+    L.stat = sb_take<float>(ws, off, (int64_t)(s->B > 0 ? s->B : 1) * 4 * 4);
     h.total = off;
-    char *w = (char *)ws;
-    L.gcount = (int *)(w + h.off_count);
-    L.rec = (float4 *)(w + h.off_rec);
-    L.ovf = (float4 *)(w + h.off_ovf);
-    L.chunk = (int4 *)(w + h.off_chunk);
-    L.spart = (double *)(w + h.off_spart);
-    L.stat = (float *)(w + h.off_stat);
     return h;
 }
 
@@ -534,16 +431,10 @@ extern "C" int mpc_repr_grid(const mpc_repr_shape *s, const float *x, const floa
     const ReprHostLayout h = repr_layout(s, G, rows, ws);
     const ReprLayout &L = h.L;
     hipStream_t st = (hipStream_t)stream;
-    static mpc_device_once attr_once;   // raising the dynamic-LDS cap: idempotent, once per device
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_repr_accum<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_repr_accum<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_repr_accum<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
-        attr_once.mark();
-    }
-    const int e0 = mpc_zero_async(L.gcount, (size_t)(L.NBk + 2 * s->B + 8) * 4, st);
-    if (e0) return e0;
+    static mpc_device_once attr_once;
+    rc = sb_raise_lds_cap(attr_once, __func__, k_repr_accum<0>, k_repr_accum<1>, k_repr_accum<2>);
+    if (!rc) rc = sb_zero_counters(L, s->B, st);
+    if (rc) return rc;
     if (s->N > 0) {
         const int nblk = mpc_cdiv(s->N, 256 * REPR_PER_THREAD) * s->B;
         const size_t bin_lds = ((size_t)s->C * G.NS * 3 + 2 * G.NS + 1) * sizeof(int);

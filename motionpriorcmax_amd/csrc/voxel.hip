@@ -2,41 +2,25 @@
 // build on the CPU from the same event window (src/loader/dsec/utils.py:29-77, VoxelGrid.convert):
 // trilinear accumulation of +-1 polarity votes into [C][H][W], then normalisation of the non-zero
 // entries.  Same machinery as the IWE (events.hip): one binning pass appends 16-byte records to
-// per-(sample, channel, row-strip) buckets, one workgroup per bucket accumulates its strip in LDS as
-// Q33.30 fixed point (ds_add_u64) and writes it with plain stores; an overflowing bucket spills to its sample's
-// spill region in CHUNKS (one contiguous run per binning workgroup and bucket, named in a per-sample chunk list), and only
-// the workgroup of a bucket that did overflow looks at its sample's chunk list and reads its own runs.  With mean_std / max
-// normalisation the strips are accumulated twice -- statistics first, then written normalised -- so the
-// grid is written once and never read back (k_vox_accum).
+// per-(sample, channel, row-strip) buckets (strip_buckets.h: a crowded bucket spills in chunks to its sample's spill
+// region), one workgroup per bucket accumulates its strip in LDS as Q33.30 fixed point (ds_add_u64) and writes it
+// with plain stores.  With mean_std / max normalisation the strips are accumulated twice -- statistics first, then
+// written normalised -- so the grid is written once and never read back (k_vox_accum).
 //
 // Arithmetic follows the reference op for op: x0 = int(x) (truncation), tap weight
 // value * (1-|xl-x|) * (1-|yl-y|) * (1-|tl-t_norm|) (left to right; value = 2p-1 is +-1, so its sign
 // commutes exactly), t_norm = (C-1) * (t - t[0]) / (t[-1] - t[0]).
-#include "common.h"
-#include "bounds.h"
+#include "strip_buckets.h"
 
-#define VOX_FIX_SHIFT 30
 #define VOX_PER_THREAD 2
 
-struct VoxLayout {
-    int SR, NS, NBk, cap;
-    int spcap, chcap;     // spill records / chunk descriptors per sample
-    int *gcount;          // [NBk + 2 B]   fill of every bucket; then per sample: spilled records, chunks
-    float4 *rec, *ovf;    // ovf: [B][spcap]
-    int4 *chunk;          // [B][chcap]  {bucket within the sample, first spill record, records, -}
+struct VoxLayout : StripBuckets {
+    int SR, NS;           // rows per strip, strips
     double *part;         // [B][nblk][4]   partial statistics of k_vox_stats (quantile clipping: the entries change after the strips)
     double *spart;        // [NBk][4]       partial statistics of the strips (k_vox_accum<1>)
     float *stat;          // [B][4]  mean, 1/std (or 1/max), flag
     int nstat_blocks;
 };
-
-__device__ __forceinline__ long long vox_to_fixed(float v) {         // |v| < 2^31
-    const float hi = truncf(v);
-    return ((long long)(int)hi << VOX_FIX_SHIFT) + (long long)(int)((v - hi) * (float)(1 << VOX_FIX_SHIFT));
-}
-__device__ __forceinline__ float vox_from_fixed(long long a) {
-    return (float)((double)a * (1.0 / (double)(1 << VOX_FIX_SHIFT)));
-}
 
 // taps of one record restricted to rows [row0, row1): f(yy, xx, value)
 template <typename F>
@@ -62,13 +46,11 @@ __global__ __launch_bounds__(256) void k_vox_bin(const mpc_vox_shape s, const Vo
                                                  const float4 *__restrict__ ev, const int *__restrict__ counts) {
     extern __shared__ int s_cnt[];
     const int chunks = (s.N + 256 * VOX_PER_THREAD - 1) / (256 * VOX_PER_THREAD);
-    const int per = (chunks * s.B + 7) >> 3;
-    const int lblk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);        // XCD-contiguous order
+    const int lblk = sb_bin_block(chunks * s.B);
     if (lblk >= chunks * s.B) return;
     const int tid = threadIdx.x, b = lblk / chunks, chunk = lblk - b * chunks;
     const int nloc = s.C * L.NS;
-    int *s_base = s_cnt + nloc;
-    int *s_spill = s_base + nloc;         // slot - s_spill[lb] = place in the sample's spill region, for the slots >= cap
+    int *s_base = s_cnt + nloc, *s_spill = s_base + nloc;
     for (int i = tid; i < nloc; i += 256) s_cnt[i] = 0;
     __syncthreads();
     const int n = min(counts[b], s.N);
@@ -113,39 +95,16 @@ __global__ __launch_bounds__(256) void k_vox_bin(const mpc_vox_shape s, const Vo
         }
     }
     __syncthreads();
-    for (int i = tid; i < nloc; i += 256) {
-        const int c = s_cnt[i];
-        const int base = c > 0 ? atomicAdd(&L.gcount[b * nloc + i], c) : 0;
-        s_base[i] = base;
-        // the slots [max(base, cap), base + c) of this workgroup lie beyond the bucket: ONE run of the sample's spill region,
-        // named in the sample's chunk list (the bucket's own workgroup reads the list and then only its runs)
-        const int first = max(base, L.cap), nsp = base + c - first;
-        if (nsp > 0) {
-            const int sp0 = atomicAdd(&L.gcount[L.NBk + 2 * b], nsp);
-            const int ci = atomicAdd(&L.gcount[L.NBk + 2 * b + 1], 1);
-            if (ci < L.chcap) L.chunk[(size_t)b * L.chcap + MPC_IDX(ci, L.chcap)] = make_int4(i, sp0, nsp, 0);
-            s_spill[i] = first - sp0;
-        }
-    }
-    __syncthreads();
+    sb_reserve(L, b, nloc, s_cnt, s_base, s_spill);
 #pragma unroll
     for (int k = 0; k < VOX_PER_THREAD; ++k)
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int lb = bk[k][u];
-            if (lb < 0) continue;
-            const int g = b * nloc + lb;
-            const int slot = s_base[lb] + rk[k][u];
-            const float4 rec = make_float4(ry[k], rx[k], rw[k][u >> 1], __int_as_float(g));
-            if (slot < L.cap) L.rec[MPC_IDX((size_t)g * L.cap + slot, (long long)L.NBk * L.cap)] = rec;
-            else { const int k = slot - s_spill[lb]; MPC_EXPECT(k >= 0 && k < L.spcap); if (k >= 0 && k < L.spcap) L.ovf[(size_t)b * L.spcap + k] = rec; }
-        }
+        for (int u = 0; u < 4; ++u)
+            if (bk[k][u] >= 0) sb_store(L, b, nloc, bk[k][u], rk[k][u], ry[k], rx[k], rw[k][u >> 1], s_base, s_spill);
 }
 
 // grid NBk, 1024 threads, dynamic LDS = SR * W * 8.  One strip of one channel image accumulated in LDS (64-bit fixed point:
-// integer sums, any order, bitwise reproducible) from its bucket of records and -- only a bucket beyond its capacity (events
-// piled up in a few rows) -- from its runs of the sample's spill region: the workgroup reads the sample's chunk list once
-// (16 bytes per (binning workgroup, overflowed bucket) pair) and then its own runs, nothing of the other buckets' spills.
+// integer sums, any order, bitwise reproducible) from the records of its bucket, spilled ones included (sb_drain).
 //   MODE 0: the strip written as it is (no normalisation, or quantile clipping follows)
 //   MODE 1: nothing written -- the strip's share of the per-sample statistics of the non-zero entries (count, sum, sum of
 //           squares, largest magnitude) to spart[g]
@@ -156,73 +115,41 @@ __global__ __launch_bounds__(256) void k_vox_bin(const mpc_vox_shape s, const Vo
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_vox_accum(const VoxLayout L, float *__restrict__ grid, int H, int W, int C, int norm) {
     extern __shared__ unsigned long long s_acc[];
-    __shared__ double s_red[4][16];
+    __shared__ double s_red[3][16];
     const int tid = threadIdx.x;
     const int g = blockIdx.x, img = g / L.NS, strip = g - img * L.NS;
     const int row0 = strip * L.SR, row1 = min(row0 + L.SR, H);
     const int npix = (row1 - row0) * W;
     for (int i = tid; i < npix; i += 1024) s_acc[i] = 0ull;
     __syncthreads();
-    const int filled = L.gcount[g], n = min(filled, L.cap);
-    const float4 *rec = L.rec + (size_t)g * L.cap;
-    for (int r = tid; r < n; r += 1024) {
-        const float4 e = rec[r];
+    sb_drain(L, g, C * L.NS, [&](const float4 e) {
         vox_taps(e.x, e.y, e.z, H, W, row0, row1, [&](int yy, int xx, float v) {
-            atomicAdd(&s_acc[MPC_IDX((yy - row0) * W + xx, npix)], (unsigned long long)vox_to_fixed(v));
+            atomicAdd(&s_acc[MPC_IDX((yy - row0) * W + xx, npix)], (unsigned long long)mpc_to_fixed(v));
         });
-    }
-    if (filled > L.cap) {                                 // (workgroup-uniform) this bucket spilled
-        const int nloc = C * L.NS, b = g / nloc, lb = g - b * nloc;
-        const int nch = min(L.gcount[L.NBk + 2 * b + 1], L.chcap);
-        const int4 *ch = L.chunk + (size_t)b * L.chcap;
-        const float4 *ovf = L.ovf + (size_t)b * L.spcap;
-        for (int c0 = 0; c0 < nch; c0 += 1024) {          // the chunk list, a descriptor per thread; a wavefront takes the runs its lanes found
-            int4 d = make_int4(-1, 0, 0, 0);
-            if (c0 + tid < nch) d = ch[c0 + tid];
-            unsigned long long mm = __ballot(d.x == lb);
-            while (mm != 0ull) {
-                const int l = __ffsll((long long)mm) - 1;
-                mm &= mm - 1ull;
-                const int sp0 = __shfl(d.y, l, 64);
-                const int cnt = min(__shfl(d.z, l, 64), max(L.spcap - sp0, 0));
-                for (int r = (tid & 63); r < cnt; r += 64) {
-                    const float4 e = ovf[MPC_IDX(sp0 + r, L.spcap)];
-                    vox_taps(e.x, e.y, e.z, H, W, row0, row1, [&](int yy, int xx, float v) {
-                        atomicAdd(&s_acc[MPC_IDX((yy - row0) * W + xx, npix)], (unsigned long long)vox_to_fixed(v));
-                    });
-                }
-            }
-        }
-    }
+    });
     __syncthreads();
     if (MODE == 1) {
         // per-thread partials in fp32 (a thread sees ~20 entries), everything above them in fp64
         int cnt = 0;
         float sum = 0.f, sq = 0.f, mx = 0.f;
         for (int i = tid; i < npix; i += 1024) {
-            const float v = vox_from_fixed((long long)s_acc[i]);
+            const float v = mpc_from_fixed((long long)s_acc[i]);
             if (v != 0.f) { ++cnt; sum += v; sq = fmaf(v, v, sq); mx = fmaxf(mx, fabsf(v)); }
         }
+        double *p = L.spart + (size_t)MPC_IDX(g, L.NBk) * 4;
+        const double r3 = block_max_d<1024>((double)mx, s_red[0]);
+        if (tid == 0) p[3] = r3;                         // (stored now: nothing of it lives across the three sums)
         const double r0 = block_sum_d<1024>((double)cnt, s_red[0]);
         const double r1 = block_sum_d<1024>((double)sum, s_red[1]);
         const double r2 = block_sum_d<1024>((double)sq, s_red[2]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_down(mx, o, 64));
-        if ((tid & 63) == 0) s_red[3][tid >> 6] = (double)mx;
-        __syncthreads();
-        if (tid == 0) {
-            double m = 0.0;
-            for (int w = 0; w < 16; ++w) m = fmax(m, s_red[3][w]);
-            double *p = L.spart + (size_t)g * 4;
-            p[0] = r0; p[1] = r1; p[2] = r2; p[3] = m;
-        }
+        if (tid == 0) { p[0] = r0; p[1] = r1; p[2] = r2; }
         return;
     }
     float sub = 0.f, mul = 1.f;
     if (MODE == 2) { const int b = img / C; sub = L.stat[b * 4 + 0]; mul = L.stat[b * 4 + 1]; }
     float *dst = grid + ((size_t)img * H + row0) * W;
     for (int i = tid; i < npix; i += 1024) {
-        float v = vox_from_fixed((long long)s_acc[i]);
+        float v = mpc_from_fixed((long long)s_acc[i]);
         if (MODE == 2) {                                 // (k_vox_norm's arithmetic)
             if (norm == 1) { if (v != 0.f) v = (v - sub) * mul; }
             else v = v * mul;
@@ -233,7 +160,7 @@ __global__ __launch_bounds__(1024) void k_vox_accum(const VoxLayout L, float *__
 
 // per-sample statistics of the non-zero entries: grid (nblk, B), 256 threads -> part[b][blk][4]
 __global__ __launch_bounds__(256) void k_vox_stats(const float *__restrict__ grid, double *__restrict__ part, int64_t per_sample) {
-    __shared__ double s_red[4][4];
+    __shared__ double s_red[3][4];
     const float *g = grid + (size_t)blockIdx.y * per_sample;
     double cnt = 0.0, sum = 0.0, sq = 0.0, mx = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_sample; i += (int64_t)gridDim.x * 256) {
@@ -243,23 +170,17 @@ __global__ __launch_bounds__(256) void k_vox_stats(const float *__restrict__ gri
     const double r0 = block_sum_d<256>(cnt, s_red[0]);
     const double r1 = block_sum_d<256>(sum, s_red[1]);
     const double r2 = block_sum_d<256>(sq, s_red[2]);
-    // max via the same reduction shape
-    double m = mx;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
-    if ((threadIdx.x & 63) == 0) s_red[3][threadIdx.x >> 6] = m;
-    __syncthreads();
+    const double r3 = block_max_d<256>(mx, s_red[0]);
     if (threadIdx.x == 0) {
         double *p = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
-        p[0] = r0; p[1] = r1; p[2] = r2;
-        p[3] = fmax(fmax(s_red[3][0], s_red[3][1]), fmax(s_red[3][2], s_red[3][3]));
+        p[0] = r0; p[1] = r1; p[2] = r2; p[3] = r3;
     }
 }
 
 // one workgroup per sample: mean / std of the non-zero entries (unbiased std, torch.std) or max
 // (part: nblk partials per sample -- those of the strips, or of k_vox_stats)
 __global__ __launch_bounds__(256) void k_vox_finalize(const double *__restrict__ part, float *__restrict__ stat, int nblk, int norm) {
-    __shared__ double s_red[4][4];
+    __shared__ double s_red[3][4];
     const int b = blockIdx.x;
     double cnt = 0.0, sum = 0.0, sq = 0.0, mx = 0.0;
     for (int i = threadIdx.x; i < nblk; i += 256) {
@@ -269,13 +190,8 @@ __global__ __launch_bounds__(256) void k_vox_finalize(const double *__restrict__
     const double n = block_sum_d<256>(cnt, s_red[0]);
     const double s1 = block_sum_d<256>(sum, s_red[1]);
     const double s2 = block_sum_d<256>(sq, s_red[2]);
-    double m = mx;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_down(m, o, 64));
-    if ((threadIdx.x & 63) == 0) s_red[3][threadIdx.x >> 6] = m;
-    __syncthreads();
+    const double m = block_max_d<256>(mx, s_red[0]);
     if (threadIdx.x == 0) {
-        m = fmax(fmax(s_red[3][0], s_red[3][1]), fmax(s_red[3][2], s_red[3][3]));
         float sub = 0.f, mul = 1.f;
         if (norm == 1 && n > 0.0) {                      // utils.py:61-69
             const double mean = s1 / n;
@@ -416,7 +332,7 @@ static int vox_validate(const mpc_vox_shape *s) {
     return 0;
 }
 
-struct VoxHostLayout { VoxLayout L; int64_t off_count, off_rec, off_ovf, off_chunk, off_part, off_spart, off_stat, off_qhist, off_qstate, total; unsigned *qhist, *qstate; };
+struct VoxHostLayout { VoxLayout L; int64_t total; unsigned *qhist, *qstate; };
 
 static VoxHostLayout vox_layout(const mpc_vox_shape *s, void *ws) {
     VoxHostLayout h;
@@ -426,42 +342,16 @@ static VoxHostLayout vox_layout(const mpc_vox_shape *s, void *ws) {
     if (L.SR > s->H) L.SR = s->H;
     L.NS = mpc_cdiv(s->H, L.SR);
     L.SR = mpc_cdiv(s->H, L.NS);
-    L.NBk = s->B * s->C * L.NS;
-    int64_t cap = 4 * ((2 * (int64_t)s->N + (int64_t)s->C * L.NS - 1) / ((int64_t)s->C * L.NS));
-    if (cap < 4096) cap = 4096;
-    if (cap > 2 * (int64_t)s->N) cap = 2 * (int64_t)s->N;
-    L.cap = (int)(cap > 0 ? cap : 1);
     L.nstat_blocks = 256;
-    int64_t off = 0;
-    // spill region of a sample: every record it can produce (an event votes into two channels x up to two strips); chunk
-    // list of a sample: one descriptor per (binning workgroup, bucket it overflowed) -- a binning workgroup holds
-    // 256 * VOX_PER_THREAD events, i.e. at most that many x 4 records, in at most C * NS buckets
-    L.spcap = (int)(4 * (int64_t)s->N > 0 ? 4 * (int64_t)s->N : 1);
-    {
-        const int64_t wgs = mpc_cdiv(s->N > 0 ? s->N : 1, 256 * VOX_PER_THREAD);
-        const int64_t per_wg = (int64_t)s->C * L.NS < 256 * VOX_PER_THREAD * 4 ? (int64_t)s->C * L.NS : 256 * VOX_PER_THREAD * 4;
-        L.chcap = (int)(wgs * per_wg);
-    }
-    h.off_count = off; off += mpc_align((int64_t)(L.NBk + 2 * (s->B > 0 ? s->B : 1) + 8) * 4);
-    h.off_rec = off;   off += mpc_align((int64_t)L.NBk * L.cap * 16);
-    h.off_ovf = off;   off += mpc_align((int64_t)(s->B > 0 ? s->B : 1) * L.spcap * 16 + 16);
-    h.off_chunk = off; off += mpc_align((int64_t)(s->B > 0 ? s->B : 1) * L.chcap * 16 + 16);
-    h.off_part = off;  off += mpc_align((int64_t)(s->B > 0 ? s->B : 1) * L.nstat_blocks * 4 * 8);
-    h.off_spart = off; off += mpc_align((int64_t)(L.NBk > 0 ? L.NBk : 1) * 4 * 8);
-    h.off_stat = off;  off += mpc_align((int64_t)(s->B > 0 ? s->B : 1) * 4 * 4);
-    h.off_qhist = off; off += mpc_align((int64_t)(s->B > 0 ? s->B : 1) * VOX_QBINS * 4);
-    h.off_qstate = off; off += mpc_align((int64_t)(s->B > 0 ? s->B : 1) * 8 * 4);
+    const int64_t B1 = s->B > 0 ? s->B : 1;
+    // an event votes into two channels x up to two strips
+    int64_t off = sb_layout(L, s->B, s->N, (int64_t)s->C * L.NS, 4, 256 * VOX_PER_THREAD, ws);
+    L.part = sb_take<double>(ws, off, B1 * L.nstat_blocks * 4 * 8);
+    L.spart = sb_take<double>(ws, off, (int64_t)(L.NBk > 0 ? L.NBk : 1) * 4 * 8);
+    L.stat = sb_take<float>(ws, off, B1 * 4 * 4);
+    h.qhist = sb_take<unsigned>(ws, off, B1 * VOX_QBINS * 4);
+    h.qstate = sb_take<unsigned>(ws, off, B1 * 8 * 4);
     h.total = off;
-    char *w = (char *)ws;
-    L.gcount = (int *)(w + h.off_count);
-    L.rec = (float4 *)(w + h.off_rec);
-    L.ovf = (float4 *)(w + h.off_ovf);
-    L.chunk = (int4 *)(w + h.off_chunk);
-    L.part = (double *)(w + h.off_part);
-    L.spart = (double *)(w + h.off_spart);
-    L.stat = (float *)(w + h.off_stat);
-    h.qhist = (unsigned *)(w + h.off_qhist);
-    h.qstate = (unsigned *)(w + h.off_qstate);
     return h;
 }
 
@@ -481,16 +371,10 @@ extern "C" int mpc_voxel_grid(const mpc_vox_shape *s, const float *xytp, const i
     const VoxHostLayout h = vox_layout(s, ws);
     const VoxLayout &L = h.L;
     hipStream_t st = (hipStream_t)stream;
-    static mpc_device_once attr_once;   // raising the dynamic-LDS cap: idempotent, once per device
-    if (attr_once.need()) {
-        hipError_t e = hipFuncSetAttribute((const void *)k_vox_accum<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vox_accum<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_vox_accum<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
-        attr_once.mark();
-    }
-    const int e0 = mpc_zero_async(L.gcount, (size_t)(L.NBk + 2 * s->B + 8) * 4, st);
-    if (e0) return e0;
+    static mpc_device_once attr_once;
+    rc = sb_raise_lds_cap(attr_once, __func__, k_vox_accum<0>, k_vox_accum<1>, k_vox_accum<2>);
+    if (!rc) rc = sb_zero_counters(L, s->B, st);
+    if (rc) return rc;
     if (s->N > 0) {
         const int nblk = mpc_cdiv(s->N, 256 * VOX_PER_THREAD) * s->B;
         MPC_LAUNCH(k_vox_bin, dim3(((nblk + 7) / 8) * 8), dim3(256), (size_t)s->C * L.NS * 3 * sizeof(int), st,

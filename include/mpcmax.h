@@ -397,6 +397,31 @@ int mpc_curve_traj_fwd(const float *params, const float *basis, const float *pos
 int mpc_curve_traj_bwd(const float *grad_traj, const float *basis, float scale, float *grad_params,
                        int32_t B, int32_t d, int32_t T, int32_t n, void *stream);
 
+/* ---- the RAFT-spline output head: control points on the 1/8 grid + convex-upsampling mask -> `trajectories` / dense flows.
+ * Reference: src/models/raft_spline/curves/base.py:35-38 (create_upsampled), src/models/raft_spline/utils.py:30-45 (cvx_upsample:
+ * softmax over the 9 neighbours, F.unfold's row-major 3 x 3 order, zero padding, the factor 8 of the change in resolution),
+ * base.py:95-123 + bezier.py:92-113 (get_flow_from_reference), src/modules/raft_spline.py:122-154 (the flows validation evaluates).
+ *   params [B][2][d][h][w]   control points 1..d on the 1/8 grid, channel 0 = x, channel 1 = y
+ *   mask   [B][576][h][w]    logits, channel = k * 64 + sy * 8 + sx (k: neighbour, (sy, sx): position inside the 8 x 8 cell)
+ *   basis  [T][d]            as for mpc_curve_traj_fwd
+ *   up[c] at pixel (y, x) = sum_k softmax_k(mask[k][y % 8][x % 8][y / 8][x / 8]) * 8 * P0[c][y / 8 + k / 3 - 1][x / 8 + k % 3 - 1]
+ *   traj   [B][T][n][2]      (out)  (y, x) = tile centre + scale * sum_j basis[t][j] * (up.y[j], up.x[j]) at the tile centres
+ *                            (iy * tile + tile / 2, ix * tile + tile / 2) of the 8h x 8w image in row-major order (computed by the
+ *                            kernel; src/utils/trajectories.py:3-13), n = their count
+ *   flows  [T][B][2][8h][8w] (out)  scale * sum_j basis[t][j] * up[j] at every pixel, (x, y) order (forward only)
+ * mpc_cvx_traj_bwd: the adjoint applied to grad_traj [B][T][n][2]: grad_params [B][2d][h][w] and the DENSE grad_mask [B][576][h][w]
+ * (every element written, 0 off the channels the tile centres read), either may be NULL and is then not computed; gather form, no
+ * float atomics: bitwise reproducible.  ws: mpc_cvx_traj_bwd_workspace_bytes() bytes, needed (non-NULL) only with grad_params.
+ * Limits: d <= 16, T * d * 4 <= 48 KB (else MPC_E_UNSUPPORTED); tile >= 1.  B = 0 or an empty grid launches nothing.  */
+int mpc_cvx_traj_fwd(const float *params, const float *mask, const float *basis, float scale, float *traj,
+                     int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile, void *stream);
+int64_t mpc_cvx_traj_bwd_workspace_bytes(int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile);
+int mpc_cvx_traj_bwd(const float *grad_traj, const float *params, const float *mask, const float *basis, float scale,
+                     float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile,
+                     void *ws, void *stream);
+int mpc_cvx_flow_fwd(const float *params, const float *mask, const float *basis, float scale, float *flows,
+                     int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream);
+
 /* ---- row A3 of SURVEY.md 8(a): the network's coefficient grid -> `trajectories` for the loss, and back.
  * Reference: src/modules/trajectory_net.py:57-119 (compute_basis, calculate_coords, calculate_trajectories_at_t: the reference's
  * TrajectoryNet.step, :142-161), src/utils/trajectories.py:3-52 (tile mask, coeffs_grid_to_list), src/utils/basis.py:4-46.

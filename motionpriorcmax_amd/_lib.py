@@ -37,7 +37,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_ingest_ordered_workspace_bytes', 'mpc_ingest_scatter_ordered', 'mpc_pool2_fwd', 'mpc_pool2_bwd_add', 'mpc_event_pos_grad', 'mpc_pe_warp', 'mpc_pe_grad', 'mpc_pe_grad_ordered', 'mpc_pe_grad_ordered_supported', 'mpc_bounds_check', 'mpc_curve_traj_fwd', 'mpc_curve_traj_bwd',
            'mpc_pe_tile_rows', 'mpc_pe_tile_rows_bwd', 'mpc_pe_basis_field', 'mpc_pe_rows_grad_finish',
            'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd',
-           'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm']
+           'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm',
+           'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd']
 
 
 class Shape(ctypes.Structure):
@@ -163,6 +164,11 @@ def lib():
     L.mpc_repr_norm_workspace_bytes.argtypes = [i32]
     L.mpc_repr_norm_workspace_bytes.restype = i64
     L.mpc_repr_norm.argtypes = [vp, i32, i64, vp, vp]
+    L.mpc_cvx_traj_fwd.argtypes = [vp, vp, vp, f32, vp] + [i32] * 6 + [vp]
+    L.mpc_cvx_traj_bwd_workspace_bytes.argtypes = [i32] * 6
+    L.mpc_cvx_traj_bwd_workspace_bytes.restype = i64
+    L.mpc_cvx_traj_bwd.argtypes = [vp, vp, vp, vp, f32, vp, vp] + [i32] * 6 + [vp, vp]
+    L.mpc_cvx_flow_fwd.argtypes = [vp, vp, vp, f32, vp] + [i32] * 5 + [vp]
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

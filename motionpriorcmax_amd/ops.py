@@ -1166,6 +1166,67 @@ class CurveTrajFn(torch.autograd.Function):
         return gp, None, None, None
 
 
+class CvxCurveTrajFn(torch.autograd.Function):
+    """The RAFT-spline output head -> `trajectories`: control points on the 1/8 grid params [B, 2d, h, w] ((x, y) channel order) and
+    the convex-upsampling logits up_mask [B, 576, h, w] (reference raft_spline/utils.py:30-45 cvx_upsample, curves/base.py:35-38,
+    95-123) with basis [T, d] on the device -> [B, T, n, 2] at the tile centres of the 8h x 8w image, one kernel forward and two
+    backward (csrc/cvx_curves.hip) instead of the softmax / unfold / [B, 2d, 9, 8, 8, h, w] product / sum / permute chain.  The
+    backward computes only the gradients autograd asks for: without a mask gradient the dense [B, 576, h, w] tensor is neither
+    allocated nor filled.  No host synchronisation either way."""
+
+    @staticmethod
+    def forward(ctx, params, up_mask, basis, scale: float, tile: int):
+        _require_gpu(params, 'params')
+        _require_gpu(up_mask, 'up_mask')
+        B, c2, h, w = params.shape
+        d, T, tile = c2 // 2, basis.shape[0], int(tile)
+        dev = params.device
+        p = _f32c(params.detach())
+        m = _f32c(up_mask.detach())
+        bm = _f32c(basis.detach())
+        s = tile // 2
+        nty, ntx = ((v - s + tile - 1) // tile if v > s else 0 for v in (8 * h, 8 * w))          # (the count of the tile mask's centres)
+        n = nty * ntx
+        traj = torch.empty((B, T, n, 2), dtype=torch.float32, device=dev)
+        C.check(C.lib().mpc_cvx_traj_fwd(_ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile, _stream(dev)), 'mpc_cvx_traj_fwd')
+        ctx.save_for_backward(p, m, bm)
+        ctx.dims = (B, d, T, h, w, tile, float(scale))
+        return traj
+
+    @staticmethod
+    def backward(ctx, g):
+        p, m, bm = ctx.saved_tensors
+        B, d, T, h, w, tile, scale = ctx.dims
+        g = _f32c(g)
+        dev = g.device
+        gp = gm = ws = None
+        if ctx.needs_input_grad[0]:
+            gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
+            nws = int(C.lib().mpc_cvx_traj_bwd_workspace_bytes(B, d, T, h, w, tile))
+            if nws < 0:
+                C.check(nws, 'mpc_cvx_traj_bwd_workspace_bytes')
+            ws = torch.empty(max(nws, 4) // 4, dtype=torch.float32, device=dev)
+        if ctx.needs_input_grad[1]:
+            gm = torch.empty((B, 576, h, w), dtype=torch.float32, device=dev)          # (every element is written by the kernel)
+        if gp is not None or gm is not None:
+            C.check(C.lib().mpc_cvx_traj_bwd(_ptr(g), _ptr(p), _ptr(m), _ptr(bm), scale, _ptr(gp), _ptr(gm), B, d, T, h, w, tile,
+                                             _ptr(ws), _stream(dev)), 'mpc_cvx_traj_bwd')
+        return gp, gm, None, None, None
+
+
+def cvx_flows(params, up_mask, basis, scale: float):
+    """Dense flows of the upsampled curves [T, B, 2, 8h, 8w] ((x, y) order; reference: create_upsampled(mask).get_flow_from_reference
+    (times) stacked): one kernel, forward only (csrc/cvx_curves.hip: mpc_cvx_flow_fwd)."""
+    _require_gpu(params, 'params')
+    _require_gpu(up_mask, 'up_mask')
+    B, c2, h, w = params.shape
+    d, T, dev = c2 // 2, basis.shape[0], params.device
+    flows = torch.empty((T, B, 2, 8 * h, 8 * w), dtype=torch.float32, device=dev)
+    p, m, bm = _f32c(params.detach()), _f32c(up_mask.detach()), _f32c(basis.detach())
+    C.check(C.lib().mpc_cvx_flow_fwd(_ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(flows), B, d, T, h, w, _stream(dev)), 'mpc_cvx_flow_fwd')
+    return flows
+
+
 class GridTrajFn(torch.autograd.Function):
     """The network's coefficient grid [B, S, 2k, H, W] -> `trajectories` [B, n_t, n, 2] (y, x) at the tile centres (row A3 of SURVEY.md
     8(a): reference trajectory_net.py:57-119): one kernel forward, one backward (two when `dphi` needs a gradient), csrc/grid_traj.hip,

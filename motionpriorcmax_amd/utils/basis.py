@@ -118,6 +118,77 @@ def _curve_trajectories(params, bm, tile_size, H, W, scale):
     return disp + pos_dev[None, None], pos
 
 
+def _cvx_upsample(params, up_mask):
+    """The convex upsampling of reference src/models/raft_spline/utils.py:30-45 written from its formula (a softmax over the nine
+    neighbours, a zero pad, nine shifted multiply-adds in F.unfold's row-major order, the factor 8 inside):
+    params [B, C, h, w], up_mask [B, 576, h, w] (channel = k * 64 + sy * 8 + sx) -> [B, C, 8h, 8w]."""
+    B, C, h, w = params.shape
+    wts = torch.softmax(up_mask.reshape(B, 9, 8, 8, h, w), dim=1)
+    p8 = torch.nn.functional.pad(8 * params, (1, 1, 1, 1))
+    up = None
+    for k in range(9):
+        dy, dx = k // 3, k % 3
+        term = wts[:, None, k] * p8[:, :, None, None, dy:dy + h, dx:dx + w]            # [B, C, 8, 8, h, w]
+        up = term if up is None else up + term
+    return up.permute(0, 1, 4, 2, 5, 3).reshape(B, C, 8 * h, 8 * w)
+
+
+_CVX_KERNEL_TILES = (2, 4, 8, 16)
+
+
+def _cvx_kernels_serve(params, up_mask, bm):
+    """The routing rule of `_curve_trajectories`: the kernels take fp32 GPU tensors with d <= 16 and a basis matrix within their
+    48 KB LDS slice; everything else (CPU tensors, other dtypes, d > 16, more times) runs in plain torch."""
+    return (params.is_cuda and up_mask.is_cuda and params.dtype == torch.float32 and up_mask.dtype == torch.float32
+            and params.shape[1] // 2 <= 16 and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024)
+
+
+def _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale):
+    """Plain torch: the upsampled control points at the tile centres, then the curve product of `_curve_trajectories`."""
+    B, c2, h, w = params.shape
+    d = c2 // 2
+    idx = pos_dev.long()
+    up = _cvx_upsample(params, up_mask)[:, :, idx[:, 0], idx[:, 1]]                     # [B, 2d, n]
+    flow = torch.einsum('bcdn,td->btcn', up.reshape(B, 2, d, -1), bm) * scale           # [B, n_t, (x, y), n]
+    disp = torch.stack((flow[:, :, 1], flow[:, :, 0]), dim=-1)
+    return disp + pos_dev[None, None]
+
+
+def _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale):
+    """`_curve_trajectories` for control points on the 1/8 grid with their convex-upsampling mask (the RAFT-spline output head):
+    on the GPU ops.CvxCurveTrajFn (csrc/cvx_curves.hip; tile sizes 2, 4, 8, 16), else the plain-torch mirror."""
+    B, c2, h, w = params.shape
+    if up_mask.dim() != 4 or tuple(up_mask.shape) != (B, 576, h, w):
+        raise ValueError(f'up_mask must be [B, 576, h, w] = {(B, 576, h, w)}, got {tuple(up_mask.shape)}')
+    if (H, W) != (8 * h, 8 * w):
+        raise ValueError(f'with up_mask, image_shape must be 8 x the grid of params: {(8 * h, 8 * w)}, got {(H, W)}')
+    pos, pos_dev = _tile_positions(H, W, tile_size, params.device, params.dtype)
+    if _cvx_kernels_serve(params, up_mask, bm) and tile_size in _CVX_KERNEL_TILES:
+        from .. import ops
+        return ops.CvxCurveTrajFn.apply(params, up_mask, bm, float(scale), int(tile_size)), pos
+    return _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale), pos
+
+
+def flows_from_bezier(params, times, up_mask=None, scale=1.0):
+    """The dense flows of Bezier curves at `times`, [n_t, B, 2, H, W] in (x, y) order: with `up_mask` [B, 576, h, w] what the
+    reference's `curve.create_upsampled(mask).get_flow_from_reference(times)` returns (curves/base.py:35-38, 95-123; evaluated per
+    timestamp by src/modules/raft_spline.py:122-154) times `scale`, H x W = 8h x 8w; without it the flows of `params` on their own
+    grid.  One kernel on the GPU (ops.cvx_flows) when nothing requires grad; plain torch (differentiable) otherwise."""
+    B, c2, h, w = params.shape
+    assert c2 % 2 == 0, params.shape
+    d = c2 // 2
+    bm = _device_basis('bernstein', times, (int(d),), params.device, params.dtype)    # [n_t, d]
+    if up_mask is not None:
+        if up_mask.dim() != 4 or tuple(up_mask.shape) != (B, 576, h, w):
+            raise ValueError(f'up_mask must be [B, 576, h, w] = {(B, 576, h, w)}, got {tuple(up_mask.shape)}')
+        needs_grad = torch.is_grad_enabled() and (params.requires_grad or up_mask.requires_grad)
+        if not needs_grad and _cvx_kernels_serve(params, up_mask, bm):
+            from .. import ops
+            return ops.cvx_flows(params, up_mask, bm, float(scale))
+        params = _cvx_upsample(params, up_mask)
+    return torch.einsum('bcdhw,td->tbchw', params.reshape(B, 2, d, *params.shape[-2:]), bm) * scale
+
+
 def bernstein_basis(times, degree):
     """[n_t] -> [n_t, degree]: C(d,i) (1-t)^(d-i) t^i for i = 1..d (P0 == 0), float64 then fp32.  (The caller's own copy: the cached
     matrix is shared by every later step.)"""
@@ -133,7 +204,7 @@ def _bernstein_basis_eval(times, degree):
     return torch.from_numpy(out).float()
 
 
-def trajectories_from_bezier(params, times, tile_size, image_shape, scale=1.0):
+def trajectories_from_bezier(params, times, tile_size, image_shape, scale=1.0, up_mask=None):
     """RAFT-spline adapter: sample Bezier flow curves at the tile centres as `trajectories`
     for `FocusLoss.calc`.
 
@@ -143,13 +214,19 @@ def trajectories_from_bezier(params, times, tile_size, image_shape, scale=1.0):
     anchor t = 0.  Returns (trajectories [B, n_t, n, 2] in (y, x) pixel coordinates, pixel_positions [n, 2]) with
     the tile centres of `get_optical_flow_tile_mask` as start points -- the layout `calc` expects
     (focus.py:66-72); `pixel_positions` is a cached tensor shared by all calls: do not modify it in place.  `scale` multiplies the flow (8.0 if the curve lives on RAFT's 1/8 grid units).
-    Differentiable w.r.t. `params` (plain torch: 2*d*n_t multiply-adds per tile)."""
-    from .trajectories import get_optical_flow_tile_mask
+    Differentiable w.r.t. `params` (plain torch: 2*d*n_t multiply-adds per tile).
+
+    With `up_mask` [B, 576, h, w] (the RAFT-spline output head: reference curves/base.py:35-38, raft_spline/utils.py:30-45) `params`
+    are the control points on the 1/8 grid, `image_shape` must be (8h, 8w) (ValueError otherwise), and the curves are those of
+    `BezierCurves(params).create_upsampled(up_mask)` sampled at the tile centres: the factor 8 of cvx_upsample is applied inside,
+    `scale` multiplies on top.  Differentiable w.r.t. `params` and `up_mask`."""
     B, c2, h, w = params.shape
     H, W = (int(v) for v in image_shape)
-    assert c2 % 2 == 0 and h == H // tile_size and w == W // tile_size, (params.shape, image_shape, tile_size)
+    assert c2 % 2 == 0 and (up_mask is not None or (h == H // tile_size and w == W // tile_size)), (params.shape, image_shape, tile_size)
     d = c2 // 2
     bm = _device_basis('bernstein', times, (int(d),), params.device, params.dtype)    # [n_t, d]
+    if up_mask is not None:
+        return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale)
     return _curve_trajectories(params, bm, tile_size, H, W, scale)
 
 
@@ -187,13 +264,14 @@ def _bspline_basis_eval(times, num_ctrl, degree=3):
     return torch.from_numpy(N[:, 1:m]).float()
 
 
-def trajectories_from_bspline(params, times, tile_size, image_shape, scale=1.0, degree=3):
-    """As trajectories_from_bezier, for a clamped uniform B-spline flow curve (cubic by default) with control points
-    P_1 .. P_{m-1} = params [B, 2*(m-1), h, w] ((x, y) channel order) and P_0 = 0.  UNPINNED EXTENSION (see bspline_basis)."""
-    from .trajectories import get_optical_flow_tile_mask
+def trajectories_from_bspline(params, times, tile_size, image_shape, scale=1.0, degree=3, up_mask=None):
+    """As trajectories_from_bezier (`up_mask` included), for a clamped uniform B-spline flow curve (cubic by default) with control
+    points P_1 .. P_{m-1} = params [B, 2*(m-1), h, w] ((x, y) channel order) and P_0 = 0.  UNPINNED EXTENSION (see bspline_basis)."""
     B, c2, h, w = params.shape
     H, W = (int(v) for v in image_shape)
-    assert c2 % 2 == 0 and h == H // tile_size and w == W // tile_size, (params.shape, image_shape, tile_size)
+    assert c2 % 2 == 0 and (up_mask is not None or (h == H // tile_size and w == W // tile_size)), (params.shape, image_shape, tile_size)
     d = c2 // 2
     bm = _device_basis('bspline', times, (int(d + 1), int(degree)), params.device, params.dtype)      # [n_t, d]
+    if up_mask is not None:
+        return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale)
     return _curve_trajectories(params, bm, tile_size, H, W, scale)

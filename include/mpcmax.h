@@ -362,6 +362,46 @@ int mpc_ingest_scatter_ordered(const mpc_ingest_shape *s, const mpc_shape *loss,
                                const int64_t *t_us, const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg,
                                float *events, int32_t *offsets, float *xytp, void *ws, void *ws_order, void *stream);
 
+/* ---- event ingest for the EVIMO2 and MultiFlow configurations: the raw window -> the same `events` tensor, without the in-image
+ * filter of the DSEC loader.  x, y [B][N] int32 (xy_int = 1) or fp32; p [B][N] int64 (p_int64 = 1) or fp32, in {0, 1} (for EVIMO2
+ * the flipped polarity 1 - p of datasubset.py:154); t_us [B][N] int64, NON-DECREASING within a sample; counts [B] int32 (device;
+ * rows beyond counts[b] are ignored).  The same padded arrays mpc_repr_grid takes.
+ *   time_mode = MPC_WINDOW_TIME_FP32_SUFFIX: reference src/loader/evimo2/datasubset.py:206-215, whose arithmetic is FLOAT32 from
+ *     the first subtraction on (f32() = round to nearest, n = counts[b]):
+ *       ts_start = f32(t[n-1]) - duration_us          duration_us = f32(flow_duration_ms * 1e3), rounded by the caller
+ *       kept     : f32(t[i]) > ts_start               (strict; a suffix of the window)
+ *       t_i      = (f32(t[i]) - ts_start) / (f32(t[n-1]) - ts_start)          correctly rounded fp32 quotient
+ *       bin_i    = max(#{k : edges[k] < t_i} - 1, 0)  edges [nb + 1] fp32 (device): the values of torch.linspace(0, 1, nb + 1) as
+ *                                                     computed on the CPU (datasubset.py:77), handed in by the caller
+ *   time_mode = MPC_WINDOW_TIME_MINMAX64: reference src/loader/multiflow/sample.py:224-236 -- (t - min) / (max - min) in float64
+ *     over all counts[b] events, the float64 edges of np.linspace (as mpc_ingest_scatter), cast to fp32 last; edges is not read.
+ *   row = (y * y_scale, x * x_scale, t, p, bin, 1) in fp32.  The scales (one fp32 multiply each; 1 = coordinates as they are) are
+ *     UNPINNED: the reference hands X_SCALE / Y_SCALE along (datasubset.py:227-228) but ships no code that applies them.
+ *   split = 1 (polarity_aware_batching; datasubset.py:217-221, multiflow/datasubset.py:149-154, src/modules/data_loading.py:14-47):
+ *     rows with p == 1, zero padded to the batch maximum max_pos, then rows with p == 0 padded to max_neg; input order inside
+ *     each block.  split = 0 (data_loading.py:35-37): one block of max_pos rows, max_neg = 0, p is copied and not looked at.
+ *   counts[b] == 0 gives zero rows (the EVIMO2 reference raises on ts[-1]).
+ * mpc_ingest_window_count   -> out_max[2] (device) = max_pos, max_neg: the caller reads them to size events [B][max_pos + max_neg][6]
+ * mpc_ingest_window_scatter -> events, every element written.  ws: mpc_ingest_window_workspace_bytes(s) bytes, unchanged between
+ * the two calls.  Kernels only, on `stream`.  MPC_E_UNSUPPORTED: nb + 1 > 4096 in the fp32 mode (the edges live in LDS). */
+#define MPC_WINDOW_TIME_FP32_SUFFIX 0
+#define MPC_WINDOW_TIME_MINMAX64 1
+typedef struct mpc_window_shape {
+    int32_t B, N, nb;
+    int32_t time_mode;          /* MPC_WINDOW_TIME_* */
+    int32_t xy_int;             /* x, y: 1 = int32, 0 = fp32 */
+    int32_t p_int64;            /* p: 1 = int64, 0 = fp32 */
+    int32_t split;              /* 1 = positive block then negative block, 0 = one block */
+    float duration_us;          /* fp32 mode only */
+    float x_scale, y_scale;
+} mpc_window_shape;
+int64_t mpc_ingest_window_workspace_bytes(const mpc_window_shape *s);
+int mpc_ingest_window_count(const mpc_window_shape *s, const int64_t *t_us, const void *p, const int32_t *counts,
+                            int32_t *out_max, void *ws, void *stream);
+int mpc_ingest_window_scatter(const mpc_window_shape *s, const void *x, const void *y, const int64_t *t_us, const void *p,
+                              const int32_t *counts, const float *edges, int32_t max_pos, int32_t max_neg, float *events,
+                              void *ws, void *stream);
+
 /* ---- next row: dense flow from tile trajectories and flow error metrics.
  * mpc_dense_flow = reference src/utils/flow.py:12-16 (dense_flow_from_traj): list_to_grid
  *   (src/utils/trajectories.py:54-76) at pixel_positions // patch, then the anti-aliased bicubic resize

@@ -38,7 +38,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_pe_tile_rows', 'mpc_pe_tile_rows_bwd', 'mpc_pe_basis_field', 'mpc_pe_rows_grad_finish',
            'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd',
            'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm',
-           'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd']
+           'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd',
+           'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter']
 
 
 class Shape(ctypes.Structure):
@@ -64,6 +65,14 @@ class ReprShape(ctypes.Structure):
 
 class IngestShape(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ('B', 'N', 'H', 'W', 'nb')]
+
+
+WINDOW_TIME_FP32_SUFFIX, WINDOW_TIME_MINMAX64 = 0, 1        # include/mpcmax.h
+
+
+class WindowShape(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ('B', 'N', 'nb', 'time_mode', 'xy_int', 'p_int64', 'split')] + \
+               [(k, ctypes.c_float) for k in ('duration_us', 'x_scale', 'y_scale')]
 
 
 class FlowShape(ctypes.Structure):
@@ -169,6 +178,11 @@ def lib():
     L.mpc_cvx_traj_bwd_workspace_bytes.restype = i64
     L.mpc_cvx_traj_bwd.argtypes = [vp, vp, vp, vp, f32, vp, vp] + [i32] * 6 + [vp, vp]
     L.mpc_cvx_flow_fwd.argtypes = [vp, vp, vp, f32, vp] + [i32] * 5 + [vp]
+    wsp = ctypes.POINTER(WindowShape)
+    L.mpc_ingest_window_workspace_bytes.argtypes = [wsp]
+    L.mpc_ingest_window_workspace_bytes.restype = i64
+    L.mpc_ingest_window_count.argtypes = [wsp, vp, vp, vp, vp, vp, vp]
+    L.mpc_ingest_window_scatter.argtypes = [wsp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

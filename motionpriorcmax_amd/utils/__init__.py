@@ -2,7 +2,7 @@ from .trajectories import get_optical_flow_tile_mask, coeffs_grid_to_list  # noq
 from .basis import compute_basis, basis_values, bernstein_basis, trajectories_from_bezier, bspline_basis, trajectories_from_bspline, flows_from_bezier  # noqa: F401
 from .event_image_converter import EventImageConverter  # noqa: F401
 from .voxel_grid import VoxelGrid, voxel_grids  # noqa: F401
-from .ingest import ingest_events  # noqa: F401
+from .ingest import ingest_events, ingest_raw_events  # noqa: F401
 from .flow import dense_flow_from_traj, calculate_flow_error, ErrorCalculatorFactory, OpticalFlowError  # noqa: F401
 from .grid_traj import trajectories_from_grid, flow_from_grid  # noqa: F401
 from . import representation  # noqa: F401  (representation.VoxelGrid is the EVIMO2 / MultiFlow class; VoxelGrid above is the DSEC one)

@@ -1,6 +1,8 @@
 """Event ingest on the GPU: raw windows -> the padded [B, M, 6] event tensor and
 `num_pos_events` that `FocusLoss.calc` consumes, and (optionally) the (x, y, t, p) rows for the
-voxel-grid builder.  Mirrors reference src/loader/dsec/loader.py:152-167 + 360-415; numerics in
+voxel-grid builder.  `ingest_events` mirrors reference src/loader/dsec/loader.py:152-167 + 360-415,
+`ingest_raw_events` the EVIMO2 and MultiFlow loaders (src/loader/evimo2/datasubset.py:206-228,
+src/loader/multiflow/sample.py:224-236) with the collate of src/modules/data_loading.py:14-47; numerics in
 libmpcmax.so (csrc/ingest.hip)."""
 import ctypes
 
@@ -54,4 +56,95 @@ def ingest_events(x, y, t_us, p, counts, image_shape, num_bins, want_voxel_input
         C.check(C.lib().mpc_ingest_scatter(ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt),
                                            max_pos, max_neg, _ptr(events), _ptr(xytp), _ptr(ws), st), 'mpc_ingest_scatter')
     out = {'events': events, 'num_pos_events': max_pos, 'xytp': xytp}
+    return out if order_for is None else order_for.order_events(out)
+
+
+_EDGES = {}          # (device, num_bins) -> the fp32 bin edges of the EVIMO2 loader on that device
+
+
+def _window_edges(dev, num_bins):
+    """torch.linspace(0, 1, num_bins + 1) as the CPU computes it (datasubset.py:77), uploaded once per (device, num_bins)."""
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device(), int(num_bins))
+    e = _EDGES.get(key)
+    if e is None:
+        e = _EDGES[key] = torch.linspace(0, 1, int(num_bins) + 1, dtype=torch.float32, device='cpu').to(dev)
+    return e
+
+
+def _c(t, dtype=None):
+    t = t if dtype is None or t.dtype == dtype else t.to(dtype)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def ingest_raw_events(x, y, t_us, p, counts, num_bins, dataset, *, flow_duration_ms=None, polarity_aware_batching=True,
+                      xy_scale=None, order_for=None):
+    """The loss events of the EVIMO2 / MultiFlow configurations from the padded raw window `representation_grids` takes.
+
+    x, y, p: [B, N]; t_us: [B, N] int64, NON-DECREASING per sample; counts: [B] valid lengths.  x / y are read as int32 or fp32
+    and p as fp32 or int64 without a conversion pass; other dtypes are converted with torch on the device first.  p is in
+    {0, 1}; for EVIMO2 it is the flipped polarity `1 - p` of datasubset.py:154.
+    dataset='evimo2' (flow_duration_ms required): datasubset.py:206-215.  The reference cuts the window, normalises time and
+        bins in FLOAT32 (`ts[-1] - flow_duration * 1e3` promotes to fp32, where one ulp of a microsecond stamp is 4 to 16 us);
+        the kernels restate that chain operation by operation, with the bin edges of torch.linspace as the CPU computes them
+        (cached on the device per (device, num_bins)).  Events with fp32(t) <= fp32(t_last) - fp32(flow_duration_ms * 1e3) are
+        dropped.  A sample with counts[b] == 0 gives zero rows (the reference raises on `ts[-1]`).
+    dataset='multiflow' (flow_duration_ms rejected): sample.py:224-236 -- (t - min) / (max - min) in float64 over the
+        window's counts[b] events, np.linspace edges, cast to fp32 last; the caller cuts the window (sample.py:156-170).
+    Neither has an in-image filter.  polarity_aware_batching=True: rows with p == 1, zero padded to the batch maximum, then
+    rows with p == 0 (data_loading.py:38-43), `num_pos_events` = the positive maximum; False: one block per sample in input
+    order and `num_pos_events` = -1, as the reference's collate returns.
+    xy_scale=(x_scale, y_scale): column 0 is y * fp32(y_scale) and column 1 x * fp32(x_scale), one fp32 multiply each when the
+        row is written (EVIMO2's X_SCALE / Y_SCALE = 0.8).  UNPINNED: the reference hands the two scales along
+        (datasubset.py:227-228) but ships no code that applies them.  None leaves the coordinates as they are.
+    order_for: a FocusLoss -- the result goes through its `order_events` (a second pass over the tensor) and carries
+        'event_offsets'.
+    Returns {'events': [B, M, 6] float32, 'num_pos_events': int}.  One host round trip (two integers) sizes the output."""
+    if dataset not in ('evimo2', 'multiflow'):
+        raise ValueError(f"dataset must be 'evimo2' or 'multiflow', got {dataset!r}")
+    if dataset == 'evimo2':
+        if flow_duration_ms is None:
+            raise ValueError("dataset='evimo2' needs flow_duration_ms (EVIMO2_Datasubset's flow_time)")
+        if not float(flow_duration_ms) >= 0:
+            raise ValueError(f'flow_duration_ms must not be negative, got {flow_duration_ms}')
+    elif flow_duration_ms is not None:
+        raise ValueError("dataset='multiflow' takes no flow_duration_ms: the caller cuts the window (sample.py:156-170)")
+    for name, t in (('x', x), ('y', y), ('t_us', t_us), ('p', p)):
+        _require_gpu(t, name)
+    if not (x.shape == y.shape == p.shape == t_us.shape) or x.ndim != 2:
+        raise ValueError(f'x, y, t_us, p must share one [B, N] shape (got {tuple(x.shape)}, {tuple(y.shape)}, '
+                         f'{tuple(t_us.shape)}, {tuple(p.shape)})')
+    dev = x.device
+    B, N = x.shape
+    if counts.ndim != 1 or counts.shape[0] != B:
+        raise ValueError(f'counts must be [B] = [{B}], got {tuple(counts.shape)}')
+    xy_int = x.dtype == torch.int32 and y.dtype == torch.int32
+    if xy_int:
+        x, y = _c(x), _c(y)
+    else:
+        x, y = _c(x, torch.float32), _c(y, torch.float32)
+    p_int64 = p.dtype == torch.int64
+    p = _c(p) if p_int64 else _c(p, torch.float32)
+    t_us = _c(t_us, torch.int64)
+    cnt = _c(counts.to(dev), torch.int32)
+    xs, ys = (1.0, 1.0) if xy_scale is None else (float(xy_scale[0]), float(xy_scale[1]))
+    evimo2 = dataset == 'evimo2'
+    shape = C.WindowShape(B=B, N=N, nb=int(num_bins), time_mode=C.WINDOW_TIME_FP32_SUFFIX if evimo2 else C.WINDOW_TIME_MINMAX64,
+                          xy_int=int(xy_int), p_int64=int(p_int64), split=int(bool(polarity_aware_batching)),
+                          duration_us=float(flow_duration_ms) * 1e3 if evimo2 else 0.0, x_scale=xs, y_scale=ys)
+    nbytes = C.lib().mpc_ingest_window_workspace_bytes(ctypes.byref(shape))
+    if nbytes < 0:
+        C.check(int(nbytes), 'mpc_ingest_window_workspace_bytes')
+    edges = _window_edges(dev, num_bins) if evimo2 else None
+    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    out_max = torch.empty(2, dtype=torch.int32, device=dev)
+    st = _stream(dev)
+    with _stage('mpc_ingest_window_count', dev):
+        C.check(C.lib().mpc_ingest_window_count(ctypes.byref(shape), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(out_max), _ptr(ws), st),
+                'mpc_ingest_window_count')
+    max_pos, max_neg = (int(v) for v in out_max.tolist())          # the collate's host decision
+    events = torch.empty((B, max_pos + max_neg, 6), dtype=torch.float32, device=dev)
+    with _stage('mpc_ingest_window_scatter', dev):
+        C.check(C.lib().mpc_ingest_window_scatter(ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(edges),
+                                                  max_pos, max_neg, _ptr(events), _ptr(ws), st), 'mpc_ingest_window_scatter')
+    out = {'events': events, 'num_pos_events': max_pos if polarity_aware_batching else -1}
     return out if order_for is None else order_for.order_events(out)

@@ -211,8 +211,12 @@ int32_t mpc_pe_grad_ordered_supported(const mpc_shape *s, int32_t k);
  * dozen torch operators -- the per-event step was bound by the host).
  *   mpc_pe_tile_rows      coef_rows [B*hq*wq][c2] = sum over the S scales of grid [B][S][c2][H][W] at the tile centres
  *                         (y, x) = (iy * tile + tile / 2, ix * tile + tile / 2): get_optical_flow_tile_mask + coeffs_grid_to_list,
- *                         src/utils/trajectories.py:3-52, scales summed as compute_basis does (basis.py:29-31); hq = ceil(H / tile)
- *   mpc_pe_tile_rows_bwd  its adjoint: EVERY element of grad_grid [B][S][c2][H][W] is written (0 off the tile centres)
+ *                         src/utils/trajectories.py:3-52, scales summed as compute_basis does (basis.py:29-31); hq = ceil(H / tile).
+ *                         A tile without a centre -- 0 < H % tile <= tile / 2: the centre of the last row of cells lies outside the
+ *                         image (W and the last column likewise) -- gets ZERO coefficients: its events are not warped and it enters
+ *                         the smoothness field with zero flow
+ *   mpc_pe_tile_rows_bwd  its adjoint: EVERY element of grad_grid [B][S][c2][H][W] is written (0 off the tile centres; the gradient
+ *                         of a tile without a centre goes nowhere)
  *   mpc_pe_basis_field    field [B*nb][G][2] = sum_j coef_rows[(b, cell)][d][j] * phim[t][j] -- the flow from the bin mid-times to
  *                         t_ref per tile, the field the smoothness term takes (mpc_lut_smooth: nimg = B * nb, C = 2); k <= 8, nb <= 64
  *   mpc_pe_rows_grad_finish  grad_coef_rows [B*G][2][k] = sum over the `split` partial results of mpc_pe_grad_ordered (split = 1: of

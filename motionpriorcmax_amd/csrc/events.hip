@@ -895,6 +895,12 @@ __global__ __launch_bounds__(256) void k_pe_grad(const mpc_shape s, const float 
 //               [cell][2][k] accumulators in LDS -- 64-bit fixed point like k_lut_accum: integer sums, bitwise reproducible -- and
 //               writes every cell of the strip once (global float atomics ran at ~20 G/s on this chip: 0.83 ms for the 17 M of a C3 step)
 #define PE_NT 1024
+// Q33.30 of one phi * gradient product, rounded to NEAREST: at most 2^-31 per row added, and no bias (with small event weights a
+// product is a few units of 2^-30, and a conversion that truncates towards zero shrinks every sum by half a unit per row)
+__device__ __forceinline__ long long pe_to_fixed(float v) {         // |v| < 2^31
+    const float hi = truncf(v);
+    return ((long long)(int)hi << MPC_FIX_SHIFT) + (long long)__float2int_rn((v - hi) * (float)(1 << MPC_FIX_SHIFT));
+}
 #define PE_NIF 4
 template <int KB>
 __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, int NCS, int SPLIT, const int *__restrict__ offsets,
@@ -962,8 +968,8 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
             unsigned long long *a = s_pacc + (size_t)lc * 2 * kk;
             for (int j = 0; j < kk; ++j) {
                 const float f = j < PE_KMAX ? ph[j] : phi[grow[u] * k + j];
-                atomicAdd(a + j, (unsigned long long)mpc_to_fixed(f * gy[u]));
-                atomicAdd(a + kk + j, (unsigned long long)mpc_to_fixed(f * gx[u]));
+                atomicAdd(a + j, (unsigned long long)pe_to_fixed(f * gy[u]));
+                atomicAdd(a + kk + j, (unsigned long long)pe_to_fixed(f * gx[u]));
             }
         }
     }

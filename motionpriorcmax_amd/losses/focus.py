@@ -158,7 +158,12 @@ class FocusLoss(base.TrajectoryLossBase):
         (not w.r.t. the weights of a 'learned' basis: the basis values enter as constants).  With a bucket-ordered batch
         (`order_events` / `ingest_events(order_for=...)`: `event_offsets`) the backward accumulates per LUT strip in LDS fixed point
         and is bitwise reproducible; without the table it uses global float atomics (slow: ~20 G atomics/s, and not
-        reproducible).  fused=False: the same in plain torch around the vote / objective kernels (cross-check)."""
+        reproducible).  fused=False: the same in plain torch around the vote / objective kernels (cross-check).
+
+        A tile without a centre: there are ceil(H / sp) x ceil(W / sp) cells, and where 0 < H % sp <= sp // 2 (W likewise) the
+        centre sp // 2 of the last row (column) of cells lies outside the image.  Such a cell carries zero coefficients: its
+        events are not warped, it enters the smoothness field with zero flow, and no element of coeff_grid receives its
+        gradient."""
         from ..utils import basis_values
         if self.num_tref != 1:
             raise ValueError('calc_per_event_basis needs num_tref == 1')

@@ -990,8 +990,13 @@ class TileCoeffRowsFn(torch.autograd.Function):
     def forward(ctx, coeff_grid, tile):
         ctx.shape_in, ctx.tile = tuple(coeff_grid.shape), int(tile)
         cs = coeff_grid[:, :, :, tile // 2::tile, tile // 2::tile]
-        cs = cs[:, 0] if cs.shape[1] == 1 else cs.sum(1)                      # [B, 2k, hq, wq]
-        B, c2, hq, wq = cs.shape
+        cs = cs[:, 0] if cs.shape[1] == 1 else cs.sum(1)                      # [B, 2k, hc, wc]
+        B, c2, hc, wc = cs.shape
+        hq, wq = -(-coeff_grid.shape[3] // tile), -(-coeff_grid.shape[4] // tile)
+        if (hc, wc) != (hq, wq):
+            # (0 < H % tile <= tile // 2: the centre of the last row of cells lies outside the image -- zero coefficients, as
+            # k_tile_rows writes them)
+            cs = torch.nn.functional.pad(cs, (0, wq - wc, 0, hq - hc))
         return cs.permute(0, 2, 3, 1).reshape(B * hq * wq, c2)
 
     @staticmethod
@@ -1000,7 +1005,9 @@ class TileCoeffRowsFn(torch.autograd.Function):
         t = ctx.tile
         out = torch.zeros(ctx.shape_in, dtype=g.dtype, device=g.device)
         view = out[:, :, :, t // 2::t, t // 2::t]
-        view.copy_(g.view(B, view.shape[3], view.shape[4], c2).permute(0, 3, 1, 2)[:, None].expand_as(view))
+        hq, wq = -(-H // t), -(-W // t)
+        gc = g.reshape(B, hq, wq, c2)[:, :view.shape[3], :view.shape[4]]      # (cells without a centre in the image: dropped)
+        view.copy_(gc.permute(0, 3, 1, 2)[:, None].expand_as(view))
         return out, None
 
 

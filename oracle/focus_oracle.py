@@ -415,7 +415,11 @@ class FocusLossOracle:
             warped = (y, x) + sum_k c_k[tile(y, x)] * (basis_k(t_ref) - basis_k(t_event))
         with the tile coefficients of trajectories.py:15-52 and the basis of basis.py:18-31 (the flow to t_ref of the trajectory
         that starts at the event's tile), then focus.py:197-230 / loss.py unchanged; smoothness (loss.py:29-56) on the same
-        flow at the bin mid-times."""
+        flow at the bin mid-times.
+        A tile without a centre: the look-up table has ceil(h / sp) x ceil(w / sp) cells, but the centre sp // 2 of the last
+        row (column) of cells lies outside the image where 0 < h % sp <= sp // 2 (w likewise), and the grid holds no coefficients
+        for it.  Such a cell carries ZERO coefficients: its events are not warped, and it takes part in the smoothness field
+        with zero flow."""
         events = batch['events']
         num_pos = batch['num_pos_events'] if 'num_pos_events' in batch else -1
         h, w = self.image_shape
@@ -424,9 +428,12 @@ class FocusLossOracle:
             coeff_grid = coeff_grid[:, None]
         coeffs, _ = coeff_grid_to_list(coeff_grid, mask, num_basis)              # [b,s,2,n,k]
         hq, wq = -(-h // self.sp), -(-w // self.sp)
+        hc, wc = len(range(self.sp // 2, h, self.sp)), len(range(self.sp // 2, w, self.sp))     # rows / columns of tile centres
         b, m, _ = events.shape
-        c = coeffs.sum(1).reshape(b, 2, hq, wq, num_basis)
-        t_ref = torch.as_tensor(t_ref, dtype=torch.float32).reshape(1)
+        c = coeffs.sum(1).reshape(b, 2, hc, wc, num_basis)
+        if (hc, wc) != (hq, wq):
+            c = F.pad(c, (0, 0, 0, wq - wc, 0, hq - hc))                          # cells without a centre: zero coefficients
+        t_ref = torch.as_tensor(t_ref, dtype=events.dtype).reshape(1)            # (float64 events: the whole definition in float64)
         ib = torch.arange(b)[:, None].expand(b, m)
         iy = torch.div(events[..., 0], self.sp, rounding_mode='floor').to(torch.int64).clamp(0, hq - 1)
         ix = torch.div(events[..., 1], self.sp, rounding_mode='floor').to(torch.int64).clamp(0, wq - 1)
@@ -439,7 +446,7 @@ class FocusLossOracle:
         focus = 1 / contrast_value(iwes, self.loss_type, self.focus_loss_norm)
         smooth = torch.tensor(0.)
         if self.smooth_weight > 0:
-            phim = basis_matrix(t_ref, num_basis, basis_type) - basis_matrix(bin_mid_times(self.num_bins), num_basis, basis_type)
+            phim = basis_matrix(t_ref, num_basis, basis_type) - basis_matrix(bin_mid_times(self.num_bins).to(t_ref.dtype), num_basis, basis_type)
             field = torch.einsum('bdhwk,tk->btdhw', c, phim).reshape(-1, 2, hq, wq)
             smooth = self.smooth_weight * smoothness(field)
         return focus + smooth, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}

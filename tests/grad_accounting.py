@@ -194,7 +194,7 @@ def per_event_tiles(cell_mask):
 
 
 def assert_accountable(got, want, explained, *, tight=LUT_TIGHT, max_mismatch=0.01, max_explained=0.25, excuse=None, origin=None,
-                       label=''):
+                       label='', caps=True):
     """got / want: `explained.shape` or `explained.shape + (D,)` (the last axis, e.g. (y, x), is judged as one element).
     An element mismatches when |got - want| (max over the last axis) exceeds tight[0] * max|want| + tight[1] * |want|.  Asserts:
     no unexplained mismatch, mismatch fraction <= max_mismatch (1 % at most), explained fraction <= max_explained (25 % at most).
@@ -203,6 +203,8 @@ def assert_accountable(got, want, explained, *, tight=LUT_TIGHT, max_mismatch=0.
       origin = (cell_elems [C, F], number of LUT cells): the mismatch cap applies to the LUT cells it takes to account for the
                mismatching elements (_cells_needed);
       excuse (the explained LUT cells): the explained cap applies to them (K = 32 at DSEC size).
+    caps=False: only 'no unexplained mismatch' is asserted here; the caller reads the two fractions from the result and must judge
+    a case that passes a cap by another rule (tools/fuzz_per_event.py: images of a dozen tiles, where 1 % is less than one tile).
     Returns the counts and fractions (and prints them: pytest -s)."""
     assert max_mismatch <= 0.01 and max_explained <= 0.25
     got = torch.as_tensor(got).detach().double().cpu()
@@ -236,6 +238,9 @@ def assert_accountable(got, want, explained, *, tight=LUT_TIGHT, max_mismatch=0.
     assert res['unexplained'] == 0, (f'{label}: {res["unexplained"]} of {n} elements differ with nothing to explain them '
                                      f'({res["mismatch"]} mismatching, {res["explained"]} explained); worst unexplained '
                                      f'{res["worst_unexplained"]:.2e} of max')
+    res['caps_hold'] = res['frac_mismatch_origin'] <= max_mismatch and res['frac_excuse'] <= max_explained
+    if not caps:
+        return res
     assert res['frac_mismatch_origin'] <= max_mismatch, (
         f'{label}: {100 * res["frac_mismatch"]:.3f} % mismatching ({res["mismatch"]} of {n})' +
         ('' if origin is None else f', from {100 * res["frac_mismatch_origin"]:.3f} % of the LUT cells'))
@@ -323,7 +328,9 @@ def per_event_accounting(cfg, events, num_pos, coeff, t_ref, num_basis, basis_ty
     B, M, _ = ev.shape
     c = torch.as_tensor(coeff).detach().cpu()
     c = c[:, None] if c.dim() == 4 else c
-    c = c.sum(1)[:, :, sp // 2::sp, sp // 2::sp].reshape(B, 2, num_basis, hq, wq).permute(0, 1, 3, 4, 2)
+    c = c.sum(1)[:, :, sp // 2::sp, sp // 2::sp]
+    hc, wc = c.shape[-2:]                        # (< hq, wq where the last cells have no centre in the image: zero coefficients)
+    c = F.pad(c, (0, wq - wc, 0, hq - hc)).reshape(B, 2, num_basis, hq, wq).permute(0, 1, 3, 4, 2)
     t = torch.as_tensor(t_ref, dtype=torch.float32).reshape(1)
     iy = torch.div(ev[..., 0], sp, rounding_mode='floor').long().clamp(0, hq - 1)
     ix = torch.div(ev[..., 1], sp, rounding_mode='floor').long().clamp(0, wq - 1)
@@ -339,7 +346,7 @@ def per_event_accounting(cfg, events, num_pos, coeff, t_ref, num_basis, basis_ty
     tiles = per_event_tiles(explained_lut_cells(ev, warped, num_pos, shape, sp, cfg['num_bins'], aff, bnd, split))
     m = O.tile_mask(shape, sp)
     sel = lambda g: _grid_layout(torch.as_tensor(g).detach().cpu()[..., m])                # noqa: E731
-    res = assert_accountable(sel(got), sel(want), tiles.reshape(B, -1), tight=POINT_TIGHT, label=label, **kw)
+    res = assert_accountable(sel(got), sel(want), tiles[:, :hc, :wc].reshape(B, -1), tight=POINT_TIGHT, label=label, **kw)
     res['boundary_events'] = int(bnd.sum())
     if aff is None:
         assert res['mismatch'] <= HANDFUL, f'{label}: {res["mismatch"]} elements mismatch with no sign() to explain them'

@@ -494,6 +494,59 @@ int mpc_grid_traj_bwd(const float *grad_traj, const float *times, const float *d
                       float *grad_grid, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W,
                       int32_t tile, int32_t n_t, void *stream);
 
+/* ---- the RAFT-spline validation step's flow metrics (what scripts/trajectory_inference.py logs) as one fused reduction.
+ * Reference: src/modules/raft_spline.py:88-215 (validation_step: which metric sees which prediction and mask), src/modules/utils.py
+ * :85-102 epe_masked, :104-126 epe_masked_multi, :128-184 ae_masked(_multi), :186-218 n_pixel_error_masked, :220-296
+ * calculate_flow_error / calculate_trajectory_flow_error, :335-541 the Metric classes (when update() adds a value), :67-74 the
+ * linear-motion baseline.
+ *   predictions P_m, m < M, (x, y) order, from ONE of
+ *     params [B][2][d][h][w] + up_mask [B][576][h][w] + basis [M][d] (d >= 1; H = 8h, W = 8w): the curves of mpc_cvx_flow_fwd evaluated
+ *       in registers, never written (the same device functions: the same bits), or
+ *     flows  [M][B][2][H][W] (d = 0; h, w ignored);
+ *     both times `scale`
+ *   timestamps [M] fp32 (device)   the baseline's prediction at step m is timestamps[m] * P_{M-1}
+ *   flow_gt    [B][M][2][H][W]     finite (the loaders zero NaN; the reference itself yields NaN on inf)
+ *   flow_valid [B][M][H][W] bytes (non-zero = true), or NULL: V_m
+ *   ev_repr    [B][C][H][W] (E = any channel != 0, a NaN counts), or event_mask [B][H][W] bytes: exactly one of the two
+ *   values [MPC_VAL_COUNT] fp32, updated [MPC_VAL_COUNT] int32 (out, device): the keys below; updated = 1 where the reference's
+ *     Metric.update adds the value, 0 where it skips (the epe family with every mask empty: value NaN) or raises (NPE with an empty
+ *     mask, utils.py:199: the five singles of that mask are NaN / 0 -- unpinned) and for the EPE_STEP slots >= M (value 0).
+ * Per pixel, step and sample: e = |P - G|, a = acos(clamp((P.G + 1) / (|(P, 1)| |(G, 1)|))), r_k = e > k && e / max(|G|, 1e-6) >= 0.05
+ * in fp32 (the angle as atan2(|u x v|, u.v), u = (P, 1), v = (G, 1): the same angle without the loss of acos near 1); every sum in
+ * fp64, every count an integer; a fixed reduction order, no atomics: bitwise reproducible.
+ *   epe = sum_K e / |K|, ae = sum_K a / |K| (degrees), kpe = 100 sum_K r_k / |K|     over the whole batch, step M - 1
+ *   epe_multi = mean over the steps with |K_m| > 0 of epe_m; ae_multi = sum_m ae_m / M (0 / 0 = NaN, as the reference)
+ *   TEPE / T3PE / TAE = mean over the M * B images of sum_F e, #_F(e > 3), sum_F a (degrees) / (|F| + 1e-5), F = K_m && Gx != 0 &&
+ *     Gy != 0 && both finite; EPE_STEPmm = the mean over the B images of step m of the first
+ * Kernels only on `stream` (no memset / memcpy nodes: capturable), nothing read back.  ws: mpc_val_metrics_workspace_bytes() bytes.
+ * Limits: d <= 16, M <= 16 (else MPC_E_UNSUPPORTED).  B = 0 launches nothing (values / updated are left as they are).  */
+#define MPC_VAL_MAX_STEPS 16
+#define MPC_VAL_EPE 0                  /* val/epe ae 1pe 2pe 3pe: no mask, step M - 1 */
+#define MPC_VAL_AE 1
+#define MPC_VAL_1PE 2
+#define MPC_VAL_2PE 3
+#define MPC_VAL_3PE 4
+#define MPC_VAL_MASKED_SINGLE 5        /* + the five above: val/masked_epe ..: mask E */
+#define MPC_VAL_MULTI 10               /* val/<..>: no mask */
+#define MPC_VAL_EV_MASKED_MULTI 31     /* val/ev_masked_<..>: E && V_m (E alone without flow_valid) */
+#define MPC_VAL_MASKED_MULTI 52        /* val/masked_<..>: V_m (no mask without flow_valid) */
+#define MPC_VAL_EPE_MULTI 0            /* offsets inside each of the three groups of 5 + MPC_VAL_MAX_STEPS */
+#define MPC_VAL_AE_MULTI 1
+#define MPC_VAL_T3PE 2
+#define MPC_VAL_TEPE 3
+#define MPC_VAL_TAE 4
+#define MPC_VAL_EPE_STEP 5             /* + m */
+#define MPC_VAL_EPE_MULTI_LIN 73
+#define MPC_VAL_AE_MULTI_LIN 74
+#define MPC_VAL_COUNT 75
+typedef struct mpc_val_shape {
+    int32_t B, M, d, h, w, H, W, C;    /* d = 0: predictions from `flows`; C = 0: E from `event_mask` */
+} mpc_val_shape;
+int64_t mpc_val_metrics_workspace_bytes(const mpc_val_shape *s);
+int mpc_val_metrics(const mpc_val_shape *s, const float *params, const float *up_mask, const float *basis, const float *flows,
+                    float scale, const float *timestamps, const float *flow_gt, const uint8_t *flow_valid, const float *ev_repr,
+                    const uint8_t *event_mask, float *values, int32_t *updated, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

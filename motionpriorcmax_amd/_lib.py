@@ -39,7 +39,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd',
            'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm',
            'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd',
-           'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter']
+           'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter',
+           'mpc_val_metrics_workspace_bytes', 'mpc_val_metrics']
 
 
 class Shape(ctypes.Structure):
@@ -82,6 +83,16 @@ class FlowShape(ctypes.Structure):
 class ErrShape(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ('B', 'H', 'W')]
 
+
+class ValShape(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ('B', 'M', 'd', 'h', 'w', 'H', 'W', 'C')]
+
+
+# key order of mpc_val_metrics, mirror of the MPC_VAL_* macros of include/mpcmax.h
+VAL_MAX_STEPS, VAL_COUNT = 16, 75
+VAL_SINGLE, VAL_MASKED_SINGLE, VAL_MULTI, VAL_EV_MASKED_MULTI, VAL_MASKED_MULTI, VAL_EPE_MULTI_LIN, VAL_AE_MULTI_LIN = 0, 5, 10, 31, 52, 73, 74
+VAL_SINGLE_KEYS = ('epe', 'ae', '1pe', '2pe', '3pe')
+VAL_MULTI_KEYS = ('epe_multi', 'ae_multi', 'T3PE', 'TEPE', 'TAE')          # then EPE_STEP00 .. at + 5
 
 _lib = None
 
@@ -183,6 +194,9 @@ def lib():
     L.mpc_ingest_window_workspace_bytes.restype = i64
     L.mpc_ingest_window_count.argtypes = [wsp, vp, vp, vp, vp, vp, vp]
     L.mpc_ingest_window_scatter.argtypes = [wsp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
+    L.mpc_val_metrics_workspace_bytes.argtypes = [ctypes.POINTER(ValShape)]
+    L.mpc_val_metrics_workspace_bytes.restype = i64
+    L.mpc_val_metrics.argtypes = [ctypes.POINTER(ValShape), vp, vp, vp, vp, f32] + [vp] * 9
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

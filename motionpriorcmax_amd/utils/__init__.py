@@ -7,3 +7,4 @@ from .flow import dense_flow_from_traj, calculate_flow_error, ErrorCalculatorFac
 from .grid_traj import trajectories_from_grid, flow_from_grid  # noqa: F401
 from . import representation  # noqa: F401  (representation.VoxelGrid is the EVIMO2 / MultiFlow class; VoxelGrid above is the DSEC one)
 from .representation import representation_grids  # noqa: F401
+from .val_metrics import trajectory_val_metrics, TrajectoryValMetrics, val_metric_keys  # noqa: F401

@@ -547,6 +547,44 @@ int mpc_val_metrics(const mpc_val_shape *s, const float *params, const float *up
                     float scale, const float *timestamps, const float *flow_gt, const uint8_t *flow_valid, const float *ev_repr,
                     const uint8_t *event_mask, float *values, int32_t *updated, void *ws, void *stream);
 
+/* ---- the RAFT-spline correlation lookup: the one gather inside the network's update loop, 12 times per forward.
+ * Reference: src/models/raft_spline/corr.py:304-348 (CorrBlockParallelMultiTarget.__call__), raft_spline/utils.py:4-20
+ * (bilinear_sampler: grid_sample, align_corners=True, zero padding), raft.py:165-189 (flows = bezier.get_flow_from_reference(times);
+ * coords1 = coords0 + flows; corr_block(coords1)), corr.py:262-270, 106-123, 296-302 (the pyramid the lookup reads).
+ *   level l (num_levels of them)  [n_l][B*h*w][h_l][w_l]  the correlation volume of the n_l targets that have more than l levels
+ *                                 (level_target[l][0..n_l), ascending), avg-pooled l times: h_l = h >> l, w_l = w >> l
+ *   entries e = (level, slot) in level-major order, E = sum_l n_l; K = 2 * radius + 1
+ *   centre of (target t, sample b, pixel (y, x)):  coords [T][B][2][h][w] ((x, y) order), or -- coords == NULL -- the Bezier mode:
+ *                                 (x, y) + sum_j basis[t][j] * params[b][(x: j, y: d + j)][y][x], params [B][2d][h][w], basis [T][d]
+ *   out [B][E * K * K][h][w]      channel e * K * K + i * K + j = the bilinear sample (zero outside, per tap) of the query's OWN slice
+ *                                 level[l][slot][b * h * w + y * w + x] at (centre.x / 2^l + j - radius, centre.y / 2^l + i - radius)
+ * The offsets are integers: the K * K samples of one (query, entry) share one pair of fractions and read one (K + 1)^2 window.
+ * mpc_corr_lookup_bwd: the adjoint applied to grad_out [B][E * K * K][h][w] -- grad_coords [T][B][2][h][w] (coords mode) or grad_params
+ * [B][2d][h][w] (Bezier mode: the curve adjoint in the same launch), and for every level with desc->grad_level[l] != NULL the whole
+ * of grad_level[l] (window cells in gather form, every other element 0: nothing to pre-zero).  A NULL gradient pointer drops its
+ * part.  A query's slice is read by that query alone: no atomics, every sum in a fixed order, bitwise reproducible.  One launch
+ * each way; the descriptor travels by value as a kernel argument (no copy to the device).
+ * Limits: radius <= 4, d <= 16, T <= 16, num_levels <= 6 (else MPC_E_UNSUPPORTED); level sizes that are not (h >> l, w >> l), are
+ * below 2 (the reference divides by w_l - 1), or a target list that is not ascending / nested: MPC_E_SHAPE.
+ * mpc_corr_lookup_supported: the same checks on the host alone, 0 or the error code.  */
+#define MPC_CORR_MAX_LEVELS 6
+#define MPC_CORR_MAX_TARGETS 16
+#define MPC_CORR_MAX_RADIUS 4
+typedef struct mpc_corr_desc {
+    int32_t B, h, w, T, d, radius, num_levels;     /* d: control points per axis (Bezier mode; ignored with coords) */
+    int32_t flags;                                  /* diagnostics: MPC_CORR_F_LANE_PER_QUERY */
+    int32_t level_h[MPC_CORR_MAX_LEVELS], level_w[MPC_CORR_MAX_LEVELS], level_n[MPC_CORR_MAX_LEVELS];
+    uint8_t level_target[MPC_CORR_MAX_LEVELS][MPC_CORR_MAX_TARGETS];
+    const float *level[MPC_CORR_MAX_LEVELS];
+    float *grad_level[MPC_CORR_MAX_LEVELS];         /* mpc_corr_lookup_bwd only */
+} mpc_corr_desc;
+#define MPC_CORR_F_LANE_PER_QUERY 1                    /* forward: one thread per (query, entry) instead of a wave per window (probe A/B) */
+int mpc_corr_lookup_supported(const mpc_corr_desc *desc);
+int mpc_corr_lookup_fwd(const mpc_corr_desc *desc, const float *coords, const float *params, const float *basis, float *out,
+                        void *stream);
+int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coords, const float *params, const float *basis,
+                        const float *grad_out, float *grad_coords, float *grad_params, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

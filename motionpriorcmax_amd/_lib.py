@@ -40,7 +40,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm',
            'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd',
            'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter',
-           'mpc_val_metrics_workspace_bytes', 'mpc_val_metrics']
+           'mpc_val_metrics_workspace_bytes', 'mpc_val_metrics',
+           'mpc_corr_lookup_supported', 'mpc_corr_lookup_fwd', 'mpc_corr_lookup_bwd']
 
 
 class Shape(ctypes.Structure):
@@ -86,6 +87,17 @@ class ErrShape(ctypes.Structure):
 
 class ValShape(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ('B', 'M', 'd', 'h', 'w', 'H', 'W', 'C')]
+
+
+CORR_MAX_LEVELS, CORR_MAX_TARGETS, CORR_MAX_RADIUS, CORR_F_LANE_PER_QUERY = 6, 16, 4, 1        # include/mpcmax.h
+
+
+class CorrDesc(ctypes.Structure):
+    """include/mpcmax.h: struct mpc_corr_desc (passed to the kernels by value)."""
+    _fields_ = [(k, ctypes.c_int32) for k in ('B', 'h', 'w', 'T', 'd', 'radius', 'num_levels', 'flags')] + \
+               [(k, ctypes.c_int32 * CORR_MAX_LEVELS) for k in ('level_h', 'level_w', 'level_n')] + \
+               [('level_target', (ctypes.c_uint8 * CORR_MAX_TARGETS) * CORR_MAX_LEVELS),
+                ('level', ctypes.c_void_p * CORR_MAX_LEVELS), ('grad_level', ctypes.c_void_p * CORR_MAX_LEVELS)]
 
 
 # key order of mpc_val_metrics, mirror of the MPC_VAL_* macros of include/mpcmax.h
@@ -197,6 +209,10 @@ def lib():
     L.mpc_val_metrics_workspace_bytes.argtypes = [ctypes.POINTER(ValShape)]
     L.mpc_val_metrics_workspace_bytes.restype = i64
     L.mpc_val_metrics.argtypes = [ctypes.POINTER(ValShape), vp, vp, vp, vp, f32] + [vp] * 9
+    cdp = ctypes.POINTER(CorrDesc)
+    L.mpc_corr_lookup_supported.argtypes = [cdp]
+    L.mpc_corr_lookup_fwd.argtypes = [cdp, vp, vp, vp, vp, vp]
+    L.mpc_corr_lookup_bwd.argtypes = [cdp, vp, vp, vp, vp, vp, vp, vp]
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

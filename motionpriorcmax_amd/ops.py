@@ -1234,6 +1234,50 @@ def cvx_flows(params, up_mask, basis, scale: float):
     return flows
 
 
+class CorrLookupFn(torch.autograd.Function):
+    """The RAFT-spline correlation lookup (utils.CorrLookup; reference corr.py:304-348, raft_spline/utils.py:4-20, raft.py:178-180):
+    x = coords [T, B, 2, h, w] (basis None) or the Bezier control points params [B, 2d, h, w] with basis [T, d] on the device, and the
+    pyramid levels of `lookup` as inputs of their own (so that autograd asks for their gradients) -> [B, E * (2r+1)^2, h, w], one
+    kernel forward and one backward (csrc/corr_lookup.hip) instead of the coordinate tensor / grid_sample / cat / permute chain.
+    The backward computes only what autograd asks for; every element of a gradient it returns is written by the kernel (no memset).
+    The descriptor of the pyramid travels by value with the launch: no host synchronisation and no copy either way."""
+
+    @staticmethod
+    def forward(ctx, x, basis, lookup, *levels):
+        _require_gpu(x, 'coords / params')
+        dev = x.device
+        bezier = basis is not None
+        d = x.shape[1] // 2 if bezier else 0
+        desc = lookup.descriptor(d)
+        K = 2 * lookup.radius + 1
+        out = torch.empty((lookup.B, lookup.num_entries * K * K, lookup.h, lookup.w), dtype=torch.float32, device=dev)
+        xd = x.detach()
+        C.check(C.lib().mpc_corr_lookup_fwd(ctypes.byref(desc), None if bezier else _ptr(xd), _ptr(xd) if bezier else None,
+                                            _ptr(basis), _ptr(out), _stream(dev)), 'mpc_corr_lookup_fwd')
+        ctx.lookup, ctx.bezier, ctx.d = lookup, bezier, d
+        ctx.save_for_backward(xd, basis, *levels)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, basis, *levels = ctx.saved_tensors
+        g = _f32c(g)
+        dev = g.device
+        want_x = ctx.needs_input_grad[0]
+        want_l = [ctx.needs_input_grad[3 + l] for l in range(len(levels))]
+        if not want_x and not any(want_l):
+            return (None,) * (3 + len(levels))
+        desc = C.CorrDesc.from_buffer_copy(ctx.lookup.descriptor(ctx.d))
+        gx = torch.empty_like(x) if want_x else None
+        gl = [torch.empty_like(lv) if w else None for lv, w in zip(levels, want_l)]          # (every element is written by the kernel)
+        for l, t in enumerate(gl):
+            desc.grad_level[l] = None if t is None else t.data_ptr()
+        bez = ctx.bezier
+        C.check(C.lib().mpc_corr_lookup_bwd(ctypes.byref(desc), None if bez else _ptr(x), _ptr(x) if bez else None, _ptr(basis), _ptr(g),
+                                            None if bez else _ptr(gx), _ptr(gx) if bez else None, _stream(dev)), 'mpc_corr_lookup_bwd')
+        return (gx, None, None) + tuple(gl)
+
+
 class GridTrajFn(torch.autograd.Function):
     """The network's coefficient grid [B, S, 2k, H, W] -> `trajectories` [B, n_t, n, 2] (y, x) at the tile centres (row A3 of SURVEY.md
     8(a): reference trajectory_net.py:57-119): one kernel forward, one backward (two when `dphi` needs a gradient), csrc/grid_traj.hip,

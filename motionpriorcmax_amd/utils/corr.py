@@ -1,0 +1,199 @@
+"""The RAFT-spline correlation pyramid and its lookup (reference src/models/raft_spline/corr.py:125-348, raft_spline/utils.py:4-28;
+the loop that calls it: raft.py:165-189).
+
+`corr_pyramid` is dense algebra (a batched matmul and average pools) and stays plain torch.  `CorrLookup` is the network's one gather,
+12 times per forward: on the GPU one kernel each way (ops.CorrLookupFn, csrc/corr_lookup.hip); everything the kernels do not take --
+CPU tensors, other dtypes, non-contiguous tensors, radius > 4, more than 16 targets or control points, more than 6 levels -- runs the
+plain-torch mirror below, which is written as the reference's own operator chain (coordinate tensor, normalisation to [-1, 1],
+grid_sample, cat / permute / reshape) and therefore also the comparator the probe times the kernels against."""
+import torch
+import torch.nn.functional as F
+
+from .basis import _device_basis
+
+_KERNEL_MAX_RADIUS, _KERNEL_MAX_TARGETS, _KERNEL_MAX_D, _KERNEL_MAX_LEVELS = 4, 16, 16, 6
+
+
+def _levels_list(num_levels_per_target):
+    if isinstance(num_levels_per_target, int):
+        return [int(num_levels_per_target)]
+    nl = [int(v) for v in num_levels_per_target]
+    if not nl or min(nl) < 1:
+        raise ValueError(f'num_levels_per_target must hold positive level counts, got {nl}')
+    return nl
+
+
+def level_target_indices(num_levels_per_target):
+    """Host lists: level l holds the targets with num_levels >= l + 1, ascending (corr.py:296-302)."""
+    nl = _levels_list(num_levels_per_target)
+    return [[t for t, v in enumerate(nl) if v >= l + 1] for l in range(max(nl))]
+
+
+def corr_pyramid(fmap1, fmap2, num_levels_per_target):
+    """fmap1 [B, D, h, w], fmap2 [n, B, D, h, w] (or [B, D, h, w] for one target) -> (levels, target_indices): levels[l]
+    [n_l, B*h*w, 1, h_l, w_l] = fmap1^T @ fmap2 / sqrt(D), 2 x 2 average-pooled l times (the pool drops an odd last row / column), for
+    the targets of `level_target_indices` -- the reference's CorrComputation.get_correlation_volume and CorrData.get_downsampled
+    (corr.py:262-270, 106-123) operator for operator.  target_indices are host lists."""
+    nl = _levels_list(num_levels_per_target)
+    if fmap2.dim() == 4:
+        fmap2 = fmap2[None]
+    n, B, D, h, w = fmap2.shape
+    if tuple(fmap1.shape) != (B, D, h, w) or len(nl) != n:
+        raise ValueError(f'fmap1 {tuple(fmap1.shape)}, fmap2 {tuple(fmap2.shape)} and {len(nl)} level counts do not belong together')
+    corr = fmap1.reshape(B, D, h * w).transpose(-1, -2) @ fmap2.reshape(n, B, D, h * w)
+    corr = corr / torch.sqrt(torch.tensor(D, device=corr.device).float())
+    tix = level_target_indices(nl)
+    levels = [corr.reshape(n, B * h * w, 1, h, w)]
+    for l in range(1, len(tix)):
+        prev = levels[-1]
+        pick = [tix[l - 1].index(t) for t in tix[l]]
+        sel = prev if len(pick) == prev.shape[0] else prev[pick]
+        down = F.avg_pool2d(sel.reshape(-1, 1, *prev.shape[-2:]), 2, stride=2)
+        levels.append(down.view(len(pick), B * h * w, 1, *down.shape[-2:]))
+    return levels, tix
+
+
+def coords_grid(batch, ht, wd, device, dtype=torch.float32):
+    """[batch, 2, ht, wd], channel 0 = x, channel 1 = y (raft_spline/utils.py:22-28)."""
+    ys, xs = torch.meshgrid(torch.arange(ht, device=device), torch.arange(wd, device=device), indexing='ij')
+    return torch.stack((xs, ys), dim=0).to(dtype)[None].repeat(batch, 1, 1, 1)
+
+
+def _lookup_mirror(levels, target_indices, radius, coords):
+    """corr.py:304-348 with bilinear_sampler (utils.py:4-20) written out: coords [T, B, 2, h, w] -> [B, E * K * K, h, w]."""
+    coords = coords.permute(0, 1, 3, 4, 2)
+    T, B, h1, w1, _ = coords.shape
+    r = radius
+    K = 2 * r + 1
+    d = torch.linspace(-r, r, K, device=coords.device, dtype=coords.dtype)
+    dy, dx = torch.meshgrid(d, d, indexing='ij')
+    delta = torch.stack((dx, dy), dim=-1).view(1, K, K, 2)                     # [..., 0] = x offset (j - r), [..., 1] = y offset (i - r)
+    out = []
+    for l, (corr, tix) in enumerate(zip(levels, target_indices)):
+        sel = coords if len(tix) == T else coords[tix]
+        centroid = sel.reshape(len(tix) * B * h1 * w1, 1, 1, 2) / 2 ** l
+        xg, yg = (centroid + delta).split([1, 1], dim=-1)
+        H, W = corr.shape[-2:]
+        grid = torch.cat((2 * xg / (W - 1) - 1, 2 * yg / (H - 1) - 1), dim=-1)
+        feat = F.grid_sample(corr.reshape(-1, 1, H, W), grid, align_corners=True)
+        out.append(feat.view(len(tix), B, h1, w1, K * K))
+    out = torch.cat(out, dim=0).permute(1, 0, 4, 2, 3).reshape(B, -1, h1, w1)
+    return out if out.dtype == torch.float64 else out.float()                  # (float64 stays: the tests measure the fp32 error against it)
+
+
+class CorrLookup:
+    """The lookup of CorrBlockParallelMultiTarget (corr.py:272-348) over a pyramid built elsewhere.
+
+    levels[l] [n_l, B*h*w, 1, h_l, w_l] as `corr_pyramid` returns them; num_levels_per_target the host list that built them (level l
+    holds the targets with more than l levels, ascending).  `lookup(coords)` / `__call__`: coords [T, B, 2, h, w] or a list of T
+    tensors [B, 2, h, w] in (x, y) order -> [B, E * (2r+1)^2, h, w] fp32 in the reference's channel order: entries level-major, then
+    by target within a level; inside an entry channel i * (2r+1) + j samples at (coords / 2^l) + (x: j - r, y: i - r), bilinear,
+    align_corners=True, zero padding per tap.  `lookup_bezier(params, times)`: the reference's three lines
+    `flows = bezier.get_flow_from_reference(times); coords1 = coords0 + flows; corr_block(coords1)` as one node.  Both are
+    differentiable w.r.t. coords / params and every level that requires grad; only requested gradients are computed.
+    A level below 2 x 2 raises ValueError (the reference divides by size - 1 there and returns NaN)."""
+
+    def __init__(self, levels, num_levels_per_target, radius=4):
+        self.levels = list(levels)
+        self.num_levels_per_target = _levels_list(num_levels_per_target)
+        self.target_indices = level_target_indices(self.num_levels_per_target)
+        self.radius = int(radius)
+        if self.radius < 1:
+            raise ValueError(f'radius must be at least 1, got {radius}')
+        if len(self.levels) != len(self.target_indices):
+            raise ValueError(f'{len(self.levels)} levels given, the level counts {self.num_levels_per_target} need {len(self.target_indices)}')
+        n0, bhw, one, h, w = self.levels[0].shape
+        if one != 1 or bhw % (h * w):
+            raise ValueError(f'level 0 must be [n, B*h*w, 1, h, w], got {tuple(self.levels[0].shape)}')
+        self.B, self.h, self.w = bhw // (h * w), h, w
+        for l, (lv, tix) in enumerate(zip(self.levels, self.target_indices)):
+            if lv.dim() != 5 or tuple(lv.shape[:3]) != (len(tix), bhw, 1) or tuple(lv.shape[3:]) != (h >> l, w >> l):
+                raise ValueError(f'level {l} must be {(len(tix), bhw, 1, h >> l, w >> l)}, got {tuple(lv.shape)}')
+            if lv.shape[3] < 2 or lv.shape[4] < 2:
+                raise ValueError(f'level {l} is {lv.shape[3]} x {lv.shape[4]}: a level below 2 x 2 cannot be sampled '
+                                 '(align_corners=True divides by size - 1)')
+        self.num_entries = sum(len(t) for t in self.target_indices)
+        self._descs = {}
+        self._bases = {}
+
+    @classmethod
+    def from_block(cls, block, num_levels_per_target=None):
+        """From the reference's CorrBlockParallelMultiTarget (duck-typed: block._corr_pyramid[i].corr, block._radius).  With
+        `num_levels_per_target` (what the block's CorrComputation objects were built with, events then frames) nothing is read back
+        from the device; without it the target indices are read from the block's device tensors
+        (block._corr_pyramid[i].target_indices), which costs one device synchronisation."""
+        pyramid = list(block._corr_pyramid)
+        levels = [cd.corr for cd in pyramid]
+        if num_levels_per_target is None:
+            tix = torch.cat([torch.cat((cd.target_indices.reshape(-1), cd.target_indices.new_full((1,), -1))) for cd in pyramid]).tolist()
+            n = levels[0].shape[0]
+            num_levels_per_target = [0] * n
+            for t in tix:
+                if t >= 0:
+                    num_levels_per_target[int(t)] += 1
+        return cls(levels, num_levels_per_target, radius=int(block._radius))
+
+    # ---- routing
+
+    def _kernels_serve(self, x, d):
+        tensors = [x] + self.levels
+        return (all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device for t in tensors)
+                and self.radius <= _KERNEL_MAX_RADIUS and len(self.num_levels_per_target) <= _KERNEL_MAX_TARGETS
+                and d <= _KERNEL_MAX_D and len(self.levels) <= _KERNEL_MAX_LEVELS)
+
+    def descriptor(self, d=0, flags=None):
+        """The C descriptor (include/mpcmax.h: mpc_corr_desc) of this pyramid: built once per d, the kernels receive it by value."""
+        from .. import _lib as C
+        if flags is None:
+            flags = getattr(self, 'flags', 0)
+        key = (int(d), int(flags))
+        desc = self._descs.get(key)
+        if desc is None:
+            desc = C.CorrDesc(B=self.B, h=self.h, w=self.w, T=len(self.num_levels_per_target), d=int(d), radius=self.radius,
+                              num_levels=len(self.levels), flags=int(flags))
+            for l, (lv, tix) in enumerate(zip(self.levels, self.target_indices)):
+                desc.level_h[l], desc.level_w[l], desc.level_n[l] = lv.shape[3], lv.shape[4], len(tix)
+                for s, t in enumerate(tix):
+                    desc.level_target[l][s] = t
+                desc.level[l] = lv.data_ptr()
+            self._descs[key] = desc
+        return desc
+
+    def _basis(self, times, d, device, dtype):
+        if torch.is_tensor(times):
+            return _device_basis('bernstein', times, (int(d),), device, dtype)
+        key = (tuple(float(t) for t in times), int(d), device, dtype)           # (a list: uploaded once per lookup object, not per call)
+        bm = self._bases.get(key)
+        if bm is None:
+            bm = self._bases[key] = _device_basis('bernstein', list(key[0]), (int(d),), device, dtype)
+        return bm
+
+    # ---- the two calls
+
+    def lookup(self, coords):
+        if isinstance(coords, (list, tuple)):
+            coords = torch.stack(tuple(coords), dim=0)
+        T = len(self.num_levels_per_target)
+        if coords.dim() != 5 or tuple(coords.shape) != (T, self.B, 2, self.h, self.w):
+            raise ValueError(f'coords must be [T, B, 2, h, w] = {(T, self.B, 2, self.h, self.w)}, got {tuple(coords.shape)}')
+        if self._kernels_serve(coords, 0):
+            from .. import ops
+            return ops.CorrLookupFn.apply(coords, None, self, *self.levels)
+        return _lookup_mirror(self.levels, self.target_indices, self.radius, coords)
+
+    __call__ = lookup
+
+    def lookup_bezier(self, params, times):
+        T = len(self.num_levels_per_target)
+        if params.dim() != 4 or params.shape[1] % 2 or params.shape[1] < 2 or (params.shape[0], params.shape[2], params.shape[3]) != (self.B, self.h, self.w):
+            raise ValueError(f'params must be [B, 2d, h, w] with (B, h, w) = {(self.B, self.h, self.w)}, got {tuple(params.shape)}')
+        if len(times) != T:
+            raise ValueError(f'{len(times)} times for {T} targets')
+        d = params.shape[1] // 2
+        bm = self._basis(times, d, params.device, params.dtype)                  # [T, d]
+        if self._kernels_serve(params, d):
+            from .. import ops
+            return ops.CorrLookupFn.apply(params, bm, self, *self.levels)
+        flows = torch.einsum('bcdhw,td->tbchw', params.reshape(self.B, 2, d, self.h, self.w), bm)
+        coords = coords_grid(self.B, self.h, self.w, params.device, params.dtype)[None] + flows
+        return _lookup_mirror(self.levels, self.target_indices, self.radius, coords)

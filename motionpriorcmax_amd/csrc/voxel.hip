@@ -69,6 +69,9 @@ __global__ __launch_bounds__(256) void k_vox_bin(const mpc_vox_shape s, const Vo
         if (i >= n) continue;
         const float4 v = e[i];                       // x, y, t, p
         const float tn = (float)(s.C - 1) * (v.z - t_first) / t_span;       // utils.py:35-36
+        // zero time span (0 / 0, x / 0) or a time far outside the window: the reference's int conversion gives INT_MIN there and
+        // masks every tap; here the conversion would be undefined (and a NaN weight would reach mpc_to_fixed)
+        if (!(fabsf(tn) < 1e9f)) continue;
         const int t0 = (int)tn;
         const int y0 = (int)fminf(fmaxf(v.y, -8.f), (float)s.H + 8.f);
         const float val = 2.f * v.w - 1.f;

@@ -38,6 +38,57 @@ def voxel_grid(x, y, t, p, shape, norm_type='mean_std', quantile=0.0):
     return grid
 
 
+def voxel_grid64(x, y, t, p, shape, norm_type='mean_std', quantile=0.0):
+    """The same operation with every DECISION taken in fp32 as the reference takes it (t_norm, the truncations x0 / y0 / t0, the
+    masks, `std > 0`) and every product, sum and statistic in float64.  The quantile's rank is the exception: pos = fp32(1 - q) *
+    fp32(n - 1), its floor and its weight stay in fp32 and the at::lerp form is used -- what torch.quantile does for a float32
+    input.  Returns (grid [C, H, W] float64, taps [C, H, W] int64: the taps that land on each entry, raw [C, H, W] float64: the
+    grid before clipping and normalisation, m: the multiplier applied last -- 1, 1 / std or 1 / max)."""
+    C, H, W = shape
+    x, y, t, p = (v.float() for v in (x, y, t, p))
+    grid = torch.zeros(C * H * W, dtype=torch.float64)
+    taps = torch.zeros(C * H * W, dtype=torch.int64)
+    if x.numel() > 0:
+        tn = (C - 1) * (t - t[0]) / (t[-1] - t[0])       # fp32: it decides t0
+        x0, y0, t0 = x.int(), y.int(), tn.int()
+        xd, yd, td, val = x.double(), y.double(), tn.double(), 2 * p.double() - 1
+        for xl in (x0, x0 + 1):
+            for yl in (y0, y0 + 1):
+                for tl in (t0, t0 + 1):
+                    m = (xl < W) & (xl >= 0) & (yl < H) & (yl >= 0) & (tl >= 0) & (tl < C)
+                    w = val * (1 - (xl - xd).abs()) * (1 - (yl - yd).abs()) * (1 - (tl - td).abs())
+                    idx = H * W * tl.long() + W * yl.long() + xl.long()
+                    grid.put_(idx[m], w[m], accumulate=True)
+                    taps.put_(idx[m], torch.ones_like(idx[m]), accumulate=True)
+    raw = grid.clone().reshape(C, H, W)
+    mult = 1.0
+    if quantile > 0:
+        srt = torch.sort(grid.abs()).values
+        pos = torch.tensor(1 - quantile, dtype=torch.float32) * torch.tensor(float(grid.numel() - 1), dtype=torch.float32)
+        fl = torch.floor(pos)
+        wgt = float(pos - fl)                             # (fp32 arithmetic, then widened)
+        below, above = float(srt[int(fl)]), float(srt[int(torch.ceil(pos))])
+        d = above - below
+        thr = below + wgt * d if wgt < 0.5 else above - d * (1 - wgt)
+        grid = torch.where(grid.abs() > thr, grid.sign() * thr, grid)
+    if norm_type == 'mean_std':
+        nz = grid != 0
+        if int(nz.sum()) > 0:
+            v = grid[nz]
+            mean, std = v.mean(), v.std()
+            if bool(v.float().std() > 0):                # the reference's decision, on its fp32 values
+                grid[nz] = (v - mean) / std
+                mult = 1.0 / float(std)
+            else:
+                grid[nz] = v - mean
+    elif norm_type == 'max':
+        mx = float(grid.abs().max())
+        if mx > 0:
+            grid = grid / mx
+            mult = 1.0 / mx
+    return grid.reshape(C, H, W), taps.reshape(C, H, W), raw, mult
+
+
 def synth_raw_events(n, shape, seed=0, spill=2.0):
     """Seeded raw events as the DSEC slicer hands them to the voxel grid: rectified float coordinates
     that may fall slightly outside the sensor, increasing timestamps, polarity in {0, 1}."""

@@ -585,6 +585,32 @@ int mpc_corr_lookup_fwd(const mpc_corr_desc *desc, const float *coords, const fl
 int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coords, const float *params, const float *basis,
                         const float *grad_out, float *grad_coords, float *grad_params, void *stream);
 
+/* ---- the ground-truth flow targets of the EVIMO2 / MultiFlow configurations (what mpc_val_metrics takes as flow_gt / flow_valid)
+ * from the raw multi-step flow, as one launch.
+ * Reference: src/loader/evimo2/datasubset.py:171-188 (mode 0), src/loader/multiflow/sample.py:108-139 with downsample=True (mode 1).
+ *   mode 0  raw_flow [B][S][2][H][W], (x, y) order, NaN = invalid pixel
+ *           valid_src = neither channel NaN (:171); every NaN element -> 0 on its own (:173)
+ *           flow [B][S][2][Ho][Wo] (out) = F.interpolate(bilinear, align_corners=False) of the zeroed field: source coordinate
+ *             max(fp32(H / Ho) * (j + 0.5) - 0.5, 0), neighbour clamped to the last row, columns blended first, rows last (the
+ *             arithmetic of mpc_repr_grid's resize: one shared device function); then channel 0 * fp32(Wo / W), channel 1 *
+ *             fp32(Ho / H): one fp32 multiply after the blend (:185-188)
+ *           flow_valid [B][S][Ho][Wo] bytes 0 / 1 (out) = F.interpolate(nearest) of valid_src: source index
+ *             min(floor(j * fp32(H / Ho)), H - 1), likewise in x (:179-181)
+ *           id_out [B][Ho][Wo] (out, has_id = 1) = the same nearest pick of id_mask [B][H][W] (fp32) (:182-184)
+ *   mode 1  raw_flow [B][S][H][W][2], channels last as the h5 files hold it (the np.moveaxis of :133 is folded into the read)
+ *           flow [B][S][2][Ho][Wo] (out) = F.interpolate(bilinear, align_corners=True): source coordinate fp32((H - 1) / (Ho - 1)) * j,
+ *             the same blend order, then * 0.5 (:113, :137).  No NaN treatment (a NaN propagates as in the reference), no validity:
+ *             flow_valid, id_mask and id_out are ignored and may be NULL; has_id = 1 is an error.
+ * Every output element is written by the kernel (nothing to pre-zero); one kernel on `stream`, no workspace, no memset / memcpy
+ * nodes (capturable), nothing read back.  flow must be 4-byte aligned, and flow_valid too (its bytes are stored four at a time);
+ * with Wo % 4 == 0 and 16-byte aligned flow (and id_out) the rows are written in 16-byte stores.
+ * Limits: B, S, H, W, Ho, Wo >= 1; Ho, Wo >= 2 in mode 1 (the reference divides by Ho - 1): MPC_E_SHAPE otherwise.
+ * mpc_flow_targets_supported: the same checks on the host alone, 0 or the error code (+ mpc_last_error_string()).  */
+typedef struct mpc_targets_shape { int32_t B, S, H, W, Ho, Wo, mode /* 0 evimo2, 1 multiflow */, has_id; } mpc_targets_shape;
+int mpc_flow_targets_supported(const mpc_targets_shape *s);
+int mpc_flow_targets(const mpc_targets_shape *s, const float *raw_flow, const float *id_mask,
+                     float *flow, uint8_t *flow_valid, float *id_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

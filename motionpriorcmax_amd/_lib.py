@@ -41,7 +41,8 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd',
            'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter',
            'mpc_val_metrics_workspace_bytes', 'mpc_val_metrics',
-           'mpc_corr_lookup_supported', 'mpc_corr_lookup_fwd', 'mpc_corr_lookup_bwd']
+           'mpc_corr_lookup_supported', 'mpc_corr_lookup_fwd', 'mpc_corr_lookup_bwd',
+           'mpc_flow_targets_supported', 'mpc_flow_targets']
 
 
 class Shape(ctypes.Structure):
@@ -98,6 +99,13 @@ class CorrDesc(ctypes.Structure):
                [(k, ctypes.c_int32 * CORR_MAX_LEVELS) for k in ('level_h', 'level_w', 'level_n')] + \
                [('level_target', (ctypes.c_uint8 * CORR_MAX_TARGETS) * CORR_MAX_LEVELS),
                 ('level', ctypes.c_void_p * CORR_MAX_LEVELS), ('grad_level', ctypes.c_void_p * CORR_MAX_LEVELS)]
+
+
+TARGETS_EVIMO2, TARGETS_MULTIFLOW = 0, 1        # include/mpcmax.h: mpc_targets_shape.mode
+
+
+class TargetsShape(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ('B', 'S', 'H', 'W', 'Ho', 'Wo', 'mode', 'has_id')]
 
 
 # key order of mpc_val_metrics, mirror of the MPC_VAL_* macros of include/mpcmax.h
@@ -213,6 +221,9 @@ def lib():
     L.mpc_corr_lookup_supported.argtypes = [cdp]
     L.mpc_corr_lookup_fwd.argtypes = [cdp, vp, vp, vp, vp, vp]
     L.mpc_corr_lookup_bwd.argtypes = [cdp, vp, vp, vp, vp, vp, vp, vp]
+    tsp = ctypes.POINTER(TargetsShape)
+    L.mpc_flow_targets_supported.argtypes = [tsp]
+    L.mpc_flow_targets.argtypes = [tsp, vp, vp, vp, vp, vp, vp]
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

@@ -20,6 +20,7 @@
 //     The write pass normalises the four source values as it reads them and stores Ho x Wo rows; the H x W grid never exists in
 //     HBM.  Without a resize the same code runs with lo / hi = the strip's own rows.
 #include "strip_buckets.h"
+#include "resize_src.h"
 
 #define REPR_PER_THREAD 2
 #define REPR_SLOTS 6          // buckets one event can vote into: 2 channels x up to 3 strips (rows y0, y0 + 1 across a shared row)
@@ -38,17 +39,7 @@ struct ReprLayout : StripBuckets {
     float *stat;          // [B][4]      mean, std (0: subtract only)
 };
 
-// source index and weight of output index j along an axis of `size` entries: F.interpolate(mode='bilinear',
-// align_corners=False) -- max(scale * (j + 0.5) - 0.5, 0), the neighbour clamped to the last entry
-__host__ __device__ __forceinline__ void repr_src(float scale, int j, int size, int resize, int &i0, int &i1, float &lam) {
-    if (!resize) { i0 = i1 = j; lam = 0.f; return; }
-    float r = scale * ((float)j + 0.5f) - 0.5f;
-    if (r < 0.f) r = 0.f;
-    i0 = (int)floorf(r);
-    if (i0 > size - 1) i0 = size - 1;
-    i1 = i0 + 1 < size ? i0 + 1 : size - 1;
-    lam = fminf(fmaxf(r - (float)i0, 0.f), 1.f);
-}
+// repr_src (source index and weight of output index j along an axis): resize_src.h, shared with flow_targets.hip
 
 // input rows of strip s: held in LDS [lo, hi), owned (statistics) [lo, own_hi); own_hi = lo of the next strip
 __host__ __device__ __forceinline__ void repr_strip_rows(const ReprGeom &g, int s, int &lo, int &hi, int &own_hi) {

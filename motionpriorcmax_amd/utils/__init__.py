@@ -8,4 +8,5 @@ from .grid_traj import trajectories_from_grid, flow_from_grid  # noqa: F401
 from . import representation  # noqa: F401  (representation.VoxelGrid is the EVIMO2 / MultiFlow class; VoxelGrid above is the DSEC one)
 from .representation import representation_grids  # noqa: F401
 from .val_metrics import trajectory_val_metrics, TrajectoryValMetrics, val_metric_keys  # noqa: F401
+from .flow_targets import flow_targets  # noqa: F401
 from .corr import corr_pyramid, CorrLookup, coords_grid, level_target_indices  # noqa: F401

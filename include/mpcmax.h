@@ -585,6 +585,30 @@ int mpc_corr_lookup_fwd(const mpc_corr_desc *desc, const float *coords, const fl
 int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coords, const float *params, const float *basis,
                         const float *grad_out, float *grad_coords, float *grad_params, void *stream);
 
+/* ---- the RAFT-spline correlation pyramid the lookup reads, built from the two feature maps on the fp32 matrix cores.
+ * Reference: src/models/raft_spline/corr.py:235-270 (CorrComputation._corr_dot_prod_1_to_N / get_correlation_volume:
+ * fmap1^T fmap2 / sqrt(D)), corr.py:106-123 (CorrData.get_downsampled: avg_pool2d 2 x 2 stride 2 per level, an odd last row /
+ * column dropped), corr.py:296-302 (level l holds the targets with more than l levels), raft.py:126 (fp32).
+ *   fmap1 [B][D][h][w], fmap2 [T][B][D][h][w]; the descriptor gives B, h, w, T, num_levels, level_h / level_w / level_n /
+ *   level_target as for the lookup; `radius`, `d` and `flags` are ignored.
+ * mpc_corr_pyramid_fwd (replaces corr.py:262-270 and :106-123): writes desc->level[l] [n_l][B*h*w][h_l][w_l] for every level,
+ *   level_l[slot][b*h*w + i][j] = (sum_c fmap1[b][c][i] * P_l(fmap2[t][b])[c][j]) / sqrt(D), P_l the 2 x 2 mean applied l times
+ *   (pooling commutes with the product), c ascending in one fma chain (v_mfma_f32_32x32x2_f32): one GEMM launch over all levels
+ *   after one small pooling launch per level >= 1; every level written once, none read back.
+ * mpc_corr_pyramid_bwd (replaces the autograd of the same lines): cotangents desc->grad_level[l] (inputs; NULL = zero),
+ *   grad_fmap1 [B][D][h][w] and / or grad_fmap2 [T][B][D][h][w] (NULL drops it and its launches); every element of a gradient is
+ *   written by a kernel (nothing to pre-zero), no atomics, every sum in a fixed order: bitwise reproducible.  desc->level[] is not read.
+ * mpc_corr_pyramid_workspace_bytes (>= 16; < 0: the error code): the caller owns `ws` (16-byte aligned); the forward's holds
+ *   the pooled feature maps, the backward's (backward != 0) also the per-level feature-map gradients and the split-k partials.
+ * Limits: D a multiple of 4 in [4, 512], T <= 16, num_levels <= 6 (else MPC_E_UNSUPPORTED); level sizes that are not
+ * (h >> l, w >> l) or are empty, D < 1, or a target list that is not ascending / nested: MPC_E_SHAPE.
+ * mpc_corr_pyramid_supported: these checks on the host alone, 0 or the error code.  B = 0 launches nothing.  */
+long long mpc_corr_pyramid_workspace_bytes(const mpc_corr_desc *desc, int D, int backward);
+int mpc_corr_pyramid_supported(const mpc_corr_desc *desc, int D);
+int mpc_corr_pyramid_fwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, void *ws, void *stream);
+int mpc_corr_pyramid_bwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, float *grad_fmap1,
+                         float *grad_fmap2, void *ws, void *stream);
+
 /* ---- the ground-truth flow targets of the EVIMO2 / MultiFlow configurations (what mpc_val_metrics takes as flow_gt / flow_valid)
  * from the raw multi-step flow, as one launch.
  * Reference: src/loader/evimo2/datasubset.py:171-188 (mode 0), src/loader/multiflow/sample.py:108-139 with downsample=True (mode 1).

@@ -42,6 +42,7 @@ EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_k
            'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter',
            'mpc_val_metrics_workspace_bytes', 'mpc_val_metrics',
            'mpc_corr_lookup_supported', 'mpc_corr_lookup_fwd', 'mpc_corr_lookup_bwd',
+           'mpc_corr_pyramid_workspace_bytes', 'mpc_corr_pyramid_supported', 'mpc_corr_pyramid_fwd', 'mpc_corr_pyramid_bwd',
            'mpc_flow_targets_supported', 'mpc_flow_targets']
 
 
@@ -221,6 +222,11 @@ def lib():
     L.mpc_corr_lookup_supported.argtypes = [cdp]
     L.mpc_corr_lookup_fwd.argtypes = [cdp, vp, vp, vp, vp, vp]
     L.mpc_corr_lookup_bwd.argtypes = [cdp, vp, vp, vp, vp, vp, vp, vp]
+    L.mpc_corr_pyramid_workspace_bytes.argtypes = [cdp, i32, i32]
+    L.mpc_corr_pyramid_workspace_bytes.restype = ctypes.c_longlong
+    L.mpc_corr_pyramid_supported.argtypes = [cdp, i32]
+    L.mpc_corr_pyramid_fwd.argtypes = [cdp, i32, vp, vp, vp, vp]
+    L.mpc_corr_pyramid_bwd.argtypes = [cdp, i32, vp, vp, vp, vp, vp, vp]
     tsp = ctypes.POINTER(TargetsShape)
     L.mpc_flow_targets_supported.argtypes = [tsp]
     L.mpc_flow_targets.argtypes = [tsp, vp, vp, vp, vp, vp, vp]

@@ -1,0 +1,494 @@
+// RAFT-spline correlation pyramid: the all-pairs volume of the reference frame against every target, and its average-pooled levels.
+//   reference: src/models/raft_spline/corr.py:235-270 (CorrComputation._corr_dot_prod_1_to_N, get_correlation_volume: the batched
+//   matmul and the division by sqrt(D)), corr.py:106-123 (CorrData.get_downsampled: avg_pool2d 2 x 2, stride 2, per level),
+//   corr.py:296-302 (which targets a level holds), raft.py:126 (fp32).
+// Pooling is linear, so level l of target t is a GEMM of its own against the l-times pooled feature map P_l of that target:
+//   level_l[slot][b * hw + i][j] = (sum_c fmap1[b][c][i] * P_l(fmap2[t][b])[c][j]) / sqrt(D)
+// -- every level is written once, level 0 is never read back (plain torch writes it, rewrites it for the division and reads it
+// again to pool), and the backward needs no volume-sized temporary:
+//   grad_fmap1[b][c][i] = (sum over (level, slot, j) of G_l[slot][b * hw + i][j] * P_l[t][b][c][j]) / sqrt(D)
+//   gP_l[slot][b][c][j] = (sum_i fmap1[b][c][i] * G_l[slot][b * hw + i][j]) / sqrt(D)
+//   grad_fmap2[t][b][c][y][x] = sum_l 4^-l gP_l[slot_l(t)][b][c][y >> l][x >> l]   (levels ascending; only (y >> l) < h_l, (x >> l) < w_l)
+//   k_corr_pyr_pool     P_l from P_(l-1) (P_0 = fmap2), one launch per level >= 1, into the workspace: rows [c] of pitch
+//                       round_up(h_l * w_l, 4), the pad written 0.  ((a00 + a01) + a10) + a11, then * 0.25.
+//   k_corr_pyr_gemm<M>  the one GEMM core: 128 x 128 x 32 workgroup tile, four waves of 2 x 2 tiles of 32 x 32 on
+//                       v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered fma chain per element), operands through LDS, the next k
+//                       block's global loads in flight during the MFMAs; ragged edges in m, n and k by predication.
+//                       M = 0 forward: one launch over every (level, slot, sample, tile).
+//                       M = 1 gP: one launch over every (split, level with a cotangent, slot, sample, tile); k = i.
+//                       M = 2 grad_fmap1: k = the concatenation over (level, slot, j).
+//                       Both backward products have few tiles at batch 1 (244 and 48 at the shipped shape): k is split into S1 / S
+//                       contiguous ranges of k blocks (from the sizes alone); the ranges write partials.
+//   k_corr_pyr_reduce   grad_fmap1 = (partial_0 + partial_1 + ... in index order) / sqrt(D)   (S > 1 only)
+//   k_corr_pyr_gather   grad_fmap2 from the gP_l (their partials in index order, levels ascending); writes every element (0 where
+//                       no level reaches); four x per thread and 16-byte accesses where w % 4 == 0.
+// No atomics, every sum in one fixed order: bitwise reproducible.  Volume offsets are 64-bit.
+#include <algorithm>
+#include <math.h>
+#include "common.h"
+#include "bounds.h"
+
+#define CP_MAX_D 512
+#define CP_BM 128
+#define CP_BK 32
+#define CP_LDK 33                          // row pitch of a k-contiguous operand tile [128][32] in LDS: (x + k) % 32 banks, conflict free
+#define CP_TILE (CP_BM * CP_LDK)           // floats of LDS per operand ([32][128] for an operand that is contiguous along m / n)
+#define CP_MAX_SPLIT 16
+
+typedef float cp_f32x16 __attribute__((ext_vector_type(16)));
+
+// sub-buffers of the workspace, in floats: P_l (l >= 1), gP_l (backward), split-k partials (backward)
+struct cp_plan {
+    long long p_off[MPC_CORR_MAX_LEVELS], gp_off[MPC_CORR_MAX_LEVELS], part_off, total;
+    int pitch[MPC_CORR_MAX_LEVELS];
+    int D, S, kblocks;                     // grad_fmap1: S ranges of the kblocks k blocks of the concatenation
+    int S1;                                // gP: S1 ranges of the k blocks of i; gP_l is [S1][n_l][B][D][pitch_l]
+    float sq;                              // sqrt(D) in fp32, as torch.sqrt(torch.tensor(D).float()) gives it
+};
+
+struct cp_operand {
+    const float *p;                        // at the tile's origin in m / n and the range's origin in k
+    long long ld;
+    int rem;                               // valid m / n from the origin
+    bool vec;                              // 16-byte loads allowed (pointer and pitch are multiples of 4 floats)
+};
+
+__device__ __forceinline__ float4 cp_ld4(const float *p, int n, bool vec) {
+    if (vec && n >= 4) return *reinterpret_cast<const float4 *>(p);
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (n > 0) v.x = p[0];
+    if (n > 1) v.y = p[1];
+    if (n > 2) v.z = p[2];
+    if (n > 3) v.w = p[3];
+    return v;
+}
+
+// KC = false: element (k, x) at p[k * ld + x] (contiguous along m / n); KC = true: at p[x * ld + k] (contiguous along k)
+template <bool KC>
+__device__ __forceinline__ void cp_load(float4 (&r)[4], const cp_operand &o, int kb, int k1) {
+    const int t = threadIdx.x;
+    if (o.vec && o.rem >= CP_BM && kb + CP_BK <= k1) {
+        // an interior tile (uniform branch): four 16-byte loads back to back, no predicate between them
+        const float *p = KC ? o.p + (long long)(t >> 3) * o.ld + kb + (t & 7) * 4 : o.p + (long long)(kb + (t >> 5)) * o.ld + (t & 31) * 4;
+        const long long step = (KC ? 32 : 8) * o.ld;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r[q] = *reinterpret_cast<const float4 *>(p + q * step);
+        return;
+    }
+    if (!KC) {
+        const int x4 = (t & 31) * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = kb + (t >> 5) + 8 * q;
+            r[q] = k < k1 ? cp_ld4(o.p + (long long)k * o.ld + x4, o.rem - x4, o.vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    } else {
+        const int k4 = kb + (t & 7) * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int x = (t >> 3) + 32 * q;
+            r[q] = x < o.rem ? cp_ld4(o.p + (long long)x * o.ld + k4, k1 - k4, o.vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+}
+
+template <bool KC>
+__device__ __forceinline__ void cp_store(float *s, const float4 (&r)[4]) {
+    const int t = threadIdx.x;
+    if (!KC) {
+        const int x4 = (t & 31) * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int k = (t >> 5) + 8 * q;
+            *reinterpret_cast<float4 *>(s + MPC_IDX(k * CP_BM + x4, CP_TILE - 3)) = r[q];
+        }
+    } else {
+        const int k4 = (t & 7) * 4;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float *d = s + MPC_IDX(((t >> 3) + 32 * q) * CP_LDK + k4, CP_TILE - 3);
+            d[0] = r[q].x; d[1] = r[q].y; d[2] = r[q].z; d[3] = r[q].w;
+        }
+    }
+}
+
+template <bool KC>
+__device__ __forceinline__ float cp_frag(const float *s, int x, int k) {
+    return KC ? s[MPC_IDX(x * CP_LDK + k, CP_TILE)] : s[MPC_IDX(k * CP_BM + x, CP_TILE)];
+}
+
+// acc += A^T B over k in [k0, k1) of the operands' own k axis (k0 a multiple of 4 where the operand is vectorised along k)
+template <bool AK, bool BK>
+__device__ __forceinline__ void cp_gemm_range(cp_f32x16 (&acc)[2][2], const cp_operand &A, const cp_operand &B, int k0, int k1,
+                                              float *sA, float *sB) {
+    if (k0 >= k1) return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int xa = (wv >> 1) * 64 + (lane & 31), xb = (wv & 1) * 64 + (lane & 31), kh = lane >> 5;
+    float4 ra[4], rb[4];
+    cp_load<AK>(ra, A, k0, k1);
+    cp_load<BK>(rb, B, k0, k1);
+    for (int kb = k0; kb < k1; kb += CP_BK) {
+        __syncthreads();                                   // the previous block's fragments are read
+        cp_store<AK>(sA, ra);
+        cp_store<BK>(sB, rb);
+        __syncthreads();
+        if (kb + CP_BK < k1) {
+            cp_load<AK>(ra, A, kb + CP_BK, k1);
+            cp_load<BK>(rb, B, kb + CP_BK, k1);
+        }
+#pragma unroll 4
+        for (int kk = 0; kk < CP_BK; kk += 2) {
+            const float a0 = cp_frag<AK>(sA, xa, kk + kh), a1 = cp_frag<AK>(sA, xa + 32, kk + kh);
+            const float b0 = cp_frag<BK>(sB, xb, kk + kh), b1 = cp_frag<BK>(sB, xb + 32, kk + kh);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+}
+
+// C[m][n] = acc (/ sq) for the tile's valid part; `ext`: floats of C's buffer from c on (bounds build)
+__device__ __forceinline__ void cp_write(const cp_f32x16 (&acc)[2][2], float *c, long long ldc, int mrem, int nrem, bool div, float sq,
+                                         long long ext) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    // v / sq as the division gives it, without the division sequence, where sq is a power of two (D = 4, 16, 64, 256: the
+    // reciprocal is exact and the product is the same scaling of the exponent); uniform branch
+    const bool pow2 = (__float_as_uint(sq) & 0x007fffffu) == 0;
+    const float inv = 1.f / sq;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int col = (wv & 1) * 64 + b * 32 + (lane & 31);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (wv >> 1) * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                if (row < mrem && col < nrem) {
+                    const float v = acc[a][b][r];
+                    c[MPC_IDX((long long)row * ldc + col, ext)] = !div ? v : pow2 ? v * inv : v / sq;
+                }
+            }
+        }
+}
+
+__device__ __forceinline__ bool cp_al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
+
+// the operand P_l of (level l, slot k, sample b): fmap2 itself at level 0, the workspace above
+__device__ __forceinline__ const float *cp_pooled(const mpc_corr_desc &D, const cp_plan &P, const float *fmap2, const float *ws, int l,
+                                                  int k, int b, long long &ld) {
+    const long long hw = (long long)D.h * D.w;
+    if (l == 0) { ld = hw; return fmap2 + ((long long)D.level_target[0][k] * D.B + b) * P.D * hw; }
+    ld = P.pitch[l];
+    return ws + P.p_off[l] + ((long long)k * D.B + b) * P.D * ld;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_corr_pyr_gemm(const mpc_corr_desc D, const cp_plan P, const float *__restrict__ fmap1,
+                                                       const float *__restrict__ fmap2, float *__restrict__ ws,
+                                                       float *__restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) float s_cp[];          // [CP_TILE] A | [CP_TILE] B
+    float *sA = s_cp, *sB = s_cp + CP_TILE;
+    const long long hw = (long long)D.h * D.w;
+    const int Dm = P.D;
+    cp_f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    long long bid = blockIdx.x;
+    if (MODE == 0 || MODE == 1) {
+        // (level, slot, sample, tile m, tile n), n fastest.  forward: m = i, n = j, k = c; gP: m = c, n = j, k = i
+        const int tm = MODE == 0 ? (int)((hw + CP_BM - 1) / CP_BM) : (Dm + CP_BM - 1) / CP_BM;
+        int l = 0, tn = 1, s = 0;
+        for (; l < D.num_levels; ++l) {
+            tn = (D.level_h[l] * D.level_w[l] + CP_BM - 1) / CP_BM;
+            const long long per = (long long)D.level_n[l] * D.B * tm * tn, cnt = MODE == 0 ? per : D.grad_level[l] ? per * P.S1 : 0;
+            if (bid < cnt) { s = (int)(bid / per); bid -= s * per; break; }
+            bid -= cnt;
+        }
+        MPC_EXPECT(l < D.num_levels);
+        if (l >= D.num_levels) return;
+        const int in = (int)(bid % tn); bid /= tn;
+        const int im = (int)(bid % tm); bid /= tm;
+        const int b = (int)(bid % D.B), k = (int)(bid / D.B);
+        const int N = D.level_h[l] * D.level_w[l], m0 = im * CP_BM, n0 = in * CP_BM;
+        if (MODE == 0) {
+            long long ldb;
+            const float *pb = cp_pooled(D, P, fmap2, ws, l, k, b, ldb);
+            const cp_operand A = {fmap1 + (long long)b * Dm * hw + m0, hw, (int)(hw - m0), (hw & 3) == 0 && cp_al16(fmap1)};
+            const cp_operand B = {pb + n0, ldb, N - n0, (ldb & 3) == 0 && cp_al16(pb)};
+            cp_gemm_range<false, false>(acc, A, B, 0, Dm, sA, sB);
+            const long long row0 = (long long)k * D.B * hw + (long long)b * hw + m0;
+            const long long ext = ((long long)D.level_n[l] * D.B * hw - row0) * N - n0;
+            cp_write(acc, const_cast<float *>(D.level[l]) + row0 * N + n0, N, (int)(hw - m0), N - n0, true, P.sq, ext);
+        } else {
+            const float *g = D.grad_level[l] + ((long long)k * D.B + b) * hw * N;
+            const cp_operand A = {fmap1 + ((long long)b * Dm + m0) * hw, hw, Dm - m0, (hw & 3) == 0 && cp_al16(fmap1)};
+            const cp_operand B = {g + n0, N, N - n0, (N & 3) == 0 && cp_al16(g)};
+            const int nkb = (int)((hw + CP_BK - 1) / CP_BK);
+            const int kb0 = (int)((long long)s * nkb / P.S1), kb1 = (int)((long long)(s + 1) * nkb / P.S1);
+            cp_gemm_range<true, false>(acc, A, B, kb0 * CP_BK, min((long long)kb1 * CP_BK, hw), sA, sB);
+            const long long ld = P.pitch[l], row0 = (((long long)s * D.level_n[l] + k) * D.B + b) * Dm + m0;
+            const long long ext = ((long long)P.S1 * D.level_n[l] * D.B * Dm - row0) * ld - n0;
+            cp_write(acc, ws + P.gp_off[l] + row0 * ld + n0, ld, Dm - m0, N - n0, true, P.sq, ext);
+        }
+    } else {
+        // (split, sample, tile m, tile n), n fastest: m = c, n = i, k = (level, slot, j) in k blocks [kb0, kb1) of the concatenation
+        const int tm = (Dm + CP_BM - 1) / CP_BM, tn = (int)((hw + CP_BM - 1) / CP_BM);
+        const int in = (int)(bid % tn); bid /= tn;
+        const int im = (int)(bid % tm); bid /= tm;
+        const int b = (int)(bid % D.B), s = (int)(bid / D.B);
+        const int m0 = im * CP_BM, n0 = in * CP_BM;
+        const int kb0 = (int)((long long)s * P.kblocks / P.S), kb1 = (int)((long long)(s + 1) * P.kblocks / P.S);
+        int first = 0;
+        for (int l = 0; l < D.num_levels; ++l) {
+            if (!D.grad_level[l]) continue;
+            const int N = D.level_h[l] * D.level_w[l], nkb = (N + CP_BK - 1) / CP_BK;
+            for (int k = 0; k < D.level_n[l]; ++k, first += nkb) {
+                const int lo = max(kb0, first) - first, hi = min(kb1, first + nkb) - first;
+                if (lo >= hi) continue;
+                long long lda;
+                const float *pa = cp_pooled(D, P, fmap2, ws, l, k, b, lda);
+                const float *g = D.grad_level[l] + (((long long)k * D.B + b) * hw + n0) * N;
+                const cp_operand A = {pa + (long long)m0 * lda, lda, Dm - m0, (lda & 3) == 0 && cp_al16(pa)};
+                const cp_operand B = {g, N, (int)(hw - n0), (N & 3) == 0 && cp_al16(D.grad_level[l])};
+                cp_gemm_range<true, true>(acc, A, B, lo * CP_BK, min(hi * CP_BK, N), sA, sB);
+            }
+        }
+        const long long row0 = (long long)b * Dm + m0;
+        if (P.S == 1) {
+            cp_write(acc, out + row0 * hw + n0, hw, Dm - m0, (int)(hw - n0), true, P.sq, ((long long)D.B * Dm - row0) * hw - n0);
+        } else {
+            const long long prow0 = (long long)s * D.B * Dm + row0;
+            cp_write(acc, ws + P.part_off + prow0 * hw + n0, hw, Dm - m0, (int)(hw - n0), false, 1.f,
+                     ((long long)P.S * D.B * Dm - prow0) * hw - n0);
+        }
+    }
+}
+
+// P_l [n_l][B][D][pitch_l] from P_(l-1) (fmap2 [T][B][D][hw] at l = 1): a thread per element, the pad of a row included
+__global__ __launch_bounds__(256) void k_corr_pyr_pool(const mpc_corr_desc D, const cp_plan P, const float *__restrict__ fmap2,
+                                                       float *__restrict__ ws, int l) {
+    const int pitch = P.pitch[l], wl = D.level_w[l], N = D.level_h[l] * wl;
+    const long long rows = (long long)D.level_n[l] * D.B * P.D, total = rows * pitch;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const long long row = e / pitch;
+    const int j = (int)(e - row * pitch);
+    float v = 0.f;
+    if (j < N) {
+        const int c = (int)(row % P.D);
+        const long long kb = row / P.D;
+        const int b = (int)(kb % D.B), k = (int)(kb / D.B), t = D.level_target[l][k];
+        int u = 0;
+        while (u < D.level_n[l - 1] - 1 && D.level_target[l - 1][u] != t) ++u;
+        const int ws_ = D.level_w[l - 1];
+        const float *src;
+        if (l == 1) {
+            src = fmap2 + (((long long)t * D.B + b) * P.D + c) * ((long long)D.h * D.w);
+        } else {
+            src = ws + P.p_off[l - 1] + MPC_IDX(((long long)u * D.B + b) * P.D + c, (long long)D.level_n[l - 1] * D.B * P.D) * P.pitch[l - 1];
+        }
+        const int y = j / wl, x = j - y * wl;
+        const float *q = src + (long long)(2 * y) * ws_ + 2 * x;
+        v = (((q[0] + q[1]) + q[ws_]) + q[ws_ + 1]) * 0.25f;
+    }
+    ws[P.p_off[l] + MPC_IDX(e, total)] = v;
+}
+
+__global__ __launch_bounds__(256) void k_corr_pyr_reduce(const cp_plan P, const float *__restrict__ ws, float *__restrict__ out, long long n) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n) return;
+    const float *part = ws + P.part_off;
+    float v = part[MPC_IDX(e, n * P.S)];
+    for (int s = 1; s < P.S; ++s) v = v + part[MPC_IDX((long long)s * n + e, n * P.S)];
+    out[e] = v / P.sq;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_corr_pyr_gather(const mpc_corr_desc D, const cp_plan P, const float *__restrict__ ws,
+                                                         float *__restrict__ grad_fmap2) {
+    const long long hw = (long long)D.h * D.w, total = (long long)D.T * D.B * P.D * hw;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * V;          // V = 4: w % 4 == 0, the V elements share a row
+    if (e >= total) return;
+    const long long row = e / hw;                      // (t * B + b) * D + c
+    const int pix = (int)(e - row * hw), y = pix / D.w, x = pix - y * D.w;
+    const long long tb = row / P.D;
+    const int c = (int)(row - tb * P.D), b = (int)(tb % D.B), t = (int)(tb / D.B);
+    float v[V];
+#pragma unroll
+    for (int u = 0; u < V; ++u) v[u] = 0.f;
+    float wgt = 1.f;
+    for (int l = 0; l < D.num_levels; ++l, wgt *= 0.25f) {
+        if (!D.grad_level[l]) continue;
+        int k = -1;
+        for (int u = 0; u < D.level_n[l]; ++u) if (D.level_target[l][u] == t) k = u;
+        const int yl = y >> l, wl = D.level_w[l];
+        if (k < 0 || yl >= D.level_h[l]) continue;
+        const long long rows = (long long)D.level_n[l] * D.B * P.D;
+        for (int s = 0; s < P.S1; ++s) {
+            const float *gp = ws + P.gp_off[l] + MPC_IDX(s * rows + ((long long)k * D.B + b) * P.D + c, rows * P.S1) * P.pitch[l] + yl * wl;
+            if (V == 4 && l == 0) {
+                const float4 q = *reinterpret_cast<const float4 *>(gp + MPC_IDX(x, wl - 3));
+                v[0] = v[0] + q.x; v[1 % V] = v[1 % V] + q.y; v[2 % V] = v[2 % V] + q.z; v[3 % V] = v[3 % V] + q.w;
+            } else {
+#pragma unroll
+                for (int u = 0; u < V; ++u) {
+                    const int xl = (x + u) >> l;
+                    if (xl < wl) v[u] = v[u] + wgt * gp[MPC_IDX(xl, wl)];
+                }
+            }
+        }
+    }
+    if (V == 4) *reinterpret_cast<float4 *>(grad_fmap2 + e) = make_float4(v[0], v[1 % V], v[2 % V], v[3 % V]);
+    else grad_fmap2[e] = v[0];
+}
+
+// ---- host
+
+static int cp_check(const char *who, const mpc_corr_desc *D, int Dm) {
+    if (!D) { mpc_set_error("%s: null descriptor", who); return MPC_E_NULL; }
+    if (D->B < 0 || D->h < 1 || D->w < 1 || D->T < 1 || D->num_levels < 1 || Dm < 1) {
+        mpc_set_error("%s: bad B / h / w / T / num_levels / D", who); return MPC_E_SHAPE;
+    }
+    if (Dm < 4 || Dm > CP_MAX_D || (Dm & 3) || D->T > MPC_CORR_MAX_TARGETS || D->num_levels > MPC_CORR_MAX_LEVELS) {
+        mpc_set_error("%s: D %d is not a multiple of 4 in [4, %d], T %d > %d or %d levels > %d", who, Dm, CP_MAX_D, D->T,
+                      MPC_CORR_MAX_TARGETS, D->num_levels, MPC_CORR_MAX_LEVELS);
+        return MPC_E_UNSUPPORTED;
+    }
+    for (int l = 0; l < D->num_levels; ++l) {
+        const int hl = D->level_h[l], wl = D->level_w[l], n = D->level_n[l];
+        if (hl != (D->h >> l) || wl != (D->w >> l)) { mpc_set_error("%s: level %d is %d x %d, expected %d x %d", who, l, hl, wl, D->h >> l, D->w >> l); return MPC_E_SHAPE; }
+        if (hl < 1 || wl < 1) { mpc_set_error("%s: level %d is empty (%d x %d)", who, l, hl, wl); return MPC_E_SHAPE; }
+        if (n < 1 || n > D->T || (l == 0 && n != D->T)) { mpc_set_error("%s: level %d holds %d targets of %d", who, l, n, D->T); return MPC_E_SHAPE; }
+        for (int s = 0; s < n; ++s) {
+            const int t = D->level_target[l][s];
+            bool ok = t < D->T && (s == 0 || t > D->level_target[l][s - 1]);
+            if (ok && l > 0) {
+                ok = false;
+                for (int u = 0; u < D->level_n[l - 1]; ++u) ok = ok || D->level_target[l - 1][u] == t;
+            }
+            if (!ok) { mpc_set_error("%s: the targets of level %d are not ascending / not among those of level %d", who, l, l - 1); return MPC_E_SHAPE; }
+        }
+    }
+    const long long hw = (long long)D->h * D->w;
+    if (hw > (1ll << 24) || (long long)D->B * hw > (1ll << 30) || (long long)D->B * hw * D->T * hw > (1ll << 42) ||
+        (long long)D->T * D->B * Dm * hw > (1ll << 38)) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
+    return 0;
+}
+
+// `all_levels`: size for a cotangent at every level (the workspace query); else by desc->grad_level
+static cp_plan cp_make_plan(const mpc_corr_desc *D, int Dm, int backward, bool all_levels) {
+    cp_plan P = {};
+    const long long hw = (long long)D->h * D->w;
+    P.D = Dm; P.S = 1; P.S1 = 1;
+    P.sq = sqrtf((float)Dm);
+    long long off = 0;
+    for (int l = 0; l < D->num_levels; ++l) {
+        P.pitch[l] = (D->level_h[l] * D->level_w[l] + 3) / 4 * 4;
+        if (l >= 1) { P.p_off[l] = off; off += (long long)D->level_n[l] * D->B * Dm * P.pitch[l]; }
+    }
+    if (backward) {
+        // the two backward products have few tiles at batch 1: split k until about three workgroups per CU, at least four k
+        // blocks each -- from the sizes alone (S1: as if every level had a cotangent), so that equal calls sum in equal order
+        long long tiles1 = 0;
+        for (int l = 0; l < D->num_levels; ++l)
+            tiles1 += (long long)D->level_n[l] * std::max(D->B, 1) * ((Dm + CP_BM - 1) / CP_BM) * ((D->level_h[l] * D->level_w[l] + CP_BM - 1) / CP_BM);
+        P.S1 = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(CP_MAX_SPLIT, (768 + tiles1 - 1) / tiles1), (hw + CP_BK - 1) / CP_BK / 4));
+        for (int l = 0; l < D->num_levels; ++l) {
+            P.gp_off[l] = off; off += (long long)P.S1 * D->level_n[l] * D->B * Dm * P.pitch[l];
+            if (all_levels || D->grad_level[l]) P.kblocks += D->level_n[l] * ((D->level_h[l] * D->level_w[l] + CP_BK - 1) / CP_BK);
+        }
+        const long long tiles = (long long)std::max(D->B, 1) * ((Dm + CP_BM - 1) / CP_BM) * ((hw + CP_BM - 1) / CP_BM);
+        long long S = std::min<long long>(CP_MAX_SPLIT, (768 + tiles - 1) / tiles);
+        S = std::max<long long>(1, std::min<long long>(S, P.kblocks / 4));
+        P.S = (int)S;
+        P.part_off = off;
+        if (P.S > 1) off += (long long)P.S * D->B * Dm * hw;
+    }
+    P.total = off;
+    return P;
+}
+
+extern "C" int mpc_corr_pyramid_supported(const mpc_corr_desc *desc, int D) { return cp_check(__func__, desc, D); }
+
+extern "C" long long mpc_corr_pyramid_workspace_bytes(const mpc_corr_desc *desc, int D, int backward) {
+    const int rc = cp_check(__func__, desc, D);
+    if (rc) return rc;
+    return std::max<long long>(16, cp_make_plan(desc, D, backward, true).total * (long long)sizeof(float));
+}
+
+static int cp_pool_levels(const mpc_corr_desc *desc, const cp_plan &P, const float *fmap2, float *ws, hipStream_t st) {
+    for (int l = 1; l < desc->num_levels; ++l) {
+        const long long total = (long long)desc->level_n[l] * desc->B * P.D * P.pitch[l];
+        MPC_LAUNCH(k_corr_pyr_pool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *desc, P, fmap2, ws, l);
+    }
+    return 0;
+}
+
+static long long cp_gemm_blocks(const mpc_corr_desc *D, int Dm, int mode, int split) {
+    const long long hw = (long long)D->h * D->w, tm = mode == 0 ? (hw + CP_BM - 1) / CP_BM : (Dm + CP_BM - 1) / CP_BM;
+    long long nb = 0;
+    for (int l = 0; l < D->num_levels; ++l)
+        if (mode == 0 || D->grad_level[l])
+            nb += (long long)split * D->level_n[l] * D->B * tm * ((D->level_h[l] * D->level_w[l] + CP_BM - 1) / CP_BM);
+    return nb;
+}
+
+#define CP_LDS (2 * CP_TILE * sizeof(float))
+
+extern "C" int mpc_corr_pyramid_fwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, void *ws, void *stream) {
+    int rc = cp_check(__func__, desc, D);
+    if (rc) return rc;
+    if (desc->B == 0) return 0;
+    if (!fmap1 || !fmap2 || !ws || (((uintptr_t)ws) & 15)) { mpc_set_error("%s: null argument (or a workspace that is not 16-byte aligned)", __func__); return MPC_E_NULL; }
+    for (int l = 0; l < desc->num_levels; ++l) if (!desc->level[l]) { mpc_set_error("%s: level %d is null", __func__, l); return MPC_E_NULL; }
+    const cp_plan P = cp_make_plan(desc, D, 0, true);
+    const hipStream_t st = (hipStream_t)stream;
+    cp_pool_levels(desc, P, fmap2, (float *)ws, st);
+    const long long nb = cp_gemm_blocks(desc, D, 0, 1);
+    if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+    MPC_LAUNCH(k_corr_pyr_gemm<0>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, fmap1, fmap2, (float *)ws, (float *)nullptr);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mpc_corr_pyramid_bwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, float *grad_fmap1,
+                                    float *grad_fmap2, void *ws, void *stream) {
+    int rc = cp_check(__func__, desc, D);
+    if (rc) return rc;
+    if (desc->B == 0 || (!grad_fmap1 && !grad_fmap2)) return 0;
+    if (!fmap1 || !fmap2 || !ws || (((uintptr_t)ws) & 15)) { mpc_set_error("%s: null argument (or a workspace that is not 16-byte aligned)", __func__); return MPC_E_NULL; }
+    const cp_plan P = cp_make_plan(desc, D, 1, false);
+    const hipStream_t st = (hipStream_t)stream;
+    const long long hw = (long long)desc->h * desc->w;
+    if (grad_fmap1) {
+        bool pooled = false;
+        for (int l = 1; l < desc->num_levels; ++l) pooled = pooled || desc->grad_level[l];
+        if (pooled) cp_pool_levels(desc, P, fmap2, (float *)ws, st);
+        const long long nb = (long long)P.S * desc->B * ((D + CP_BM - 1) / CP_BM) * ((hw + CP_BM - 1) / CP_BM);
+        if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+        MPC_LAUNCH(k_corr_pyr_gemm<2>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, fmap1, fmap2, (float *)ws, grad_fmap1);
+        if (P.S > 1) {
+            const long long n = (long long)desc->B * D * hw;
+            MPC_LAUNCH(k_corr_pyr_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, (const float *)ws, grad_fmap1, n);
+        }
+    }
+    if (grad_fmap2) {
+        const long long nb = cp_gemm_blocks(desc, D, 1, P.S1);
+        if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+        if (nb > 0) MPC_LAUNCH(k_corr_pyr_gemm<1>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, fmap1, fmap2, (float *)ws, (float *)nullptr);
+        const long long n = (long long)desc->T * desc->B * D * hw;
+        if ((desc->w & 3) == 0 && (((uintptr_t)grad_fmap2) & 15) == 0)
+            MPC_LAUNCH(k_corr_pyr_gather<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, *desc, P, (const float *)ws, grad_fmap2);
+        else
+            MPC_LAUNCH(k_corr_pyr_gather<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *desc, P, (const float *)ws, grad_fmap2);
+    }
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+MPC_BOUNDS_UNIT("corr_pyramid.hip")

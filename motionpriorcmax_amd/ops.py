@@ -1278,6 +1278,72 @@ class CorrLookupFn(torch.autograd.Function):
         return (gx, None, None) + tuple(gl)
 
 
+def corr_pyramid_desc(B, h, w, num_levels_per_target):
+    """The C descriptor (include/mpcmax.h: mpc_corr_desc) of a pyramid over a [B, ., h, w] grid, without level pointers."""
+    nl = [int(v) for v in num_levels_per_target]
+    tix = [[t for t, v in enumerate(nl) if v >= l + 1] for l in range(max(nl))]
+    desc = C.CorrDesc(B=int(B), h=int(h), w=int(w), T=len(nl), d=0, radius=1, num_levels=len(tix))
+    for l, ts in enumerate(tix[:C.CORR_MAX_LEVELS]):
+        desc.level_h[l], desc.level_w[l], desc.level_n[l] = h >> l, w >> l, len(ts)
+        for s, t in enumerate(ts[:C.CORR_MAX_TARGETS]):
+            desc.level_target[l][s] = t
+    return desc, tix
+
+
+def _corr_pyramid_ws(desc, D, backward, dev):
+    nws = int(C.lib().mpc_corr_pyramid_workspace_bytes(ctypes.byref(desc), D, backward))
+    if nws < 0:
+        C.check(nws, 'mpc_corr_pyramid_workspace_bytes')
+    return torch.empty((nws + 3) // 4, dtype=torch.float32, device=dev)
+
+
+class CorrPyramidFn(torch.autograd.Function):
+    """The RAFT-spline correlation pyramid (utils.corr_pyramid_fused; reference corr.py:235-270, 106-123): fmap1 [B, D, h, w],
+    fmap2 [T, B, D, h, w] (fp32, contiguous, on the GPU) and the host list of level counts -> the levels [n_l, B*h*w, 1, h_l, w_l] as a
+    tuple, one autograd node (csrc/corr_pyramid.hip: every level is its own fp32-MFMA GEMM against the pooled feature map, written
+    once).  The backward computes only the requested gradients, takes a missing level cotangent as zero, and every element of a
+    gradient it returns is written by a kernel (no memset).  No host synchronisation; bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, fmap1, fmap2, num_levels_per_target):
+        _require_gpu(fmap1, 'fmap1')
+        _require_gpu(fmap2, 'fmap2')
+        T, B, D, h, w = fmap2.shape
+        dev = fmap1.device
+        desc, tix = corr_pyramid_desc(B, h, w, num_levels_per_target)
+        levels = [torch.empty((len(ts), B * h * w, 1, h >> l, w >> l), dtype=torch.float32, device=dev) for l, ts in enumerate(tix)]
+        f1, f2 = fmap1.detach(), fmap2.detach()
+        if B > 0:
+            for l, lv in enumerate(levels):
+                desc.level[l] = lv.data_ptr()
+            ws = _corr_pyramid_ws(desc, D, 0, dev)
+            C.check(C.lib().mpc_corr_pyramid_fwd(ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(ws), _stream(dev)), 'mpc_corr_pyramid_fwd')
+        ctx.nl = [int(v) for v in num_levels_per_target]
+        ctx.set_materialize_grads(False)                              # (an unused level arrives as None, not as a volume of zeros)
+        ctx.save_for_backward(f1, f2)
+        return tuple(levels)
+
+    @staticmethod
+    def backward(ctx, *gl):
+        f1, f2 = ctx.saved_tensors
+        T, B, D, h, w = f2.shape
+        dev = f1.device
+        want1, want2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not want1 and not want2:
+            return None, None, None
+        g1 = torch.empty_like(f1) if want1 else None                  # (every element is written by a kernel)
+        g2 = torch.empty_like(f2) if want2 else None
+        if B > 0:
+            desc, _ = corr_pyramid_desc(B, h, w, ctx.nl)
+            gl = [None if g is None else _f32c(g) for g in gl]
+            for l, g in enumerate(gl):
+                desc.grad_level[l] = None if g is None else g.data_ptr()
+            ws = _corr_pyramid_ws(desc, D, 1, dev)
+            C.check(C.lib().mpc_corr_pyramid_bwd(ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(g1), _ptr(g2), _ptr(ws), _stream(dev)),
+                    'mpc_corr_pyramid_bwd')
+        return g1, g2, None
+
+
 class GridTrajFn(torch.autograd.Function):
     """The network's coefficient grid [B, S, 2k, H, W] -> `trajectories` [B, n_t, n, 2] (y, x) at the tile centres (row A3 of SURVEY.md
     8(a): reference trajectory_net.py:57-119): one kernel forward, one backward (two when `dphi` needs a gradient), csrc/grid_traj.hip,

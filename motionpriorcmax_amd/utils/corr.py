@@ -1,8 +1,11 @@
 """The RAFT-spline correlation pyramid and its lookup (reference src/models/raft_spline/corr.py:125-348, raft_spline/utils.py:4-28;
 the loop that calls it: raft.py:165-189).
 
-`corr_pyramid` is dense algebra (a batched matmul and average pools) and stays plain torch.  `CorrLookup` is the network's one gather,
-12 times per forward: on the GPU one kernel each way (ops.CorrLookupFn, csrc/corr_lookup.hip); everything the kernels do not take --
+`corr_pyramid` is the reference's batched matmul, division and average pools in plain torch: the mirror, the CPU path and the comparator.
+`corr_pyramid_fused` builds the same pyramid on the GPU as one autograd node (ops.CorrPyramidFn, csrc/corr_pyramid.hip): every level
+is its own fp32-MFMA GEMM against the pooled feature map, written once; inputs the kernels do not take -- CPU tensors, other dtypes,
+non-contiguous tensors, D that is no multiple of 4 or above 512, more than 16 targets or 6 levels -- go to `corr_pyramid`.
+`CorrLookup` is the network's one gather, 12 times per forward: on the GPU one kernel each way (ops.CorrLookupFn, csrc/corr_lookup.hip); everything the kernels do not take --
 CPU tensors, other dtypes, non-contiguous tensors, radius > 4, more than 16 targets or control points, more than 6 levels -- runs the
 plain-torch mirror below, which is written as the reference's own operator chain (coordinate tensor, normalisation to [-1, 1],
 grid_sample, cat / permute / reshape) and therefore also the comparator the probe times the kernels against."""
@@ -51,6 +54,30 @@ def corr_pyramid(fmap1, fmap2, num_levels_per_target):
         down = F.avg_pool2d(sel.reshape(-1, 1, *prev.shape[-2:]), 2, stride=2)
         levels.append(down.view(len(pick), B * h * w, 1, *down.shape[-2:]))
     return levels, tix
+
+
+def corr_pyramid_fused(fmap1, fmap2, num_levels_per_target):
+    """`corr_pyramid` with the same arguments, checks, level shapes and target_indices, built on the GPU by ops.CorrPyramidFn where the
+    kernels serve the inputs (fp32, contiguous, CUDA, D a multiple of 4 up to 512, at most 16 targets and 6 levels): one autograd
+    node with gradients to fmap1 and fmap2, no host synchronisation, bitwise reproducible.  Everything else returns
+    `corr_pyramid(...)`.  Only the single-reference form (fmap1 [B, D, h, w]: corr.py:235-260, _corr_dot_prod_1_to_N)."""
+    nl = _levels_list(num_levels_per_target)
+    f2 = fmap2[None] if fmap2.dim() == 4 else fmap2
+    if f2.dim() != 5:
+        return corr_pyramid(fmap1, fmap2, nl)
+    n, B, D, h, w = f2.shape
+    if tuple(fmap1.shape) != (B, D, h, w) or len(nl) != n:
+        raise ValueError(f'fmap1 {tuple(fmap1.shape)}, fmap2 {tuple(f2.shape)} and {len(nl)} level counts do not belong together')
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == fmap1.device for t in (fmap1, f2)):
+        return corr_pyramid(fmap1, fmap2, nl)
+    import ctypes
+    from .. import ops, _lib as C
+    if n > C.CORR_MAX_TARGETS or max(nl) > C.CORR_MAX_LEVELS:
+        return corr_pyramid(fmap1, fmap2, nl)
+    desc, tix = ops.corr_pyramid_desc(B, h, w, nl)
+    if C.lib().mpc_corr_pyramid_supported(ctypes.byref(desc), D) != 0:
+        return corr_pyramid(fmap1, fmap2, nl)
+    return list(ops.CorrPyramidFn.apply(fmap1, f2, nl)), tix
 
 
 def coords_grid(batch, ht, wd, device, dtype=torch.float32):
@@ -132,6 +159,13 @@ class CorrLookup:
                 if t >= 0:
                     num_levels_per_target[int(t)] += 1
         return cls(levels, num_levels_per_target, radius=int(block._radius))
+
+    @classmethod
+    def from_fmaps(cls, fmap1, fmap2, num_levels_per_target, radius=4):
+        """The lookup over the pyramid of `corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)`: what raft.py:129 / :161 build
+        from the two feature maps (single-reference form), with the pyramid as one autograd node back to the feature maps."""
+        levels, _ = corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)
+        return cls(levels, num_levels_per_target, radius=radius)
 
     # ---- routing
 

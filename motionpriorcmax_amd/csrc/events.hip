@@ -429,14 +429,21 @@ __global__ __launch_bounds__(1024) void k_iwe_accum(const BinLayout L, float *__
     const int g = blockIdx.x, img = g / L.NS, strip = g - img * L.NS;
     const int row0 = strip * L.SR, row1 = min(row0 + L.SR, H);
     const int npix = (row1 - row0) * W;
-    for (int i = tid; i < npix; i += 1024) s_acc[i] = 0ull;
-    __syncthreads();
+    // the count and, without waiting for it, the first four records of every thread are requested ahead of the zeroing and its
+    // barrier: one round trip where there were two.  The index is clamped to the bucket's CAPACITY, so the load stays in the
+    // bucket's own records; what comes back from beyond the count is uninitialised and is never looked at
     const int n = L.gcount[g];
     const rec3 *rec = reinterpret_cast<const rec3 *>(L.frec) + (size_t)g * L.fcap;
-    for (int r0 = tid; r0 < n; r0 += 4 * 1024) {           // four record loads in flight per thread
-        rec3 e[4];
+    rec3 e[4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) e[u] = rec[min(r0 + u * 1024, n - 1)];
+    for (int u = 0; u < 4; ++u) e[u] = rec[MPC_IDX(min(tid + u * 1024, L.fcap - 1), L.fcap)];
+    for (int i = tid; i < npix; i += 1024) s_acc[i] = 0ull;
+    __syncthreads();
+    for (int r0 = tid; r0 < n; r0 += 4 * 1024) {           // four record loads in flight per thread
+        if (r0 != tid) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) e[u] = rec[min(r0 + u * 1024, n - 1)];
+        }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (r0 + u * 1024 >= n) continue;
@@ -511,6 +518,7 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
     extern __shared__ unsigned long long s_acc[];
     LA_STAMP_DECL
     constexpr int NT = ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, NIF = ORDERED ? EV_LUT_INFLIGHT_ORD : EV_LUT_INFLIGHT;
+    constexpr int APF = ORDERED ? 0 : EV_LUT_ADD_PF;      // cells of add_term requested at the top
     const EvParams p = make_params(s);
     const int tid = threadIdx.x;
     // logical order (sample, LUT strip, bin): the bins of one strip read the same adjoint-image rows
@@ -522,6 +530,45 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
     const int g = bt * L.NCS + cst;                   // bucket id: (b*nb + it)*NCS + cstrip
     const int crow0 = cst * L.CSR, crow1 = min(crow0 + L.CSR, p.hq);
     const int ncell = (crow1 - crow0) * p.wq;
+    const int NK = p.nb * L.NCS, key = it * L.NCS + cst;
+    // Record variant: everything the workgroup reads that does not hang on a record is requested HERE -- the marker, the count, the
+    // two scalars, this thread's first APF cells of add_term and, without waiting for the count, the first NIF records of every
+    // thread -- so that one dependent pair of round trips is left (records -> adjoint taps) where there were four (marker + count
+    // -> records -> taps -> scalars + add_term); the reach side job, the zeroing of the strip and its barrier run while these are
+    // in flight.  The speculative record index is clamped to the CAPACITY (the count is not here yet): fixed-capacity buckets to
+    // the bucket's own bcap records, exact-size ones to the end of the sample's region, so no load leaves the records of the
+    // workspace whatever M and the counters hold; what comes back from beyond the count is uninitialised and is replaced by a
+    // zero record (polarity 0, cell 0, weight 0) before anything is derived from it.  (The ordered variant keeps its loads where
+    // they are used: the same treatment measured no gain there, profiles/event_chains_runs.md.)
+    float4 e[NIF];
+    float2 addv[APF > 0 ? APF : 1];
+    int mark = 0, n = 0;
+    float gcoef = 0.f, gout = 1.f;
+    const float4 *rec = L.brec;
+    int rcap = L.bcap;                                // records from `rec` to the end of the region it points into
+    const float2 *add = add_term ? reinterpret_cast<const float2 *>(add_term) + ((size_t)bt * p.hq + crow0) * p.wq : nullptr;
+    // (a layout without backward records -- MPC_F_NO_BWD_RECORDS -- has no region to read ahead from)
+    const bool spec = !ORDERED && !(p.flags & MPC_F_NO_BWD_RECORDS);
+    if (!ORDERED) {
+        mark = L.gcount[L.NF + L.NBk + 2];
+        n = L.gcount[L.NF + g];
+        // the bucket's records: behind those of the sample's buckets before it (first records: ev_prefix_block)
+        int first = 0;
+        if (L.exact) first = min(max(L.bcapcnt[L.NBk + (size_t)b * NK + key], 0), L.bcap - 1);
+        rec = L.brec + (size_t)(L.exact ? b : g) * L.bcap + first;
+        rcap = L.bcap - first;
+        // (unconditional, so that nothing waits for them here: without a region the four loads read the first counters instead)
+        const float4 *src = spec ? rec : reinterpret_cast<const float4 *>(L.gcount);
+        const int last = spec ? rcap - 1 : 0;
+#pragma unroll
+        for (int u = 0; u < NIF; ++u) e[u] = src[MPC_IDX(min(tid + u * NT, last), last + 1)];
+        gcoef = scal[MPC_SCAL_GCOEF];
+        if (grad_out) gout = grad_out[0];
+        if (add && ncell > 0) {
+#pragma unroll
+            for (int k = 0; k < APF; ++k) addv[k] = add[MPC_IDX(min(tid + k * NT, ncell - 1), ncell)];
+        }
+    }
     // mpc_focus_bwd: the KNN backward follows on the stream and needs the reach of every 16x16 tile of every (sample, bin); the
     // first workgroup of each (sample, bin) here works it out on the side (knn_device.h) -- this kernel leaves the vector pipes
     // almost idle, and the gather that follows loses two dependent round trips per workgroup (132 -> 117 us at C3)
@@ -540,24 +587,20 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
     }
     __syncthreads();
     LA_STAMP(1);
-    const bool valid = ORDERED || L.gcount[L.NF + L.NBk + 2] == EV_MARKER;
-    const int NK = p.nb * L.NCS, key = it * L.NCS + cst;
-    int n, n_pos = 0, o_pos = 0, o_neg = 0;
+    const bool valid = ORDERED || mark == EV_MARKER;
+    int n_pos = 0, o_pos = 0, o_neg = 0;
     if (ORDERED) {
         const int *ob = offsets + (size_t)b * 2 * (NK + 1);
         // (clamped: a table that does not belong to this tensor must not make the kernel read outside it)
         o_pos = min(max(ob[key], 0), p.M); n_pos = min(max(ob[key + 1] - o_pos, 0), p.M - o_pos);
         o_neg = min(max(ob[NK + 1 + key], 0), p.M);
         n = n_pos + min(max(ob[NK + 1 + key + 1] - o_neg, 0), p.M - o_neg);
-    } else n = valid ? L.gcount[L.NF + g] : 0;
+    } else if (!valid) n = 0;
     LA_STAMP(2);
-    // the bucket's records: behind those of the sample's buckets before it (first records: ev_prefix_block)
-    const float4 *rec = L.brec;
-    if (!ORDERED) rec = L.exact ? L.brec + (size_t)b * L.bcap + L.bcapcnt[L.NBk + (size_t)b * NK + key] : L.brec + (size_t)g * L.bcap;
     const float tref = (ORDERED && (p.flags & MPC_F_SCALE_BY_DT)) ? t_ref[0] : 0.f;
     // record r of this bucket: from the forward's list, or rebuilt from event row r of the ordered tensor
     auto fetch = [&](int r) -> float4 {
-        if (!ORDERED) return rec[MPC_IDX(r, L.bcap)];
+        if (!ORDERED) return rec[MPC_IDX(r, rcap)];
         const int pol = r >= n_pos ? 1 : 0;
         const int row = pol ? o_neg + (r - n_pos) : o_pos + r;
         float e[6];
@@ -574,9 +617,13 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
     };
     // four records per thread in flight: their adjoint-image gathers (the latency of this kernel) overlap
     for (int r0 = tid; r0 < n; r0 += NIF * NT) {
-        float4 e[NIF];
+        if (spec && r0 == tid) {                      // first trip: requested at the top; beyond the count: the zero record
 #pragma unroll
-        for (int u = 0; u < NIF; ++u) e[u] = fetch(min(r0 + u * NT, n - 1));
+            for (int u = 0; u < NIF; ++u) if (r0 + u * NT >= n) e[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+#pragma unroll
+            for (int u = 0; u < NIF; ++u) e[u] = fetch(min(r0 + u * NT, n - 1));
+        }
         LA_STAMP(3);
         float gy[NIF], gx[NIF];
 #pragma unroll
@@ -596,15 +643,17 @@ __global__ __launch_bounds__(ORDERED ? EV_LUT_THREADS_ORD : EV_LUT_THREADS, ORDE
     }
     __syncthreads();
     LA_STAMP(5);
-    const float gout = grad_out ? grad_out[0] : 1.f;
-    const float coef = valid ? scal[MPC_SCAL_GCOEF] * gout : __int_as_float(0x7fc00000);
+    if (ORDERED) { gout = grad_out ? grad_out[0] : 1.f; gcoef = scal[MPC_SCAL_GCOEF]; }
+    const float coef = valid ? gcoef * gout : __int_as_float(0x7fc00000);
     float2 *dst = reinterpret_cast<float2 *>(glut) + ((size_t)bt * p.hq + crow0) * p.wq;
-    const float2 *add = add_term ? reinterpret_cast<const float2 *>(add_term) + ((size_t)bt * p.hq + crow0) * p.wq : nullptr;
-    for (int i = tid; i < ncell; i += NT) {
+    auto put = [&](int i, bool have, float2 o) {
         float2 v = make_float2(coef * mpc_from_fixed((long long)s_acc[2 * i]), coef * mpc_from_fixed((long long)s_acc[2 * i + 1]));
-        if (add) { const float2 o = add[i]; v.x += gout * o.x; v.y += gout * o.y; }
+        if (add) { if (!have) o = add[i]; v.x += gout * o.x; v.y += gout * o.y; }
         dst[i] = v;
-    }
+    };
+#pragma unroll
+    for (int k = 0; k < APF; ++k) if (tid + k * NT < ncell) put(tid + k * NT, true, addv[k]);
+    for (int i = tid + APF * NT; i < ncell; i += NT) put(i, false, make_float2(0.f, 0.f));      // (strips beyond the cells held in registers)
     LA_STAMP_WRITE(tid, dst, n);
 }
 

@@ -49,6 +49,12 @@
                             // three workgroups per CU (EV_LUT_MINWAVES): 4: 55.9 us at C3 / 44.7 at C4 batch 6, 5: 56.9 / 45.7, 6: 63.0 / 51.2
 #endif
 
+#ifndef EV_LUT_ADD_PF
+#define EV_LUT_ADD_PF 6     // k_lut_accum<false>: cells of add_term a thread requests at the top of the kernel, with the records (12 VGPRs); 6 x 512
+                            // threads cover the 2 880 cells of a C3 strip, the cells beyond are read where they are used.  k_lut_accum<false>,
+                            // rocprofv3 averages: 0: 47.2 us at C3 / 40.3 at C4 batch 6, 6: 44.1 / 39.9 (parent 53.1 / 45.4)
+#endif
+
 // ---- knn.hip -------------------------------------------------------------------------------------------------------
 #ifndef KNN_BW_CH
 #define KNN_BW_CH 4       // bwd_window_fast: cells of a window row whose LDS reads are issued together

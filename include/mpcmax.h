@@ -564,6 +564,12 @@ int mpc_val_metrics(const mpc_val_shape *s, const float *params, const float *up
  * of grad_level[l] (window cells in gather form, every other element 0: nothing to pre-zero).  A NULL gradient pointer drops its
  * part.  A query's slice is read by that query alone: no atomics, every sum in a fixed order, bitwise reproducible.  One launch
  * each way; the descriptor travels by value as a kernel argument (no copy to the device).
+ * MPC_CORR_F_GRAD_ACCUM (mpc_corr_lookup_bwd only): every non-NULL grad_level[l] holds a gradient already (a call without the flag
+ * wrote it) and the window cells of this call are ADDED to it -- per in-slice window cell of each (slot, query) one read, one add of
+ * the cell's gathered cotangent (formed first, the same up-to-four-term sum in the same order) and one store; every other element
+ * is left untouched, a cell is visited once per launch, work and traffic follow the windows and not the slices.  grad_coords /
+ * grad_params are written as without the flag; with every grad_level NULL the flag changes nothing.  The calls that share a buffer
+ * must be ordered on one stream.
  * Limits: radius <= 4, d <= 16, T <= 16, num_levels <= 6 (else MPC_E_UNSUPPORTED); level sizes that are not (h >> l, w >> l), are
  * below 2 (the reference divides by w_l - 1), or a target list that is not ascending / nested: MPC_E_SHAPE.
  * mpc_corr_lookup_supported: the same checks on the host alone, 0 or the error code.  */
@@ -572,13 +578,14 @@ int mpc_val_metrics(const mpc_val_shape *s, const float *params, const float *up
 #define MPC_CORR_MAX_RADIUS 4
 typedef struct mpc_corr_desc {
     int32_t B, h, w, T, d, radius, num_levels;     /* d: control points per axis (Bezier mode; ignored with coords) */
-    int32_t flags;                                  /* diagnostics: MPC_CORR_F_LANE_PER_QUERY */
+    int32_t flags;                                  /* MPC_CORR_F_LANE_PER_QUERY (diagnostics), MPC_CORR_F_GRAD_ACCUM */
     int32_t level_h[MPC_CORR_MAX_LEVELS], level_w[MPC_CORR_MAX_LEVELS], level_n[MPC_CORR_MAX_LEVELS];
     uint8_t level_target[MPC_CORR_MAX_LEVELS][MPC_CORR_MAX_TARGETS];
     const float *level[MPC_CORR_MAX_LEVELS];
     float *grad_level[MPC_CORR_MAX_LEVELS];         /* mpc_corr_lookup_bwd only */
 } mpc_corr_desc;
 #define MPC_CORR_F_LANE_PER_QUERY 1                    /* forward: one thread per (query, entry) instead of a wave per window (probe A/B) */
+#define MPC_CORR_F_GRAD_ACCUM 2                        /* backward: add the window cells into grad_level, leave the rest of it untouched */
 int mpc_corr_lookup_supported(const mpc_corr_desc *desc);
 int mpc_corr_lookup_fwd(const mpc_corr_desc *desc, const float *coords, const float *params, const float *basis, float *out,
                         void *stream);

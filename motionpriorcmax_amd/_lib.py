@@ -92,6 +92,7 @@ class ValShape(ctypes.Structure):
 
 
 CORR_MAX_LEVELS, CORR_MAX_TARGETS, CORR_MAX_RADIUS, CORR_F_LANE_PER_QUERY = 6, 16, 4, 1        # include/mpcmax.h
+CORR_F_GRAD_ACCUM = 2                                   # mpc_corr_lookup_bwd: add the window cells into grad_level (include/mpcmax.h)
 
 
 class CorrDesc(ctypes.Structure):

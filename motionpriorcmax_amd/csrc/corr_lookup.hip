@@ -25,6 +25,13 @@
 //                               (t in index order).  Workgroups [nA, ..): a wave per (level that wants a gradient, slot, query) writes
 //                               the WHOLE slice of grad_level: a window cell gathers its up to four cotangents, every other element is
 //                               0 (no memset, no atomics: another query never touches this slice); 16-byte stores where w_l % 4 == 0.
+//   k_corr_lookup_bwd<R, 1>     MPC_CORR_F_GRAD_ACCUM: the centre role as above; workgroups [nA, ..) ADD into grad_level instead of writing
+//                               it (the 12 lookups of a forward share one gradient buffer: ops.CorrLookupSharedFn).  The forward's mapping
+//                               run backwards: a workgroup takes 64 consecutive queries of one (level that wants a gradient, slot, sample);
+//                               their [K * K][64] cotangent tile enters LDS through coalesced loads, a wave forms the (K + 1)^2 cell
+//                               gradients of its 16 queries in registers (lanes over the cells, the fill's four-term sum), THEN loads the
+//                               in-slice window cells of all 16 (row pieces of K + 1 floats, all loads in flight), adds once and stores:
+//                               work and traffic follow the windows, every other element of the slice is left as it is.
 // Sums run in index order with one rounding per multiply and per add (-ffp-contract=off): bitwise reproducible.
 #include <algorithm>
 #include "common.h"
@@ -208,13 +215,97 @@ __device__ __forceinline__ float corr_cell_grad(const float *__restrict__ g, siz
     return v;
 }
 
+// MPC_CORR_F_GRAD_ACCUM, workgroups [nA, ..): fb-th workgroup of the role -> 64 consecutive queries of one (level that wants a gradient,
+// slot, sample).  No load of the read-modify-write stream waits behind a store: the cell gradients are in registers before its first
+// load, and every load of a wave is issued before its first store (loads and stores share one in-order counter).
 template <int R>
+__device__ __forceinline__ void corr_bwd_accum(const mpc_corr_desc &D, const float *__restrict__ coords, const float *__restrict__ params,
+                                               const float *__restrict__ basis, const float *__restrict__ grad_out, float *s_mem,
+                                               long long fb, int chunks, int E) {
+    // [K * K][65] cotangent tile | [64] x0 | [64] y0 | [64] fx | [64] fy | [d] basis row
+    constexpr int K = 2 * R + 1, WN = 2 * R + 2, KK = K * K, NT = KK * CORR_TILE_LD, NW = WN * WN, NP = (NW + 63) / 64;
+    float *s_tile = s_mem, *s_fx = s_mem + NT + 128, *s_fy = s_fx + 64, *s_brow = s_fy + 64;
+    int *s_x0 = reinterpret_cast<int *>(s_mem + NT), *s_y0 = s_x0 + 64;
+    const size_t hw = (size_t)D.h * D.w, nq = (size_t)D.B * hw;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long long per = (long long)D.B * chunks;
+    int l = 0, ebase = 0;
+    for (; l < D.num_levels; ++l) {
+        if (D.grad_level[l]) {
+            const long long cnt = (long long)D.level_n[l] * per;
+            if (fb < cnt) break;
+            fb -= cnt;
+        }
+        ebase += D.level_n[l];
+    }
+    MPC_EXPECT(l < D.num_levels);
+    if (l >= D.num_levels) return;
+    const int k = (int)(fb / per);
+    const int rem = (int)(fb - (long long)k * per), b = rem / chunks, chunk = rem - b * chunks;
+    const int t = D.level_target[l][k];
+    const int hl = D.level_h[l], wl = D.level_w[l], sl = hl * wl;
+    if (!coords) {
+        for (int i = threadIdx.x; i < D.d; i += 256) s_brow[MPC_IDX(i, D.d)] = basis[t * D.d + i];
+        __syncthreads();
+    }
+    const size_t pix0 = (size_t)chunk * 64;
+    const int nlive = hw - pix0 < 64 ? (int)(hw - pix0) : 64;                         // (pix0 < hw: the first query of a chunk exists)
+    if (threadIdx.x < 64) {
+        corr_frac f = {0, 0, 0.f, 0.f};
+        if (lane < nlive) f = corr_split(corr_centre(D, coords, params, s_brow, t, b, (int)(pix0 + lane), hw), 1.f / (float)(1 << l));
+        s_x0[MPC_IDX(lane, 64)] = f.x0; s_y0[MPC_IDX(lane, 64)] = f.y0; s_fx[MPC_IDX(lane, 64)] = f.fx; s_fy[MPC_IDX(lane, 64)] = f.fy;
+    }
+    // the cotangent tile, coalesced along w; a lane past the grid reads the chunk's first query (never used)
+    const float *g = grad_out + ((size_t)b * E + ebase + k) * KK * hw + pix0 + (lane < nlive ? lane : 0);
+    for (int c = wv; c < KK; c += 4) s_tile[MPC_IDX(c * CORR_TILE_LD + lane, NT)] = g[(size_t)c * hw];
+    __syncthreads();
+    // the cell gradients of this wave's 16 queries: lanes over the (K + 1)^2 cells; off < 0: outside the slice or past the grid
+    float v[16][NP];
+    int off[16][NP];
+#pragma unroll
+    for (int qi = 0; qi < 16; ++qi) {
+        const int ql = wv * 16 + qi;
+        const int x0 = s_x0[MPC_IDX(ql, 64)], y0 = s_y0[MPC_IDX(ql, 64)];
+        const float fx = s_fx[MPC_IDX(ql, 64)], fy = s_fy[MPC_IDX(ql, 64)];
+        const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int c = lane + 64 * p, ci = c / WN, cj = c - ci * WN;
+            const int yy = y0 - R + ci, xx = x0 - R + cj;
+            const bool ok = ql < nlive && c < NW && yy >= 0 && yy < hl && xx >= 0 && xx < wl;
+            // the fill's sum (corr_cell_grad), its cotangents read from the tile: the same terms in the same order
+            float a = 0.f;
+            if (ok) {
+                if (ci < K && cj < K) a = a + s_tile[MPC_IDX((ci * K + cj) * CORR_TILE_LD + ql, NT)] * w00;
+                if (ci < K && cj >= 1) a = a + s_tile[MPC_IDX((ci * K + cj - 1) * CORR_TILE_LD + ql, NT)] * w01;
+                if (ci >= 1 && cj < K) a = a + s_tile[MPC_IDX(((ci - 1) * K + cj) * CORR_TILE_LD + ql, NT)] * w10;
+                if (ci >= 1 && cj >= 1) a = a + s_tile[MPC_IDX(((ci - 1) * K + cj - 1) * CORR_TILE_LD + ql, NT)] * w11;
+            }
+            v[qi][p] = a;
+            off[qi][p] = ok ? ql * sl + yy * wl + xx : -1;
+        }
+    }
+    // read, add once, store: every load first (a cell outside reads the chunk's first element, which exists, and stores nothing)
+    float *gs = D.grad_level[l] + ((size_t)k * nq + (size_t)b * hw + pix0) * (size_t)sl;
+    float o[16][NP];
+#pragma unroll
+    for (int qi = 0; qi < 16; ++qi)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) o[qi][p] = gs[MPC_IDX(off[qi][p] < 0 ? 0 : off[qi][p], (long long)nlive * sl)];
+#pragma unroll
+    for (int qi = 0; qi < 16; ++qi)
+#pragma unroll
+        for (int p = 0; p < NP; ++p)
+            if (off[qi][p] >= 0) gs[MPC_IDX(off[qi][p], (long long)nlive * sl)] = o[qi][p] + v[qi][p];
+}
+
+template <int R, int ACC = 0>
 __global__ __launch_bounds__(256) void k_corr_lookup_bwd(const mpc_corr_desc D, const float *__restrict__ coords,
                                                          const float *__restrict__ params, const float *__restrict__ basis,
                                                          const float *__restrict__ grad_out, float *__restrict__ grad_coords,
                                                          float *__restrict__ grad_params, int chunks, int nA, int E, int groups) {
     extern __shared__ float s_mem[];           // [T][d] basis (Bezier mode) | [E][2][64] per-entry centre gradients | [T][2][64] per-target sums;
-                                               // the slice-fill workgroups: [4][(K + 1)^2] window gradients
+                                               // the slice-fill workgroups: [4][(K + 1)^2] window gradients; ACC: corr_bwd_accum's carve-up
     constexpr int K = 2 * R + 1, WN = 2 * R + 2;
     const int T = D.T, d = D.d, nbas = coords ? 0 : T * d;
     float *s_basis = s_mem, *s_ge = s_mem + nbas, *s_gc = s_ge + E * 128;
@@ -302,6 +393,11 @@ __global__ __launch_bounds__(256) void k_corr_lookup_bwd(const mpc_corr_desc D, 
             for (int t = 0; t < T; ++t) acc = acc + s_basis[MPC_IDX(t * d + j, nbas)] * s_gc[MPC_IDX((t * 2 + axis) * 64 + lane, T * 128)];
             if (live) grad_params[((size_t)b * 2 * d + c) * hw + pix] = acc;
         }
+        return;
+    }
+    if constexpr (ACC != 0) {
+        // ---- grad_level, MPC_CORR_F_GRAD_ACCUM: the window cells are added into it, nothing else is touched (groups is unused)
+        corr_bwd_accum<R>(D, coords, params, basis, grad_out, s_mem, (long long)blockIdx.x - nA, chunks, E);
         return;
     }
     // ---- grad_level: a wave per (level that wants a gradient, slot, query) writes the whole slice
@@ -471,14 +567,28 @@ extern "C" int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coord
     const int E = corr_entries(desc);
     const int chunks = (int)((hw + 63) / 64), groups = (int)((nq + 3) / 4);
     const long long nA = (grad_coords || grad_params) ? (long long)desc->B * chunks : 0;
+    const bool accum = (desc->flags & MPC_CORR_F_GRAD_ACCUM) != 0;        // (with every grad_level NULL the flag changes nothing)
     long long nfill = 0;
-    for (int l = 0; l < desc->num_levels; ++l) if (desc->grad_level[l]) nfill += (long long)desc->level_n[l] * groups;
+    for (int l = 0; l < desc->num_levels; ++l)
+        if (desc->grad_level[l]) nfill += (long long)desc->level_n[l] * (accum ? (long long)desc->B * chunks : (long long)groups);
     if (nA + nfill == 0) return 0;
     if (nA + nfill > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
     const size_t WN = 2 * (size_t)desc->radius + 2;
     const size_t lds = std::max(((coords ? 0 : (size_t)desc->T * desc->d) + ((size_t)E + desc->T) * 128) * sizeof(float),
                                 4 * WN * WN * sizeof(float));                       // (the slice-fill workgroups' window gradients)
     const dim3 grid((unsigned)(nA + nfill));
+    if (accum && nfill > 0) {
+        const size_t K = 2 * (size_t)desc->radius + 1;
+        const size_t lds_acc = std::max(lds, (K * K * CORR_TILE_LD + 256 + (coords ? 0 : (size_t)desc->d)) * sizeof(float));
+        switch (desc->radius) {
+        case 1: MPC_LAUNCH((k_corr_lookup_bwd<1, 1>), grid, dim3(256), lds_acc, (hipStream_t)stream, *desc, coords, params, basis, grad_out, grad_coords, grad_params, chunks, (int)nA, E, groups); break;
+        case 2: MPC_LAUNCH((k_corr_lookup_bwd<2, 1>), grid, dim3(256), lds_acc, (hipStream_t)stream, *desc, coords, params, basis, grad_out, grad_coords, grad_params, chunks, (int)nA, E, groups); break;
+        case 3: MPC_LAUNCH((k_corr_lookup_bwd<3, 1>), grid, dim3(256), lds_acc, (hipStream_t)stream, *desc, coords, params, basis, grad_out, grad_coords, grad_params, chunks, (int)nA, E, groups); break;
+        default: MPC_LAUNCH((k_corr_lookup_bwd<4, 1>), grid, dim3(256), lds_acc, (hipStream_t)stream, *desc, coords, params, basis, grad_out, grad_coords, grad_params, chunks, (int)nA, E, groups); break;
+        }
+        MPC_CHECK_LAUNCH();
+        return 0;
+    }
     CORR_DISPATCH(k_corr_lookup_bwd, grid, lds, (hipStream_t)stream, *desc, coords, params, basis, grad_out, grad_coords, grad_params,
                   chunks, (int)nA, E, groups);
     MPC_CHECK_LAUNCH();

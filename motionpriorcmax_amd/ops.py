@@ -1278,6 +1278,89 @@ class CorrLookupFn(torch.autograd.Function):
         return (gx, None, None) + tuple(gl)
 
 
+class CorrGradGate:
+    """What the lookups of one `utils.CorrLookup(..., shared_grad=True)` share during a backward pass: `bufs`, one gradient buffer per
+    level (None for a level that does not require grad), allocated and wholly written by the first lookup backward of the pass, added
+    to by every later one, handed over and dropped by CorrGradGateFn.backward.  None between passes."""
+
+    def __init__(self):
+        self.bufs = None
+
+
+class CorrGradGateFn(torch.autograd.Function):
+    """The gate of `shared_grad=True`: the levels -> a one-element fp32 token that requires grad (nothing is copied, nothing is
+    launched).  Every lookup of the object takes the token as its autograd input in the place of the levels
+    (CorrLookupSharedFn), so this node's backward runs once, after the last lookup backward of the pass; it returns the shared buffers
+    as the levels' gradients (None for a level that does not require grad, and for all of them when no lookup wrote any) and drops
+    its references first: the next pass starts with a fresh whole fill.  No double backward."""
+
+    @staticmethod
+    def forward(ctx, gate, *levels):
+        ctx.gate = gate
+        ctx.set_materialize_grads(False)                              # (the lookups return no gradient for the token: None arrives)
+        return torch.empty(1, dtype=torch.float32, device=levels[0].device)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        bufs, ctx.gate.bufs = ctx.gate.bufs, None
+        n = len(ctx.needs_input_grad) - 1
+        if bufs is None:
+            return (None,) * (1 + n)
+        return (None,) + tuple(b if ctx.needs_input_grad[1 + l] else None for l, b in enumerate(bufs))
+
+
+class CorrLookupSharedFn(torch.autograd.Function):
+    """CorrLookupFn under `shared_grad=True`: the same kernels over the same level storage (`lookup.levels`), with the gate's token as the
+    autograd input in the place of the levels.  The backward writes grad_coords / grad_params as CorrLookupFn does.  When the engine is
+    going to run the gate's node in this pass (some level's gradient was asked for), the level cotangents go into the gate's buffers:
+    the first lookup backward of the pass allocates them (torch.empty_like) and runs the whole-slice fill, every later one runs
+    MPC_CORR_F_GRAD_ACCUM, which adds its window cells and touches nothing else.  The token gets no gradient (None): the edge alone keeps
+    the gate's backward after every lookup's.  One launch per backward, no host synchronisation, capturable on one stream."""
+
+    @staticmethod
+    def forward(ctx, x, basis, lookup, token):
+        _require_gpu(x, 'coords / params')
+        dev = x.device
+        bezier = basis is not None
+        d = x.shape[1] // 2 if bezier else 0
+        desc = lookup.descriptor(d)
+        K = 2 * lookup.radius + 1
+        out = torch.empty((lookup.B, lookup.num_entries * K * K, lookup.h, lookup.w), dtype=torch.float32, device=dev)
+        xd = x.detach()
+        C.check(C.lib().mpc_corr_lookup_fwd(ctypes.byref(desc), None if bezier else _ptr(xd), _ptr(xd) if bezier else None,
+                                            _ptr(basis), _ptr(out), _stream(dev)), 'mpc_corr_lookup_fwd')
+        ctx.lookup, ctx.bezier, ctx.d, ctx.gate_node = lookup, bezier, d, token.grad_fn
+        ctx.save_for_backward(xd, basis)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, basis = ctx.saved_tensors
+        g = _f32c(g)
+        dev = g.device
+        lookup, gate = ctx.lookup, ctx.lookup._gate
+        want_x = ctx.needs_input_grad[0]
+        # needs_input_grad is fixed at the forward; whether THIS pass reaches the levels is the engine's to say
+        want_l = ctx.needs_input_grad[3] and ctx.gate_node is not None and torch._C._will_engine_execute_node(ctx.gate_node)
+        if not want_x and not want_l:
+            return None, None, None, None
+        desc = C.CorrDesc.from_buffer_copy(lookup.descriptor(ctx.d))
+        gx = torch.empty_like(x) if want_x else None
+        if want_l:
+            if gate.bufs is None:                                     # the first of the pass: every element is written by the kernel
+                gate.bufs = [torch.empty_like(lv) if lv.requires_grad else None for lv in lookup.levels]
+            else:
+                desc.flags |= C.CORR_F_GRAD_ACCUM
+            for l, t in enumerate(gate.bufs):
+                desc.grad_level[l] = None if t is None else t.data_ptr()
+        bez = ctx.bezier
+        C.check(C.lib().mpc_corr_lookup_bwd(ctypes.byref(desc), None if bez else _ptr(x), _ptr(x) if bez else None, _ptr(basis), _ptr(g),
+                                            None if bez else _ptr(gx), _ptr(gx) if bez else None, _stream(dev)), 'mpc_corr_lookup_bwd')
+        return gx, None, None, None
+
+
 def corr_pyramid_desc(B, h, w, num_levels_per_target):
     """The C descriptor (include/mpcmax.h: mpc_corr_desc) of a pyramid over a [B, ., h, w] grid, without level pointers."""
     nl = [int(v) for v in num_levels_per_target]

@@ -118,9 +118,14 @@ class CorrLookup:
     align_corners=True, zero padding per tap.  `lookup_bezier(params, times)`: the reference's three lines
     `flows = bezier.get_flow_from_reference(times); coords1 = coords0 + flows; corr_block(coords1)` as one node.  Both are
     differentiable w.r.t. coords / params and every level that requires grad; only requested gradients are computed.
-    A level below 2 x 2 raises ValueError (the reference divides by size - 1 there and returns NaN)."""
+    A level below 2 x 2 raises ValueError (the reference divides by size - 1 there and returns NaN).
 
-    def __init__(self, levels, num_levels_per_target, radius=4):
+    `shared_grad=True` (opt-in; it applies where a level requires grad and the kernels serve the levels, and changes nothing
+    elsewhere): the lookups of this object add their level cotangents into ONE set of gradient buffers, which the levels receive once
+    per backward pass (ops.CorrGradGateFn / CorrLookupSharedFn), instead of one volume-sized gradient per lookup that autograd then
+    sums.  Same values; the lookups' backwards must run on one stream (they do under loss.backward() / autograd.grad)."""
+
+    def __init__(self, levels, num_levels_per_target, radius=4, shared_grad=False):
         self.levels = list(levels)
         self.num_levels_per_target = _levels_list(num_levels_per_target)
         self.target_indices = level_target_indices(self.num_levels_per_target)
@@ -142,9 +147,15 @@ class CorrLookup:
         self.num_entries = sum(len(t) for t in self.target_indices)
         self._descs = {}
         self._bases = {}
+        self.shared_grad = bool(shared_grad)
+        self._gate = self._token = None
+        if self.shared_grad and torch.is_grad_enabled() and any(lv.requires_grad for lv in self.levels) and self._levels_served():
+            from .. import ops
+            self._gate = ops.CorrGradGate()
+            self._token = ops.CorrGradGateFn.apply(self._gate, *self.levels)
 
     @classmethod
-    def from_block(cls, block, num_levels_per_target=None):
+    def from_block(cls, block, num_levels_per_target=None, shared_grad=False):
         """From the reference's CorrBlockParallelMultiTarget (duck-typed: block._corr_pyramid[i].corr, block._radius).  With
         `num_levels_per_target` (what the block's CorrComputation objects were built with, events then frames) nothing is read back
         from the device; without it the target indices are read from the block's device tensors
@@ -158,16 +169,28 @@ class CorrLookup:
             for t in tix:
                 if t >= 0:
                     num_levels_per_target[int(t)] += 1
-        return cls(levels, num_levels_per_target, radius=int(block._radius))
+        return cls(levels, num_levels_per_target, radius=int(block._radius), shared_grad=shared_grad)
 
     @classmethod
-    def from_fmaps(cls, fmap1, fmap2, num_levels_per_target, radius=4):
+    def from_fmaps(cls, fmap1, fmap2, num_levels_per_target, radius=4, shared_grad=False):
         """The lookup over the pyramid of `corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)`: what raft.py:129 / :161 build
         from the two feature maps (single-reference form), with the pyramid as one autograd node back to the feature maps."""
         levels, _ = corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)
-        return cls(levels, num_levels_per_target, radius=radius)
+        return cls(levels, num_levels_per_target, radius=radius, shared_grad=shared_grad)
 
     # ---- routing
+
+    def _levels_served(self):
+        dev = self.levels[0].device
+        return (all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in self.levels)
+                and self.radius <= _KERNEL_MAX_RADIUS and len(self.num_levels_per_target) <= _KERNEL_MAX_TARGETS
+                and len(self.levels) <= _KERNEL_MAX_LEVELS)
+
+    def _apply(self, x, basis):
+        from .. import ops
+        if self._token is not None:                                             # shared_grad: the token stands in for the levels
+            return ops.CorrLookupSharedFn.apply(x, basis, self, self._token)
+        return ops.CorrLookupFn.apply(x, basis, self, *self.levels)
 
     def _kernels_serve(self, x, d):
         tensors = [x] + self.levels
@@ -211,8 +234,7 @@ class CorrLookup:
         if coords.dim() != 5 or tuple(coords.shape) != (T, self.B, 2, self.h, self.w):
             raise ValueError(f'coords must be [T, B, 2, h, w] = {(T, self.B, 2, self.h, self.w)}, got {tuple(coords.shape)}')
         if self._kernels_serve(coords, 0):
-            from .. import ops
-            return ops.CorrLookupFn.apply(coords, None, self, *self.levels)
+            return self._apply(coords, None)
         return _lookup_mirror(self.levels, self.target_indices, self.radius, coords)
 
     __call__ = lookup
@@ -226,8 +248,7 @@ class CorrLookup:
         d = params.shape[1] // 2
         bm = self._basis(times, d, params.device, params.dtype)                  # [T, d]
         if self._kernels_serve(params, d):
-            from .. import ops
-            return ops.CorrLookupFn.apply(params, bm, self, *self.levels)
+            return self._apply(params, bm)
         flows = torch.einsum('bcdhw,td->tbchw', params.reshape(self.B, 2, d, self.h, self.w), bm)
         coords = coords_grid(self.B, self.h, self.w, params.device, params.dtype)[None] + flows
         return _lookup_mirror(self.levels, self.target_indices, self.radius, coords)

@@ -111,12 +111,23 @@ def test_fused_equals_separate_launches(bands, smooth_type, norm, monkeypatch):
     assert one['gf'] is not None and one['gf'].abs().max() > 0
 
 
-@pytest.mark.parametrize('shape', [(100, 172), (48, 60), (132, 484)])
+@pytest.mark.parametrize('shape', [(100, 172), (48, 60), (132, 484), (33, 57), (17, 113)])
 @pytest.mark.parametrize('smooth_type', ['on_flow_to_tref', 'on_flow_to_next'])
 def test_odd_sizes(shape, smooth_type, monkeypatch):
-    """Partial tiles in both directions of both grids; one tile column (wq = 15), several (wq = 121 = 2 * 60 + 1)."""
+    """Partial tiles in both directions of both grids; one tile column (wq = 15), several (wq = 121 = 2 * 60 + 1); and two
+    shapes that tests/test_gpu_contrast_cases.py holds element by element against float64: 33 x 57 (one row and one column past a
+    band and a 56-column group) and 17 x 113 (three column groups)."""
     one, _ = _both(shape, 3, 6000, 5, 5, monkeypatch, smooth_type=smooth_type)
     _assert_fused(one)
+
+
+@pytest.mark.parametrize('smooth_type', ['on_flow_to_tref', 'on_flow_to_next'])
+def test_single_lut_column(smooth_type, monkeypatch):
+    """32-pixel cells on a 40 x 32 image: hq = 2, wq = 1 -- a smoothness workgroup with one cell column, both neighbours the
+    zero padding."""
+    one, _ = _both((40, 32), 3, 6000, 5, 5, monkeypatch, smooth_type=smooth_type, lut_superpixel_size=32)
+    _assert_fused(one)
+    assert one['gf'] is not None and one['gf'].abs().max() > 0
 
 
 def test_fused_step_launches_neither_separate_kernel(monkeypatch):

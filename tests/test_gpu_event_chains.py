@@ -5,7 +5,8 @@ stage entry points are driven here with a zero-flow LUT and events placed so tha
 bucket receive exactly n records and every other bucket none, n at the edges of that load pattern.
 
 Every case is compared with the CPU oracle at the tolerances of tests/test_gpu_parity.py for the same stage outputs
-(raw IWE: atol 1e-5 * max, d/dLUT: relative L2 1e-4), and bit for bit between two runs and between the time-ordered
+(raw IWE: atol 1e-5 * max, d/dLUT: relative L2 1e-4), element by element with the float64 reference of tests/event_cases.py under its
+counted rounding bound, and bit for bit between two runs and between the time-ordered
 and the bucket-ordered layout of the same events (integer accumulators: no order dependence)."""
 import os
 import subprocess
@@ -14,6 +15,8 @@ import sys
 import numpy as np
 import pytest
 import torch
+
+import event_cases as E
 
 pytestmark = pytest.mark.gpu
 
@@ -103,6 +106,16 @@ def _check(n, M, num_pos, split=True, sample=0):
     err = _rel_l2(g0.cpu().numpy(), want.numpy())
     print(f'n {n} M {M} num_pos {num_pos} split {split}: d/dLUT rel L2 {err:.3e}')
     assert err < 1e-4
+    # every element against the float64 reference, under the bound counted from the kernels' roundings (tests/event_cases.py)
+    c = E.Case(name='chain', H=IMG[0], W=IMG[1], sp=SP, nb=NB, T=1, B=B, split=split, scale_dt=True, mask=True,
+               num_pos=num_pos if split else M, ev=ev.numpy(), kind=(ev[..., 5] != 0).long().numpy(), kinds=['pad', 'live'],
+               lut=np.zeros((B, NB, hq, wq, 1, 2), dtype=np.float32), gimg=gimg.numpy(), add=add.numpy(),
+               t_ref=np.array([T_REF], dtype=np.float32))
+    f = E.reference_fwd(c)
+    E.check(f'n {n} M {M}', 'fwd', raw.cpu().numpy(), f['ref'], f['allow'], c, f['prov'])
+    for with_add, got in ((False, g0), (True, g1)):
+        r = E.reference_bwd(c, add=with_add, gcoef=GCOEF, gout=GOUT)
+        E.check(f'n {n} M {M}', f'bwd add_term={with_add}', got.cpu().numpy(), r['ref'], r['allow'], c, r['prov'])
     # add_term: one product and one sum per element on top of the same value (no contraction in either place)
     assert torch.equal(g1, g0 + GOUT * ad)
     # two runs

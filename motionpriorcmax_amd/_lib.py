@@ -27,25 +27,6 @@ E_NULL, E_SHAPE, E_UNSUPPORTED = -1, -2, -4        # include/mpcmax.h
 BASIS_POLY, BASIS_DCT, BASIS_MATRIX = 0, 1, 2
 SCAL_LOSS, SCAL_FOCUS, SCAL_SMOOTH, SCAL_VAL, SCAL_GCOEF, SCAL_COUNT = 0, 1, 2, 3, 4, 8
 
-EXPORTS = ['mpc_version', 'mpc_last_error_string', 'mpc_workspace_bytes', 'mpc_knn_lut_fwd',
-           'mpc_knn_lut_bwd', 'mpc_event_splat_fwd', 'mpc_contrast_fwd', 'mpc_lut_smooth',
-           'mpc_finalize', 'mpc_event_splat_bwd', 'mpc_scale', 'mpc_voxel_workspace_bytes', 'mpc_voxel_grid', 'mpc_ingest_workspace_bytes', 'mpc_ingest_count',
-           'mpc_ingest_scatter', 'mpc_dense_flow', 'mpc_flow_error_workspace_bytes', 'mpc_flow_error',
-           'mpc_knn_fail_list_offset', 'mpc_knn_list_offsets', 'mpc_knn_tail_counters_offset', 'mpc_knn_state_floats', 'mpc_focus_fwd', 'mpc_focus_bwd',
-           'mpc_event_lut_strips', 'mpc_event_order_workspace_bytes', 'mpc_event_bucket_order', 'mpc_event_splat_bwd_ordered',
-           'mpc_profile_start', 'mpc_profile_stop', 'mpc_event_splat_fwd_fixed', 'mpc_iwe_from_fixed',
-           'mpc_ingest_ordered_workspace_bytes', 'mpc_ingest_scatter_ordered', 'mpc_pool2_fwd', 'mpc_pool2_bwd_add', 'mpc_event_pos_grad', 'mpc_pe_warp', 'mpc_pe_grad', 'mpc_pe_grad_ordered', 'mpc_pe_grad_ordered_supported', 'mpc_bounds_check', 'mpc_curve_traj_fwd', 'mpc_curve_traj_bwd',
-           'mpc_pe_tile_rows', 'mpc_pe_tile_rows_bwd', 'mpc_pe_basis_field', 'mpc_pe_rows_grad_finish',
-           'mpc_grid_traj_scratch_floats', 'mpc_grid_traj_fwd', 'mpc_grid_traj_bwd',
-           'mpc_repr_workspace_bytes', 'mpc_repr_grid', 'mpc_repr_norm_workspace_bytes', 'mpc_repr_norm',
-           'mpc_cvx_traj_fwd', 'mpc_cvx_traj_bwd_workspace_bytes', 'mpc_cvx_traj_bwd', 'mpc_cvx_flow_fwd',
-           'mpc_ingest_window_workspace_bytes', 'mpc_ingest_window_count', 'mpc_ingest_window_scatter',
-           'mpc_val_metrics_workspace_bytes', 'mpc_val_metrics',
-           'mpc_corr_lookup_supported', 'mpc_corr_lookup_fwd', 'mpc_corr_lookup_bwd',
-           'mpc_corr_pyramid_workspace_bytes', 'mpc_corr_pyramid_supported', 'mpc_corr_pyramid_fwd', 'mpc_corr_pyramid_bwd',
-           'mpc_flow_targets_supported', 'mpc_flow_targets']
-
-
 class Shape(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in
                 ('B', 'M', 'Mp', 'nb', 'T', 'H', 'W', 'sp', 'hq', 'wq', 'n', 'K')] + \
@@ -116,6 +97,91 @@ VAL_SINGLE, VAL_MASKED_SINGLE, VAL_MULTI, VAL_EV_MASKED_MULTI, VAL_MASKED_MULTI,
 VAL_SINGLE_KEYS = ('epe', 'ae', '1pe', '2pe', '3pe')
 VAL_MULTI_KEYS = ('epe_multi', 'ae_multi', 'T3PE', 'TEPE', 'TAE')          # then EPE_STEP00 .. at + 5
 
+vp, i32, i64, f32, cint = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_int
+sp, fb, vsp, isp, wsp, cdp, tsp = (ctypes.POINTER(t) for t in (Shape, FocusBuffers, VoxShape, IngestShape, WindowShape, CorrDesc, TargetsShape))
+fsp, esp, rsp, vlp = (ctypes.POINTER(t) for t in (FlowShape, ErrShape, ReprShape, ValShape))
+
+# The whole binding: every export of include/mpcmax.h -> (restype, argtypes), in the header's order.  lib() applies the table and
+# EXPORTS is its key list, so an export cannot exist without a signature (a symbol left without argtypes would pass 64-bit
+# pointers as C int: a wild GPU write, not a Python error).  tests/test_abi_and_host.py holds arity and return size against the header.
+SIGNATURES = {
+    'mpc_version': (cint, []),
+    'mpc_last_error_string': (ctypes.c_char_p, []),
+    'mpc_bounds_check': (cint, []),
+    'mpc_profile_start': (cint, []),
+    'mpc_profile_stop': (cint, [ctypes.c_char_p, i32, ctypes.POINTER(f32), i32]),
+    'mpc_workspace_bytes': (i64, [sp]),
+    'mpc_knn_lut_fwd': (cint, [sp] + [vp] * 7),
+    'mpc_knn_state_floats': (i64, [sp]),
+    'mpc_knn_fail_list_offset': (i64, [sp]),
+    'mpc_knn_list_offsets': (cint, [sp, ctypes.POINTER(i64)]),
+    'mpc_knn_tail_counters_offset': (i64, [sp]),
+    'mpc_knn_lut_bwd': (cint, [sp] + [vp] * 7),
+    'mpc_event_splat_fwd': (cint, [sp] + [vp] * 6),
+    'mpc_event_splat_fwd_fixed': (cint, [sp] + [vp] * 6),
+    'mpc_iwe_from_fixed': (cint, [vp, vp, i64, vp]),
+    'mpc_contrast_fwd': (cint, [sp] + [vp] * 5),
+    'mpc_lut_smooth': (cint, [sp, vp, i32, i32, f32, vp, vp, vp]),
+    'mpc_finalize': (cint, [sp, i32, i32, f32, vp, vp, vp]),
+    'mpc_event_pos_grad': (cint, [sp] + [vp] * 7),
+    'mpc_pe_warp': (cint, [sp, vp, vp, vp, i32, vp, vp, vp]),
+    'mpc_pe_grad': (cint, [sp, vp, vp, i32] + [vp] * 6),
+    'mpc_pe_grad_ordered': (cint, [sp, vp, vp, vp, i32] + [vp] * 5 + [i32, vp]),
+    'mpc_pe_grad_ordered_supported': (i32, [sp, i32]),
+    'mpc_pe_tile_rows': (cint, [vp, vp] + [i32] * 6 + [vp]),
+    'mpc_pe_tile_rows_bwd': (cint, [vp, vp] + [i32] * 6 + [vp]),
+    'mpc_pe_basis_field': (cint, [vp, vp, vp] + [i32] * 4 + [vp]),
+    'mpc_pe_rows_grad_finish': (cint, [vp, i32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
+    'mpc_event_splat_bwd': (cint, [sp] + [vp] * 10),
+    'mpc_focus_fwd': (cint, [sp, fb, vp, vp]),
+    'mpc_focus_bwd': (cint, [sp, fb] + [vp] * 6),
+    'mpc_event_lut_strips': (i32, [sp]),
+    'mpc_event_order_workspace_bytes': (i64, [sp]),
+    'mpc_event_bucket_order': (cint, [sp] + [vp] * 5),
+    'mpc_event_splat_bwd_ordered': (cint, [sp] + [vp] * 11),
+    'mpc_pool2_fwd': (cint, [vp, vp, i32, i32, i32, vp]),
+    'mpc_pool2_bwd_add': (cint, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    'mpc_scale': (cint, [vp, vp, vp, i64, vp]),
+    'mpc_voxel_workspace_bytes': (i64, [vsp]),
+    'mpc_voxel_grid': (cint, [vsp] + [vp] * 5),
+    'mpc_repr_workspace_bytes': (i64, [rsp]),
+    'mpc_repr_grid': (cint, [rsp] + [vp] * 9),
+    'mpc_repr_norm_workspace_bytes': (i64, [i32]),
+    'mpc_repr_norm': (cint, [vp, i32, i64, vp, vp]),
+    'mpc_ingest_workspace_bytes': (i64, [isp]),
+    'mpc_ingest_count': (cint, [isp] + [vp] * 8),
+    'mpc_ingest_scatter': (cint, [isp] + [vp] * 5 + [i32, i32] + [vp] * 4),
+    'mpc_ingest_ordered_workspace_bytes': (i64, [isp, sp]),
+    'mpc_ingest_scatter_ordered': (cint, [isp, sp] + [vp] * 5 + [i32, i32] + [vp] * 6),
+    'mpc_ingest_window_workspace_bytes': (i64, [wsp]),
+    'mpc_ingest_window_count': (cint, [wsp] + [vp] * 6),
+    'mpc_ingest_window_scatter': (cint, [wsp] + [vp] * 6 + [i32, i32] + [vp] * 3),
+    'mpc_dense_flow': (cint, [fsp] + [vp] * 5),
+    'mpc_flow_error_workspace_bytes': (i64, [esp]),
+    'mpc_flow_error': (cint, [esp] + [vp] * 7),
+    'mpc_curve_traj_fwd': (cint, [vp, vp, vp, f32, vp] + [i32] * 4 + [vp]),
+    'mpc_curve_traj_bwd': (cint, [vp, vp, f32, vp] + [i32] * 4 + [vp]),
+    'mpc_cvx_traj_fwd': (cint, [vp, vp, vp, f32, vp] + [i32] * 6 + [vp]),
+    'mpc_cvx_traj_bwd_workspace_bytes': (i64, [i32] * 6),
+    'mpc_cvx_traj_bwd': (cint, [vp, vp, vp, vp, f32, vp, vp] + [i32] * 6 + [vp, vp]),
+    'mpc_cvx_flow_fwd': (cint, [vp, vp, vp, f32, vp] + [i32] * 5 + [vp]),
+    'mpc_grid_traj_scratch_floats': (i64, [i32] * 6),
+    'mpc_grid_traj_fwd': (cint, [vp, vp, vp, i32, f32, i32, vp, vp] + [i32] * 7 + [vp]),
+    'mpc_grid_traj_bwd': (cint, [vp, vp, vp, i32, f32, vp, vp, vp, vp] + [i32] * 7 + [vp]),
+    'mpc_val_metrics_workspace_bytes': (i64, [vlp]),
+    'mpc_val_metrics': (cint, [vlp, vp, vp, vp, vp, f32] + [vp] * 9),
+    'mpc_corr_lookup_supported': (cint, [cdp]),
+    'mpc_corr_lookup_fwd': (cint, [cdp] + [vp] * 5),
+    'mpc_corr_lookup_bwd': (cint, [cdp] + [vp] * 7),
+    'mpc_corr_pyramid_workspace_bytes': (ctypes.c_longlong, [cdp, cint, cint]),
+    'mpc_corr_pyramid_supported': (cint, [cdp, cint]),
+    'mpc_corr_pyramid_fwd': (cint, [cdp, cint] + [vp] * 4),
+    'mpc_corr_pyramid_bwd': (cint, [cdp, cint] + [vp] * 6),
+    'mpc_flow_targets_supported': (cint, [tsp]),
+    'mpc_flow_targets': (cint, [tsp] + [vp] * 6),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -128,109 +194,9 @@ def lib():
             f'{LIB_PATH} is missing: build it with `python -m motionpriorcmax_amd.build` '
             '(hipcc --offload-arch=gfx950).  There is no CPU or PyTorch fallback for this path.')
     L = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
-    sp = ctypes.POINTER(Shape)
-    L.mpc_version.restype = ctypes.c_int
-    L.mpc_version.argtypes = []
-    L.mpc_last_error_string.restype = ctypes.c_char_p
-    L.mpc_last_error_string.argtypes = []
-    L.mpc_workspace_bytes.restype = i64
-    L.mpc_workspace_bytes.argtypes = [sp]
-    L.mpc_knn_fail_list_offset.argtypes = [sp]
-    L.mpc_knn_tail_counters_offset.argtypes = [sp]
-    L.mpc_knn_list_offsets.argtypes = [sp, ctypes.POINTER(ctypes.c_int64)]
-    L.mpc_knn_state_floats.argtypes = [sp]
-    L.mpc_knn_lut_fwd.argtypes = [sp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_knn_lut_bwd.argtypes = [sp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_event_splat_fwd.argtypes = [sp, vp, vp, vp, vp, vp, vp]
-    L.mpc_contrast_fwd.argtypes = [sp, vp, vp, vp, vp, vp]
-    L.mpc_lut_smooth.argtypes = [sp, vp, i32, i32, f32, vp, vp, vp]
-    L.mpc_finalize.argtypes = [sp, i32, i32, f32, vp, vp, vp]
-    L.mpc_event_splat_bwd.argtypes = [sp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_event_pos_grad.argtypes = [sp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_pe_warp.argtypes = [sp, vp, vp, vp, ctypes.c_int32, vp, vp, vp]
-    L.mpc_pe_grad.argtypes = [sp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, vp]
-    L.mpc_pe_grad_ordered.argtypes = [sp, vp, vp, vp, ctypes.c_int32, vp, vp, vp, vp, vp, ctypes.c_int32, vp]
-    L.mpc_pe_grad_ordered_supported.argtypes = [sp, ctypes.c_int32]
-    L.mpc_pe_grad_ordered_supported.restype = ctypes.c_int32
-    L.mpc_scale.argtypes = [vp, vp, vp, i64, vp]
-    fb = ctypes.POINTER(FocusBuffers)
-    L.mpc_focus_fwd.argtypes = [sp, fb, vp, vp]
-    L.mpc_focus_bwd.argtypes = [sp, fb, vp, vp, vp, vp, vp, vp]
-    vsp = ctypes.POINTER(VoxShape)
-    L.mpc_voxel_workspace_bytes.argtypes = [vsp]
-    L.mpc_voxel_grid.argtypes = [vsp, vp, vp, vp, vp, vp]
-    for name in EXPORTS[3:]:
-        getattr(L, name).restype = ctypes.c_int
-    L.mpc_voxel_workspace_bytes.restype = i64
-    L.mpc_knn_fail_list_offset.restype = i64
-    L.mpc_knn_tail_counters_offset.restype = i64
-    L.mpc_knn_state_floats.restype = i64
-    L.mpc_event_lut_strips.argtypes = [sp]
-    L.mpc_event_order_workspace_bytes.argtypes = [sp]
-    L.mpc_event_order_workspace_bytes.restype = i64
-    L.mpc_event_bucket_order.argtypes = [sp, vp, vp, vp, vp, vp]
-    L.mpc_event_splat_bwd_ordered.argtypes = [sp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    isp = ctypes.POINTER(IngestShape)
-    L.mpc_ingest_workspace_bytes.argtypes = [isp]
-    L.mpc_ingest_workspace_bytes.restype = i64
-    L.mpc_ingest_count.argtypes = [isp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_ingest_scatter.argtypes = [isp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    L.mpc_ingest_ordered_workspace_bytes.argtypes = [isp, sp]
-    L.mpc_ingest_ordered_workspace_bytes.restype = i64
-    L.mpc_ingest_scatter_ordered.argtypes = [isp, sp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.mpc_dense_flow.argtypes = [ctypes.POINTER(FlowShape), vp, vp, vp, vp, vp]
-    L.mpc_flow_error_workspace_bytes.argtypes = [ctypes.POINTER(ErrShape)]
-    L.mpc_flow_error_workspace_bytes.restype = i64
-    L.mpc_flow_error.argtypes = [ctypes.POINTER(ErrShape), vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_event_splat_fwd_fixed.argtypes = [sp, vp, vp, vp, vp, vp, vp]
-    L.mpc_iwe_from_fixed.argtypes = [vp, vp, i64, vp]
-    L.mpc_pool2_fwd.argtypes = [vp, vp, i32, i32, i32, vp]
-    L.mpc_pool2_bwd_add.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
-    L.mpc_profile_start.argtypes = []
-    L.mpc_bounds_check.argtypes = []
-    L.mpc_curve_traj_fwd.argtypes = [vp, vp, vp, f32, vp, i32, i32, i32, i32, vp]
-    L.mpc_curve_traj_bwd.argtypes = [vp, vp, f32, vp, i32, i32, i32, i32, vp]
-    L.mpc_pe_tile_rows.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    L.mpc_pe_tile_rows_bwd.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
-    L.mpc_pe_basis_field.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mpc_pe_rows_grad_finish.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
-    L.mpc_profile_stop.argtypes = [ctypes.c_char_p, i32, ctypes.POINTER(f32), i32]
-    L.mpc_grid_traj_scratch_floats.argtypes = [i32] * 6
-    L.mpc_grid_traj_scratch_floats.restype = i64
-    L.mpc_grid_traj_fwd.argtypes = [vp, vp, vp, i32, f32, i32, vp, vp] + [i32] * 7 + [vp]
-    L.mpc_grid_traj_bwd.argtypes = [vp, vp, vp, i32, f32, vp, vp, vp, vp] + [i32] * 7 + [vp]
-    L.mpc_repr_workspace_bytes.argtypes = [ctypes.POINTER(ReprShape)]
-    L.mpc_repr_workspace_bytes.restype = i64
-    L.mpc_repr_grid.argtypes = [ctypes.POINTER(ReprShape), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_repr_norm_workspace_bytes.argtypes = [i32]
-    L.mpc_repr_norm_workspace_bytes.restype = i64
-    L.mpc_repr_norm.argtypes = [vp, i32, i64, vp, vp]
-    L.mpc_cvx_traj_fwd.argtypes = [vp, vp, vp, f32, vp] + [i32] * 6 + [vp]
-    L.mpc_cvx_traj_bwd_workspace_bytes.argtypes = [i32] * 6
-    L.mpc_cvx_traj_bwd_workspace_bytes.restype = i64
-    L.mpc_cvx_traj_bwd.argtypes = [vp, vp, vp, vp, f32, vp, vp] + [i32] * 6 + [vp, vp]
-    L.mpc_cvx_flow_fwd.argtypes = [vp, vp, vp, f32, vp] + [i32] * 5 + [vp]
-    wsp = ctypes.POINTER(WindowShape)
-    L.mpc_ingest_window_workspace_bytes.argtypes = [wsp]
-    L.mpc_ingest_window_workspace_bytes.restype = i64
-    L.mpc_ingest_window_count.argtypes = [wsp, vp, vp, vp, vp, vp, vp]
-    L.mpc_ingest_window_scatter.argtypes = [wsp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
-    L.mpc_val_metrics_workspace_bytes.argtypes = [ctypes.POINTER(ValShape)]
-    L.mpc_val_metrics_workspace_bytes.restype = i64
-    L.mpc_val_metrics.argtypes = [ctypes.POINTER(ValShape), vp, vp, vp, vp, f32] + [vp] * 9
-    cdp = ctypes.POINTER(CorrDesc)
-    L.mpc_corr_lookup_supported.argtypes = [cdp]
-    L.mpc_corr_lookup_fwd.argtypes = [cdp, vp, vp, vp, vp, vp]
-    L.mpc_corr_lookup_bwd.argtypes = [cdp, vp, vp, vp, vp, vp, vp, vp]
-    L.mpc_corr_pyramid_workspace_bytes.argtypes = [cdp, i32, i32]
-    L.mpc_corr_pyramid_workspace_bytes.restype = ctypes.c_longlong
-    L.mpc_corr_pyramid_supported.argtypes = [cdp, i32]
-    L.mpc_corr_pyramid_fwd.argtypes = [cdp, i32, vp, vp, vp, vp]
-    L.mpc_corr_pyramid_bwd.argtypes = [cdp, i32, vp, vp, vp, vp, vp, vp]
-    tsp = ctypes.POINTER(TargetsShape)
-    L.mpc_flow_targets_supported.argtypes = [tsp]
-    L.mpc_flow_targets.argtypes = [tsp, vp, vp, vp, vp, vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.mpc_version() != 107:
         raise RuntimeError(f'libmpcmax.so version {L.mpc_version()} does not match the binding (107)')
     _lib = L

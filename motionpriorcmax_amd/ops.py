@@ -113,19 +113,21 @@ class KernelTimer:
         return self.records or {}
 
 
+def _is_current(device):
+    # the library launches on the CURRENT HIP device: the tensors' device has to be current for the call (tensors on
+    # cuda:1 while cuda:0 is current would otherwise launch in the wrong device context).  The usual case -- it is
+    # current already -- skips the guard object (~10 us of host time per call, a B = 1 step is host bound)
+    idx = device.index
+    return idx is None or idx == torch.cuda.current_device()
+
+
 class _stage:
     def __init__(self, name, device):
         self.name, self.device = name, device
 
     def __enter__(self):
-        # the library launches on the CURRENT HIP device: make the tensors' device current for the call (tensors on
-        # cuda:1 while cuda:0 is current would otherwise launch in the wrong device context).  The usual case -- it is
-        # current already -- skips the guard object (~10 us of host time per call, a B = 1 step is host bound)
-        idx = self.device.index
-        if idx is None or idx == torch.cuda.current_device():
-            self.guard = None
-        else:
-            self.guard = torch.cuda.device(self.device)
+        self.guard = None if _is_current(self.device) else torch.cuda.device(self.device)
+        if self.guard is not None:
             self.guard.__enter__()
         if STAGE_TIMER is not None:
             self.a = torch.cuda.Event(enable_timing=True)
@@ -167,6 +169,39 @@ def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _call(name, dev, *args, label=None, accept=()):
+    """THE way into a launch symbol of libmpcmax.so: `name`(*args, stream) with `dev` current, on torch's current stream of `dev`,
+    timed as stage `label` when a StageTimer is set; a return code other than 0 raises the library's error under `name`, except
+    the codes in `accept`, which are handed back (a call that may answer MPC_E_UNSUPPORTED).  The label is an interface --
+    bench.py keys its byte counts and its kernel-to-stage map on it -- and is the symbol's name unless `label` says otherwise.
+    Pointers are spelt at the call site (_ptr): this function does nothing per argument, and with no timer set and `dev` current
+    already it builds no _stage either (a B = 1 step is host bound: ~1 us per call, two calls per fused step)."""
+    fn = getattr(C.lib(), name)
+    if STAGE_TIMER is None and _is_current(dev):
+        rc = fn(*args, _stream(dev))
+    else:
+        with _stage(label or name, dev):
+            rc = fn(*args, _stream(dev))
+    if rc != 0 and rc not in accept:
+        C.check(rc, name)
+    return rc
+
+
+def _query(name, dev, *args, accept=()):
+    """A host-side question to libmpcmax.so (a size, a count, whether a shape is served: no launch, no stream) as an int, asked with
+    `dev` current: the workspace layouts follow the CU count of the device the kernels will run on (api.hip: mpc_layout).  A
+    negative answer is an error code and raises the library's error, except the codes in `accept`."""
+    fn = getattr(C.lib(), name)
+    if _is_current(dev):
+        n = int(fn(*args))
+    else:
+        with torch.cuda.device(dev):
+            n = int(fn(*args))
+    if n < 0 and n not in accept:
+        C.check(n, name)
+    return n
+
+
 def make_shape(cfg: PathConfig, B, M, Mp, n, extra_flags=0, K=None):
     hq, wq = cfg.lut_grid
     return C.Shape(B=B, M=M, Mp=Mp, nb=cfg.num_bins, T=cfg.num_tref, H=cfg.image_shape[0],
@@ -175,12 +210,7 @@ def make_shape(cfg: PathConfig, B, M, Mp, n, extra_flags=0, K=None):
 
 
 def alloc_workspace(shape: C.Shape, device) -> torch.Tensor:
-    # (sized under the device the kernels will run on: the layout follows its CU count, api.hip: mpc_layout)
-    with torch.cuda.device(device):
-        nbytes = C.lib().mpc_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_workspace_bytes')
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return torch.empty(max(_query('mpc_workspace_bytes', device, ctypes.byref(shape)), 256), dtype=torch.uint8, device=device)
 
 
 # ------------------------------------------------------------------------------------------
@@ -195,20 +225,15 @@ def knn_lut_fwd(cfg, shape, traj, ws, want_idx=False):
     flow_next = None
     if shape.flags & C.F_WANT_NEXT:
         flow_next = torch.empty((B, max(nb - 1, 0), hq, wq, 1, 2), dtype=torch.float32, device=dev)
-    state = torch.empty(int(C.lib().mpc_knn_state_floats(ctypes.byref(shape))), dtype=torch.float32, device=dev)
+    state = torch.empty(_query('mpc_knn_state_floats', dev, ctypes.byref(shape)), dtype=torch.float32, device=dev)
     idx = torch.empty((B, nb, Q, K), dtype=torch.int32, device=dev) if want_idx else None
-    with _stage('mpc_knn_lut_fwd', dev):
-        C.check(C.lib().mpc_knn_lut_fwd(ctypes.byref(shape), _ptr(traj), _ptr(flow_lut), _ptr(flow_next),
-                                        _ptr(state), _ptr(idx), _ptr(ws), _stream(dev)), 'mpc_knn_lut_fwd')
+    _call('mpc_knn_lut_fwd', dev, ctypes.byref(shape), _ptr(traj), _ptr(flow_lut), _ptr(flow_next), _ptr(state), _ptr(idx), _ptr(ws))
     return flow_lut, flow_next, state, idx
 
 
 def knn_lut_bwd(shape, traj, g_lut, g_next, state, ws):
     g_traj = torch.empty_like(traj)
-    with _stage('mpc_knn_lut_bwd', traj.device):
-        C.check(C.lib().mpc_knn_lut_bwd(ctypes.byref(shape), _ptr(traj), _ptr(g_lut), _ptr(g_next),
-                                        _ptr(state), _ptr(g_traj), _ptr(ws), _stream(traj.device)),
-                'mpc_knn_lut_bwd')
+    _call('mpc_knn_lut_bwd', traj.device, ctypes.byref(shape), _ptr(traj), _ptr(g_lut), _ptr(g_next), _ptr(state), _ptr(g_traj), _ptr(ws))
     return g_traj
 
 
@@ -216,9 +241,7 @@ def event_splat_fwd(shape, events, flow_lut, t_ref, ws):
     dev = events.device
     P = 2 if shape.flags & C.F_POLARITY_SPLIT else 1
     raw = torch.empty((shape.B * shape.T, P, shape.H, shape.W), dtype=torch.float32, device=dev)
-    with _stage('mpc_event_splat_fwd', dev):
-        C.check(C.lib().mpc_event_splat_fwd(ctypes.byref(shape), _ptr(events), _ptr(flow_lut), _ptr(t_ref),
-                                            _ptr(raw), _ptr(ws), _stream(dev)), 'mpc_event_splat_fwd')
+    _call('mpc_event_splat_fwd', dev, ctypes.byref(shape), _ptr(events), _ptr(flow_lut), _ptr(t_ref), _ptr(raw), _ptr(ws))
     return raw
 
 
@@ -227,57 +250,45 @@ def event_splat_fwd_fixed(shape, events, flow_lut, t_ref, ws):
     dev = events.device
     P = 2 if shape.flags & C.F_POLARITY_SPLIT else 1
     fixed = torch.empty((shape.B * shape.T, P, shape.H, shape.W), dtype=torch.int64, device=dev)
-    with _stage('mpc_event_splat_fwd_fixed', dev):
-        C.check(C.lib().mpc_event_splat_fwd_fixed(ctypes.byref(shape), _ptr(events), _ptr(flow_lut), _ptr(t_ref),
-                                                  _ptr(fixed), _ptr(ws), _stream(dev)), 'mpc_event_splat_fwd_fixed')
+    _call('mpc_event_splat_fwd_fixed', dev, ctypes.byref(shape), _ptr(events), _ptr(flow_lut), _ptr(t_ref), _ptr(fixed), _ptr(ws))
     return fixed
 
 
 def iwe_from_fixed(fixed):
     raw = torch.empty(fixed.shape, dtype=torch.float32, device=fixed.device)
-    with _stage('mpc_iwe_from_fixed', fixed.device):
-        C.check(C.lib().mpc_iwe_from_fixed(_ptr(fixed), _ptr(raw), fixed.numel(), _stream(fixed.device)), 'mpc_iwe_from_fixed')
+    _call('mpc_iwe_from_fixed', fixed.device, _ptr(fixed), _ptr(raw), fixed.numel())
     return raw
 
 
 def contrast_fwd(shape, raw, ws, want_grad):
     blur = torch.empty_like(raw)
     gimg = torch.empty_like(raw) if want_grad else None
-    with _stage('mpc_contrast_fwd', raw.device):
-        C.check(C.lib().mpc_contrast_fwd(ctypes.byref(shape), _ptr(raw), _ptr(blur), _ptr(gimg), _ptr(ws),
-                                         _stream(raw.device)), 'mpc_contrast_fwd')
+    _call('mpc_contrast_fwd', raw.device, ctypes.byref(shape), _ptr(raw), _ptr(blur), _ptr(gimg), _ptr(ws))
     return blur, gimg
 
 
 def lut_smooth(shape, field, nimg, Cch, weight, ws, want_grad):
     g = torch.empty_like(field) if want_grad else None
-    with _stage('mpc_lut_smooth', field.device):
-        C.check(C.lib().mpc_lut_smooth(ctypes.byref(shape), _ptr(field), nimg, Cch, float(weight), _ptr(g),
-                                       _ptr(ws), _stream(field.device)), 'mpc_lut_smooth')
+    _call('mpc_lut_smooth', field.device, ctypes.byref(shape), _ptr(field), nimg, Cch, float(weight), _ptr(g), _ptr(ws))
     return g
 
 
 def finalize(shape, smooth_nimg, smooth_C, weight, ws, device):
     scal = torch.empty(C.SCAL_COUNT, dtype=torch.float32, device=device)
-    with _stage('mpc_finalize', device):
-        C.check(C.lib().mpc_finalize(ctypes.byref(shape), smooth_nimg, smooth_C, float(weight), _ptr(scal),
-                                     _ptr(ws), _stream(device)), 'mpc_finalize')
+    _call('mpc_finalize', device, ctypes.byref(shape), smooth_nimg, smooth_C, float(weight), _ptr(scal), _ptr(ws))
     return scal
 
 
 def event_splat_bwd(shape, events, flow_lut, t_ref, gimg, scal, grad_out, g_lut, add_term, ws, offs=None):
-    with _stage('mpc_event_splat_bwd', events.device):
-        C.check(C.lib().mpc_event_splat_bwd_ordered(ctypes.byref(shape), _ptr(events), _ptr(offs), _ptr(flow_lut), _ptr(t_ref),
-                                            _ptr(gimg), _ptr(scal), _ptr(grad_out), _ptr(g_lut),
-                                            _ptr(add_term), _ptr(ws), _stream(events.device)),
-                'mpc_event_splat_bwd')
+    # (the ordered entry point serves both layouts -- offs None: the records of the forward; it keeps the stage name bench.py knows)
+    _call('mpc_event_splat_bwd_ordered', events.device, ctypes.byref(shape), _ptr(events), _ptr(offs), _ptr(flow_lut), _ptr(t_ref),
+          _ptr(gimg), _ptr(scal), _ptr(grad_out), _ptr(g_lut), _ptr(add_term), _ptr(ws), label='mpc_event_splat_bwd')
     return g_lut
 
 
 def scale(x, a):
     y = torch.empty_like(x)
-    with _stage('mpc_scale', x.device):
-        C.check(C.lib().mpc_scale(_ptr(x), _ptr(a), _ptr(y), x.numel(), _stream(x.device)), 'mpc_scale')
+    _call('mpc_scale', x.device, _ptr(x), _ptr(a), _ptr(y), x.numel())
     return y
 
 
@@ -294,22 +305,19 @@ class _Plan:
     flow_next, KNN state, smoothness gradient, raw IWE, adjoint image, scalars).  A B = 1 step is host bound: building these
     per step (two ctypes size queries, ~10 torch.empty, two struct fills) cost ~100 us of Python per direction."""
 
-    def __init__(self, cfg, B, M, Mp, n, need_grad, has_offs):
+    def __init__(self, cfg, B, M, Mp, n, need_grad, has_offs, dev):
         self.cfg = cfg
         # (bucket-ordered events: the backward reads the rows themselves -- no record region in the workspace either)
         self.shape = make_shape(cfg, B, M, Mp, n, extra_flags=0 if (need_grad and not has_offs) else C.F_NO_BWD_RECORDS)
         self.shape_ref = ctypes.byref(self.shape)
         self.need_grad = need_grad
-        nbytes = C.lib().mpc_workspace_bytes(self.shape_ref)
-        if nbytes < 0:
-            C.check(int(nbytes), 'mpc_workspace_bytes')
-        self.ws_bytes = max(int(nbytes), 256)
+        self.ws_bytes = max(_query('mpc_workspace_bytes', dev, self.shape_ref), 256)
         s = self.shape
         self.P = 2 if s.flags & C.F_POLARITY_SPLIT else 1
         self.lut_shape = (B, s.nb, s.hq, s.wq, s.T, 2)
         n_lut = B * s.nb * s.hq * s.wq * s.T * 2
         n_nxt = B * max(s.nb - 1, 0) * s.hq * s.wq * 2 if s.flags & C.F_WANT_NEXT else 0
-        n_state = int(C.lib().mpc_knn_state_floats(self.shape_ref))
+        n_state = _query('mpc_knn_state_floats', dev, self.shape_ref)
         n_gf = 0
         if cfg.smooth_weight > 0 and need_grad:
             n_gf = n_nxt if cfg.smooth_on_next else n_lut
@@ -350,15 +358,13 @@ def _plan(cfg, B, M, Mp, n, need_grad, has_offs, dev):
     if p is None:
         if len(_PLANS) > 256:
             _PLANS.clear()
-        with torch.cuda.device(dev):
-            p = _PLANS[key] = _Plan(cfg, B, M, Mp, n, need_grad, has_offs)
+        p = _PLANS[key] = _Plan(cfg, B, M, Mp, n, need_grad, has_offs, dev)
     return p
 
 
 def _focus_fwd_call(p, dev, traj, ev, tr, buf, blur, ws, offs, out3=None):
     io = p.io(buf.data_ptr(), traj.data_ptr(), ev.data_ptr(), tr.data_ptr(), blur.data_ptr(), _vp(offs), _vp(out3))
-    with _stage('mpc_focus_fwd', dev):
-        C.check(C.lib().mpc_focus_fwd(p.shape_ref, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()), _stream(dev)), 'mpc_focus_fwd')
+    _call('mpc_focus_fwd', dev, p.shape_ref, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()))
 
 
 def _focus_bwd_call(p, dev, traj, ev, tr, buf, ws, offs, grad_out, scratch, g_traj):
@@ -367,10 +373,8 @@ def _focus_bwd_call(p, dev, traj, ev, tr, buf, ws, offs, grad_out, scratch, g_tr
     io.iwe_raw = None
     g_lut = scratch.data_ptr()
     g_next = g_lut + 4 * ((p.n_glut + 63) // 64 * 64) if p.n_gnext else None
-    with _stage('mpc_focus_bwd', dev):
-        C.check(C.lib().mpc_focus_bwd(p.shape_ref, ctypes.byref(io), ctypes.c_void_p(grad_out.data_ptr()), ctypes.c_void_p(g_lut),
-                                      ctypes.c_void_p(g_next) if g_next else None, ctypes.c_void_p(g_traj.data_ptr()),
-                                      ctypes.c_void_p(ws.data_ptr()), _stream(dev)), 'mpc_focus_bwd')
+    _call('mpc_focus_bwd', dev, p.shape_ref, ctypes.byref(io), ctypes.c_void_p(grad_out.data_ptr()), ctypes.c_void_p(g_lut),
+          ctypes.c_void_p(g_next) if g_next else None, ctypes.c_void_p(g_traj.data_ptr()), ctypes.c_void_p(ws.data_ptr()))
 
 
 def _bwd_scratch_floats(p):
@@ -391,11 +395,8 @@ def event_bucket_order(cfg: PathConfig, events, num_pos):
         raise ValueError('no bucketed event layout for this configuration (num_tref > 1 or the atomic debugging path)')
     out = torch.empty_like(ev)
     offs = torch.empty((B, 2, cfg.num_bins * ncs + 1), dtype=torch.int32, device=dev)
-    nbytes = int(C.lib().mpc_event_order_workspace_bytes(ctypes.byref(shape)))
-    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-    with _stage('mpc_event_bucket_order', dev):
-        C.check(C.lib().mpc_event_bucket_order(ctypes.byref(shape), _ptr(ev), _ptr(out), _ptr(offs), _ptr(ws), _stream(dev)),
-                'mpc_event_bucket_order')
+    ws = torch.empty(max(_query('mpc_event_order_workspace_bytes', dev, ctypes.byref(shape)), 256), dtype=torch.uint8, device=dev)
+    _call('mpc_event_bucket_order', dev, ctypes.byref(shape), _ptr(ev), _ptr(out), _ptr(offs), _ptr(ws))
     return out, offs
 
 
@@ -404,12 +405,11 @@ _NCS_CACHE = {}
 
 def _lut_strips(shape, device):
     """LUT strips of the backward buckets for `shape` on `device` (the count follows the device's layout, so the query runs
-    under that device and the cache is keyed on it)."""
+    under that device and the cache is keyed on it); <= 0: no bucketed layout (a shape the library rejects included)."""
     key = (shape.B, shape.M, shape.Mp, shape.nb, shape.T, shape.H, shape.W, shape.sp, shape.flags, device.index)
     ncs = _NCS_CACHE.get(key)
     if ncs is None:
-        with torch.cuda.device(device):
-            ncs = _NCS_CACHE[key] = int(C.lib().mpc_event_lut_strips(ctypes.byref(shape)))
+        ncs = _NCS_CACHE[key] = _query('mpc_event_lut_strips', device, ctypes.byref(shape), accept=(C.E_SHAPE,))
     return ncs
 
 
@@ -456,6 +456,40 @@ def _calc_inputs(trajectories, events, t_ref, cfg, num_pos):
     return B, M, Mp, traj.shape[2], dev, traj, ev, tr
 
 
+def _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad):
+    """The loss one library call per stage: KNN LUT -> smoothness (where weighted) -> warp + vote (on `fshape`: `shape`, or without
+    backward records for bucket-ordered events) -> blur + objective -> scalars.  The route the tests hold the fused call against
+    and bench.py's instrumented pass times; the pyramid starts from it."""
+    B, T, nb = shape.B, cfg.num_tref, cfg.num_bins
+    flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
+    g_field = None
+    s_nimg = s_C = 0
+    if cfg.smooth_weight > 0:
+        if cfg.smooth_on_next:
+            field, s_nimg, s_C = flow_next, B * (nb - 1), 2
+        else:
+            field, s_nimg, s_C = flow_lut, B * nb, 2 * T
+        if s_nimg > 0:
+            g_field = lut_smooth(shape, field, s_nimg, s_C, cfg.smooth_weight, ws, need_grad)
+    raw = event_splat_fwd(fshape, ev, flow_lut, tr, ws)
+    blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
+    scal = finalize(shape, s_nimg, s_C, cfg.smooth_weight, ws, traj.device)
+    return flow_lut, state, g_field, raw, blur, gimg, scal
+
+
+def _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, g, ws, offs=None):
+    """The backward of _staged_fwd from the adjoint image to dL/dtrajectories: event backward (+ smoothness) -> KNN backward."""
+    g_next = None
+    g_lut = torch.empty_like(flow_lut)
+    if g_field is not None and not cfg.smooth_on_next:
+        event_splat_bwd(shape, ev, flow_lut, tr, gimg, scal, g, g_lut, g_field, ws, offs)   # smoothness folded in
+    else:
+        event_splat_bwd(shape, ev, flow_lut, tr, gimg, scal, g, g_lut, None, ws, offs)
+        if g_field is not None:
+            g_next = scale(g_field, g)
+    return knn_lut_bwd(shape, traj, g_lut, g_next, state, ws)
+
+
 class FocusCalcFn(torch.autograd.Function):
     """FocusLoss.calc (reference focus.py:66-113) as one differentiable op: KNN LUT -> smoothness
     -> warp + vote -> blur + objective in forward, hand-derived backward to `trajectories`."""
@@ -463,7 +497,6 @@ class FocusCalcFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, trajectories, events, t_ref, cfg: PathConfig, num_pos: int, event_offsets=None):
         B, M, Mp, n, dev, traj, ev, tr = _calc_inputs(trajectories, events, t_ref, cfg, num_pos)
-        T, nb = cfg.num_tref, cfg.num_bins
         need_grad = trajectories.requires_grad
         ctx.cfg = cfg
         ctx.set_materialize_grads(False)      # no zero-filled [B,P,H,W] gradient for the detached outputs
@@ -488,20 +521,8 @@ class FocusCalcFn(torch.autograd.Function):
         shape = make_shape(cfg, B, M, Mp, n, extra_flags=0 if need_grad else C.F_NO_BWD_RECORDS)
         ws = alloc_workspace(shape, dev)
         offs = _check_offsets(event_offsets, cfg, shape, dev)
-        flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
-        g_field = None
-        s_nimg = s_C = 0
-        if cfg.smooth_weight > 0:
-            if cfg.smooth_on_next:
-                field, s_nimg, s_C = flow_next, B * (nb - 1), 2
-            else:
-                field, s_nimg, s_C = flow_lut, B * nb, 2 * T
-            if s_nimg > 0:
-                g_field = lut_smooth(shape, field, s_nimg, s_C, cfg.smooth_weight, ws, need_grad)
         fshape = shape if offs is None else make_shape(cfg, B, M, Mp, n, extra_flags=C.F_NO_BWD_RECORDS)
-        raw = event_splat_fwd(fshape, ev, flow_lut, tr, ws)
-        blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
-        scal = finalize(shape, s_nimg, s_C, cfg.smooth_weight, ws, dev)
+        flow_lut, state, g_field, _, blur, gimg, scal = _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad)
         ctx.plan = None
         ctx.shape = shape
         ctx.offs = offs
@@ -527,16 +548,7 @@ class FocusCalcFn(torch.autograd.Function):
             return g_traj, None, None, None, None, None
         shape = ctx.shape
         traj, ev, tr, flow_lut, state, gimg, scal, g_field = ctx.saved_tensors
-        g_next = None
-        g_lut = torch.empty_like(flow_lut)
-        if g_field is not None and not cfg.smooth_on_next:
-            event_splat_bwd(shape, ev, flow_lut, tr, gimg, scal, g, g_lut, g_field, ws, offs)   # smoothness folded in
-        else:
-            event_splat_bwd(shape, ev, flow_lut, tr, gimg, scal, g, g_lut, None, ws, offs)
-            if g_field is not None:
-                g_next = scale(g_field, g)
-        g_traj = knn_lut_bwd(shape, traj, g_lut, g_next, state, ws)
-        return g_traj, None, None, None, None, None
+        return _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, g, ws, offs), None, None, None, None, None
 
 
 class PyramidFocusFn(torch.autograd.Function):
@@ -555,23 +567,14 @@ class PyramidFocusFn(torch.autograd.Function):
         need_grad = trajectories.requires_grad
         shape = make_shape(cfg, B, M, Mp, n, extra_flags=0 if need_grad else C.F_NO_BWD_RECORDS)
         ws = alloc_workspace(shape, dev)
-        flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
-        g_field, s_nimg, s_C = None, 0, 0
-        if cfg.smooth_weight > 0:
-            field, s_nimg, s_C = (flow_next, B * (cfg.num_bins - 1), 2) if cfg.smooth_on_next else (flow_lut, B * cfg.num_bins, 2 * cfg.num_tref)
-            if s_nimg > 0:
-                g_field = lut_smooth(shape, field, s_nimg, s_C, cfg.smooth_weight, ws, need_grad)
-        raw = event_splat_fwd(shape, ev, flow_lut, tr, ws)
+        flow_lut, state, g_field, raw, blur0, gimg0, scal0 = _staged_fwd(cfg, shape, shape, traj, ev, tr, ws, need_grad)
         nimg = raw.shape[0] * raw.shape[1]
-        blur0, gimg0 = contrast_fwd(shape, raw, ws, need_grad)
-        scal0 = finalize(shape, s_nimg, s_C, cfg.smooth_weight, ws, dev)
         gimgs, scals, sizes = [gimg0], [scal0], [(H, W)]
         focus_total = scal0[C.SCAL_FOCUS].clone()
         cur, h, w = raw, H, W
         for lv in range(1, levels):
             nxt = torch.empty((raw.shape[0], raw.shape[1], h // 2, w // 2), dtype=torch.float32, device=dev)
-            with _stage('mpc_pool2_fwd', dev):
-                C.check(C.lib().mpc_pool2_fwd(_ptr(cur), _ptr(nxt), nimg, h, w, _stream(dev)), 'mpc_pool2_fwd')
+            _call('mpc_pool2_fwd', dev, _ptr(cur), _ptr(nxt), nimg, h, w)
             h, w = h // 2, w // 2
             cfg_l = PathConfig(**{**cfg.__dict__, 'image_shape': (h, w), 'smooth_weight': 0.0})
             sh_l = make_shape(cfg_l, B, 0, 0, 0, K=0)
@@ -606,19 +609,9 @@ class PyramidFocusFn(torch.autograd.Function):
         # the coarser levels' adjoint images into the finer ones, each in units of its own level's 1 / val^2 coefficient
         for lv in range(L - 1, 0, -1):
             h, w = ctx.sizes[lv - 1]
-            with _stage('mpc_pool2_bwd_add', dev):
-                C.check(C.lib().mpc_pool2_bwd_add(_ptr(gimgs[lv]), ctypes.c_void_p(scals[lv].data_ptr() + 4 * C.SCAL_GCOEF), _ptr(gimgs[lv - 1]),
-                                                  ctypes.c_void_p(scals[lv - 1].data_ptr() + 4 * C.SCAL_GCOEF), ctx.nimg, h, w, _stream(dev)),
-                        'mpc_pool2_bwd_add')
-        g_lut = torch.empty_like(flow_lut)
-        g_next = None
-        if g_field is not None and not cfg.smooth_on_next:
-            event_splat_bwd(shape, ev, flow_lut, tr, gimgs[0], scals[0], g, g_lut, g_field, ws)
-        else:
-            event_splat_bwd(shape, ev, flow_lut, tr, gimgs[0], scals[0], g, g_lut, None, ws)
-            if g_field is not None:
-                g_next = scale(g_field, g)
-        return knn_lut_bwd(shape, traj, g_lut, g_next, state, ws), None, None, None, None, None
+            _call('mpc_pool2_bwd_add', dev, _ptr(gimgs[lv]), ctypes.c_void_p(scals[lv].data_ptr() + 4 * C.SCAL_GCOEF), _ptr(gimgs[lv - 1]),
+                  ctypes.c_void_p(scals[lv - 1].data_ptr() + 4 * C.SCAL_GCOEF), ctx.nimg, h, w)
+        return _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimgs[0], scals[0], g_field, g, ws), None, None, None, None, None
 
 
 class _Marker:
@@ -709,7 +702,7 @@ class StaticFocusCalcFn(torch.autograd.Function):
     def forward(ctx, trajectories, events, t_ref, cfg: PathConfig, num_pos: int, event_offsets, plans: dict, auto: bool = False):
         B, M, Mp, n, dev, traj, ev, tr = _calc_inputs(trajectories, events, t_ref, cfg, num_pos)
         need_grad = trajectories.requires_grad
-        key = (B, M, Mp, n, need_grad, dev.index, event_offsets is not None)      # shape only: every input is copied in
+        key = StaticFocusCalcFn.plan_key(trajectories, events, cfg, num_pos, event_offsets)
         sp = plans.get(key)
         if sp is None:
             if len(plans) >= 8:              # every shape holds its buffers: keep the set small
@@ -813,6 +806,46 @@ class EventFocusFn(torch.autograd.Function):
         return g_lut, None, None, None, None
 
 
+def _pe_fwd(shape, ev, coef_rows, ph, k, tr, ws, need_grad):
+    """The per-event forward core: mpc_pe_warp -> mpc_event_splat_fwd (MPC_F_NO_WARP) -> mpc_contrast_fwd -> (warped rows, blurred
+    images, adjoint images or None)."""
+    rows = torch.empty_like(ev)
+    if shape.B * shape.M > 0:                 # (an empty tensor has no pointer to hand over)
+        _call('mpc_pe_warp', ev.device, ctypes.byref(shape), _ptr(ev), _ptr(coef_rows), _ptr(ph), k, _ptr(tr), _ptr(rows))
+    raw = event_splat_fwd(shape, rows, None, tr, ws)
+    blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
+    return rows, blur, gimg
+
+
+def _pe_ordered_offsets(offsets, cfg, shape, k, dev):
+    """The checked offsets table when the ordered backward will serve this shape, else None."""
+    # bucket-ordered events: the backward accumulates per LUT strip in LDS (no global atomics) where a strip's accumulators fit
+    # (the library says whether the ordered backward serves this shape -- one copy of the rule; where it does not, an offsets
+    # table is simply not used: the atomic backward needs none)
+    if offsets is None or _query('mpc_pe_grad_ordered_supported', dev, ctypes.byref(shape), k) != 1:
+        return None
+    return _check_offsets(offsets, cfg, shape, dev)
+
+
+def _pe_pos_grad(shape, k, rows, offs, ph, tr, gimg, scal, go):
+    """d objective / d tile coefficients through the warped positions, as partial results [split, B*hq*wq, 2k] for the caller to sum:
+    the ordered kernel on bucket-ordered rows (`offs`), the atomic kernel (split = 1) otherwise."""
+    dev = rows.device
+    n = shape.B * shape.hq * shape.wq
+    if offs is not None:
+        # (a few workgroups per (sample, LUT strip), each with a share of the strip's row ranges and a partial result)
+        split = max(1, min(16, 512 // max(1, shape.B * _lut_strips(shape, dev))))
+        gp = torch.empty((split, n, 2 * k), dtype=torch.float32, device=dev)
+        rc = _call('mpc_pe_grad_ordered', dev, ctypes.byref(shape), _ptr(rows), _ptr(offs), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal),
+                   _ptr(go), _ptr(gp), split, accept=(C.E_UNSUPPORTED,))
+        if rc == 0:
+            return gp
+        # (unsupported after all: the atomic backward below serves every shape)
+    gp = torch.empty((1, n, 2 * k), dtype=torch.float32, device=dev)
+    _call('mpc_pe_grad', dev, ctypes.byref(shape), _ptr(rows), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal), _ptr(go), _ptr(gp))
+    return gp
+
+
 class PerEventBasisFocusFn(torch.autograd.Function):
     """UNPINNED extension (FocusLoss.calc_per_event_basis), fused form: tile coefficients coef_rows [B*hq*wq, 2k] (differentiable),
     events [B, M, 6], phi [B, M, k] = basis(t_ref) - basis(t_event) -> (focus_loss, iwes_blurred).
@@ -833,20 +866,10 @@ class PerEventBasisFocusFn(torch.autograd.Function):
         if tuple(cr.shape) != (B * shape.hq * shape.wq, 2 * k) or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coef_rows {tuple(cr.shape)} / phi do not match [B*hq*wq, 2k] / [B, M, k] (k <= 8 without phi)')
         ws = alloc_workspace(shape, dev)
-        rows = torch.empty_like(ev)
-        if B * M > 0:                 # (an empty tensor has no pointer to hand over)
-            with _stage('mpc_pe_warp', dev):
-                C.check(C.lib().mpc_pe_warp(ctypes.byref(shape), _ptr(ev), _ptr(cr), _ptr(ph), k, _ptr(tr), _ptr(rows), _stream(dev)), 'mpc_pe_warp')
-        raw = event_splat_fwd(shape, rows, None, tr, ws)
-        blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
+        rows, blur, gimg = _pe_fwd(shape, ev, cr, ph, k, tr, ws, need_grad)
         scal = finalize(shape, 0, 0, 0.0, ws, dev)
-        ctx.shape, ctx.k, ctx.n = shape, k, cr.shape[0]
-        # bucket-ordered events: the backward accumulates per LUT strip in LDS (no global atomics) where a strip's accumulators fit
-        # (the library says whether the ordered backward serves this shape -- one copy of the rule; where it does not, an offsets
-        # table is simply not used: the atomic backward needs none)
-        with torch.cuda.device(dev):
-            ordered = offsets is not None and int(C.lib().mpc_pe_grad_ordered_supported(ctypes.byref(shape), k)) == 1
-        offs = _check_offsets(offsets, cfg, shape, dev) if ordered else None
+        ctx.shape, ctx.k = shape, k
+        offs = _pe_ordered_offsets(offsets, cfg, shape, k, dev)
         ctx.has_offs = offs is not None
         ctx.set_materialize_grads(False)
         ctx.has_phi = ph is not None
@@ -863,21 +886,8 @@ class PerEventBasisFocusFn(torch.autograd.Function):
         if g_focus is None:
             return None, None, None, None, None, None, None
         go = _f32c(g_focus.reshape(1))
-        if ctx.has_offs:
-            # (a few workgroups per (sample, LUT strip), each with a share of the strip's row ranges and a partial result)
-            split = max(1, min(16, 512 // max(1, ctx.shape.B * _lut_strips(ctx.shape, rows.device))))
-            gp = torch.empty((split, ctx.n, 2 * ctx.k), dtype=torch.float32, device=rows.device)
-            with _stage('mpc_pe_grad_ordered', rows.device):
-                rc = C.lib().mpc_pe_grad_ordered(ctypes.byref(ctx.shape), _ptr(rows), _ptr(offs), _ptr(ph), ctx.k, _ptr(tr), _ptr(gimg),
-                                                 _ptr(scal), _ptr(go), _ptr(gp), split, _stream(rows.device))
-            if rc != C.E_UNSUPPORTED:         # (unsupported after all: the atomic backward below serves every shape)
-                C.check(rc, 'mpc_pe_grad_ordered')
-                return (gp.sum(0) if split > 1 else gp[0]), None, None, None, None, None, None
-        g = torch.empty((ctx.n, 2 * ctx.k), dtype=torch.float32, device=rows.device)
-        with _stage('mpc_pe_grad', rows.device):
-            C.check(C.lib().mpc_pe_grad(ctypes.byref(ctx.shape), _ptr(rows), _ptr(ph), ctx.k, _ptr(tr), _ptr(gimg), _ptr(scal),
-                                        _ptr(go), _ptr(g), _stream(rows.device)), 'mpc_pe_grad')
-        return g, None, None, None, None, None, None
+        gp = _pe_pos_grad(ctx.shape, ctx.k, rows, offs if ctx.has_offs else None, ph, tr, gimg, scal, go)
+        return (gp.sum(0) if gp.shape[0] > 1 else gp[0]), None, None, None, None, None, None
 
 
 class PerEventBasisCalcFn(torch.autograd.Function):
@@ -905,30 +915,19 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         G = hq * wq
         if Bc != B or c2 != 2 * k or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coeff_grid {tuple(cg.shape)} / phi do not match [B, S, 2k, H, W] / [B, M, k] (k <= 8 without phi)')
-        st = _stream(dev)
-        L = C.lib()
         c_rows = torch.empty((B * G, 2 * k), dtype=torch.float32, device=dev)
-        with _stage('mpc_pe_tile_rows', dev):
-            C.check(L.mpc_pe_tile_rows(_ptr(cg), _ptr(c_rows), B, S, c2, H, W, tile, st), 'mpc_pe_tile_rows')
+        _call('mpc_pe_tile_rows', dev, _ptr(cg), _ptr(c_rows), B, S, c2, H, W, tile)
         ws = alloc_workspace(shape, dev)
-        rows = torch.empty_like(ev)
-        if B * M > 0:
-            with _stage('mpc_pe_warp', dev):
-                C.check(L.mpc_pe_warp(ctypes.byref(shape), _ptr(ev), _ptr(c_rows), _ptr(ph), k, _ptr(tr), _ptr(rows), st), 'mpc_pe_warp')
-        raw = event_splat_fwd(shape, rows, None, tr, ws)
-        blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
+        rows, blur, gimg = _pe_fwd(shape, ev, c_rows, ph, k, tr, ws, need_grad)
         g_field, s_nimg = None, 0
         if pm is not None and cfg.smooth_weight > 0:
             nb = pm.shape[0]
             field = torch.empty((B * nb, hq, wq, 2), dtype=torch.float32, device=dev)
-            with _stage('mpc_pe_basis_field', dev):
-                C.check(L.mpc_pe_basis_field(_ptr(c_rows), _ptr(pm), _ptr(field), B, G, k, nb, st), 'mpc_pe_basis_field')
+            _call('mpc_pe_basis_field', dev, _ptr(c_rows), _ptr(pm), _ptr(field), B, G, k, nb)
             s_nimg = B * nb
             g_field = lut_smooth(shape, field, s_nimg, 2, cfg.smooth_weight, ws, need_grad)
         scal = finalize(shape, s_nimg, 2 if s_nimg else 0, cfg.smooth_weight if s_nimg else 0.0, ws, dev)
-        with torch.cuda.device(dev):
-            ordered = offsets is not None and int(L.mpc_pe_grad_ordered_supported(ctypes.byref(shape), k)) == 1
-        offs = _check_offsets(offsets, cfg, shape, dev) if ordered else None
+        offs = _pe_ordered_offsets(offsets, cfg, shape, k, dev)
         ctx.shape, ctx.k, ctx.tile, ctx.grid_shape = shape, k, tile, (B, S, c2, H, W)
         ctx.has = (ph is not None, pm is not None and g_field is not None, offs is not None)
         ctx.set_materialize_grads(False)
@@ -951,33 +950,14 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         B, S, c2, H, W = ctx.grid_shape
         G = shape.hq * shape.wq
         dev = rows.device
-        st = _stream(dev)
-        L = C.lib()
         go = _f32c(g_loss.reshape(1))
-        split, gp = 1, None
-        if has_offs:
-            split = max(1, min(16, 512 // max(1, B * _lut_strips(shape, dev))))
-            gp = torch.empty((split, B * G, 2 * k), dtype=torch.float32, device=dev)
-            with _stage('mpc_pe_grad_ordered', dev):
-                rc = L.mpc_pe_grad_ordered(ctypes.byref(shape), _ptr(rows), _ptr(offs), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal), _ptr(go),
-                                           _ptr(gp), split, st)
-            if rc == C.E_UNSUPPORTED:
-                gp = None
-            else:
-                C.check(rc, 'mpc_pe_grad_ordered')
-        if gp is None:
-            split = 1
-            gp = torch.empty((1, B * G, 2 * k), dtype=torch.float32, device=dev)
-            with _stage('mpc_pe_grad', dev):
-                C.check(L.mpc_pe_grad(ctypes.byref(shape), _ptr(rows), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal), _ptr(go), _ptr(gp), st), 'mpc_pe_grad')
+        gp = _pe_pos_grad(shape, k, rows, offs if has_offs else None, ph, tr, gimg, scal, go)
         g_rows = torch.empty((B * G, 2 * k), dtype=torch.float32, device=dev)
         nb = pm.shape[0] if has_smooth else 0
-        with _stage('mpc_pe_rows_grad_finish', dev):
-            C.check(L.mpc_pe_rows_grad_finish(_ptr(gp), split, _ptr(g_field) if has_smooth else None, _ptr(pm) if has_smooth else None, _ptr(go),
-                                              _ptr(g_rows), B, G, k, max(nb, 1), st), 'mpc_pe_rows_grad_finish')
+        _call('mpc_pe_rows_grad_finish', dev, _ptr(gp), gp.shape[0], _ptr(g_field) if has_smooth else None, _ptr(pm) if has_smooth else None,
+              _ptr(go), _ptr(g_rows), B, G, k, max(nb, 1))
         g_grid = torch.empty(ctx.grid_shape, dtype=torch.float32, device=dev)
-        with _stage('mpc_pe_tile_rows_bwd', dev):
-            C.check(L.mpc_pe_tile_rows_bwd(_ptr(g_rows), _ptr(g_grid), B, S, c2, H, W, ctx.tile, st), 'mpc_pe_tile_rows_bwd')
+        _call('mpc_pe_tile_rows_bwd', dev, _ptr(g_rows), _ptr(g_grid), B, S, c2, H, W, ctx.tile)
         return (g_grid,) + (None,) * 9
 
 
@@ -1053,9 +1033,7 @@ def event_pos_grad(shape, rows, t_ref, gimg, scal, grad_out):
     """UNPINNED extension: d objective / d warped position per event row -> [B, M, 2] (mpc_event_pos_grad)."""
     B, M = rows.shape[0], rows.shape[1]
     g = torch.empty((B, M, 2), dtype=torch.float32, device=rows.device)
-    with _stage('mpc_event_pos_grad', rows.device):
-        C.check(C.lib().mpc_event_pos_grad(ctypes.byref(shape), _ptr(rows), _ptr(t_ref), _ptr(gimg), _ptr(scal), _ptr(grad_out),
-                                           _ptr(g), _stream(rows.device)), 'mpc_event_pos_grad')
+    _call('mpc_event_pos_grad', rows.device, ctypes.byref(shape), _ptr(rows), _ptr(t_ref), _ptr(gimg), _ptr(scal), _ptr(grad_out), _ptr(g))
     return g
 
 
@@ -1158,7 +1136,7 @@ class CurveTrajFn(torch.autograd.Function):
         bm = _f32c(basis.detach())
         ps = _f32c(pos.detach())
         traj = torch.empty((B, T, n, 2), dtype=torch.float32, device=dev)
-        C.check(C.lib().mpc_curve_traj_fwd(_ptr(p), _ptr(bm), _ptr(ps), float(scale), _ptr(traj), B, d, T, n, _stream(dev)), 'mpc_curve_traj_fwd')
+        _call('mpc_curve_traj_fwd', dev, _ptr(p), _ptr(bm), _ptr(ps), float(scale), _ptr(traj), B, d, T, n)
         ctx.save_for_backward(bm)
         ctx.dims = (B, d, T, n, h, w, float(scale))
         return traj
@@ -1169,7 +1147,7 @@ class CurveTrajFn(torch.autograd.Function):
         B, d, T, n, h, w, scale = ctx.dims
         g = _f32c(g)
         gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=g.device)
-        C.check(C.lib().mpc_curve_traj_bwd(_ptr(g), _ptr(bm), scale, _ptr(gp), B, d, T, n, _stream(g.device)), 'mpc_curve_traj_bwd')
+        _call('mpc_curve_traj_bwd', g.device, _ptr(g), _ptr(bm), scale, _ptr(gp), B, d, T, n)
         return gp, None, None, None
 
 
@@ -1195,7 +1173,7 @@ class CvxCurveTrajFn(torch.autograd.Function):
         nty, ntx = ((v - s + tile - 1) // tile if v > s else 0 for v in (8 * h, 8 * w))          # (the count of the tile mask's centres)
         n = nty * ntx
         traj = torch.empty((B, T, n, 2), dtype=torch.float32, device=dev)
-        C.check(C.lib().mpc_cvx_traj_fwd(_ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile, _stream(dev)), 'mpc_cvx_traj_fwd')
+        _call('mpc_cvx_traj_fwd', dev, _ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile)
         ctx.save_for_backward(p, m, bm)
         ctx.dims = (B, d, T, h, w, tile, float(scale))
         return traj
@@ -1209,15 +1187,11 @@ class CvxCurveTrajFn(torch.autograd.Function):
         gp = gm = ws = None
         if ctx.needs_input_grad[0]:
             gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
-            nws = int(C.lib().mpc_cvx_traj_bwd_workspace_bytes(B, d, T, h, w, tile))
-            if nws < 0:
-                C.check(nws, 'mpc_cvx_traj_bwd_workspace_bytes')
-            ws = torch.empty(max(nws, 4) // 4, dtype=torch.float32, device=dev)
+            ws = torch.empty(max(_query('mpc_cvx_traj_bwd_workspace_bytes', dev, B, d, T, h, w, tile), 4) // 4, dtype=torch.float32, device=dev)
         if ctx.needs_input_grad[1]:
             gm = torch.empty((B, 576, h, w), dtype=torch.float32, device=dev)          # (every element is written by the kernel)
         if gp is not None or gm is not None:
-            C.check(C.lib().mpc_cvx_traj_bwd(_ptr(g), _ptr(p), _ptr(m), _ptr(bm), scale, _ptr(gp), _ptr(gm), B, d, T, h, w, tile,
-                                             _ptr(ws), _stream(dev)), 'mpc_cvx_traj_bwd')
+            _call('mpc_cvx_traj_bwd', dev, _ptr(g), _ptr(p), _ptr(m), _ptr(bm), scale, _ptr(gp), _ptr(gm), B, d, T, h, w, tile, _ptr(ws))
         return gp, gm, None, None, None
 
 
@@ -1230,8 +1204,37 @@ def cvx_flows(params, up_mask, basis, scale: float):
     d, T, dev = c2 // 2, basis.shape[0], params.device
     flows = torch.empty((T, B, 2, 8 * h, 8 * w), dtype=torch.float32, device=dev)
     p, m, bm = _f32c(params.detach()), _f32c(up_mask.detach()), _f32c(basis.detach())
-    C.check(C.lib().mpc_cvx_flow_fwd(_ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(flows), B, d, T, h, w, _stream(dev)), 'mpc_cvx_flow_fwd')
+    _call('mpc_cvx_flow_fwd', dev, _ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(flows), B, d, T, h, w)
     return flows
+
+
+def _corr_lookup_fwd(x, basis, lookup):
+    """The forward launch of both lookup nodes -> (out, the detached x, d); basis None: x are coordinates, else Bezier control points."""
+    _require_gpu(x, 'coords / params')
+    dev = x.device
+    bezier = basis is not None
+    d = x.shape[1] // 2 if bezier else 0
+    desc = lookup.descriptor(d)
+    K = 2 * lookup.radius + 1
+    out = torch.empty((lookup.B, lookup.num_entries * K * K, lookup.h, lookup.w), dtype=torch.float32, device=dev)
+    xd = x.detach()
+    _call('mpc_corr_lookup_fwd', dev, ctypes.byref(desc), None if bezier else _ptr(xd), _ptr(xd) if bezier else None, _ptr(basis), _ptr(out))
+    return out, xd, d
+
+
+def _corr_lookup_bwd(lookup, d, x, basis, g, want_x, grad_levels, flags=0):
+    """The backward launch of both lookup nodes: the gradient of x (None unless `want_x`), and the level cotangents into the tensors of
+    `grad_levels` (None: a level nobody asked for), written whole or, under MPC_CORR_F_GRAD_ACCUM in `flags`, added to."""
+    g = _f32c(g)
+    desc = C.CorrDesc.from_buffer_copy(lookup.descriptor(d))
+    desc.flags |= flags
+    gx = torch.empty_like(x) if want_x else None
+    for l, t in enumerate(grad_levels):
+        desc.grad_level[l] = None if t is None else t.data_ptr()
+    bez = basis is not None
+    _call('mpc_corr_lookup_bwd', g.device, ctypes.byref(desc), None if bez else _ptr(x), _ptr(x) if bez else None, _ptr(basis), _ptr(g),
+          None if bez else _ptr(gx), _ptr(gx) if bez else None)
+    return gx
 
 
 class CorrLookupFn(torch.autograd.Function):
@@ -1244,37 +1247,20 @@ class CorrLookupFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, basis, lookup, *levels):
-        _require_gpu(x, 'coords / params')
-        dev = x.device
-        bezier = basis is not None
-        d = x.shape[1] // 2 if bezier else 0
-        desc = lookup.descriptor(d)
-        K = 2 * lookup.radius + 1
-        out = torch.empty((lookup.B, lookup.num_entries * K * K, lookup.h, lookup.w), dtype=torch.float32, device=dev)
-        xd = x.detach()
-        C.check(C.lib().mpc_corr_lookup_fwd(ctypes.byref(desc), None if bezier else _ptr(xd), _ptr(xd) if bezier else None,
-                                            _ptr(basis), _ptr(out), _stream(dev)), 'mpc_corr_lookup_fwd')
-        ctx.lookup, ctx.bezier, ctx.d = lookup, bezier, d
+        out, xd, ctx.d = _corr_lookup_fwd(x, basis, lookup)
+        ctx.lookup = lookup
         ctx.save_for_backward(xd, basis, *levels)
         return out
 
     @staticmethod
     def backward(ctx, g):
         x, basis, *levels = ctx.saved_tensors
-        g = _f32c(g)
-        dev = g.device
         want_x = ctx.needs_input_grad[0]
         want_l = [ctx.needs_input_grad[3 + l] for l in range(len(levels))]
         if not want_x and not any(want_l):
             return (None,) * (3 + len(levels))
-        desc = C.CorrDesc.from_buffer_copy(ctx.lookup.descriptor(ctx.d))
-        gx = torch.empty_like(x) if want_x else None
         gl = [torch.empty_like(lv) if w else None for lv, w in zip(levels, want_l)]          # (every element is written by the kernel)
-        for l, t in enumerate(gl):
-            desc.grad_level[l] = None if t is None else t.data_ptr()
-        bez = ctx.bezier
-        C.check(C.lib().mpc_corr_lookup_bwd(ctypes.byref(desc), None if bez else _ptr(x), _ptr(x) if bez else None, _ptr(basis), _ptr(g),
-                                            None if bez else _ptr(gx), _ptr(gx) if bez else None, _stream(dev)), 'mpc_corr_lookup_bwd')
+        gx = _corr_lookup_bwd(ctx.lookup, ctx.d, x, basis, g, want_x, gl)
         return (gx, None, None) + tuple(gl)
 
 
@@ -1320,17 +1306,8 @@ class CorrLookupSharedFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, basis, lookup, token):
-        _require_gpu(x, 'coords / params')
-        dev = x.device
-        bezier = basis is not None
-        d = x.shape[1] // 2 if bezier else 0
-        desc = lookup.descriptor(d)
-        K = 2 * lookup.radius + 1
-        out = torch.empty((lookup.B, lookup.num_entries * K * K, lookup.h, lookup.w), dtype=torch.float32, device=dev)
-        xd = x.detach()
-        C.check(C.lib().mpc_corr_lookup_fwd(ctypes.byref(desc), None if bezier else _ptr(xd), _ptr(xd) if bezier else None,
-                                            _ptr(basis), _ptr(out), _stream(dev)), 'mpc_corr_lookup_fwd')
-        ctx.lookup, ctx.bezier, ctx.d, ctx.gate_node = lookup, bezier, d, token.grad_fn
+        out, xd, ctx.d = _corr_lookup_fwd(x, basis, lookup)
+        ctx.lookup, ctx.gate_node = lookup, token.grad_fn
         ctx.save_for_backward(xd, basis)
         return out
 
@@ -1338,27 +1315,19 @@ class CorrLookupSharedFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         x, basis = ctx.saved_tensors
-        g = _f32c(g)
-        dev = g.device
         lookup, gate = ctx.lookup, ctx.lookup._gate
         want_x = ctx.needs_input_grad[0]
         # needs_input_grad is fixed at the forward; whether THIS pass reaches the levels is the engine's to say
         want_l = ctx.needs_input_grad[3] and ctx.gate_node is not None and torch._C._will_engine_execute_node(ctx.gate_node)
         if not want_x and not want_l:
             return None, None, None, None
-        desc = C.CorrDesc.from_buffer_copy(lookup.descriptor(ctx.d))
-        gx = torch.empty_like(x) if want_x else None
+        flags = 0
         if want_l:
             if gate.bufs is None:                                     # the first of the pass: every element is written by the kernel
                 gate.bufs = [torch.empty_like(lv) if lv.requires_grad else None for lv in lookup.levels]
             else:
-                desc.flags |= C.CORR_F_GRAD_ACCUM
-            for l, t in enumerate(gate.bufs):
-                desc.grad_level[l] = None if t is None else t.data_ptr()
-        bez = ctx.bezier
-        C.check(C.lib().mpc_corr_lookup_bwd(ctypes.byref(desc), None if bez else _ptr(x), _ptr(x) if bez else None, _ptr(basis), _ptr(g),
-                                            None if bez else _ptr(gx), _ptr(gx) if bez else None, _stream(dev)), 'mpc_corr_lookup_bwd')
-        return gx, None, None, None
+                flags = C.CORR_F_GRAD_ACCUM
+        return _corr_lookup_bwd(lookup, ctx.d, x, basis, g, want_x, gate.bufs if want_l else (), flags), None, None, None
 
 
 def corr_pyramid_desc(B, h, w, num_levels_per_target):
@@ -1374,9 +1343,7 @@ def corr_pyramid_desc(B, h, w, num_levels_per_target):
 
 
 def _corr_pyramid_ws(desc, D, backward, dev):
-    nws = int(C.lib().mpc_corr_pyramid_workspace_bytes(ctypes.byref(desc), D, backward))
-    if nws < 0:
-        C.check(nws, 'mpc_corr_pyramid_workspace_bytes')
+    nws = _query('mpc_corr_pyramid_workspace_bytes', dev, ctypes.byref(desc), D, backward)
     return torch.empty((nws + 3) // 4, dtype=torch.float32, device=dev)
 
 
@@ -1400,7 +1367,7 @@ class CorrPyramidFn(torch.autograd.Function):
             for l, lv in enumerate(levels):
                 desc.level[l] = lv.data_ptr()
             ws = _corr_pyramid_ws(desc, D, 0, dev)
-            C.check(C.lib().mpc_corr_pyramid_fwd(ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(ws), _stream(dev)), 'mpc_corr_pyramid_fwd')
+            _call('mpc_corr_pyramid_fwd', dev, ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(ws))
         ctx.nl = [int(v) for v in num_levels_per_target]
         ctx.set_materialize_grads(False)                              # (an unused level arrives as None, not as a volume of zeros)
         ctx.save_for_backward(f1, f2)
@@ -1422,8 +1389,7 @@ class CorrPyramidFn(torch.autograd.Function):
             for l, g in enumerate(gl):
                 desc.grad_level[l] = None if g is None else g.data_ptr()
             ws = _corr_pyramid_ws(desc, D, 1, dev)
-            C.check(C.lib().mpc_corr_pyramid_bwd(ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(g1), _ptr(g2), _ptr(ws), _stream(dev)),
-                    'mpc_corr_pyramid_bwd')
+            _call('mpc_corr_pyramid_bwd', dev, ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(g1), _ptr(g2), _ptr(ws))
         return g1, g2, None
 
 
@@ -1450,8 +1416,8 @@ class GridTrajFn(torch.autograd.Function):
         rows = None
         if dp is not None and ctx.needs_input_grad[2]:        # (saved only when the basis itself is learned)
             rows = torch.empty((B * hq * wq, c2), dtype=torch.float32, device=dev)
-        C.check(C.lib().mpc_grid_traj_fwd(_ptr(cg), _ptr(tm), _ptr(dp), int(basis), float(anchor), int(bool(add_offsets)), _ptr(traj),
-                                          _ptr(rows), B, S, k, H, W, int(tile), n_t, _stream(dev)), 'mpc_grid_traj_fwd')
+        _call('mpc_grid_traj_fwd', dev, _ptr(cg), _ptr(tm), _ptr(dp), int(basis), float(anchor), int(bool(add_offsets)), _ptr(traj),
+              _ptr(rows), B, S, k, H, W, int(tile), n_t)
         ctx.save_for_backward(tm, dp, rows)
         ctx.dims = (B, S, k, H, W, int(tile), n_t, int(basis), float(anchor))
         return traj
@@ -1465,13 +1431,11 @@ class GridTrajFn(torch.autograd.Function):
         gg = torch.empty((B, S, 2 * k, H, W), dtype=torch.float32, device=dev)          # (every element is written by the kernel)
         gd = scratch = None
         if rows is not None:
-            nsc = int(C.lib().mpc_grid_traj_scratch_floats(B, k, H, W, tile, n_t))
-            if nsc < 0:
-                C.check(nsc, 'mpc_grid_traj_scratch_floats')
+            nsc = _query('mpc_grid_traj_scratch_floats', dev, B, k, H, W, tile, n_t)
             gd = torch.empty((n_t, k), dtype=torch.float32, device=dev)
             scratch = torch.empty(max(nsc, 1), dtype=torch.float32, device=dev)
-        C.check(C.lib().mpc_grid_traj_bwd(_ptr(g), _ptr(tm), _ptr(dp), basis, anchor, _ptr(rows), _ptr(gg), _ptr(gd), _ptr(scratch),
-                                          B, S, k, H, W, tile, n_t, _stream(dev)), 'mpc_grid_traj_bwd')
+        _call('mpc_grid_traj_bwd', dev, _ptr(g), _ptr(tm), _ptr(dp), basis, anchor, _ptr(rows), _ptr(gg), _ptr(gd), _ptr(scratch),
+              B, S, k, H, W, tile, n_t)
         return gg, None, gd, None, None, None, None
 
 

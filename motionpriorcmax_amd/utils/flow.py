@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from .. import _lib as C
-from ..ops import _ptr, _require_gpu, _stage, _stream
+from ..ops import _call, _ptr, _query, _require_gpu
 
 
 def dense_flow_from_traj(traj_flow, pixel_positions, patch_size, image_shape):
@@ -22,9 +22,7 @@ def dense_flow_from_traj(traj_flow, pixel_positions, patch_size, image_shape):
     shape = C.FlowShape(B=B, C=Cn, n=n, patch=int(patch_size), H=h, W=w)
     patch = torch.empty((B, Cn, h // int(patch_size), w // int(patch_size)), dtype=torch.float32, device=tf.device)
     dense = torch.empty((B, Cn, h, w), dtype=torch.float32, device=tf.device)
-    with _stage('mpc_dense_flow', tf.device):
-        C.check(C.lib().mpc_dense_flow(ctypes.byref(shape), _ptr(tf), _ptr(pix), _ptr(patch), _ptr(dense),
-                                       _stream(tf.device)), 'mpc_dense_flow')
+    _call('mpc_dense_flow', tf.device, ctypes.byref(shape), _ptr(tf), _ptr(pix), _ptr(patch), _ptr(dense))
     return dense, patch
 
 
@@ -42,14 +40,9 @@ def calculate_flow_error(flow_gt, flow_pred, event_mask=None, time_scale=None) -
         em = (em if em.dtype == torch.bool else em != 0).reshape(B, H, W).contiguous()
     ts = None if time_scale is None else time_scale.to(device=gt.device, dtype=torch.float32).reshape(B).contiguous()
     shape = C.ErrShape(B=B, H=H, W=W)
-    nbytes = C.lib().mpc_flow_error_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_flow_error_workspace_bytes')
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=gt.device)
+    ws = torch.empty(_query('mpc_flow_error_workspace_bytes', gt.device, ctypes.byref(shape)), dtype=torch.uint8, device=gt.device)
     out = torch.empty(5, dtype=torch.float32, device=gt.device)
-    with _stage('mpc_flow_error', gt.device):
-        C.check(C.lib().mpc_flow_error(ctypes.byref(shape), _ptr(gt), _ptr(pr), _ptr(em), _ptr(ts), _ptr(out), _ptr(ws),
-                                       _stream(gt.device)), 'mpc_flow_error')
+    _call('mpc_flow_error', gt.device, ctypes.byref(shape), _ptr(gt), _ptr(pr), _ptr(em), _ptr(ts), _ptr(out), _ptr(ws))
     return {k: out[i] for i, k in enumerate(('EPE', '1PE', '2PE', '3PE', 'AE'))}
 
 

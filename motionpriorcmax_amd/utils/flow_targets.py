@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from .. import _lib as C
-from ..ops import _ptr, _require_gpu, _stage, _stream
+from ..ops import _call, _ptr, _require_gpu
 from .ingest import _c
 
 
@@ -68,8 +68,6 @@ def flow_targets(raw_flow, out_size=None, *, dataset, id_mask=None):
     flow = torch.empty((B, S, 2, Ho, Wo), dtype=torch.float32, device=dev)
     valid = torch.empty((B, S, Ho, Wo), dtype=torch.bool, device=dev) if evimo2 else None
     id_out = None if ids is None else torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev)
-    with _stage('mpc_flow_targets', dev):
-        C.check(C.lib().mpc_flow_targets(ctypes.byref(shape), _ptr(raw), _ptr(ids), _ptr(flow), _ptr(valid), _ptr(id_out), _stream(dev)),
-                'mpc_flow_targets')
+    _call('mpc_flow_targets', dev, ctypes.byref(shape), _ptr(raw), _ptr(ids), _ptr(flow), _ptr(valid), _ptr(id_out))
     return {'flow': flow, 'flow_valid': valid, 'id_mask': id_out,
             'x_scale': Wo / W if evimo2 else 0.5, 'y_scale': Ho / H if evimo2 else 0.5}

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from .. import _lib as C
-from ..ops import _ptr, _require_gpu, _stream, _stage
+from ..ops import _call, _lut_strips, _ptr, _query, _require_gpu, make_shape
 
 
 def ingest_events(x, y, t_us, p, counts, image_shape, num_bins, want_voxel_input=False, order_for=None):
@@ -25,36 +25,26 @@ def ingest_events(x, y, t_us, p, counts, image_shape, num_bins, want_voxel_input
     t_us = t_us.to(torch.int64).contiguous()
     cnt = counts.to(device=dev, dtype=torch.int32).contiguous()
     shape = C.IngestShape(B=B, N=N, H=int(image_shape[0]), W=int(image_shape[1]), nb=int(num_bins))
-    nbytes = C.lib().mpc_ingest_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_ingest_workspace_bytes')
-    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(_query('mpc_ingest_workspace_bytes', dev, ctypes.byref(shape)), 256), dtype=torch.uint8, device=dev)
     out_max = torch.empty(2, dtype=torch.int32, device=dev)
-    st = _stream(dev)
-    with _stage('mpc_ingest_count', dev):
-        C.check(C.lib().mpc_ingest_count(ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt),
-                                         _ptr(out_max), _ptr(ws), st), 'mpc_ingest_count')
+    _call('mpc_ingest_count', dev, ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(out_max), _ptr(ws))
     max_pos, max_neg = (int(v) for v in out_max.tolist())          # the collate's host decision
     events = torch.empty((B, max_pos + max_neg, 6), dtype=torch.float32, device=dev)
     xytp = torch.empty((B, N, 4), dtype=torch.float32, device=dev) if want_voxel_input else None
     if order_for is not None:
         # the rows are written in bucket order right away (mpc_ingest_scatter_ordered): no ordering pass over the tensor
-        from ..ops import make_shape
         cfg = order_for._cfg
         lshape = make_shape(cfg, B, max_pos + max_neg, max_pos if cfg.polarity_split else max_pos + max_neg, 1)
-        ncs = int(C.lib().mpc_event_lut_strips(ctypes.byref(lshape)))
+        ncs = _lut_strips(lshape, dev)
         if ncs > 0 and cfg.polarity_split and tuple(cfg.image_shape) == (int(image_shape[0]), int(image_shape[1])) and cfg.num_bins == int(num_bins):
-            nb2 = int(C.lib().mpc_ingest_ordered_workspace_bytes(ctypes.byref(shape), ctypes.byref(lshape)))
+            nb2 = _query('mpc_ingest_ordered_workspace_bytes', dev, ctypes.byref(shape), ctypes.byref(lshape))
             ws2 = torch.empty(max(nb2, 256), dtype=torch.uint8, device=dev)
             offs = torch.empty((B, 2, cfg.num_bins * ncs + 1), dtype=torch.int32, device=dev)
-            with _stage('mpc_ingest_scatter_ordered', dev):
-                C.check(C.lib().mpc_ingest_scatter_ordered(ctypes.byref(shape), ctypes.byref(lshape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p),
-                                                           _ptr(cnt), max_pos, max_neg, _ptr(events), _ptr(offs), _ptr(xytp), _ptr(ws),
-                                                           _ptr(ws2), st), 'mpc_ingest_scatter_ordered')
+            _call('mpc_ingest_scatter_ordered', dev, ctypes.byref(shape), ctypes.byref(lshape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p),
+                  _ptr(cnt), max_pos, max_neg, _ptr(events), _ptr(offs), _ptr(xytp), _ptr(ws), _ptr(ws2))
             return {'events': events, 'num_pos_events': max_pos, 'xytp': xytp, 'event_offsets': offs}
-    with _stage('mpc_ingest_scatter', dev):
-        C.check(C.lib().mpc_ingest_scatter(ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt),
-                                           max_pos, max_neg, _ptr(events), _ptr(xytp), _ptr(ws), st), 'mpc_ingest_scatter')
+    _call('mpc_ingest_scatter', dev, ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt),
+          max_pos, max_neg, _ptr(events), _ptr(xytp), _ptr(ws))
     out = {'events': events, 'num_pos_events': max_pos, 'xytp': xytp}
     return out if order_for is None else order_for.order_events(out)
 
@@ -131,20 +121,14 @@ def ingest_raw_events(x, y, t_us, p, counts, num_bins, dataset, *, flow_duration
     shape = C.WindowShape(B=B, N=N, nb=int(num_bins), time_mode=C.WINDOW_TIME_FP32_SUFFIX if evimo2 else C.WINDOW_TIME_MINMAX64,
                           xy_int=int(xy_int), p_int64=int(p_int64), split=int(bool(polarity_aware_batching)),
                           duration_us=float(flow_duration_ms) * 1e3 if evimo2 else 0.0, x_scale=xs, y_scale=ys)
-    nbytes = C.lib().mpc_ingest_window_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_ingest_window_workspace_bytes')
+    nbytes = _query('mpc_ingest_window_workspace_bytes', dev, ctypes.byref(shape))
     edges = _window_edges(dev, num_bins) if evimo2 else None
-    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
     out_max = torch.empty(2, dtype=torch.int32, device=dev)
-    st = _stream(dev)
-    with _stage('mpc_ingest_window_count', dev):
-        C.check(C.lib().mpc_ingest_window_count(ctypes.byref(shape), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(out_max), _ptr(ws), st),
-                'mpc_ingest_window_count')
+    _call('mpc_ingest_window_count', dev, ctypes.byref(shape), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(out_max), _ptr(ws))
     max_pos, max_neg = (int(v) for v in out_max.tolist())          # the collate's host decision
     events = torch.empty((B, max_pos + max_neg, 6), dtype=torch.float32, device=dev)
-    with _stage('mpc_ingest_window_scatter', dev):
-        C.check(C.lib().mpc_ingest_window_scatter(ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(edges),
-                                                  max_pos, max_neg, _ptr(events), _ptr(ws), st), 'mpc_ingest_window_scatter')
+    _call('mpc_ingest_window_scatter', dev, ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(edges),
+          max_pos, max_neg, _ptr(events), _ptr(ws))
     out = {'events': events, 'num_pos_events': max_pos if polarity_aware_batching else -1}
     return out if order_for is None else order_for.order_events(out)

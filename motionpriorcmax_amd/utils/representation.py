@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from .. import _lib as C
-from ..ops import _ptr, _require_gpu, _stream, _stage
+from ..ops import _call, _ptr, _query, _require_gpu
 
 
 def _is_int_tensor(t: torch.Tensor) -> bool:
@@ -84,14 +84,9 @@ def representation_grids(x, y, pol, time, counts, channels, height, width, centr
     if out_size is not None and (Ho < 1 or Wo < 1):
         raise ValueError(f'out_size must be positive, got {out_size}')
     shape = C.ReprShape(B=B, N=N, C=channels, H=height, W=width, int_xy=int(int_xy), norm=int(bool(normalize)), Ho=Ho, Wo=Wo)
-    nbytes = C.lib().mpc_repr_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_repr_workspace_bytes')
-    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    ws = torch.empty(max(_query('mpc_repr_workspace_bytes', dev, ctypes.byref(shape)), 256), dtype=torch.uint8, device=dev)
     grid = torch.empty((B, channels, Ho or height, Wo or width), dtype=torch.float32, device=dev)
-    with _stage('mpc_repr_grid', dev):
-        C.check(C.lib().mpc_repr_grid(ctypes.byref(shape), _ptr(xf), _ptr(yf), _ptr(tt), _ptr(pf), _ptr(cnt), _ptr(cen), _ptr(grid),
-                                      _ptr(ws), _stream(dev)), 'mpc_repr_grid')
+    _call('mpc_repr_grid', dev, ctypes.byref(shape), _ptr(xf), _ptr(yf), _ptr(tt), _ptr(pf), _ptr(cnt), _ptr(cen), _ptr(grid), _ptr(ws))
     return grid
 
 
@@ -102,9 +97,8 @@ def norm_voxel_grid(voxel_grid: torch.Tensor) -> torch.Tensor:
     if voxel_grid.dtype != torch.float32 or not voxel_grid.is_contiguous():
         raise ValueError('voxel_grid must be a contiguous fp32 tensor (it is normalised in place)')
     dev = voxel_grid.device
-    ws = torch.empty(max(int(C.lib().mpc_repr_norm_workspace_bytes(1)), 256), dtype=torch.uint8, device=dev)
-    with _stage('mpc_repr_norm', dev):
-        C.check(C.lib().mpc_repr_norm(_ptr(voxel_grid), 1, voxel_grid.numel(), _ptr(ws), _stream(dev)), 'mpc_repr_norm')
+    ws = torch.empty(max(_query('mpc_repr_norm_workspace_bytes', dev, 1), 256), dtype=torch.uint8, device=dev)
+    _call('mpc_repr_norm', dev, _ptr(voxel_grid), 1, voxel_grid.numel(), _ptr(ws))
     return voxel_grid
 
 

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from .. import _lib as C
-from ..ops import _f32c, _ptr, _require_gpu, _stage, _stream
+from ..ops import _call, _f32c, _ptr, _query, _require_gpu
 from .basis import _device_basis
 
 
@@ -101,14 +101,9 @@ def _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_va
     else:
         ts = torch.tensor(np.asarray(timestamps, dtype=np.float64).reshape(M), dtype=torch.float32).to(dev)
     shape = C.ValShape(B=B, M=M, d=d, h=h, w=w, H=H, W=W, C=0 if ev_repr is None else int(ev_repr.shape[1]))
-    nbytes = C.lib().mpc_val_metrics_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_val_metrics_workspace_bytes')
-    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-    with _stage('mpc_val_metrics', dev):
-        C.check(C.lib().mpc_val_metrics(ctypes.byref(shape), _ptr(params), _ptr(up_mask), _ptr(bm), _ptr(flows), float(scale), _ptr(ts),
-                                        _ptr(gt), _ptr(flow_valid), _ptr(ev_repr), _ptr(event_mask), _ptr(values), _ptr(updated),
-                                        _ptr(ws), _stream(dev)), 'mpc_val_metrics')
+    ws = torch.empty(_query('mpc_val_metrics_workspace_bytes', dev, ctypes.byref(shape)), dtype=torch.uint8, device=dev)
+    _call('mpc_val_metrics', dev, ctypes.byref(shape), _ptr(params), _ptr(up_mask), _ptr(bm), _ptr(flows), float(scale), _ptr(ts),
+          _ptr(gt), _ptr(flow_valid), _ptr(ev_repr), _ptr(event_mask), _ptr(values), _ptr(updated), _ptr(ws))
     return values, updated, M
 
 

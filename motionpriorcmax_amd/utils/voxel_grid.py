@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from .. import _lib as C
-from ..ops import _ptr, _require_gpu, _stream, _stage
+from ..ops import _call, _ptr, _query, _require_gpu
 
 
 def voxel_grids(xytp: torch.Tensor, counts: torch.Tensor, input_size, norm_type='mean_std', quantile=0.0) -> torch.Tensor:
@@ -21,14 +21,9 @@ def voxel_grids(xytp: torch.Tensor, counts: torch.Tensor, input_size, norm_type=
     cnt = counts.to(device=ev.device, dtype=torch.int32).contiguous()
     shape = C.VoxShape(B=B, N=N, C=Cn, H=H, W=W, norm={None: 0, 'mean_std': 1, 'max': 2}[norm_type], quantile=float(quantile),
                        keep=float(1.0 - float(quantile)) if quantile > 0 else 0.0)      # 1 - q in double, rounded once (torch.quantile's argument)
-    nbytes = C.lib().mpc_voxel_workspace_bytes(ctypes.byref(shape))
-    if nbytes < 0:
-        C.check(int(nbytes), 'mpc_voxel_workspace_bytes')
-    ws = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=ev.device)
+    ws = torch.empty(max(_query('mpc_voxel_workspace_bytes', ev.device, ctypes.byref(shape)), 256), dtype=torch.uint8, device=ev.device)
     grid = torch.empty((B, Cn, H, W), dtype=torch.float32, device=ev.device)
-    with _stage('mpc_voxel_grid', ev.device):
-        C.check(C.lib().mpc_voxel_grid(ctypes.byref(shape), _ptr(ev), _ptr(cnt), _ptr(grid), _ptr(ws), _stream(ev.device)),
-                'mpc_voxel_grid')
+    _call('mpc_voxel_grid', ev.device, ctypes.byref(shape), _ptr(ev), _ptr(cnt), _ptr(grid), _ptr(ws))
     return grid
 
 

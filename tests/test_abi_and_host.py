@@ -27,6 +27,35 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.EXPORTS) == names
 
 
+_RETURN_BYTES = {'int': 4, 'int32_t': 4, 'int64_t': 8, 'long long': 8, 'const char *': ctypes.sizeof(ctypes.c_char_p)}
+
+
+def _header_declarations():
+    """{name: (return type, parameter count)} of every function include/mpcmax.h declares."""
+    src = open(os.path.join(ROOT, 'include', 'mpcmax.h')).read()
+    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+    src = re.sub(r'//[^\n]*', '', src)
+    out = {}
+    for ret, name, params in re.findall(r'^\s*(const char \*|long long|int64_t|int32_t|int)\s*(mpc_[a-z_0-9]+)\s*\(([^)]*)\)\s*;', src, flags=re.M):
+        assert name not in out, name
+        params = params.strip()
+        out[name] = (ret, 0 if params in ('', 'void') else params.count(',') + 1)
+    return out
+
+
+def test_binding_signatures_match_the_header():
+    """The signature table of _lib.py against the declarations: a missing or short argtypes would pass 64-bit pointers as C int, a
+    narrow restype would cut a byte count -- neither shows as a Python error."""
+    from motionpriorcmax_amd import _lib
+    decl = _header_declarations()
+    assert sorted(decl) == _header_functions()                  # every declared function parsed
+    L = _lib.lib()
+    for name, (ret, nparams) in decl.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == nparams, f'{name}: {fn.argtypes} against {nparams} declared parameters'
+        assert ctypes.sizeof(fn.restype) == _RETURN_BYTES[ret], f'{name}: restype {fn.restype} against `{ret}`'
+
+
 def _shape(**kw):
     from motionpriorcmax_amd import _lib
     d = dict(B=2, M=1000, Mp=500, nb=5, T=1, H=48, W=64, sp=4, hq=12, wq=16, n=192, K=4, flags=0)

@@ -137,6 +137,33 @@ int mpc_knn_lut_bwd(const mpc_shape *s, const float *traj, const float *grad_flo
                     const float *grad_flow_next, const float *knn_state, float *grad_traj,
                     void *ws, void *stream);
 
+/* ---- A5 for n >= 65536 (focus.py:129-178 has no limit on n; mpc_knn_lut_fwd's tables are 16 bit) -------------------------------
+ * The caller searches contiguous index chunks of at most 65535 points with mpc_knn_lut_fwd (idx_out) and hands the C sorted lists
+ * over; the K nearest of all n points are the K smallest of their union by (distance, global index) -- exact, same tie rule.
+ * Limits: n <= 2^22, C <= 64, (2 * C' + 1) * K * 4 bytes <= 64 KB with C' = C rounded up to a power of two (else
+ * MPC_E_UNSUPPORTED).  Additive: the version number is unchanged, the binding checks the three symbols by name. */
+
+/* Bytes of the scratch buffer of mpc_knn_idx_bwd for this shape (focus.py:129-178: backward of the gather). */
+int64_t mpc_knn_wide_workspace_bytes(const mpc_shape *s);
+
+/* Merge + interpolation (focus.py:129-178).
+ * traj        [B][T+nb][n][2], all n points
+ * cand        [C][B][nb][hq*wq][K] int32: list c = idx_out of mpc_knn_lut_fwd on the points [chunk_start[c], chunk_start[c+1]),
+ *             indices local to the chunk
+ * chunk_start C + 1 ascending int32 in HOST memory, chunk_start[0] = 0, chunk_start[C] = n, every chunk K .. 65535 points
+ * idx_out     [B][nb][hq*wq][K] int32 global indices, ascending by (distance, index)                            (out)
+ * flow_lut    [B][nb][hq][wq][T][2] 'mean', or 'iwd' with MPC_F_SCHEME_IWD: weights 1 / (d + 1e-9) divided by their sum,
+ *             summed over the K members in list order, in fp64 on the fp32 inputs and rounded once                (out)
+ * flow_next   [B][nb-1][hq][wq][1][2] with MPC_F_WANT_NEXT (the same neighbours, mean), else NULL                 (out)  */
+int mpc_knn_merge_fwd(const mpc_shape *s, const float *traj, const int32_t *cand, const int32_t *chunk_start,
+                      int32_t num_chunks, int32_t *idx_out, float *flow_lut, float *flow_next, void *stream);
+
+/* Backward of the interpolation over a saved index list (focus.py:129-178; 'iwd' weights are constants, recomputed from traj):
+ * idx [B][nb][hq*wq][K] as mpc_knn_merge_fwd wrote it; grad_flow_next may be NULL; grad_traj [B][T+nb][n][2] is overwritten.
+ * Sums are 64-bit fixed point: bitwise reproducible from run to run.  ws: mpc_knn_wide_workspace_bytes(s) bytes. */
+int mpc_knn_idx_bwd(const mpc_shape *s, const float *traj, const int32_t *idx, const float *grad_flow_lut,
+                    const float *grad_flow_next, float *grad_traj, void *ws, void *stream);
+
 /* ---- A6-A8: warp + weights + bilinear vote (focus.py:182-230, event_image_converter.py:333-391)
  * events   [B][M][6], flow_lut [B][nb][hq][wq][T][2], t_ref [T] (device)
  * iwe_raw  [B*T][P][H][W]  P = 2 with MPC_F_POLARITY_SPLIT else 1     (out, overwritten)   */

@@ -117,7 +117,10 @@ SIGNATURES = {
     'mpc_knn_list_offsets': (cint, [sp, ctypes.POINTER(i64)]),
     'mpc_knn_tail_counters_offset': (i64, [sp]),
     'mpc_knn_lut_bwd': (cint, [sp] + [vp] * 7),
-    'mpc_event_splat_fwd': (cint, [sp] + [vp] * 6),
+    'mpc_knn_wide_workspace_bytes': (i64, [sp]),
+    'mpc_knn_merge_fwd': (cint, [sp, vp, vp, ctypes.POINTER(i32), i32] + [vp] * 4),
+    'mpc_knn_idx_bwd': (cint, [sp] + [vp] * 7),
+    'mpc_event_splat_fwd':(cint, [sp] + [vp] * 6),
     'mpc_event_splat_fwd_fixed': (cint, [sp] + [vp] * 6),
     'mpc_iwe_from_fixed': (cint, [vp, vp, i64, vp]),
     'mpc_contrast_fwd': (cint, [sp] + [vp] * 5),

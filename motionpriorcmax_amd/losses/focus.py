@@ -239,6 +239,8 @@ class FocusLoss(base.TrajectoryLossBase):
         if not (torch.is_tensor(events) and events.is_cuda and events.dim() == 3 and torch.is_tensor(trajectories) and trajectories.is_cuda
                 and trajectories.dim() == 4):
             return False                  # (the eager path raises the proper error)
+        if ops.knn_is_wide(trajectories.shape[2]):
+            return False                  # (n >= 65536: the chunked neighbour search has no captured form)
         if events.shape[0] * events.shape[1] > self.AUTO_STATIC_MAX_EVENTS or torch.cuda.is_current_stream_capturing():
             return False
         key = ops.StaticFocusCalcFn.plan_key(trajectories, events, self._cfg, int(num_pos_events), offsets)

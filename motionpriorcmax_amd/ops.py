@@ -216,7 +216,8 @@ def alloc_workspace(shape: C.Shape, device) -> torch.Tensor:
 # ------------------------------------------------------------------------------------------
 # stage wrappers (no autograd)
 # ------------------------------------------------------------------------------------------
-def knn_lut_fwd(cfg, shape, traj, ws, want_idx=False):
+def knn_lut_fwd(cfg, shape, traj, ws, want_idx=False, idx_out=None):
+    """mpc_knn_lut_fwd; want_idx: also the sorted neighbour lists [B, nb, Q, K] int32, into `idx_out` where the caller has the place."""
     dev = traj.device
     B, nb, T, K = shape.B, shape.nb, shape.T, shape.K
     hq, wq = shape.hq, shape.wq
@@ -226,7 +227,7 @@ def knn_lut_fwd(cfg, shape, traj, ws, want_idx=False):
     if shape.flags & C.F_WANT_NEXT:
         flow_next = torch.empty((B, max(nb - 1, 0), hq, wq, 1, 2), dtype=torch.float32, device=dev)
     state = torch.empty(_query('mpc_knn_state_floats', dev, ctypes.byref(shape)), dtype=torch.float32, device=dev)
-    idx = torch.empty((B, nb, Q, K), dtype=torch.int32, device=dev) if want_idx else None
+    idx = (idx_out if idx_out is not None else torch.empty((B, nb, Q, K), dtype=torch.int32, device=dev)) if want_idx else None
     _call('mpc_knn_lut_fwd', dev, ctypes.byref(shape), _ptr(traj), _ptr(flow_lut), _ptr(flow_next), _ptr(state), _ptr(idx), _ptr(ws))
     return flow_lut, flow_next, state, idx
 
@@ -234,6 +235,77 @@ def knn_lut_fwd(cfg, shape, traj, ws, want_idx=False):
 def knn_lut_bwd(shape, traj, g_lut, g_next, state, ws):
     g_traj = torch.empty_like(traj)
     _call('mpc_knn_lut_bwd', traj.device, ctypes.byref(shape), _ptr(traj), _ptr(g_lut), _ptr(g_next), _ptr(state), _ptr(g_traj), _ptr(ws))
+    return g_traj
+
+
+# ------------------------------------------------------------------------------------------
+# more trajectories per sample than the 16-bit tables of mpc_knn_lut_fwd hold (n >= 65536): csrc/knn_wide.hip
+# ------------------------------------------------------------------------------------------
+KNN_CHUNK = 65535     # points per search of the chunked route, at most 65535 (what mpc_knn_lut_fwd serves); tests lower it
+KNN_MAX_CHUNKS = 64   # csrc/knn_wide.hip: one lane per chunk of a query
+
+
+def knn_is_wide(n):
+    """Does a point set of n trajectories per sample take the chunked route (knn_wide_fwd)?  n >= 65536 with the shipped KNN_CHUNK."""
+    return n > KNN_CHUNK
+
+
+def _wide_limit(what, n):
+    return ValueError(f'{what} serves at most {KNN_CHUNK} trajectories per sample, got {n}: larger point sets run the chunked '
+                      f'neighbour search (ops.knn_wide_fwd), which has no captured or pyramid form')
+
+
+def knn_chunk_starts(n, K):
+    """The chunked route's contiguous index ranges: ceil(n / KNN_CHUNK) chunks of near-equal length, as C + 1 starts."""
+    if not 1 <= KNN_CHUNK <= 65535:
+        raise ValueError(f'KNN_CHUNK={KNN_CHUNK} outside [1, 65535]')
+    nc = -(-n // KNN_CHUNK)
+    base, rem = divmod(n, nc)
+    if nc > KNN_MAX_CHUNKS or base < K:
+        raise ValueError(f'n={n} in chunks of {KNN_CHUNK}: {nc} chunks of {base} points; at most {KNN_MAX_CHUNKS} chunks of at least '
+                         f'num_knn={K} points are served')
+    starts = [0]
+    for c in range(nc):
+        starts.append(starts[-1] + base + (1 if c < rem else 0))
+    return starts
+
+
+def knn_wide_fwd(cfg, shape, traj):
+    """The KNN LUT of n >= 65536 points: the exact search of mpc_knn_lut_fwd on every contiguous index chunk (its sorted neighbour
+    lists kept, its LUT dropped), then mpc_knn_merge_fwd: the K smallest of the union by (distance, index) and the interpolation.
+    Slicing and copies are torch's, the numerics the library's.  -> (flow_lut, flow_next or None, merged indices [B, nb, Q, K])."""
+    dev = traj.device
+    B, nb, T, K, n = shape.B, shape.nb, shape.T, shape.K, shape.n
+    hq, wq = shape.hq, shape.wq
+    Q = hq * wq
+    starts = knn_chunk_starts(n, K)
+    nc = len(starts) - 1
+    cand = torch.empty((nc, B, nb, Q, K), dtype=torch.int32, device=dev)
+    ws, ws_len = None, -1
+    for c in range(nc):
+        lo, hi = starts[c], starts[c + 1]
+        # (the search looks at the mid-time rows only: one reference row goes along for the layout, the LUT it gives is dropped)
+        sub = traj[:, T - 1:, lo:hi].contiguous()
+        cs = C.Shape(B=B, M=0, Mp=0, nb=nb, T=1, H=shape.H, W=shape.W, sp=shape.sp, hq=hq, wq=wq, n=hi - lo, K=K, flags=shape.flags & C.F_DIST_L1)
+        if hi - lo != ws_len:
+            ws, ws_len = alloc_workspace(cs, dev), hi - lo
+        knn_lut_fwd(cfg, cs, sub, ws, want_idx=True, idx_out=cand[c])
+    flow_lut = torch.empty((B, nb, hq, wq, T, 2), dtype=torch.float32, device=dev)
+    flow_next = None
+    if shape.flags & C.F_WANT_NEXT:
+        flow_next = torch.empty((B, max(nb - 1, 0), hq, wq, 1, 2), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, nb, Q, K), dtype=torch.int32, device=dev)
+    _call('mpc_knn_merge_fwd', dev, ctypes.byref(shape), _ptr(traj), _ptr(cand), (ctypes.c_int32 * (nc + 1))(*starts), nc, _ptr(idx),
+          _ptr(flow_lut), _ptr(flow_next))
+    return flow_lut, flow_next, idx
+
+
+def knn_idx_bwd(shape, traj, g_lut, g_next, idx):
+    """mpc_knn_idx_bwd: dL/dtrajectories from dL/dLUT (and dL/dflow_next) over the merged index lists of knn_wide_fwd."""
+    dev = traj.device
+    g_traj = torch.empty_like(traj)
+    ws = torch.empty(max(_query('mpc_knn_wide_workspace_bytes', dev, ctypes.byref(shape)), 256), dtype=torch.uint8, device=dev)
+    _call('mpc_knn_idx_bwd', dev, ctypes.byref(shape), _ptr(traj), _ptr(idx), _ptr(g_lut), _ptr(g_next), _ptr(g_traj), _ptr(ws))
     return g_traj
 
 
@@ -456,12 +528,17 @@ def _calc_inputs(trajectories, events, t_ref, cfg, num_pos):
     return B, M, Mp, traj.shape[2], dev, traj, ev, tr
 
 
-def _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad):
+def _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad, kshape=None):
     """The loss one library call per stage: KNN LUT -> smoothness (where weighted) -> warp + vote (on `fshape`: `shape`, or without
     backward records for bucket-ordered events) -> blur + objective -> scalars.  The route the tests hold the fused call against
-    and bench.py's instrumented pass times; the pyramid starts from it."""
+    and bench.py's instrumented pass times; the pyramid starts from it.  `kshape`: the chunked neighbour search of n >= 65536
+    trajectories (knn_wide_fwd) on this shape -- `shape` and `ws` then serve the other stages and carry no points (n = 0), and the
+    state for the backward is the merged index lists."""
     B, T, nb = shape.B, cfg.num_tref, cfg.num_bins
-    flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
+    if kshape is not None:
+        flow_lut, flow_next, state = knn_wide_fwd(cfg, kshape, traj)
+    else:
+        flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
     g_field = None
     s_nimg = s_C = 0
     if cfg.smooth_weight > 0:
@@ -477,8 +554,9 @@ def _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad):
     return flow_lut, state, g_field, raw, blur, gimg, scal
 
 
-def _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, g, ws, offs=None):
-    """The backward of _staged_fwd from the adjoint image to dL/dtrajectories: event backward (+ smoothness) -> KNN backward."""
+def _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, g, ws, offs=None, kshape=None):
+    """The backward of _staged_fwd from the adjoint image to dL/dtrajectories: event backward (+ smoothness) -> KNN backward
+    (`kshape`: over the merged index lists, knn_idx_bwd)."""
     g_next = None
     g_lut = torch.empty_like(flow_lut)
     if g_field is not None and not cfg.smooth_on_next:
@@ -487,6 +565,8 @@ def _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, 
         event_splat_bwd(shape, ev, flow_lut, tr, gimg, scal, g, g_lut, None, ws, offs)
         if g_field is not None:
             g_next = scale(g_field, g)
+    if kshape is not None:
+        return knn_idx_bwd(kshape, traj, g_lut, g_next, state)
     return knn_lut_bwd(shape, traj, g_lut, g_next, state, ws)
 
 
@@ -501,7 +581,8 @@ class FocusCalcFn(torch.autograd.Function):
         ctx.cfg = cfg
         ctx.set_materialize_grads(False)      # no zero-filled [B,P,H,W] gradient for the detached outputs
 
-        if STAGE_TIMER is None and FUSED_CALLS:
+        wide = knn_is_wide(n)
+        if STAGE_TIMER is None and FUSED_CALLS and not wide:
             # one C-ABI call for the whole forward (mpc_focus_fwd issues the same launches); per-shape host state is cached
             p = _plan(cfg, B, M, Mp, n, need_grad, event_offsets is not None, dev)
             offs = _check_offsets(event_offsets, cfg, p.shape, dev)
@@ -518,13 +599,16 @@ class FocusCalcFn(torch.autograd.Function):
             ctx.mark_non_differentiable(focus, smooth, blur)
             return loss, focus, smooth, blur
 
-        shape = make_shape(cfg, B, M, Mp, n, extra_flags=0 if need_grad else C.F_NO_BWD_RECORDS)
+        # (n >= 65536: the neighbour search runs in chunks on a shape of its own; the other stages' shape and workspace carry no points)
+        kshape = make_shape(cfg, B, 0, 0, n) if wide else None
+        ns, Ks = (0, 0) if wide else (n, None)
+        shape = make_shape(cfg, B, M, Mp, ns, extra_flags=0 if need_grad else C.F_NO_BWD_RECORDS, K=Ks)
         ws = alloc_workspace(shape, dev)
         offs = _check_offsets(event_offsets, cfg, shape, dev)
-        fshape = shape if offs is None else make_shape(cfg, B, M, Mp, n, extra_flags=C.F_NO_BWD_RECORDS)
-        flow_lut, state, g_field, _, blur, gimg, scal = _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad)
+        fshape = shape if offs is None else make_shape(cfg, B, M, Mp, ns, extra_flags=C.F_NO_BWD_RECORDS, K=Ks)
+        flow_lut, state, g_field, _, blur, gimg, scal = _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad, kshape)
         ctx.plan = None
-        ctx.shape = shape
+        ctx.shape, ctx.kshape = shape, kshape
         ctx.offs = offs
         ctx.ws = ws
         ctx.save_for_backward(traj, ev, tr, flow_lut, state, gimg, scal, g_field)
@@ -548,7 +632,7 @@ class FocusCalcFn(torch.autograd.Function):
             return g_traj, None, None, None, None, None
         shape = ctx.shape
         traj, ev, tr, flow_lut, state, gimg, scal, g_field = ctx.saved_tensors
-        return _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, g, ws, offs), None, None, None, None, None
+        return _staged_bwd(cfg, shape, traj, ev, tr, flow_lut, state, gimg, scal, g_field, g, ws, offs, ctx.kshape), None, None, None, None, None
 
 
 class PyramidFocusFn(torch.autograd.Function):
@@ -561,6 +645,8 @@ class PyramidFocusFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, trajectories, events, t_ref, cfg: PathConfig, num_pos: int, levels: int):
         B, M, Mp, n, dev, traj, ev, tr = _calc_inputs(trajectories, events, t_ref, cfg, num_pos)
+        if knn_is_wide(n):
+            raise _wide_limit('pyramid_levels > 1', n)
         H, W = cfg.image_shape
         if H % (1 << (levels - 1)) or W % (1 << (levels - 1)) or min(H, W) >> (levels - 1) < 3:
             raise ValueError(f'pyramid_levels={levels}: image shape {H}x{W} must be divisible by {1 << (levels - 1)} and stay >= 3 pixels')
@@ -701,6 +787,8 @@ class StaticFocusCalcFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, trajectories, events, t_ref, cfg: PathConfig, num_pos: int, event_offsets, plans: dict, auto: bool = False):
         B, M, Mp, n, dev, traj, ev, tr = _calc_inputs(trajectories, events, t_ref, cfg, num_pos)
+        if knn_is_wide(n):
+            raise _wide_limit('static_shapes=True', n)
         need_grad = trajectories.requires_grad
         key = StaticFocusCalcFn.plan_key(trajectories, events, cfg, num_pos, event_offsets)
         sp = plans.get(key)
@@ -1079,8 +1167,13 @@ class KnnLutFn(torch.autograd.Function):
         traj = _f32c(trajectories.detach())
         B, _, n, _ = traj.shape
         shape = make_shape(cfg, B, 0, 0, n)
-        ws = alloc_workspace(shape, traj.device)
-        flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
+        ctx.wide = knn_is_wide(n)
+        if ctx.wide:
+            ws = None
+            flow_lut, flow_next, state = knn_wide_fwd(cfg, shape, traj)      # (state: the merged index lists)
+        else:
+            ws = alloc_workspace(shape, traj.device)
+            flow_lut, flow_next, state, _ = knn_lut_fwd(cfg, shape, traj, ws)
         ctx.shape, ctx.ws = shape, ws
         ctx.has_next = flow_next is not None
         ctx.save_for_backward(traj, state)
@@ -1093,6 +1186,8 @@ class KnnLutFn(torch.autograd.Function):
         traj, state = ctx.saved_tensors
         g_lut = _f32c(g_lut)
         g_next = _f32c(g_next) if ctx.has_next else None
+        if ctx.wide:
+            return knn_idx_bwd(ctx.shape, traj, g_lut, g_next, state), None
         return knn_lut_bwd(ctx.shape, traj, g_lut, g_next, state, ctx.ws), None
 
 
@@ -1445,6 +1540,8 @@ def knn_indices(cfg: PathConfig, trajectories):
     traj = _f32c(trajectories.detach())
     B, _, n, _ = traj.shape
     shape = make_shape(cfg, B, 0, 0, n)
+    if knn_is_wide(n):
+        return knn_wide_fwd(cfg, shape, traj)[2]
     ws = alloc_workspace(shape, traj.device)
     _, _, _, idx = knn_lut_fwd(cfg, shape, traj, ws, want_idx=True)
     return idx

@@ -393,6 +393,25 @@ int mpc_ingest_scatter_ordered(const mpc_ingest_shape *s, const mpc_shape *loss,
                                const int64_t *t_us, const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg,
                                float *events, int32_t *offsets, float *xytp, void *ws, void *ws_order, void *stream);
 
+/* The same three steps with the DSEC rectification inside the coordinate load: reference loader.py:153,187-189,
+ * x_rect, y_rect = rectify_ev_map[y, x].T.  x, y [B][N] int32 are the raw sensor pixel indices, rectify_map [Hs][Ws][2] fp32
+ * (contiguous, 8-byte aligned; last axis (x_rect, y_rect)); Hs, Ws need not equal s->H, s->W.  One 8-byte load per event after a
+ * bounds test on the raw index; no [B][N] float arrays are written.  Everything behind the load is what the float entry points
+ * compute on the gathered values (a NaN map entry fails 0 <= v and the row is dropped, as numpy's mask drops it); xytp carries the
+ * rectified coordinates of all rows (loader.py:169).  UNPINNED: an index outside the map (x >= Ws, y >= Hs, negative) raises or
+ * wraps in the reference; here the row is dropped from `events` and written to xytp as (-2, -2, t, p).  The workspace query and
+ * the order of the calls are those of the float entry points (mpc_ingest_workspace_bytes, mpc_ingest_ordered_workspace_bytes). */
+int mpc_ingest_rect_count(const mpc_ingest_shape *s, int32_t Hs, int32_t Ws, const float *rectify_map, const int32_t *x,
+                          const int32_t *y, const int64_t *t_us, const float *p, const int32_t *counts, int32_t *out_max,
+                          void *ws, void *stream);
+int mpc_ingest_rect_scatter(const mpc_ingest_shape *s, int32_t Hs, int32_t Ws, const float *rectify_map, const int32_t *x,
+                            const int32_t *y, const int64_t *t_us, const float *p, const int32_t *counts, int32_t max_pos,
+                            int32_t max_neg, float *events, float *xytp, void *ws, void *stream);
+int mpc_ingest_rect_scatter_ordered(const mpc_ingest_shape *s, const mpc_shape *loss, int32_t Hs, int32_t Ws,
+                                    const float *rectify_map, const int32_t *x, const int32_t *y, const int64_t *t_us,
+                                    const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg, float *events,
+                                    int32_t *offsets, float *xytp, void *ws, void *ws_order, void *stream);
+
 /* ---- event ingest for the EVIMO2 and MultiFlow configurations: the raw window -> the same `events` tensor, without the in-image
  * filter of the DSEC loader.  x, y [B][N] int32 (xy_int = 1) or fp32; p [B][N] int64 (p_int64 = 1) or fp32, in {0, 1} (for EVIMO2
  * the flipped polarity 1 - p of datasubset.py:154); t_us [B][N] int64, NON-DECREASING within a sample; counts [B] int32 (device;
@@ -668,6 +687,27 @@ typedef struct mpc_targets_shape { int32_t B, S, H, W, Ho, Wo, mode /* 0 evimo2,
 int mpc_flow_targets_supported(const mpc_targets_shape *s);
 int mpc_flow_targets(const mpc_targets_shape *s, const float *raw_flow, const float *id_mask,
                      float *flow, uint8_t *flow_valid, float *id_out, void *stream);
+
+/* ---- the DSEC flow files on the device.  png16 [B][H][W][3] uint16 is the 16-bit PNG payload as imageio returns / takes it:
+ * channel 0 = x, channel 1 = y, channel 2 = valid.  One kernel each on `stream` (the error: two), no memset / memcpy nodes, nothing
+ * read back.  Four pixels (24 B) per thread in 8-byte payload accesses when H * W % 4 == 0 and png16 is 8-byte, the fp32 planes
+ * 16-byte (and valid 4-byte) aligned; one pixel per thread otherwise.  B, H, W >= 1, B * H * W < 2^31.
+ * mpc_dsec_flow_decode = reference src/loader/dsec/loader.py:174-180: flow [B][2][H][W] (out): channel 0 = (png[..., 1] - 2^15) / 128,
+ *   channel 1 = (png[..., 0] - 2^15) / 128 (exact in fp32); valid [B][H][W] bytes 0 / 1 (out) = png[..., 2] != 0 (:178, astype(bool)).
+ * mpc_dsec_flow_error = mpc_flow_error (src/utils/flow.py:18-70, src/utils/metrics.py:50-56) with flow_gt and event_mask decoded
+ *   from png16 in the load: no fp32 target and no mask are written.  Same per-pixel arithmetic, the same pixels per thread and
+ *   order of the sums as mpc_flow_error, hence the same bits.  flow_pred [B][2][H][W]; time_scale [B] or NULL; out[5] (device);
+ *   ws: mpc_dsec_flow_error_workspace_bytes(s) bytes; B <= 65535.
+ * mpc_dsec_flow_encode = scripts/dsec_inference.py:33-49 (scale_optical_flow + save_flow), flow [B][2][H][W] (y, x) -> png16 (out),
+ *   every operation one correctly rounded fp32 operation, no contraction: mag = sqrt(u * u + v * v); where mag > max_magnitude
+ *   (strict) u = (u / mag) * max_magnitude and likewise v, both with that one mag; q = u * 128 + 32768 truncated to uint16;
+ *   png16[..., 0] = q(x), [..., 1] = q(y), [..., 2] = 0.  UNPINNED: a pixel with a NaN or infinite component gets payload 0 in
+ *   both channels; a finite q outside [0, 65535] (only with max_magnitude >= 256) saturates. */
+int mpc_dsec_flow_decode(const uint16_t *png16, float *flow, uint8_t *valid, int32_t B, int32_t H, int32_t W, void *stream);
+int64_t mpc_dsec_flow_error_workspace_bytes(const mpc_err_shape *s);
+int mpc_dsec_flow_error(const mpc_err_shape *s, const uint16_t *png16, const float *flow_pred, const float *time_scale,
+                        float *out, void *ws, void *stream);
+int mpc_dsec_flow_encode(const float *flow, float max_magnitude, uint16_t *png16, int32_t B, int32_t H, int32_t W, void *stream);
 
 #ifdef __cplusplus
 }

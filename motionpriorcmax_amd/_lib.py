@@ -156,6 +156,9 @@ SIGNATURES = {
     'mpc_ingest_scatter': (cint, [isp] + [vp] * 5 + [i32, i32] + [vp] * 4),
     'mpc_ingest_ordered_workspace_bytes': (i64, [isp, sp]),
     'mpc_ingest_scatter_ordered': (cint, [isp, sp] + [vp] * 5 + [i32, i32] + [vp] * 6),
+    'mpc_ingest_rect_count': (cint, [isp, i32, i32] + [vp] * 9),
+    'mpc_ingest_rect_scatter': (cint, [isp, i32, i32] + [vp] * 6 + [i32, i32] + [vp] * 4),
+    'mpc_ingest_rect_scatter_ordered': (cint, [isp, sp, i32, i32] + [vp] * 6 + [i32, i32] + [vp] * 6),
     'mpc_ingest_window_workspace_bytes': (i64, [wsp]),
     'mpc_ingest_window_count': (cint, [wsp] + [vp] * 6),
     'mpc_ingest_window_scatter': (cint, [wsp] + [vp] * 6 + [i32, i32] + [vp] * 3),
@@ -182,6 +185,10 @@ SIGNATURES = {
     'mpc_corr_pyramid_bwd': (cint, [cdp, cint] + [vp] * 6),
     'mpc_flow_targets_supported': (cint, [tsp]),
     'mpc_flow_targets': (cint, [tsp] + [vp] * 6),
+    'mpc_dsec_flow_decode': (cint, [vp, vp, vp, i32, i32, i32, vp]),
+    'mpc_dsec_flow_error_workspace_bytes': (i64, [esp]),
+    'mpc_dsec_flow_error': (cint, [esp] + [vp] * 6),
+    'mpc_dsec_flow_encode': (cint, [vp, f32, vp, i32, i32, i32, vp]),
 }
 EXPORTS = list(SIGNATURES)
 

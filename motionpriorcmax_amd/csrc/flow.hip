@@ -12,6 +12,7 @@
 // Both are pure streaming kernels (HBM roofline): the resize reads the patch grid through L1/L2 (1/16 of the
 // output at patch 4) and writes each output element once; the metrics read 17 B per pixel once.
 #include "common.h"
+#include "flow_err_device.h"
 
 // ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_list_to_grid(const mpc_flow_shape s, const float *__restrict__ list,
@@ -110,32 +111,6 @@ extern "C" int mpc_dense_flow(const mpc_flow_shape *s, const float *traj_flow, c
 }
 
 // ------------------------------------------------------------------------------------------------------
-#define FE_BLOCKS 64          // partial-sum workgroups per sample
-#define FE_NACC 6             // epe, >1, >2, >3, acos, n_points
-
-struct FeAcc {
-    double v[FE_NACC];
-};
-
-__device__ __forceinline__ void fe_pixel(float g0, float g1, float p0, float p1, bool em, float ts, bool has_ts,
-                                         FeAcc &a) {
-    const bool fm = !isinf(g0) && !isinf(g1) && fabsf(g0) > 0.f && fabsf(g1) > 0.f;
-    const float m = (fm && em) ? 1.f : 0.f;
-    g0 *= m; g1 *= m; p0 *= m; p1 *= m;                       // a product as in flow.py:48-49 (inf * 0 = nan)
-    if (has_ts) { g0 *= ts; g1 *= ts; p0 *= ts; p1 *= ts; }
-    const float d0 = g0 - p0, d1 = g1 - p1;
-    const float epe = sqrtf(d0 * d0 + d1 * d1);
-    a.v[0] += (double)epe;
-    a.v[1] += epe > 1.f ? 1.0 : 0.0;
-    a.v[2] += epe > 2.f ? 1.0 : 0.0;
-    a.v[3] += epe > 3.f ? 1.0 : 0.0;
-    // channel 0 is "u", channel 1 is "v" (flow.py:63-64)
-    float cs = (1.0f + p0 * g0 + p1 * g1) / (sqrtf(1.f + p0 * p0 + p1 * p1) * sqrtf(1.f + g0 * g0 + g1 * g1));
-    cs = cs < -1.f ? -1.f : (cs > 1.f ? 1.f : cs);            // torch.clamp keeps nan
-    a.v[4] += (double)acosf(cs);
-    a.v[5] += (double)m;
-}
-
 // grid (FE_BLOCKS, B), 256 threads
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_flow_err_partial(const mpc_err_shape s, const float *__restrict__ gt,
@@ -201,6 +176,10 @@ __global__ __launch_bounds__(64) void k_flow_err_final(const mpc_err_shape s, co
     }
 }
 
+void mpc_flow_err_final(const mpc_err_shape *s, const double *part, float *out, hipStream_t st) {
+    MPC_LAUNCH(k_flow_err_final, dim3(1), dim3(64), 0, st, *s, part, out);
+}
+
 extern "C" int64_t mpc_flow_error_workspace_bytes(const mpc_err_shape *s) {
     if (!s || s->B < 1 || s->H < 1 || s->W < 1) return -2;
     return mpc_align((int64_t)s->B * FE_BLOCKS * FE_NACC * sizeof(double));
@@ -221,7 +200,7 @@ extern "C" int mpc_flow_error(const mpc_err_shape *s, const float *flow_gt, cons
     else
         MPC_LAUNCH(k_flow_err_partial<false>, dim3(FE_BLOCKS, s->B), dim3(256), 0, st, *s, flow_gt, flow_pred,
                            event_mask, time_scale, (double *)ws);
-    MPC_LAUNCH(k_flow_err_final, dim3(1), dim3(64), 0, st, *s, (const double *)ws, out);
+    mpc_flow_err_final(s, (const double *)ws, out, st);
     MPC_CHECK_LAUNCH();
     return 0;
 }

@@ -10,6 +10,7 @@
 // The caller reads the two batch maxima to size the output (the only host round trip of ingest).
 #include "common.h"
 #include "bounds.h"
+#include <type_traits>
 
 #define ING_CHUNK 1024          // events per workgroup (256 threads x 4 consecutive events)
 
@@ -73,6 +74,31 @@ __device__ __forceinline__ IngQuadT<XY, PT> ing_load4(const XY *__restrict__ x, 
     return q;
 }
 
+// Where the coordinates of an event come from.  IngXY: the float32 values themselves (rectified by the caller).  IngRect: raw sensor
+// pixel indices looked up in the DSEC rectification map [Hs][Ws] of (x_rect, y_rect) pairs -- rectify_ev_map[y, x] of reference
+// src/loader/dsec/loader.py:153,187-189 -- as part of the coordinate load: one 8-byte load per event after a bounds test on the raw
+// index, no [B][N] float arrays in between.  An index outside the map (the reference raises or wraps: unpinned) gives (-2, -2): it
+// fails the in-image filter and both taps of the voxel builder fall outside every grid.  Everything behind the load is shared.
+struct IngXY { const float *x, *y; };
+struct IngRect { const int *x, *y; const float2 *map; int Hs, Ws; };
+__device__ __forceinline__ IngQuad ing_load4(const IngXY &c, const long long *__restrict__ t, const float *__restrict__ p, size_t base,
+                                             int i0, int n, int vec) {
+    return ing_load4(c.x, c.y, t, p, base, i0, n, vec);
+}
+__device__ __forceinline__ IngQuad ing_load4(const IngRect &c, const long long *__restrict__ t, const float *__restrict__ p, size_t base,
+                                             int i0, int n, int vec) {
+    const IngQuadT<int, float> r = ing_load4(c.x, c.y, t, p, base, i0, n, vec);
+    IngQuad q;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float2 m = make_float2(-2.f, -2.f);
+        if (i0 + k < n && (unsigned)r.x[k] < (unsigned)c.Ws && (unsigned)r.y[k] < (unsigned)c.Hs)
+            m = c.map[(size_t)r.y[k] * c.Ws + r.x[k]];
+        q.x[k] = m.x; q.y[k] = m.y; q.p[k] = r.p[k]; q.t[k] = r.t[k];
+    }
+    return q;
+}
+
 // the counts and time extrema of a workgroup's threads -> slot `o` of the per-chunk tables
 __device__ __forceinline__ void ing_chunk_reduce(int cp, int cn, long long tmin, long long tmax, const IngLayout &L, size_t o,
                                                  int (&s_c)[2][4], long long (&s_t)[2][4]) {
@@ -95,10 +121,11 @@ __device__ __forceinline__ void ing_chunk_reduce(int cp, int cn, long long tmin,
 }
 
 // grid (nchunks, B), 256 threads
-__global__ __launch_bounds__(256) void k_ingest_count(const mpc_ingest_shape s, const IngLayout L,
-                                                      const float *__restrict__ x, const float *__restrict__ y,
-                                                      const long long *__restrict__ t, const float *__restrict__ p,
-                                                      const int *__restrict__ counts, int *__restrict__ out_max, int vec) {
+template <typename SRC>
+__device__ __forceinline__ void ing_count_body(const mpc_ingest_shape s, const IngLayout L,
+                                               const SRC c,
+                                               const long long *__restrict__ t, const float *__restrict__ p,
+                                               const int *__restrict__ counts, int *__restrict__ out_max, int vec) {
     __shared__ int s_c[2][4];
     __shared__ long long s_t[2][4];
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
@@ -110,7 +137,7 @@ __global__ __launch_bounds__(256) void k_ingest_count(const mpc_ingest_shape s, 
     long long tmin = 0x7fffffffffffffffLL, tmax = -0x7fffffffffffffffLL - 1;
     const int i0 = chunk * ING_CHUNK + tid * 4;
     if (i0 < n) {
-        const IngQuad q = ing_load4(x, y, t, p, base, i0, n, vec);
+        const IngQuad q = ing_load4(c, t, p, base, i0, n, vec);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (i0 + k < n) {
@@ -122,6 +149,18 @@ __global__ __launch_bounds__(256) void k_ingest_count(const mpc_ingest_shape s, 
         }
     }
     ing_chunk_reduce(cp, cn, tmin, tmax, L, ((size_t)b * L.nchunks + chunk) * 2, s_c, s_t);
+}
+
+// the two kernels of this body: float coordinates (the signature it always had) / raw indices + the rectification map
+__global__ __launch_bounds__(256) void k_ingest_count(const mpc_ingest_shape s, const IngLayout L, const float *__restrict__ x, const float *__restrict__ y,
+    const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int *__restrict__ out_max, int vec) {
+    ing_count_body(s, L, IngXY{x, y}, t, p, counts, out_max, vec);
+}
+__global__ __launch_bounds__(256) void k_ingest_rect_count(const mpc_ingest_shape s, const IngLayout L, const int *__restrict__ x, const int *__restrict__ y,
+    const float2 *__restrict__ map, int Hs, int Ws, const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int *__restrict__ out_max, int vec) {
+    ing_count_body(s, L, IngRect{x, y, map, Hs, Ws}, t, p, counts, out_max, vec);
 }
 
 // grid B, 256 threads: exclusive scan over the chunks of one sample
@@ -237,11 +276,12 @@ __device__ __forceinline__ void ing_flush(const float2 *s_rows, const IngLayout 
 // runs of 8-byte words (a lane writing its own 24-byte row was six scattered 4-byte stores per event).  The padding rows of
 // the sample (loader.py:360-364: zero rows, valid = 0) are zeroed here too, a share per workgroup -- not by a memset of the
 // whole tensor in front of the kernel.
-__global__ __launch_bounds__(256) void k_ingest_scatter(const mpc_ingest_shape s, const IngLayout L,
-                                                        const float *__restrict__ x, const float *__restrict__ y,
-                                                        const long long *__restrict__ t, const float *__restrict__ p,
-                                                        const int *__restrict__ counts, int max_pos, int max_neg,
-                                                        float *__restrict__ events, float *__restrict__ xytp, int vec) {
+template <typename SRC>
+__device__ __forceinline__ void ing_scatter_body(const mpc_ingest_shape s, const IngLayout L,
+                                                 const SRC c,
+                                                 const long long *__restrict__ t, const float *__restrict__ p,
+                                                 const int *__restrict__ counts, int max_pos, int max_neg,
+                                                 float *__restrict__ events, float *__restrict__ xytp, int vec) {
     __shared__ int s_w[2][4];
     __shared__ float2 s_rows[ING_CHUNK * 3];          // positives from the front, the negatives behind them
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
@@ -255,7 +295,7 @@ __global__ __launch_bounds__(256) void k_ingest_scatter(const mpc_ingest_shape s
 #pragma unroll
     for (int k = 0; k < 4; ++k) cls[k] = 0;
     if (i0 < n) {
-        q = ing_load4(x, y, t, p, base, i0, n, vec);
+        q = ing_load4(c, t, p, base, i0, n, vec);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             cls[k] = (i0 + k < n) ? classify(q.x[k], q.y[k], q.p[k], s.H, s.W) : 0;
@@ -286,6 +326,18 @@ __global__ __launch_bounds__(256) void k_ingest_scatter(const mpc_ingest_shape s
     ing_flush(s_rows, L, b, chunk, np_wg, nn_wg, max_pos, max_neg, events);
 }
 
+// the two kernels of this body: float coordinates (the signature it always had) / raw indices + the rectification map
+__global__ __launch_bounds__(256) void k_ingest_scatter(const mpc_ingest_shape s, const IngLayout L, const float *__restrict__ x, const float *__restrict__ y,
+    const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int max_pos, int max_neg, float *__restrict__ events, float *__restrict__ xytp, int vec) {
+    ing_scatter_body(s, L, IngXY{x, y}, t, p, counts, max_pos, max_neg, events, xytp, vec);
+}
+__global__ __launch_bounds__(256) void k_ingest_rect_scatter(const mpc_ingest_shape s, const IngLayout L, const int *__restrict__ x, const int *__restrict__ y,
+    const float2 *__restrict__ map, int Hs, int Ws, const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int max_pos, int max_neg, float *__restrict__ events, float *__restrict__ xytp, int vec) {
+    ing_scatter_body(s, L, IngRect{x, y, map, Hs, Ws}, t, p, counts, max_pos, max_neg, events, xytp, vec);
+}
+
 // ---- ingest straight into the bucket-ordered layout (both halves in one) -----------------------------
 // The rows of each polarity block ordered by (time bin, LUT strip) -- the key of the loss's backward buckets
 // (events.hip: mpc_event_bucket_order) -- as ingest WRITES them: the key of an event is known the moment its row is
@@ -301,10 +353,11 @@ __device__ __forceinline__ int ing_key(const mpc_ingest_shape &s, const IngKey &
 }
 
 // grid (nchunks, B), 256 threads, dynamic LDS 2 * (NK + 1) ints: counts[b][pol][key][chunk]
-__global__ __launch_bounds__(256) void k_ingest_keycount(const mpc_ingest_shape s, const IngLayout L, const IngKey k,
-                                                         const float *__restrict__ x, const float *__restrict__ y,
-                                                         const long long *__restrict__ t, const float *__restrict__ p,
-                                                         const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
+template <typename SRC>
+__device__ __forceinline__ void ing_keycount_body(const mpc_ingest_shape s, const IngLayout L, const IngKey k,
+                                                  const SRC c,
+                                                  const long long *__restrict__ t, const float *__restrict__ p,
+                                                  const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
     extern __shared__ int s_k[];
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
     const int n = min(counts[b], s.N);
@@ -315,7 +368,7 @@ __global__ __launch_bounds__(256) void k_ingest_keycount(const mpc_ingest_shape 
     __syncthreads();
     const int i0 = chunk * ING_CHUNK + tid * 4;
     if (i0 < n) {
-        const IngQuad q = ing_load4(x, y, t, p, base, i0, n, vec);
+        const IngQuad q = ing_load4(c, t, p, base, i0, n, vec);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (i0 + u >= n) continue;
@@ -332,14 +385,27 @@ __global__ __launch_bounds__(256) void k_ingest_keycount(const mpc_ingest_shape 
     }
 }
 
+// the two kernels of this body: float coordinates (the signature it always had) / raw indices + the rectification map
+__global__ __launch_bounds__(256) void k_ingest_keycount(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const float *__restrict__ x, const float *__restrict__ y,
+    const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
+    ing_keycount_body(s, L, k, IngXY{x, y}, t, p, counts, kcounts, vec);
+}
+__global__ __launch_bounds__(256) void k_ingest_rect_keycount(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const int *__restrict__ x, const int *__restrict__ y,
+    const float2 *__restrict__ map, int Hs, int Ws, const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
+    ing_keycount_body(s, L, k, IngRect{x, y, map, Hs, Ws}, t, p, counts, kcounts, vec);
+}
+
 // grid (nchunks, B), 256 threads, dynamic LDS 2 * (NK + 1) ints.  kcounts (scanned in place) = first row of this chunk's
 // share inside every (polarity, key); offsets [B][2][NK + 1] = first row of every key
-__global__ __launch_bounds__(256) void k_ingest_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const IngKey k,
-                                                                const float *__restrict__ x, const float *__restrict__ y,
-                                                                const long long *__restrict__ t, const float *__restrict__ p,
-                                                                const int *__restrict__ counts, int M,
-                                                                const int *__restrict__ kcounts, const int *__restrict__ offsets,
-                                                                float *__restrict__ events, float *__restrict__ xytp, int vec) {
+template <typename SRC>
+__device__ __forceinline__ void ing_scatter_ordered_body(const mpc_ingest_shape s, const IngLayout L, const IngKey k,
+                                                         const SRC c,
+                                                         const long long *__restrict__ t, const float *__restrict__ p,
+                                                         const int *__restrict__ counts, int M,
+                                                         const int *__restrict__ kcounts, const int *__restrict__ offsets,
+                                                         float *__restrict__ events, float *__restrict__ xytp, int vec) {
     extern __shared__ int s_k[];
     const int b = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
     const int n = min(counts[b], s.N);
@@ -354,7 +420,7 @@ __global__ __launch_bounds__(256) void k_ingest_scatter_ordered(const mpc_ingest
     __syncthreads();
     const int i0 = chunk * ING_CHUNK + tid * 4;
     if (i0 < n) {
-        const IngQuad q = ing_load4(x, y, t, p, base, i0, n, vec);
+        const IngQuad q = ing_load4(c, t, p, base, i0, n, vec);
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int i = i0 + u;
@@ -386,6 +452,20 @@ __global__ __launch_bounds__(256) void k_ingest_scatter_ordered(const mpc_ingest
             if (j < pad_p) zp[j] = make_float2(0.f, 0.f); else zn[j - pad_p] = make_float2(0.f, 0.f);
         }
     }
+}
+
+// the two kernels of this body: float coordinates (the signature it always had) / raw indices + the rectification map
+__global__ __launch_bounds__(256) void k_ingest_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const float *__restrict__ x, const float *__restrict__ y,
+    const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int M, const int *__restrict__ kcounts, const int *__restrict__ offsets,
+    float *__restrict__ events, float *__restrict__ xytp, int vec) {
+    ing_scatter_ordered_body(s, L, k, IngXY{x, y}, t, p, counts, M, kcounts, offsets, events, xytp, vec);
+}
+__global__ __launch_bounds__(256) void k_ingest_rect_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const int *__restrict__ x, const int *__restrict__ y,
+    const float2 *__restrict__ map, int Hs, int Ws, const long long *__restrict__ t, const float *__restrict__ p,
+    const int *__restrict__ counts, int M, const int *__restrict__ kcounts, const int *__restrict__ offsets,
+    float *__restrict__ events, float *__restrict__ xytp, int vec) {
+    ing_scatter_ordered_body(s, L, k, IngRect{x, y, map, Hs, Ws}, t, p, counts, M, kcounts, offsets, events, xytp, vec);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -425,26 +505,51 @@ extern "C" int64_t mpc_ingest_workspace_bytes(const mpc_ingest_shape *s) {
     return ing_layout(s, nullptr).total;
 }
 
-extern "C" int mpc_ingest_count(const mpc_ingest_shape *s, const float *x, const float *y, const int64_t *t_us,
-                                const float *p, const int32_t *counts, int32_t *out_max, void *ws, void *stream) {
-    MPC_CHECK_ARG(s && counts && out_max && ws && ((x && y && t_us && p) || s->N == 0 || s->B == 0), MPC_E_NULL, "null argument");
+// The entry points below exist twice: with the float coordinates (IngXY) and with raw indices + the rectification map (IngRect).
+// One host body per entry point, a template over the source as the kernels are.
+static int ing_rect_validate(int32_t Hs, int32_t Ws, const float *map) {
+    MPC_CHECK_ARG(Hs >= 1 && Ws >= 1 && (int64_t)Hs * Ws < (1LL << 31), MPC_E_SHAPE, "bad rectification map shape");
+    MPC_CHECK_ARG(map != nullptr, MPC_E_NULL, "rectify_map is null");
+    MPC_CHECK_ARG(((uintptr_t)map & 7) == 0, MPC_E_UNSUPPORTED, "rectify_map must be 8-byte aligned (one load per (x, y) pair)");
+    return 0;
+}
+
+template <typename SRC>
+static int ing_count(const char *fn, const mpc_ingest_shape *s, const SRC &c, const int64_t *t_us, const float *p, const int32_t *counts,
+                     int32_t *out_max, void *ws, void *stream) {
+    if (!(s && counts && out_max && ws && ((c.x && c.y && t_us && p) || s->N == 0 || s->B == 0))) { mpc_set_error("%s: null argument", fn); return MPC_E_NULL; }
     int rc = ing_validate(s);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (s->B == 0) return mpc_zero_async(out_max, 2 * sizeof(int32_t), st);
     const IngLayout L = ing_layout(s, ws).L;
-    MPC_LAUNCH(k_ingest_count, dim3(L.nchunks, s->B), dim3(256), 0, st, *s, L, x, y,
-                       reinterpret_cast<const long long *>(t_us), p, counts, out_max, ing_vec(s, x, y, t_us, p));
+    const long long *t = reinterpret_cast<const long long *>(t_us);
+    const int vec = ing_vec(s, c.x, c.y, t_us, p);
+    if constexpr (std::is_same<SRC, IngXY>::value) MPC_LAUNCH(k_ingest_count, dim3(L.nchunks, s->B), dim3(256), 0, st, *s, L, c.x, c.y, t, p, counts, out_max, vec);
+    else MPC_LAUNCH(k_ingest_rect_count, dim3(L.nchunks, s->B), dim3(256), 0, st, *s, L, c.x, c.y, c.map, c.Hs, c.Ws, t, p, counts, out_max, vec);
     MPC_LAUNCH(k_ingest_scan, dim3(s->B), dim3(256), 0, st, L, out_max);
     MPC_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int mpc_ingest_scatter(const mpc_ingest_shape *s, const float *x, const float *y, const int64_t *t_us,
-                                  const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg,
-                                  float *events, float *xytp, void *ws, void *stream) {
-    MPC_CHECK_ARG(s && counts && ws && ((x && y && t_us && p) || s->N == 0 || s->B == 0), MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG(max_pos >= 0 && max_neg >= 0 && (events || max_pos + max_neg == 0 || s->B == 0), MPC_E_NULL, "events is null");
+extern "C" int mpc_ingest_count(const mpc_ingest_shape *s, const float *x, const float *y, const int64_t *t_us,
+                                const float *p, const int32_t *counts, int32_t *out_max, void *ws, void *stream) {
+    return ing_count(__func__, s, IngXY{x, y}, t_us, p, counts, out_max, ws, stream);
+}
+
+extern "C" int mpc_ingest_rect_count(const mpc_ingest_shape *s, int32_t Hs, int32_t Ws, const float *rectify_map, const int32_t *x,
+                                     const int32_t *y, const int64_t *t_us, const float *p, const int32_t *counts, int32_t *out_max,
+                                     void *ws, void *stream) {
+    int rc = ing_rect_validate(Hs, Ws, rectify_map);
+    if (rc) return rc;
+    return ing_count(__func__, s, IngRect{x, y, reinterpret_cast<const float2 *>(rectify_map), Hs, Ws}, t_us, p, counts, out_max, ws, stream);
+}
+
+template <typename SRC>
+static int ing_scatter(const char *fn, const mpc_ingest_shape *s, const SRC &c, const int64_t *t_us, const float *p, const int32_t *counts,
+                       int32_t max_pos, int32_t max_neg, float *events, float *xytp, void *ws, void *stream) {
+    if (!(s && counts && ws && ((c.x && c.y && t_us && p) || s->N == 0 || s->B == 0))) { mpc_set_error("%s: null argument", fn); return MPC_E_NULL; }
+    if (!(max_pos >= 0 && max_neg >= 0 && (events || max_pos + max_neg == 0 || s->B == 0))) { mpc_set_error("%s: events is null", fn); return MPC_E_NULL; }
     int rc = ing_validate(s);
     if (rc) return rc;
     if (s->B == 0) return 0;
@@ -452,10 +557,27 @@ extern "C" int mpc_ingest_scatter(const mpc_ingest_shape *s, const float *x, con
     const int64_t M = (int64_t)max_pos + max_neg;
     if (s->N == 0) return M > 0 ? mpc_zero_async(events, (size_t)s->B * M * 6 * sizeof(float), st) : 0;     // padding rows only
     const IngLayout L = ing_layout(s, ws).L;
-    MPC_LAUNCH(k_ingest_scatter, dim3(L.nchunks, s->B), dim3(256), 0, st, *s, L, x, y,
-                       reinterpret_cast<const long long *>(t_us), p, counts, max_pos, max_neg, events, xytp, ing_vec(s, x, y, t_us, p));
+    const long long *t = reinterpret_cast<const long long *>(t_us);
+    const int vec = ing_vec(s, c.x, c.y, t_us, p);
+    if constexpr (std::is_same<SRC, IngXY>::value) MPC_LAUNCH(k_ingest_scatter, dim3(L.nchunks, s->B), dim3(256), 0, st, *s, L, c.x, c.y, t, p, counts, max_pos, max_neg, events, xytp, vec);
+    else MPC_LAUNCH(k_ingest_rect_scatter, dim3(L.nchunks, s->B), dim3(256), 0, st, *s, L, c.x, c.y, c.map, c.Hs, c.Ws, t, p, counts, max_pos, max_neg, events, xytp, vec);
     MPC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int mpc_ingest_scatter(const mpc_ingest_shape *s, const float *x, const float *y, const int64_t *t_us,
+                                  const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg,
+                                  float *events, float *xytp, void *ws, void *stream) {
+    return ing_scatter(__func__, s, IngXY{x, y}, t_us, p, counts, max_pos, max_neg, events, xytp, ws, stream);
+}
+
+extern "C" int mpc_ingest_rect_scatter(const mpc_ingest_shape *s, int32_t Hs, int32_t Ws, const float *rectify_map, const int32_t *x,
+                                       const int32_t *y, const int64_t *t_us, const float *p, const int32_t *counts, int32_t max_pos,
+                                       int32_t max_neg, float *events, float *xytp, void *ws, void *stream) {
+    int rc = ing_rect_validate(Hs, Ws, rectify_map);
+    if (rc) return rc;
+    return ing_scatter(__func__, s, IngRect{x, y, reinterpret_cast<const float2 *>(rectify_map), Hs, Ws}, t_us, p, counts, max_pos, max_neg,
+                       events, xytp, ws, stream);
 }
 
 
@@ -477,12 +599,12 @@ extern "C" int64_t mpc_ingest_ordered_workspace_bytes(const mpc_ingest_shape *s,
 // flags of the FocusLoss; M = max_pos + max_neg, Mp = max_pos): `events` with the rows of every polarity block grouped by
 // (time bin, LUT strip) and the table `offsets` [B][2][nb * strips + 1].  `ws` = the workspace of mpc_ingest_count
 // (unchanged since that call), `ws_order` = mpc_ingest_ordered_workspace_bytes.
-extern "C" int mpc_ingest_scatter_ordered(const mpc_ingest_shape *s, const mpc_shape *loss, const float *x, const float *y,
-                                          const int64_t *t_us, const float *p, const int32_t *counts, int32_t max_pos,
-                                          int32_t max_neg, float *events, int32_t *offsets, float *xytp, void *ws, void *ws_order,
-                                          void *stream) {
-    MPC_CHECK_ARG(s && loss && counts && ws && ws_order && offsets && ((x && y && t_us && p) || s->N == 0 || s->B == 0), MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG(max_pos >= 0 && max_neg >= 0 && (events || max_pos + max_neg == 0 || s->B == 0), MPC_E_NULL, "events is null");
+template <typename SRC>
+static int ing_scatter_ordered(const char *fn, const mpc_ingest_shape *s, const mpc_shape *loss, const SRC &c, const int64_t *t_us,
+                               const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg, float *events, int32_t *offsets,
+                               float *xytp, void *ws, void *ws_order, void *stream) {
+    if (!(s && loss && counts && ws && ws_order && offsets && ((c.x && c.y && t_us && p) || s->N == 0 || s->B == 0))) { mpc_set_error("%s: null argument", fn); return MPC_E_NULL; }
+    if (!(max_pos >= 0 && max_neg >= 0 && (events || max_pos + max_neg == 0 || s->B == 0))) { mpc_set_error("%s: events is null", fn); return MPC_E_NULL; }
     int rc = ing_validate(s);
     if (rc) return rc;
     if ((rc = mpc_validate_shape(loss))) return rc;
@@ -503,13 +625,35 @@ extern "C" int mpc_ingest_scatter_ordered(const mpc_ingest_shape *s, const mpc_s
     int *totals = kcounts + (size_t)2 * s->B * (k.NK + 1) * L.nchunks;
     const size_t lds = (size_t)2 * (k.NK + 1) * sizeof(int);
     if (s->N == 0) return mpc_zero_async(offsets, (size_t)s->B * 2 * (k.NK + 1) * sizeof(int32_t), st);
-    MPC_LAUNCH(k_ingest_keycount, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, x, y, reinterpret_cast<const long long *>(t_us), p, counts, kcounts, ing_vec(s, x, y, t_us, p));
+    const long long *t = reinterpret_cast<const long long *>(t_us);
+    const int vec = ing_vec(s, c.x, c.y, t_us, p);
+    if constexpr (std::is_same<SRC, IngXY>::value) MPC_LAUNCH(k_ingest_keycount, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, t, p, counts, kcounts, vec);
+    else MPC_LAUNCH(k_ingest_rect_keycount, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, c.map, c.Hs, c.Ws, t, p, counts, kcounts, vec);
     MPC_CHECK_LAUNCH();
     if ((rc = mpc_evo_scans(loss, k.NCS, k.CSR, kcounts, totals, offsets, L.nchunks, st))) return rc;
-    MPC_LAUNCH(k_ingest_scatter_ordered, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, x, y, reinterpret_cast<const long long *>(t_us), p,
-               counts, (int)M, kcounts, (const int *)offsets, events, xytp, ing_vec(s, x, y, t_us, p));
+    if constexpr (std::is_same<SRC, IngXY>::value) MPC_LAUNCH(k_ingest_scatter_ordered, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, t, p,
+                                                              counts, (int)M, kcounts, (const int *)offsets, events, xytp, vec);
+    else MPC_LAUNCH(k_ingest_rect_scatter_ordered, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, c.map, c.Hs, c.Ws, t, p,
+                    counts, (int)M, kcounts, (const int *)offsets, events, xytp, vec);
     MPC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int mpc_ingest_scatter_ordered(const mpc_ingest_shape *s, const mpc_shape *loss, const float *x, const float *y,
+                                          const int64_t *t_us, const float *p, const int32_t *counts, int32_t max_pos,
+                                          int32_t max_neg, float *events, int32_t *offsets, float *xytp, void *ws, void *ws_order,
+                                          void *stream) {
+    return ing_scatter_ordered(__func__, s, loss, IngXY{x, y}, t_us, p, counts, max_pos, max_neg, events, offsets, xytp, ws, ws_order, stream);
+}
+
+extern "C" int mpc_ingest_rect_scatter_ordered(const mpc_ingest_shape *s, const mpc_shape *loss, int32_t Hs, int32_t Ws,
+                                               const float *rectify_map, const int32_t *x, const int32_t *y, const int64_t *t_us,
+                                               const float *p, const int32_t *counts, int32_t max_pos, int32_t max_neg, float *events,
+                                               int32_t *offsets, float *xytp, void *ws, void *ws_order, void *stream) {
+    int rc = ing_rect_validate(Hs, Ws, rectify_map);
+    if (rc) return rc;
+    return ing_scatter_ordered(__func__, s, loss, IngRect{x, y, reinterpret_cast<const float2 *>(rectify_map), Hs, Ws}, t_us, p, counts,
+                               max_pos, max_neg, events, offsets, xytp, ws, ws_order, stream);
 }
 
 // ---- raw windows of the EVIMO2 / MultiFlow configurations -> the same [B][M][6] tensor --------------------------------

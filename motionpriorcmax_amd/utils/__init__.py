@@ -9,4 +9,5 @@ from . import representation  # noqa: F401  (representation.VoxelGrid is the EVI
 from .representation import representation_grids  # noqa: F401
 from .val_metrics import trajectory_val_metrics, TrajectoryValMetrics, val_metric_keys  # noqa: F401
 from .flow_targets import flow_targets  # noqa: F401
+from .dsec_io import dsec_flow_targets, dsec_flow_error, dsec_flow_png16  # noqa: F401
 from .corr import corr_pyramid, corr_pyramid_fused, CorrLookup, coords_grid, level_target_indices  # noqa: F401

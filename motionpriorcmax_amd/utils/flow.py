@@ -51,6 +51,9 @@ class OpticalFlowError:
 
     @staticmethod
     def run(predictions, batch):
+        if 'forward_flow' not in batch and 'flow_png16' in batch:          # the 16-bit payload of the flow file itself (loader.py:174-180)
+            from .dsec_io import dsec_flow_error
+            return dsec_flow_error(batch['flow_png16'], predictions['flow'])
         return calculate_flow_error(batch['forward_flow'], predictions['flow'], batch['flow_valid'])
 
 

@@ -12,22 +12,48 @@ from .. import _lib as C
 from ..ops import _call, _lut_strips, _ptr, _query, _require_gpu, make_shape
 
 
-def ingest_events(x, y, t_us, p, counts, image_shape, num_bins, want_voxel_input=False, order_for=None):
+def _index32(t):
+    """Pixel indices of any integer dtype as contiguous int32 (uint16, as the DSEC h5 files hold them, through its bit pattern:
+    torch's unsigned 16-bit type has few kernels of its own)."""
+    if t.dtype == torch.uint16:
+        t = t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    return _c(t, torch.int32)
+
+
+def ingest_events(x, y, t_us, p, counts, image_shape, num_bins, want_voxel_input=False, order_for=None, rectify_map=None):
     """x, y, p: [B, N] float32; t_us: [B, N] int64 (increasing per sample); counts: [B] valid lengths.
     Returns {'events': [B, M, 6], 'num_pos_events': int, 'xytp': [B, N, 4] or None}.
     One host round trip (two integers) sizes the output, as the reference's CPU collate does.
     order_for: a FocusLoss -- the rows of each polarity block are then ordered by (time bin, LUT strip) for that loss
-    (FocusLoss.order_events) and the dict carries 'event_offsets'; `calc` gives the same loss and gradient bit for bit."""
+    (FocusLoss.order_events) and the dict carries 'event_offsets'; `calc` gives the same loss and gradient bit for bit.
+    rectify_map: [Hs, Ws, 2] float32, contiguous, on the device -- the DSEC `rectify_ev_map`, last axis (x_rect, y_rect) as
+    `rectify_events(...).T` unpacks it (loader.py:153,187-189).  x and y are then the raw sensor pixel INDICES (int32 is read
+    as it is, other integer dtypes are converted with torch first, floating tensors raise TypeError) and every kernel gathers
+    rectify_map[y, x] in its coordinate load: no [B, N] float arrays in between.  Everything else is what the call without a map
+    computes on the gathered values; 'xytp' carries the rectified coordinates of all rows (loader.py:169).  Hs, Ws need not equal
+    image_shape.  UNPINNED: a raw index outside the map (x >= Ws, y >= Hs, negative) raises or wraps in the reference; here the
+    row is dropped from 'events' and written to 'xytp' as (-2, -2, t, p), so both taps of the voxel builder fall outside any grid."""
     _require_gpu(x, 'x')
     dev = x.device
     B, N = x.shape
-    x = x.float().contiguous(); y = y.float().contiguous(); p = p.float().contiguous()
+    rect = ()
+    if rectify_map is not None:
+        if x.is_floating_point() or y.is_floating_point() or x.dtype == torch.bool or y.dtype == torch.bool:
+            raise TypeError(f'with rectify_map, x and y are sensor pixel indices of an integer dtype (got {x.dtype}, {y.dtype})')
+        _require_gpu(rectify_map, 'rectify_map')
+        if rectify_map.ndim != 3 or rectify_map.shape[2] != 2 or rectify_map.dtype != torch.float32 or not rectify_map.is_contiguous():
+            raise ValueError(f'rectify_map must be a contiguous float32 [Hs, Ws, 2] tensor (got {tuple(rectify_map.shape)}, {rectify_map.dtype})')
+        x = _index32(x); y = _index32(y); p = p.float().contiguous()
+        rect = (int(rectify_map.shape[0]), int(rectify_map.shape[1]), _ptr(rectify_map))
+    else:
+        x = x.float().contiguous(); y = y.float().contiguous(); p = p.float().contiguous()
+    sym = 'mpc_ingest_rect_' if rect else 'mpc_ingest_'
     t_us = t_us.to(torch.int64).contiguous()
     cnt = counts.to(device=dev, dtype=torch.int32).contiguous()
     shape = C.IngestShape(B=B, N=N, H=int(image_shape[0]), W=int(image_shape[1]), nb=int(num_bins))
     ws = torch.empty(max(_query('mpc_ingest_workspace_bytes', dev, ctypes.byref(shape)), 256), dtype=torch.uint8, device=dev)
     out_max = torch.empty(2, dtype=torch.int32, device=dev)
-    _call('mpc_ingest_count', dev, ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(out_max), _ptr(ws))
+    _call(sym + 'count', dev, ctypes.byref(shape), *rect, _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt), _ptr(out_max), _ptr(ws))
     max_pos, max_neg = (int(v) for v in out_max.tolist())          # the collate's host decision
     events = torch.empty((B, max_pos + max_neg, 6), dtype=torch.float32, device=dev)
     xytp = torch.empty((B, N, 4), dtype=torch.float32, device=dev) if want_voxel_input else None
@@ -40,10 +66,10 @@ def ingest_events(x, y, t_us, p, counts, image_shape, num_bins, want_voxel_input
             nb2 = _query('mpc_ingest_ordered_workspace_bytes', dev, ctypes.byref(shape), ctypes.byref(lshape))
             ws2 = torch.empty(max(nb2, 256), dtype=torch.uint8, device=dev)
             offs = torch.empty((B, 2, cfg.num_bins * ncs + 1), dtype=torch.int32, device=dev)
-            _call('mpc_ingest_scatter_ordered', dev, ctypes.byref(shape), ctypes.byref(lshape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p),
+            _call(sym + 'scatter_ordered', dev, ctypes.byref(shape), ctypes.byref(lshape), *rect, _ptr(x), _ptr(y), _ptr(t_us), _ptr(p),
                   _ptr(cnt), max_pos, max_neg, _ptr(events), _ptr(offs), _ptr(xytp), _ptr(ws), _ptr(ws2))
             return {'events': events, 'num_pos_events': max_pos, 'xytp': xytp, 'event_offsets': offs}
-    _call('mpc_ingest_scatter', dev, ctypes.byref(shape), _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt),
+    _call(sym + 'scatter', dev, ctypes.byref(shape), *rect, _ptr(x), _ptr(y), _ptr(t_us), _ptr(p), _ptr(cnt),
           max_pos, max_neg, _ptr(events), _ptr(xytp), _ptr(ws))
     out = {'events': events, 'num_pos_events': max_pos, 'xytp': xytp}
     return out if order_for is None else order_for.order_events(out)

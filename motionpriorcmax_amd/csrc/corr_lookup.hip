@@ -3,7 +3,7 @@
 //   (bilinear_sampler), raft.py:165-189 (flows = bezier.get_flow_from_reference(times); coords1 = coords0 + flows; corr_block(coords1)).
 // For the query q = (b, y, x), the entry e = (level l, slot k) with target t = level_target[l][k], K = 2R + 1:
 //   (cx, cy) = coords[t][b][:, y, x]   or, coords == NULL,   (x, y) + sum_j basis[t][j] * params[b][(j, d + j)][y][x]
-//   sx = cx / 2^l, sy = cy / 2^l, x0 = floor(sx), fx = sx - x0 (exact in fp32), y0, fy likewise
+//   sx = cx / 2^l, sy = cy / 2^l, x0 = floor(sx), fx = sx - x0 (exact in fp32 but for -0.5 < sx < 0: rounded there, by <= 2^-25, up to 1.0f), y0, fy likewise
 //   out[b][e * K * K + i * K + j][y][x] = w00 V[i][j] + w01 V[i][j + 1] + w10 V[i + 1][j] + w11 V[i + 1][j + 1]
 //   V[a][c] = level[l][k][q][y0 - R + a][x0 - R + c] (0 outside the slice), w00 = (1 - fx)(1 - fy), w01 = fx (1 - fy), w10 = (1 - fx) fy, w11 = fx fy
 // In plain torch this is a [n * B * h * w, K, K, 2] coordinate tensor built by half a dozen elementwise operators, its normalisation to

@@ -253,6 +253,40 @@ int mpc_pe_tile_rows_bwd(const float *grad_rows, float *grad_grid, int32_t B, in
 int mpc_pe_basis_field(const float *coef_rows, const float *phim, float *field, int32_t B, int32_t G, int32_t k, int32_t nb, void *stream);
 int mpc_pe_rows_grad_finish(const float *grad_parts, int32_t split, const float *grad_field, const float *phim, const float *grad_out,
                             float *grad_coef_rows, int32_t B, int32_t G, int32_t k, int32_t nb, void *stream);
+/* Same extension, a TABULATED basis (FocusLoss.calc_per_event_basis(basis_type='table'); additive, still version 107): the basis is a
+ * table [S + 1][k] of fp32 samples at the knots i / S, interpolated linearly at every event's time, each line one fp32 operation:
+ *   tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;
+ *   B_j(t) = table[i][j] + f * (table[i + 1][j] - table[i][j]);   phi_j(event) = B_j(t_ref) - B_j(t_event)
+ * -- a basis the kernels can read AND differentiate: no [B][M][k] tensor exists in either direction.
+ *   mpc_pe_table_supported   1 where these calls serve (shape, k, S): MPC_F_NO_WARP, num_tref == 1, k <= 8, num_bins <= 64 and
+ *                            (S + 1) * k <= mpc_pe_table_limit() (the 64-bit accumulators of mpc_pe_table_basis_grad in LDS); 0
+ *                            where the caller takes another route.  The rule lives in the library only.
+ *   mpc_pe_table_warp        mpc_pe_warp with phi from the table
+ *   mpc_pe_table_grad        mpc_pe_grad with phi from the table; grad_pos [B][M][2] or NULL: every row's UNSCALED position gradient
+ *                            (gy, gx) -- without scal[GCOEF] and grad_out; zeros for rows of weight 0 --, kept for
+ *                            mpc_pe_table_basis_grad so that the adjoint image is gathered once
+ *   mpc_pe_table_grad_ordered  mpc_pe_grad_ordered likewise (grad_pos is zeroed here: rows outside the offsets table stay zero)
+ *   mpc_pe_table_basis_grad  grad_table [S + 1][k] = scal[GCOEF] * grad_out * d objective / d table through the events: with
+ *                            G_j = gy * coef[cell][0][j] + gx * coef[cell][1][j], grad[i][j] -= (1 - f) G_j, grad[i + 1][j] -= f G_j at
+ *                            every row's (i, f), and + (1 - f_r) sum G_j, + f_r sum G_j at the two knots of t_ref.  Sums in 64-bit
+ *                            fixed point (Q33.30): bitwise reproducible for any row order and either event layout.  acc: scratch of
+ *                            (S + 2) * k int64 (zeroed here).  (The smoothness term reaches the table through phim: below.)
+ *   mpc_pe_field_basis_grad  the adjoint of mpc_pe_basis_field w.r.t. phim: grad_phim [nb][k] = grad_out[0] * sum over (b, cell, d) of
+ *                            grad_field[(b, t)][cell][d] * coef_rows[(b, cell)][d][j]; fp64 sums in a fixed order; part: scratch of
+ *                            nb * 64 * k doubles; k <= 8, nb <= 64                                                                  */
+int32_t mpc_pe_table_supported(const mpc_shape *s, int32_t k, int32_t S);
+int32_t mpc_pe_table_limit(void);
+int mpc_pe_table_warp(const mpc_shape *s, const float *events, const float *coef_rows, const float *table, int32_t S, int32_t k,
+                      const float *t_ref, float *rows_out, void *stream);
+int mpc_pe_table_grad(const mpc_shape *s, const float *rows, const float *table, int32_t S, int32_t k, const float *t_ref,
+                      const float *grad_iwe, const float *scal, const float *grad_out, float *grad_coef_rows, float *grad_pos, void *stream);
+int mpc_pe_table_grad_ordered(const mpc_shape *s, const float *rows, const int32_t *offsets, const float *table, int32_t S, int32_t k,
+                              const float *t_ref, const float *grad_iwe, const float *scal, const float *grad_out,
+                              float *grad_coef_rows, int32_t split, float *grad_pos, void *stream);
+int mpc_pe_table_basis_grad(const mpc_shape *s, const float *rows, const float *grad_pos, const float *coef_rows, int32_t S, int32_t k,
+                            const float *t_ref, const float *scal, const float *grad_out, int64_t *acc, float *grad_table, void *stream);
+int mpc_pe_field_basis_grad(const float *grad_field, const float *coef_rows, const float *grad_out, double *part, float *grad_phim,
+                            int32_t B, int32_t G, int32_t k, int32_t nb, void *stream);
 
 int mpc_event_splat_bwd(const mpc_shape *s, const float *events, const float *flow_lut,
                         const float *t_ref, const float *grad_iwe, const float *scal,

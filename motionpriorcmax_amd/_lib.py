@@ -135,6 +135,13 @@ SIGNATURES = {
     'mpc_pe_tile_rows_bwd': (cint, [vp, vp] + [i32] * 6 + [vp]),
     'mpc_pe_basis_field': (cint, [vp, vp, vp] + [i32] * 4 + [vp]),
     'mpc_pe_rows_grad_finish': (cint, [vp, i32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
+    'mpc_pe_table_supported': (i32, [sp, i32, i32]),
+    'mpc_pe_table_limit': (i32, []),
+    'mpc_pe_table_warp': (cint, [sp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    'mpc_pe_table_grad': (cint, [sp, vp, vp, i32, i32] + [vp] * 7),
+    'mpc_pe_table_grad_ordered': (cint, [sp, vp, vp, vp, i32, i32] + [vp] * 5 + [i32, vp, vp]),
+    'mpc_pe_table_basis_grad': (cint, [sp, vp, vp, vp, i32, i32] + [vp] * 6),
+    'mpc_pe_field_basis_grad': (cint, [vp] * 5 + [i32] * 4 + [vp]),
     'mpc_event_splat_bwd': (cint, [sp] + [vp] * 10),
     'mpc_focus_fwd': (cint, [sp, fb, vp, vp]),
     'mpc_focus_bwd': (cint, [sp, fb] + [vp] * 6),

@@ -871,20 +871,58 @@ int mpc_event_splat_bwd_job(const mpc_shape *s, const float *events, const int32
 #define PE_KMAX 8          // orders held in registers (beyond: the generic instantiation reads phi per use)
 // phi[j] = basis_j(t_ref) - basis_j(t), j < k, from the tensor, or -- phi == nullptr: the polynomial basis t^(j+1) (basis.py:26-27) --
 // worked out here (one multiply per order instead of 4 k bytes of traffic per event and kernel)
+// A third source (TAB; FocusLoss.calc_per_event_basis(basis_type='table')): a table T [S + 1][k] of samples of the basis at the knots
+// i / S, interpolated linearly -- the DEFINITION is these five fp32 operations, one per line, nothing fused (utils.table_basis_values
+// spells the same lines in torch and must agree bit for bit):
+//   tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;  B_j = T[i][j] + f * (T[i+1][j] - T[i][j])
+// (t == 1 lands in the last interval with f == 1).  The table is read THROUGH THE CACHE in all three kernels: a time-sorted batch puts
+// the 64 lanes of a wavefront on one or two knots (a broadcast load), a bucket-ordered one on the knots of one time bin, and an LDS
+// copy of up to 64 KB per workgroup would cost k_pe_warp / k_pe_grad their occupancy and does not fit beside k_pe_accum's strip
+// accumulators (up to 150 KB).
+__device__ __forceinline__ void pe_tab_locate(float t, int S, int &i, float &f) {
+    const float tc = fminf(fmaxf(t, 0.f), 1.f);
+    const float x = tc * (float)S;
+    i = min((int)floorf(x), S - 1);
+    f = x - (float)i;
+}
 template <int KB>
-__device__ __forceinline__ void pe_phi(const float *__restrict__ phi, size_t row, int k, float t, float tref, float *out /* [KB or min(k, 8)] */) {
+__device__ __forceinline__ void pe_tab_basis(const float *__restrict__ table, int S, int k, float t, float *out /* [KB or min(k, 8)] */) {
+    const int kk = KB > 0 ? KB : min(k, PE_KMAX);
+    int i; float f;
+    pe_tab_locate(t, S, i, f);
+    const float *r0 = table + (size_t)i * k, *r1 = r0 + k;
+    for (int j = 0; j < kk; ++j) { const float a = r0[j]; const float d = r1[j] - a; out[j] = a + f * d; }
+}
+// the table the TAB instantiations read (appended to the kernels' arguments: the other instantiations never load them); bref =
+// B(t_ref), formed once per thread before its loop over the rows
+struct PeTab { const float *table; int S; };
+template <int KB, bool TAB>
+__device__ __forceinline__ void pe_tab_ref(const PeTab tb, int k, float tref, float *bref /* [KB or min(k, 8)] */) {
+    if (TAB) pe_tab_basis<KB>(tb.table, tb.S, k, tref, bref);
+}
+template <int KB, bool TAB = false>
+__device__ __forceinline__ void pe_phi(const float *__restrict__ phi, size_t row, int k, float t, float tref, float *out /* [KB or min(k, 8)] */,
+                                       const PeTab tb = PeTab{nullptr, 0}, const float *bref = nullptr) {
     const int kk = KB > 0 ? KB : min(k, PE_KMAX);       // (k: the row stride of phi; the first PE_KMAX orders go to registers)
+    if (TAB) {
+        float bt[KB > 0 ? KB : PE_KMAX];
+        pe_tab_basis<KB>(tb.table, tb.S, k, t, bt);
+        for (int j = 0; j < kk; ++j) out[j] = bref[j] - bt[j];
+        return;
+    }
     if (phi != nullptr) { for (int j = 0; j < kk; ++j) out[j] = phi[row * k + j]; return; }
     float a = tref, c = t;
     for (int j = 0; j < kk; ++j) { out[j] = a - c; a *= tref; c *= t; }
 }
 
-template <int KB>
+template <int KB, bool TAB = false>
 __global__ __launch_bounds__(256) void k_pe_warp(const mpc_shape s, const float *__restrict__ events, const float *__restrict__ coef,
                                                  const float *__restrict__ phi, int k, const float *__restrict__ t_ref,
-                                                 float *__restrict__ rows_out) {
+                                                 float *__restrict__ rows_out, const PeTab tb) {
     const EvParams p = make_params(s);
     const float tref = t_ref ? t_ref[0] : 0.f;
+    float bref[KB > 0 ? KB : PE_KMAX];
+    pe_tab_ref<KB, TAB>(tb, k, tref, bref);
     const size_t total = (size_t)p.B * p.M;
     for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
         const int b = (int)(row / p.M);
@@ -895,7 +933,7 @@ __global__ __launch_bounds__(256) void k_pe_warp(const mpc_shape s, const float 
         const float *c = coef + (size_t)cell * 2 * k;
         float fy = 0.f, fx = 0.f;
         float ph[KB > 0 ? KB : PE_KMAX];
-        pe_phi<KB>(phi, row, k, e[2], tref, ph);
+        pe_phi<KB, TAB>(phi, row, k, e[2], tref, ph, tb, bref);
         if (KB > 0) {
 #pragma unroll
             for (int j = 0; j < KB; ++j) { fy += c[j] * ph[j]; fx += c[KB + j] * ph[j]; }
@@ -909,14 +947,18 @@ __global__ __launch_bounds__(256) void k_pe_warp(const mpc_shape s, const float 
     }
 }
 
-template <int KB>
+// (TAB with gpos: every row's UNSCALED position gradient (gy, gx) is stored as well -- zeros for the rows of weight 0 --, 8 bytes per
+// event, for k_pe_table_grad: the adjoint image's taps are gathered once)
+template <int KB, bool TAB = false>
 __global__ __launch_bounds__(256) void k_pe_grad(const mpc_shape s, const float *__restrict__ rows, const float *__restrict__ phi, int k,
                                                  const float *__restrict__ t_ref, const float *__restrict__ gimg,
                                                  const float *__restrict__ scal, const float *__restrict__ grad_out,
-                                                 float *__restrict__ gcoef) {
+                                                 float *__restrict__ gcoef, const PeTab tb, float2 *__restrict__ gpos) {
     const EvParams p = make_params(s);
     const float coef = scal[MPC_SCAL_GCOEF] * (grad_out ? grad_out[0] : 1.f);
     const float tref = t_ref[0];
+    float bref[KB > 0 ? KB : PE_KMAX];
+    pe_tab_ref<KB, TAB>(tb, k, tref, bref);
     const size_t total = (size_t)p.B * p.M;
     for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
         const int b = (int)(row / p.M), i = (int)(row - (size_t)b * p.M);
@@ -924,17 +966,21 @@ __global__ __launch_bounds__(256) void k_pe_grad(const mpc_shape s, const float 
         load_event(rows, row, e);
         const int pol = (p.P == 2 && i >= p.Mp) ? 1 : 0;
         Warped o;
-        if (!warp_event_with(p, e, make_float2(0.f, 0.f), tref, o)) continue;
+        if (!warp_event_with(p, e, make_float2(0.f, 0.f), tref, o)) {
+            if (TAB && gpos != nullptr) gpos[row] = make_float2(0.f, 0.f);
+            continue;
+        }
         float gy, gx;
         event_pos_grad(p, o, gimg + ((size_t)b * p.P + pol) * p.H * p.W, gy, gx);
+        if (TAB && gpos != nullptr) gpos[row] = make_float2(gy, gx);
         gy *= coef; gx *= coef;
         if (gy == 0.f && gx == 0.f) continue;
         const int cell = __float_as_int(e[4]);
         float *g = gcoef + (size_t)cell * 2 * k;
         const int kk = KB > 0 ? KB : k;
         float ph[KB > 0 ? KB : PE_KMAX];
-        pe_phi<KB>(phi, row, k, e[2], tref, ph);
-        for (int j = 0; j < kk; ++j) { const float f = j < PE_KMAX ? ph[j] : phi[row * k + j]; atomicAdd(g + j, f * gy); atomicAdd(g + kk + j, f * gx); }
+        pe_phi<KB, TAB>(phi, row, k, e[2], tref, ph, tb, bref);
+        for (int j = 0; j < kk; ++j) { const float f = (TAB || j < PE_KMAX) ? ph[j] : phi[row * k + j]; atomicAdd(g + j, f * gy); atomicAdd(g + kk + j, f * gx); }
     }
 }
 
@@ -951,12 +997,14 @@ __device__ __forceinline__ long long pe_to_fixed(float v) {         // |v| < 2^3
     return ((long long)(int)hi << MPC_FIX_SHIFT) + (long long)__float2int_rn((v - hi) * (float)(1 << MPC_FIX_SHIFT));
 }
 #define PE_NIF 4
-template <int KB>
+// (TAB with gpos: the unscaled (gy, gx) of every row that contributes is stored for k_pe_table_grad; the caller zeroes gpos first --
+// rows outside every range of the offsets table, and rows this kernel skips, then read as zeros)
+template <int KB, bool TAB = false>
 __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, int NCS, int SPLIT, const int *__restrict__ offsets,
                                                     const float *__restrict__ rows, const float *__restrict__ phi, int k,
                                                     const float *__restrict__ t_ref, const float *__restrict__ gimg,
                                                     const float *__restrict__ scal, const float *__restrict__ grad_out,
-                                                    float *__restrict__ gcoef) {
+                                                    float *__restrict__ gcoef, const PeTab tb, float2 *__restrict__ gpos) {
     extern __shared__ unsigned long long s_pacc[];
     __shared__ int s_r0[2 * 64 + 1], s_pre[2 * 64 + 1];          // first row / running count of the 2 * nb ranges (nb <= 64)
     const EvParams p = make_params(s);
@@ -983,6 +1031,8 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
     __syncthreads();
     const int n = s_pre[nrange];
     const float tref = t_ref[0];
+    float bref[KB > 0 ? KB : PE_KMAX];
+    pe_tab_ref<KB, TAB>(tb, k, tref, bref);
     for (int q0 = tid; q0 < n; q0 += PE_NIF * PE_NT) {
         float e[PE_NIF][6];
         size_t grow[PE_NIF];
@@ -1012,11 +1062,12 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
             const int lc = __float_as_int(e[u][4]) - cell0;
             MPC_EXPECT(!on[u] || (gy[u] == 0.f && gx[u] == 0.f) || (lc >= 0 && lc < ncell));      // (a row outside its strip: the offsets table is not this tensor's)
             if (!on[u] || lc < 0 || lc >= ncell || (gy[u] == 0.f && gx[u] == 0.f)) continue;
+            if (TAB && gpos != nullptr) gpos[grow[u]] = make_float2(gy[u], gx[u]);
             float ph[KB > 0 ? KB : PE_KMAX];
-            pe_phi<KB>(phi, grow[u], k, e[u][2], tref, ph);
+            pe_phi<KB, TAB>(phi, grow[u], k, e[u][2], tref, ph, tb, bref);
             unsigned long long *a = s_pacc + (size_t)lc * 2 * kk;
             for (int j = 0; j < kk; ++j) {
-                const float f = j < PE_KMAX ? ph[j] : phi[grow[u] * k + j];
+                const float f = (TAB || j < PE_KMAX) ? ph[j] : phi[grow[u] * k + j];
                 atomicAdd(a + j, (unsigned long long)pe_to_fixed(f * gy[u]));
                 atomicAdd(a + kk + j, (unsigned long long)pe_to_fixed(f * gx[u]));
             }
@@ -1038,9 +1089,9 @@ extern "C" int mpc_pe_warp(const mpc_shape *s, const float *events, const float 
     if (total == 0) return 0;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
     hipStream_t st = (hipStream_t)stream;
-    if (k == 1) MPC_LAUNCH(k_pe_warp<1>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out);
-    else if (k == 3) MPC_LAUNCH(k_pe_warp<3>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out);
-    else MPC_LAUNCH(k_pe_warp<0>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out);
+    if (k == 1) MPC_LAUNCH(k_pe_warp<1>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, PeTab{nullptr, 0});
+    else if (k == 3) MPC_LAUNCH(k_pe_warp<3>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, PeTab{nullptr, 0});
+    else MPC_LAUNCH(k_pe_warp<0>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, PeTab{nullptr, 0});
     MPC_CHECK_LAUNCH();
     return 0;
 }
@@ -1059,9 +1110,9 @@ extern "C" int mpc_pe_grad(const mpc_shape *s, const float *rows, const float *p
     const int64_t total = (int64_t)s->B * s->M;
     if (total == 0) return 0;
     const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (k == 1) MPC_LAUNCH(k_pe_grad<1>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows);
-    else if (k == 3) MPC_LAUNCH(k_pe_grad<3>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows);
-    else MPC_LAUNCH(k_pe_grad<0>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows);
+    if (k == 1) MPC_LAUNCH(k_pe_grad<1>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    else if (k == 3) MPC_LAUNCH(k_pe_grad<3>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    else MPC_LAUNCH(k_pe_grad<0>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
     MPC_CHECK_LAUNCH();
     return 0;
 }
@@ -1103,9 +1154,235 @@ extern "C" int mpc_pe_grad_ordered(const mpc_shape *s, const float *rows, const 
     }
     MPC_CHECK_ARG(split >= 1 && split <= 16, MPC_E_SHAPE, "1 <= split <= 16");
     const dim3 grid(s->B * L.n_cstrips * split);
-    if (k == 1) MPC_LAUNCH(k_pe_accum<1>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows);
-    else if (k == 3) MPC_LAUNCH(k_pe_accum<3>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows);
-    else MPC_LAUNCH(k_pe_accum<0>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows);
+    if (k == 1) MPC_LAUNCH(k_pe_accum<1>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    else if (k == 3) MPC_LAUNCH(k_pe_accum<3>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    else MPC_LAUNCH(k_pe_accum<0>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---- the table basis (basis_type='table'): the three kernels above as TAB instantiations, and the gradient w.r.t. the table ----
+//   k_pe_table_grad : ONE streaming pass over the rows' (t, cell), the stored unscaled (gy, gx) and the tile rows (cache-resident,
+//               cell-coherent in the ordered layout).  G_j = gy c[cell][0][j] + gx c[cell][1][j];  acc[i][j] += (1 - f) G_j,
+//               acc[i + 1][j] += f G_j, sum[j] += G_j, with (i, f) of the row's time (pe_tab_locate).  The accumulators
+//               [(S + 1) k knot entries + k sums] live in LDS as Q33.30 (pe_to_fixed: round to nearest; ds_add_u64), every workgroup
+//               adds its non-zero entries to the global 64-bit accumulators at the end: integer sums, so the result is bitwise
+//               the same for any order of the rows, any grid and either event layout.
+//               BOUNDS: pe_to_fixed takes |G_j| < 2^31 -- G is (event weight) x (a difference of adjoint-image values, O(1) in the
+//               unscaled units of MPC_SCAL_GCOEF) x (a tile coefficient: a displacement in pixels); a knot's sum over the WHOLE batch
+//               must stay below 2^33 in magnitude (S = 1 puts every event on two knots: 2.8 M events x a mean |G| of 3000).
+//               A time-sorted batch (the DSEC loader's) puts the 64 lanes of a wavefront on one or two neighbouring intervals,
+//               i.e. 64 adds to the same two or three LDS words.  Every live lane adds by itself all the same: summing the knots'
+//               integers across the lanes with shuffles first (lane 0 adding once) was measured and is no faster -- 75 against
+//               68 us on a time-sorted C3 batch, 46 against 47 us on a bucket-ordered one -- the pass is
+//               bound by its gathers of tile rows, not by the LDS.  The sums over ALL events stay in registers and are added once
+//               per wavefront (every lane of every wavefront would hit the same k words).
+//   k_pe_table_finish : grad_table[i][j] = scal[GCOEF] grad_out (-acc[i][j] + [i == ir] (1 - fr) sum[j] + [i == ir + 1] fr sum[j]),
+//               (ir, fr) of t_ref: phi_j = B_j(t_ref) - B_j(t_event), products unscaled until here
+#define PT_NT 1024
+#define PE_TABLE_MAX_ENTRIES 16384          // (S + 1) * k: 128 KB of 64-bit accumulators (+ k sums) in the CU's 160 KB
+__device__ __forceinline__ long long pe_wave_sum_ll(long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+template <int KB>
+__global__ __launch_bounds__(PT_NT) void k_pe_table_grad(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
+                                                         const float *__restrict__ coef, int S, int k,
+                                                         unsigned long long *__restrict__ acc) {
+    extern __shared__ unsigned long long s_tacc[];          // [(S + 1) * kk] knots, then [kk] sums
+    const EvParams p = make_params(s);
+    const int tid = threadIdx.x, kk = KB > 0 ? KB : min(k, PE_KMAX);
+    const int nent = (S + 1) * kk, nall = nent + kk;
+    for (int i = tid; i < nall; i += PT_NT) s_tacc[MPC_IDX(i, nall)] = 0ull;
+    __syncthreads();
+    const size_t total = (size_t)p.B * p.M;
+    const int ncell = p.B * p.hq * p.wq;
+    long long sg[KB > 0 ? KB : PE_KMAX];
+    for (int j = 0; j < kk; ++j) sg[j] = 0;
+    for (size_t base = (size_t)blockIdx.x * PT_NT; base < total; base += (size_t)gridDim.x * PT_NT) {
+        const size_t row = base + tid;
+        float2 g = make_float2(0.f, 0.f);
+        if (row < total) g = gpos[row];
+        if (g.x == 0.f && g.y == 0.f) continue;                 // (a row of weight 0, or past the end: contributes nothing)
+        const float2 tp = *reinterpret_cast<const float2 *>(rows + row * 6 + 2);         // (t, p)
+        const int cell = min(max(__float_as_int(rows[row * 6 + 4]), 0), ncell - 1);     // (rows of mpc_pe_table_warp; never outside coef)
+        int i; float f;
+        pe_tab_locate(tp.x, S, i, f);
+        const float one_f = 1.f - f;
+        const float *c = coef + (size_t)cell * 2 * k;
+        for (int j = 0; j < kk; ++j) {
+            const float py = g.x * c[j], px = g.y * c[k + j];
+            const float G = py + px;
+            // (0 <= i <= S - 1: both knots lie inside the [S + 1] rows)
+            atomicAdd(&s_tacc[MPC_IDX((size_t)i * kk + j, nent)], (unsigned long long)pe_to_fixed(one_f * G));
+            atomicAdd(&s_tacc[MPC_IDX((size_t)(i + 1) * kk + j, nent)], (unsigned long long)pe_to_fixed(f * G));
+            sg[j] += pe_to_fixed(G);
+        }
+    }
+    for (int j = 0; j < kk; ++j) {
+        const long long v = pe_wave_sum_ll(sg[j]);
+        if ((tid & 63) == 0 && v != 0) atomicAdd(&s_tacc[MPC_IDX(nent + j, nall)], (unsigned long long)v);
+    }
+    __syncthreads();
+    for (int i = tid; i < nall; i += PT_NT) {
+        const unsigned long long v = s_tacc[MPC_IDX(i, nall)];
+        if (v != 0ull) atomicAdd(acc + i, v);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pe_table_finish(const unsigned long long *__restrict__ acc, int S, int k, const float *__restrict__ t_ref,
+                                                         const float *__restrict__ scal, const float *__restrict__ grad_out,
+                                                         float *__restrict__ gtable) {
+    const int idx = blockIdx.x * 256 + threadIdx.x, nent = (S + 1) * k;
+    if (idx >= nent) return;
+    const int i = idx / k, j = idx - i * k;
+    const float coef = scal[MPC_SCAL_GCOEF] * (grad_out ? grad_out[0] : 1.f);
+    int ir; float fr;
+    pe_tab_locate(t_ref[0], S, ir, fr);
+    const double unit = 1.0 / (double)(1 << MPC_FIX_SHIFT);
+    const double sum = (double)(long long)acc[nent + j] * unit;
+    double v = -((double)(long long)acc[idx] * unit);
+    if (i == ir) v += (double)(1.f - fr) * sum;
+    if (i == ir + 1) v += (double)fr * sum;
+    gtable[idx] = v == 0.0 ? 0.f : coef * (float)v;            // (no contribution stays 0 where the objective's scale is not finite: no events)
+}
+
+static bool pe_table_ok(const mpc_shape *s, int32_t k, int32_t S) {
+    return (s->flags & MPC_F_NO_WARP) && s->T == 1 && k >= 1 && k <= PE_KMAX && S >= 1 && s->nb <= 64 &&
+           (int64_t)(S + 1) * k <= PE_TABLE_MAX_ENTRIES;
+}
+
+// 1 where the table kernels serve (shape, k, S) -- k <= 8, num_bins <= 64, (S + 1) * k accumulators within the LDS --, 0 where the
+// caller takes its plain-torch route (the one copy of the rule: the Python side asks and never restates it)
+extern "C" int32_t mpc_pe_table_supported(const mpc_shape *s, int32_t k, int32_t S) {
+    if (!s || mpc_validate_shape(s)) return 0;
+    return pe_table_ok(s, k, S) ? 1 : 0;
+}
+
+// the largest (S + 1) * k the table kernels take
+extern "C" int32_t mpc_pe_table_limit(void) { return PE_TABLE_MAX_ENTRIES; }
+
+#define PE_TABLE_CHECKS(who)                                                                                                              \
+    MPC_CHECK_ARG((s->flags & MPC_F_NO_WARP) && s->T == 1, MPC_E_UNSUPPORTED, who " takes MPC_F_NO_WARP shapes, num_tref == 1");            \
+    MPC_CHECK_ARG(k >= 1 && k <= PE_KMAX && S >= 1 && s->nb <= 64, MPC_E_SHAPE, "1 <= num_basis <= 8, samples >= 1, num_bins <= 64");       \
+    MPC_CHECK_ARG((int64_t)(S + 1) * k <= PE_TABLE_MAX_ENTRIES, MPC_E_UNSUPPORTED, "(samples + 1) * num_basis exceeds mpc_pe_table_limit()")
+
+extern "C" int mpc_pe_table_warp(const mpc_shape *s, const float *events, const float *coef_rows, const float *table, int32_t S, int32_t k,
+                                 const float *t_ref, float *rows_out, void *stream) {
+    MPC_CHECK_ARG(s && coef_rows && table && t_ref && rows_out && (events || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PE_TABLE_CHECKS("mpc_pe_table_warp");
+    int rc = mpc_validate_shape(s);
+    if (rc) return rc;
+    const int64_t total = (int64_t)s->B * s->M;
+    if (total == 0) return 0;
+    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    hipStream_t st = (hipStream_t)stream;
+    const PeTab tb{table, S};
+    const float *phi = nullptr;
+    if (k == 1) MPC_LAUNCH((k_pe_warp<1, true>), dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
+    else if (k == 3) MPC_LAUNCH((k_pe_warp<3, true>), dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
+    else MPC_LAUNCH((k_pe_warp<0, true>), dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mpc_pe_table_grad(const mpc_shape *s, const float *rows, const float *table, int32_t S, int32_t k, const float *t_ref,
+                                 const float *grad_iwe, const float *scal, const float *grad_out, float *grad_coef_rows, float *grad_pos,
+                                 void *stream) {
+    MPC_CHECK_ARG(s && table && t_ref && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PE_TABLE_CHECKS("mpc_pe_table_grad");
+    int rc = mpc_validate_shape(s);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int e0 = mpc_zero_async(grad_coef_rows, (size_t)s->B * s->hq * s->wq * 2 * k * sizeof(float), st);
+    if (e0) return e0;
+    const int64_t total = (int64_t)s->B * s->M;
+    if (total == 0) return 0;
+    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const PeTab tb{table, S};
+    const float *phi = nullptr;
+    float2 *gpos = reinterpret_cast<float2 *>(grad_pos);
+    if (k == 1) MPC_LAUNCH((k_pe_grad<1, true>), dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
+    else if (k == 3) MPC_LAUNCH((k_pe_grad<3, true>), dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
+    else MPC_LAUNCH((k_pe_grad<0, true>), dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mpc_pe_table_grad_ordered(const mpc_shape *s, const float *rows, const int32_t *offsets, const float *table, int32_t S, int32_t k,
+                                         const float *t_ref, const float *grad_iwe, const float *scal, const float *grad_out,
+                                         float *grad_coef_rows, int32_t split, float *grad_pos, void *stream) {
+    MPC_CHECK_ARG(s && offsets && table && t_ref && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PE_TABLE_CHECKS("mpc_pe_table_grad_ordered");
+    int rc = mpc_validate_shape(s);
+    if (rc) return rc;
+    if (s->B == 0) return 0;
+    const mpc_ws_layout L = mpc_layout(s);
+    MPC_CHECK_ARG(L.n_cstrips > 0, MPC_E_UNSUPPORTED, "no bucketed event layout for this shape");
+    const size_t lds = (size_t)L.cstrip_rows * s->wq * 2 * k * 8;
+    MPC_CHECK_ARG(lds <= 150 * 1024, MPC_E_UNSUPPORTED, "a LUT strip's accumulators do not fit the LDS (use mpc_pe_table_grad)");
+    MPC_CHECK_ARG(split >= 1 && split <= 16, MPC_E_SHAPE, "1 <= split <= 16");
+    hipStream_t st = (hipStream_t)stream;
+    static mpc_device_once attr_once;
+    if (attr_once.need()) {
+        const void *fns[3] = {(const void *)k_pe_accum<1, true>, (const void *)k_pe_accum<3, true>, (const void *)k_pe_accum<0, true>};
+        for (const void *fn : fns) {
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+            if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
+        }
+        attr_once.mark();
+    }
+    if (grad_pos != nullptr && (int64_t)s->B * s->M > 0) {
+        // (rows outside every range of the table, and rows the kernel skips, carry no gradient)
+        const int e0 = mpc_zero_async(grad_pos, (size_t)s->B * s->M * 2 * sizeof(float), st);
+        if (e0) return e0;
+    }
+    const dim3 grid(s->B * L.n_cstrips * split);
+    const PeTab tb{table, S};
+    const float *phi = nullptr;
+    float2 *gpos = reinterpret_cast<float2 *>(grad_pos);
+    if (k == 1) MPC_LAUNCH((k_pe_accum<1, true>), grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
+    else if (k == 3) MPC_LAUNCH((k_pe_accum<3, true>), grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
+    else MPC_LAUNCH((k_pe_accum<0, true>), grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mpc_pe_table_basis_grad(const mpc_shape *s, const float *rows, const float *grad_pos, const float *coef_rows, int32_t S, int32_t k,
+                                       const float *t_ref, const float *scal, const float *grad_out, int64_t *acc, float *grad_table,
+                                       void *stream) {
+    MPC_CHECK_ARG(s && coef_rows && t_ref && scal && acc && grad_table && ((rows && grad_pos) || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PE_TABLE_CHECKS("mpc_pe_table_basis_grad");
+    int rc = mpc_validate_shape(s);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int nent = (S + 1) * k, nall = nent + k;
+    const int e0 = mpc_zero_async(acc, (size_t)nall * 8, st);
+    if (e0) return e0;
+    const int64_t total = (int64_t)s->B * s->M;
+    if (total > 0) {
+        const size_t lds = (size_t)nall * 8;
+        static mpc_device_once attr_once;
+        if (attr_once.need()) {
+            const void *fns[3] = {(const void *)k_pe_table_grad<1>, (const void *)k_pe_table_grad<3>, (const void *)k_pe_table_grad<0>};
+            for (const void *fn : fns) {
+                hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (PE_TABLE_MAX_ENTRIES + PE_KMAX) * 8);
+                if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
+            }
+            attr_once.mark();
+        }
+        // (one workgroup per CU and 1024 rows per trip; a batch of more than 256 Ki rows makes further trips)
+        const int grid = (int)((total + PT_NT - 1) / PT_NT < 256 ? (total + PT_NT - 1) / PT_NT : 256);
+        unsigned long long *a = reinterpret_cast<unsigned long long *>(acc);
+        const float2 *gpos = reinterpret_cast<const float2 *>(grad_pos);
+        if (k == 1) MPC_LAUNCH(k_pe_table_grad<1>, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
+        else if (k == 3) MPC_LAUNCH(k_pe_table_grad<3>, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
+        else MPC_LAUNCH(k_pe_table_grad<0>, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
+        MPC_CHECK_LAUNCH();
+    }
+    MPC_LAUNCH(k_pe_table_finish, dim3((nent + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(acc), S, k, t_ref, scal,
+               grad_out, grad_table);
     MPC_CHECK_LAUNCH();
     return 0;
 }

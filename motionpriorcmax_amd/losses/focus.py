@@ -142,7 +142,7 @@ class FocusLoss(base.TrajectoryLossBase):
         return out
 
     def calc_per_event_basis(self, coeff_grid, t_ref, batch, num_basis, basis_type='polynomial', basis_network=None, tile_size=None,
-                             fused=True):
+                             fused=True, basis_table=None):
         """UNPINNED EXTENSION -- no reference code exists for it (the reference warps through a binned, KNN-inverted flow LUT,
         focus.py:115-195); BASELINE.json's north_star names it: the per-event continuous-time warp.
 
@@ -155,19 +155,36 @@ class FocusLoss(base.TrajectoryLossBase):
 
         coeff_grid [B, 1, 2k, H, W] (first k channels y, next k x: the network's dense output, trajectory_net.py:142-161),
         t_ref scalar tensor / float in [0, 1], batch as for `calc`.  Returns the triple of `calc`.  Differentiable w.r.t. coeff_grid
-        (not w.r.t. the weights of a 'learned' basis: the basis values enter as constants).  With a bucket-ordered batch
+        (not w.r.t. the weights of a 'learned' basis: the basis values enter as constants -- to TRAIN a basis through this warp, hand
+        it over as a table: basis_type='table', below).  With a bucket-ordered batch
         (`order_events` / `ingest_events(order_for=...)`: `event_offsets`) the backward accumulates per LUT strip in LDS fixed point
         and is bitwise reproducible; without the table it uses global float atomics (slow: ~20 G atomics/s, and not
         reproducible).  fused=False: the same in plain torch around the vote / objective kernels (cross-check).
+
+        basis_type='table', basis_table=T: the basis is T [S + 1, num_basis] (fp32, on the events' device), samples at the knots
+        i / S interpolated linearly at every event's time (utils.table_basis_values is the definition; utils.basis_table samples any
+        basis of utils.basis_values, e.g. T = basis_table('learned', k, 1024, net)).  Differentiable w.r.t. coeff_grid AND T: the
+        kernels read the table and reduce the whole batch's gradient onto its (S + 1) * num_basis entries (bitwise reproducible in
+        either event layout); ordinary autograd carries it on into the weights of `net`, or T is an nn.Parameter itself.  The fused
+        node serves what the library says it serves (num_basis <= 8, num_bins <= 64, a table within its LDS limit); anything else,
+        and fused=False, runs in plain torch around the vote / objective kernels with the same gradients from autograd.
 
         A tile without a centre: there are ceil(H / sp) x ceil(W / sp) cells, and where 0 < H % sp <= sp // 2 (W likewise) the
         centre sp // 2 of the last row (column) of cells lies outside the image.  Such a cell carries zero coefficients: its
         events are not warped, it enters the smoothness field with zero flow, and no element of coeff_grid receives its
         gradient."""
-        from ..utils import basis_values
+        from ..utils import basis_values, table_basis_values
         if self.num_tref != 1:
             raise ValueError('calc_per_event_basis needs num_tref == 1')
         events = batch['events']
+        if (basis_type == 'table') != (basis_table is not None):
+            raise ValueError("basis_type='table' and basis_table go together")
+        if basis_table is not None:
+            if not (torch.is_tensor(basis_table) and basis_table.dim() == 2 and basis_table.dtype == torch.float32
+                    and basis_table.device == events.device and basis_table.shape[0] >= 2):
+                raise ValueError("basis_table must be a 2-D float32 tensor [samples + 1, num_basis] on the events' device")
+            if basis_table.shape[1] != num_basis:
+                raise ValueError(f'basis_table has {basis_table.shape[1]} columns, num_basis is {num_basis}')
         num_pos_events = batch['num_pos_events'] if 'num_pos_events' in batch else -1
         assert not self.polarity_aware_batching or num_pos_events > -1
         dev = events.device
@@ -191,8 +208,17 @@ class FocusLoss(base.TrajectoryLossBase):
         else:
             t_ref = torch.full((1,), float(t_ref), dtype=torch.float32, device=dev)
         offsets = batch['event_offsets'] if 'event_offsets' in batch else None     # from order_events / ingest (optional)
-        phi = None           # (fused + polynomial basis of up to 8 orders: worked out inside the kernels)
-        if not (fused and basis_type == 'polynomial' and num_basis <= 8):
+        # a table: the fused node where the library serves (k, num_bins, table size) -- the kernels read the table --, else the
+        # plain-torch chain below with phi from the table INSIDE the graph (autograd carries its gradient to the table)
+        tab_fused = basis_table is not None and bool(fused) and ops.pe_table_supported(self._cfg, events, int(num_pos_events), num_basis,
+                                                                                      basis_table.shape[0] - 1)
+        if basis_table is not None and not tab_fused:
+            fused = False
+        phi = None           # (fused + polynomial basis of up to 8 orders, or a table: worked out inside the kernels)
+        if basis_table is not None:
+            if not tab_fused:
+                phi = table_basis_values(basis_table, t_ref) - table_basis_values(basis_table, events[..., 2])
+        elif not (fused and basis_type == 'polynomial' and num_basis <= 8):
             with torch.no_grad():
                 phi = basis_values(t_ref, num_basis, basis_type, basis_network) - basis_values(events[..., 2], num_basis, basis_type, basis_network)
         phim = None
@@ -201,8 +227,17 @@ class FocusLoss(base.TrajectoryLossBase):
             tm = self._tmid_dev.get(dev)
             if tm is None:
                 tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
-            with torch.no_grad():
-                phim = basis_values(t_ref, num_basis, basis_type, basis_network) - basis_values(tm, num_basis, basis_type, basis_network)   # [nb, k]
+            if basis_table is not None:
+                bv = table_basis_values(basis_table, torch.cat((t_ref, tm)))       # (one evaluation for t_ref and the mid-times: half the operators)
+                phim = bv[:1] - bv[1:]                                               # [nb, k], in the graph
+            else:
+                with torch.no_grad():
+                    phim = basis_values(t_ref, num_basis, basis_type, basis_network) - basis_values(tm, num_basis, basis_type, basis_network)   # [nb, k]
+        if tab_fused:
+            loss, focus, smooth, iwes = ops.PerEventBasisCalcFn.apply(coeff_grid, events, None, phim, t_ref, self._cfg, int(num_pos_events), offsets,
+                                                                      int(num_basis), tile, basis_table)
+            iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
+            return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
         if fused and num_basis <= 8 and self.num_bins <= 64:
             # one autograd node of library calls (ops.PerEventBasisCalcFn): the step is no longer bound by the host
             loss, focus, smooth, iwes = ops.PerEventBasisCalcFn.apply(coeff_grid, events, phi, phim, t_ref, self._cfg, int(num_pos_events), offsets,
@@ -222,7 +257,11 @@ class FocusLoss(base.TrajectoryLossBase):
             warped = events[..., :2] + (ce * phi[:, :, None, :]).sum(-1)                              # [B, M, 2]  (y, x)
             focus, iwes = ops.PrewarpedFocusFn.apply(warped, events, t_ref, self._cfg, int(num_pos_events))
         smooth = torch.zeros((), device=dev)
-        if phim is not None:
+        if phim is not None and basis_table is not None:
+            # (BasisFieldFn treats phim as a constant; a table's phim is in the graph: the same product in plain torch)
+            field = (c_rows.reshape(B * G * 2, num_basis) @ phim.t()).view(B, G, 2, self.num_bins).permute(0, 3, 1, 2).reshape(B * self.num_bins, hq, wq, 2)
+            smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
+        elif phim is not None:
             field = ops.BasisFieldFn.apply(c_rows, phim, B, hq, wq)                                # [B*nb, hq, wq, 2]
             smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
         loss = focus + smooth

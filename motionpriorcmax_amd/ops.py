@@ -894,11 +894,23 @@ class EventFocusFn(torch.autograd.Function):
         return g_lut, None, None, None, None
 
 
-def _pe_fwd(shape, ev, coef_rows, ph, k, tr, ws, need_grad):
-    """The per-event forward core: mpc_pe_warp -> mpc_event_splat_fwd (MPC_F_NO_WARP) -> mpc_contrast_fwd -> (warped rows, blurred
-    images, adjoint images or None)."""
+def pe_table_supported(cfg, events, num_pos, k, samples):
+    """Do the table kernels (mpc_pe_table_*) serve this batch with a [samples + 1, k] table?  The library's answer: the rule --
+    k, num_bins, the LDS the table's accumulators take -- lives there only."""
+    if not (torch.is_tensor(events) and events.is_cuda):
+        return False
+    B, M, Mp = _check_events(events, cfg, num_pos)
+    shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+    return _query('mpc_pe_table_supported', events.device, ctypes.byref(shape), int(k), int(samples)) == 1
+
+
+def _pe_fwd(shape, ev, coef_rows, ph, k, tr, ws, need_grad, tab=None):
+    """The per-event forward core: mpc_pe_warp (`tab` [S + 1, k]: mpc_pe_table_warp) -> mpc_event_splat_fwd (MPC_F_NO_WARP) ->
+    mpc_contrast_fwd -> (warped rows, blurred images, adjoint images or None)."""
     rows = torch.empty_like(ev)
-    if shape.B * shape.M > 0:                 # (an empty tensor has no pointer to hand over)
+    if shape.B * shape.M > 0 and tab is not None:
+        _call('mpc_pe_table_warp', ev.device, ctypes.byref(shape), _ptr(ev), _ptr(coef_rows), _ptr(tab), tab.shape[0] - 1, k, _ptr(tr), _ptr(rows))
+    elif shape.B * shape.M > 0:               # (an empty tensor has no pointer to hand over)
         _call('mpc_pe_warp', ev.device, ctypes.byref(shape), _ptr(ev), _ptr(coef_rows), _ptr(ph), k, _ptr(tr), _ptr(rows))
     raw = event_splat_fwd(shape, rows, None, tr, ws)
     blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
@@ -915,21 +927,30 @@ def _pe_ordered_offsets(offsets, cfg, shape, k, dev):
     return _check_offsets(offsets, cfg, shape, dev)
 
 
-def _pe_pos_grad(shape, k, rows, offs, ph, tr, gimg, scal, go):
+def _pe_pos_grad(shape, k, rows, offs, ph, tr, gimg, scal, go, tab=None, gpos=None):
     """d objective / d tile coefficients through the warped positions, as partial results [split, B*hq*wq, 2k] for the caller to sum:
-    the ordered kernel on bucket-ordered rows (`offs`), the atomic kernel (split = 1) otherwise."""
+    the ordered kernel on bucket-ordered rows (`offs`), the atomic kernel (split = 1) otherwise.  `tab` [S + 1, k]: the table
+    instantiations of the same kernels, which also leave every row's unscaled position gradient in `gpos` [B, M, 2] (or None)."""
     dev = rows.device
     n = shape.B * shape.hq * shape.wq
     if offs is not None:
         # (a few workgroups per (sample, LUT strip), each with a share of the strip's row ranges and a partial result)
         split = max(1, min(16, 512 // max(1, shape.B * _lut_strips(shape, dev))))
         gp = torch.empty((split, n, 2 * k), dtype=torch.float32, device=dev)
-        rc = _call('mpc_pe_grad_ordered', dev, ctypes.byref(shape), _ptr(rows), _ptr(offs), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal),
-                   _ptr(go), _ptr(gp), split, accept=(C.E_UNSUPPORTED,))
+        if tab is not None:
+            rc = _call('mpc_pe_table_grad_ordered', dev, ctypes.byref(shape), _ptr(rows), _ptr(offs), _ptr(tab), tab.shape[0] - 1, k, _ptr(tr),
+                       _ptr(gimg), _ptr(scal), _ptr(go), _ptr(gp), split, _ptr(gpos), accept=(C.E_UNSUPPORTED,))
+        else:
+            rc = _call('mpc_pe_grad_ordered', dev, ctypes.byref(shape), _ptr(rows), _ptr(offs), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal),
+                       _ptr(go), _ptr(gp), split, accept=(C.E_UNSUPPORTED,))
         if rc == 0:
             return gp
         # (unsupported after all: the atomic backward below serves every shape)
     gp = torch.empty((1, n, 2 * k), dtype=torch.float32, device=dev)
+    if tab is not None:
+        _call('mpc_pe_table_grad', dev, ctypes.byref(shape), _ptr(rows), _ptr(tab), tab.shape[0] - 1, k, _ptr(tr), _ptr(gimg), _ptr(scal),
+              _ptr(go), _ptr(gp), _ptr(gpos))
+        return gp
     _call('mpc_pe_grad', dev, ctypes.byref(shape), _ptr(rows), _ptr(ph), k, _ptr(tr), _ptr(gimg), _ptr(scal), _ptr(go), _ptr(gp))
     return gp
 
@@ -984,10 +1005,16 @@ class PerEventBasisCalcFn(torch.autograd.Function):
     -> scalars, and back: position gradient per LUT strip -> (+ smoothness adjoint) -> dense gradient.  Rounds 4-5 spelt the dense <->
     per-tile operators and the smoothness field in torch (TileCoeffRowsFn, BasisFieldFn, LutSmoothFn below: kept for the unfused
     cross-check): two dozen operators around 0.30 ms of kernels, and the step was bound by the host (0.74-0.97 ms at the DSEC batch
-    shape).  Returns (loss, focus, smooth, iwes_blurred); differentiable w.r.t. coeff_grid through `loss`."""
+    shape).  Returns (loss, focus, smooth, iwes_blurred); differentiable w.r.t. coeff_grid through `loss`.
+
+    `table` [S + 1, k] (basis_type='table'; phi must be None): the kernels interpolate the basis from it at every event's time
+    (mpc_pe_table_*), and the node is differentiable w.r.t. the table as well -- through the events by mpc_pe_table_basis_grad (one
+    streaming pass over 8 bytes per event of position gradients that the coefficient backward leaves behind), through the
+    smoothness term by returning the gradient of `phim` (mpc_pe_field_basis_grad), which torch chains into the table through
+    utils.table_basis_values.  With no table the node runs the calls it ran before."""
 
     @staticmethod
-    def forward(ctx, coeff_grid, events, phi, phim, t_ref, cfg: PathConfig, num_pos: int, offsets, k: int, tile: int):
+    def forward(ctx, coeff_grid, events, phi, phim, t_ref, cfg: PathConfig, num_pos: int, offsets, k: int, tile: int, table=None):
         _require_gpu(coeff_grid, 'coeff_grid')
         B, M, Mp = _check_events(events, cfg, num_pos)
         dev = coeff_grid.device
@@ -997,6 +1024,13 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         pm = _f32c(phim.detach()) if phim is not None else None     # [nb, k]: basis(t_ref) - basis(bin mid-times), or None: no smoothness term
         tr = _f32c(t_ref.detach().to(dev))
         need_grad = coeff_grid.requires_grad
+        tab = None
+        if table is not None:
+            _require_gpu(table, 'basis_table')
+            tab = _f32c(table.detach())
+            if ph is not None or tab.dim() != 2 or tab.shape[1] != k or tab.shape[0] < 2:
+                raise ValueError(f'basis_table {tuple(table.shape)} is not [samples + 1, {k}] (and takes no phi)')
+            need_grad = need_grad or table.requires_grad or (phim is not None and phim.requires_grad)
         Bc, S, c2, H, W = cg.shape
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
         hq, wq = shape.hq, shape.wq
@@ -1006,7 +1040,7 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         c_rows = torch.empty((B * G, 2 * k), dtype=torch.float32, device=dev)
         _call('mpc_pe_tile_rows', dev, _ptr(cg), _ptr(c_rows), B, S, c2, H, W, tile)
         ws = alloc_workspace(shape, dev)
-        rows, blur, gimg = _pe_fwd(shape, ev, c_rows, ph, k, tr, ws, need_grad)
+        rows, blur, gimg = _pe_fwd(shape, ev, c_rows, ph, k, tr, ws, need_grad, tab)
         g_field, s_nimg = None, 0
         if pm is not None and cfg.smooth_weight > 0:
             nb = pm.shape[0]
@@ -1018,10 +1052,13 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         offs = _pe_ordered_offsets(offsets, cfg, shape, k, dev)
         ctx.shape, ctx.k, ctx.tile, ctx.grid_shape = shape, k, tile, (B, S, c2, H, W)
         ctx.has = (ph is not None, pm is not None and g_field is not None, offs is not None)
+        ctx.has_tab = tab is not None
         ctx.set_materialize_grads(False)
         none = tr
+        # (the tile rows are kept for the table route only: both table gradients are products with them)
         ctx.save_for_backward(rows, ph if ph is not None else none, tr, gimg if gimg is not None else none, scal,
-                              offs if offs is not None else none, g_field if g_field is not None else none, pm if pm is not None else none)
+                              offs if offs is not None else none, g_field if g_field is not None else none, pm if pm is not None else none,
+                              tab if tab is not None else none, c_rows if tab is not None else none)
         out = scal[:3].clone()
         loss, focus, smooth = out[C.SCAL_LOSS], out[C.SCAL_FOCUS], out[C.SCAL_SMOOTH]
         ctx.mark_non_differentiable(focus, smooth, blur)
@@ -1030,8 +1067,8 @@ class PerEventBasisCalcFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, g_focus, g_smooth, g_blur):
         if g_loss is None:
-            return (None,) * 10
-        rows, ph, tr, gimg, scal, offs, g_field, pm = ctx.saved_tensors
+            return (None,) * 11
+        rows, ph, tr, gimg, scal, offs, g_field, pm, tab, c_rows = ctx.saved_tensors
         has_phi, has_smooth, has_offs = ctx.has
         ph = ph if has_phi else None
         shape, k = ctx.shape, ctx.k
@@ -1039,14 +1076,31 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         G = shape.hq * shape.wq
         dev = rows.device
         go = _f32c(g_loss.reshape(1))
-        gp = _pe_pos_grad(shape, k, rows, offs if has_offs else None, ph, tr, gimg, scal, go)
+        g_table = g_phim = gpos = None
+        if ctx.has_tab:
+            if ctx.needs_input_grad[10]:
+                gpos = torch.empty((shape.B, shape.M, 2), dtype=torch.float32, device=dev)
+            gp = _pe_pos_grad(shape, k, rows, offs if has_offs else None, None, tr, gimg, scal, go, tab, gpos)
+            if gpos is not None:
+                ns = tab.shape[0] - 1
+                acc = torch.empty(((ns + 2) * k,), dtype=torch.int64, device=dev)
+                g_table = torch.empty_like(tab)
+                _call('mpc_pe_table_basis_grad', dev, ctypes.byref(shape), _ptr(rows), _ptr(gpos), _ptr(c_rows), ns, k, _ptr(tr), _ptr(scal),
+                      _ptr(go), _ptr(acc), _ptr(g_table))
+            if has_smooth and ctx.needs_input_grad[3]:
+                nbm = pm.shape[0]
+                part = torch.empty((nbm * 64 * k,), dtype=torch.float64, device=dev)
+                g_phim = torch.empty_like(pm)
+                _call('mpc_pe_field_basis_grad', dev, _ptr(g_field), _ptr(c_rows), _ptr(go), _ptr(part), _ptr(g_phim), B, G, k, nbm)
+        else:
+            gp = _pe_pos_grad(shape, k, rows, offs if has_offs else None, ph, tr, gimg, scal, go)
         g_rows = torch.empty((B * G, 2 * k), dtype=torch.float32, device=dev)
         nb = pm.shape[0] if has_smooth else 0
         _call('mpc_pe_rows_grad_finish', dev, _ptr(gp), gp.shape[0], _ptr(g_field) if has_smooth else None, _ptr(pm) if has_smooth else None,
               _ptr(go), _ptr(g_rows), B, G, k, max(nb, 1))
         g_grid = torch.empty(ctx.grid_shape, dtype=torch.float32, device=dev)
         _call('mpc_pe_tile_rows_bwd', dev, _ptr(g_rows), _ptr(g_grid), B, S, c2, H, W, ctx.tile)
-        return (g_grid,) + (None,) * 9
+        return (g_grid, None, None, g_phim) + (None,) * 6 + (g_table,)
 
 
 class TileCoeffRowsFn(torch.autograd.Function):

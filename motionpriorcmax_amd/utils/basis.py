@@ -42,6 +42,39 @@ def basis_values(times, num_basis, basis_type, basis_network=None):
     raise ValueError(basis_type)
 
 
+def table_basis_values(table, times):
+    """A TABULATED basis at arbitrary times: table [S + 1, k] holds samples of the k basis functions at the knots i / S, times [...]
+    -> [..., k], interpolated linearly.  This is the definition of FocusLoss.calc_per_event_basis(basis_type='table') and the lines
+    are those of the kernels (csrc/events.hip: pe_tab_locate / pe_tab_basis), one operation each, so that the fp32 result agrees
+    with them bit for bit: times outside [0, 1] are clamped, t == 1 lies in the last interval with f == 1.  Plain torch, any floating
+    dtype (the promotion of the two arguments'), differentiable w.r.t. `table`."""
+    if table.dim() != 2 or table.shape[0] < 2:
+        raise ValueError(f'basis table must be [samples + 1, k] with samples >= 1, got {tuple(table.shape)}')
+    S = table.shape[0] - 1
+    dtype = torch.promote_types(table.dtype, times.dtype)
+    table, times = table.to(dtype), times.to(dtype)
+    tc = times.clamp(min=0).clamp(max=1)
+    x = tc * float(S)
+    i = x.floor().to(torch.int64).clamp(max=S - 1)
+    f = x - i.to(dtype)
+    lo = table[i]
+    return lo + f[..., None] * (table[i + 1] - lo)
+
+
+def basis_table(basis_type, num_basis, samples, basis_network=None, device=None):
+    """The table of `table_basis_values` for one of the bases of `basis_values`: its values at the samples + 1 knots i / samples,
+    [samples + 1, num_basis] fp32, plain torch and differentiable through `basis_network`.  Training the reference's learned basis
+    through the per-event warp is `T = basis_table('learned', k, 1024, net)` once per step: the network runs at 1025 knots
+    instead of at every event, and autograd carries the table's gradient into its weights."""
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError('samples must be >= 1')
+    if device is None and basis_network is not None:
+        device = next((p.device for p in basis_network.parameters()), None)
+    knots = torch.arange(samples + 1, dtype=torch.float32, device=device) / float(samples)
+    return basis_values(knots, num_basis, basis_type, basis_network)
+
+
 _BASIS_CACHE = {}
 
 

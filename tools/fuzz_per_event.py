@@ -25,6 +25,14 @@ With the kernels broken on purpose (each in a build of its own): without the sca
 (4, 7, 9, 22, 27), without `* go` in k_rows_grad_finish 2 (0, 28); `j / SPLIT == part` for `j % SPLIT == part` in k_pe_accum passes
 all 30 -- at these image sizes split is 16 and part 0 then takes every range; tests/test_gpu_per_event.py's split = 1 test catches it.
 The small-weight ratio of that file: 0.705 of the bound (1.276 with the truncating conversion k_pe_accum had before).
+
+`python tools/fuzz_per_event.py table [n_cases] [seed]`: the same configurations with a TABULATED basis (basis_type='table': random
+samples S -- 1, a few, 1024, past the library's limit --, k, t_ref, flags) against tests/pe_table_cases.py's definition: loss and
+IWEs as above; the coefficient AND the table gradient by relative L2 (1e-4 sign-free, 2e-3 'l1') or, past that, against float64 at
+4 times the fp32 definition's own distance; ordered cases twice, the table gradient bitwise equal.
+Measured on an MI355X with `table 150 7`, product and -DMPC_BOUNDS build alike: 0 bad, mpc_bounds_check 0; routes k_pe_table_grad 41,
+k_pe_accum 17, k_pe_grad 24, k_field_basis_grad_part 28, plain torch 72; worst loss ratio 0.049, worst relative L2 / bound: coefficients
+0.037, table 0.766; four cases judged against float64 (worst 0.007 of that rule); 2.2 s (profiles/pe_table_bounds_run.txt).
 """
 import math
 import os
@@ -243,7 +251,132 @@ def run_case(c, dev, stats):
     return fails
 
 
+def run_table_case(c, dev, stats):
+    """The `table` mode: -> list of failure strings."""
+    from motionpriorcmax_amd import LossFactory, ops
+    import pe_table_cases as PT
+    cfg, ev, num_pos, coeff, t_ref = make_inputs(c)
+    k, variant, gscale, S = c['k'], c['variant'], c['gscale'], c['samples']
+    g = torch.Generator().manual_seed(c['seed'] + 1)
+    table = torch.randn(S + 1, k, generator=g) * 0.5 if S <= 2048 else torch.cumsum(torch.randn(S + 1, k, generator=g) * 0.02, 0)
+
+    def definition(dtype):
+        co, tb = coeff.to(dtype).clone().requires_grad_(True), table.to(dtype).clone().requires_grad_(True)
+        lo, iw = PT.calc_per_event_table(cfg, co, tb, t_ref, {'events': ev.to(dtype), 'num_pos_events': num_pos})
+        if torch.isfinite(lo):
+            (lo * gscale).backward()
+        z = lambda t: (t.grad if t.grad is not None else torch.zeros_like(t)).detach()
+        return float(lo.detach()), iw, z(co), z(tb)
+    lo, iwo, gco, gto = definition(torch.float32)
+    L = LossFactory.get_loss_calculator('FOCUS', cfg)
+    batch = {'events': ev.to(dev), 'num_pos_events': num_pos}
+    if variant == 'ordered':
+        batch = L.order_events(batch)
+    t_dev = t_ref if c['t_ref_as'] == 'float' else torch.tensor(t_ref, device=dev)
+
+    def device_run():
+        cg, tb = coeff.to(dev).requires_grad_(True), table.to(dev).requires_grad_(True)
+        lg, _, mg = L.calc_per_event_basis(cg, t_dev, batch, k, 'table', fused=bool(variant), basis_table=tb)
+        if bool(torch.isfinite(lg)):
+            (lg * gscale).backward()
+        z = lambda t: (t.grad if t.grad is not None else torch.zeros_like(t)).detach()
+        return lg.detach(), mg['iwes'], z(cg), z(tb)
+    with ops.KernelTimer() as kt:
+        lg, iwg, gc, gt = device_run()
+    ran = kt.summary()
+    for r in ('k_pe_table_grad', 'k_pe_accum', 'k_pe_grad', 'k_field_basis_grad_part'):
+        stats['routes'][r] = stats['routes'].get(r, 0) + int(r in ran)
+    stats['routes']['plain torch'] = stats['routes'].get('plain torch', 0) + int('k_pe_warp' not in ran and c['M'] * c['B'] > 0)
+    fails = []
+    if not math.isfinite(lo):
+        if math.isfinite(float(lg)):
+            fails.append(f'the definition\'s loss is {lo}, the device loss {float(lg)}')
+        return fails
+    lr = abs(float(lg) - lo) / (1e-5 * abs(lo))
+    stats['loss'] = max(stats['loss'], lr)
+    if not lr <= 1.0:
+        fails.append(f'loss {float(lg)!r} against {lo!r}: {lr:.2f} of the bound')
+    iw = iwo.reshape(iwg.shape)
+    if not float((iwg.cpu() - iw).abs().max()) <= 1e-5 * float(iw.abs().max()):
+        fails.append(f'IWE differs by {float((iwg.cpu() - iw).abs().max()):.3e}, max {float(iw.abs().max()):.3e}')
+    bound = 1e-4 if (cfg['focus_loss_norm'] == 'l2' or cfg['loss_type'] == 'variance') else 2e-3
+    g64 = None
+    for what, gd, g32, idx in (('coefficient', gc.cpu(), gco, 2), ('table', gt.cpu(), gto, 3)):
+        if not bool(torch.isfinite(gd).all()):
+            fails.append(f'non-finite {what} gradient')
+            continue
+        if float(g32.abs().max()) == 0.0:
+            if float(gd.abs().max()) != 0.0:
+                fails.append(f'the definition\'s {what} gradient is zero, the device\'s up to {float(gd.abs().max()):.3e}')
+            continue
+        r32 = rel_l2(gd, g32)
+        if r32 < bound:
+            stats['l2'][what] = max(stats['l2'].get(what, 0.0), r32 / bound)
+            continue
+        g64 = g64 or definition(torch.float64)
+        d_or, d_dev = rel_l2(g32, g64[idx]), rel_l2(gd, g64[idx])
+        print(f'case {c["case"]}: {what} gradient: relative L2 to the fp32 definition {r32:.3e} >= {bound:.0e}; against float64: fp32 definition '
+              f'{d_or:.3e}, device {d_dev:.3e}', flush=True)
+        if d_or < bound:
+            fails.append(f'relative L2 {r32:.3e} of the {what} gradient (the fp32 definition is {d_or:.3e} from float64)')
+        elif not d_dev <= 4 * d_or:
+            fails.append(f'{what} gradient: relative L2 to float64 {d_dev:.3e} > 4 x {d_or:.3e} (the fp32 definition)')
+        else:
+            stats['l2_64'] = max(stats['l2_64'], d_dev / (4 * d_or))
+    if variant == 'ordered':
+        l2, _, _, t2 = device_run()
+        if not torch.equal(l2, lg):
+            fails.append('ordered batch: the loss of a second run differs')
+        if 'k_pe_table_grad' in ran and not torch.equal(t2, gt):
+            fails.append('ordered batch: the table gradient of a second run differs')
+    return fails
+
+
+def main_table(argv):
+    n_cases = int(argv[0]) if argv else 150
+    rng = random.Random(int(argv[1]) if len(argv) > 1 else 0)
+    dev = torch.device('cuda:0')
+    from motionpriorcmax_amd import _lib as _C
+    lim = int(_C.lib().mpc_pe_table_limit())
+    stats = {'routes': {}, 'loss': 0.0, 'l2': {}, 'l2_64': 0.0}
+    bad, t_dev = 0, 0.0
+    for case in range(n_cases):
+        c = draw_case(rng, case)
+        c['basis'] = 'table'
+        c['k'] = rng.choice([1, 2, 3, 4, 8, 9])
+        c['samples'] = rng.choice([1, 1, 2, 7, 37, 256, 1024, 1024, lim // c['k'] - 1, lim // c['k']])
+        c['M'] = min(c['M'], 2000) if c['samples'] > 2048 else c['M']
+        tag = 'case ' + tag_of(c)
+        try:
+            t0 = time.perf_counter()
+            fails = run_table_case(c, dev, stats)
+            torch.cuda.synchronize()
+            t_dev += time.perf_counter() - t0
+        except Exception as e:      # noqa: BLE001
+            fails = ['ERROR ' + repr(e)[:300]]
+            if any(w in repr(e) for w in ('HIP error', 'hipError', 'CUDA error', 'illegal memory access', 'rc=700', 'rc=719')):
+                bad += n_cases - case
+                print('MISMATCH', tag, '|', fails[0], '| DEVICE FAULT: stopping,', n_cases - case - 1, 'cases not run', flush=True)
+                break
+        if fails:
+            bad += 1
+            print('MISMATCH', tag, '|', ' ; '.join(fails), flush=True)
+    print('table mode routes: ' + ', '.join(f'{r}: {n}' for r, n in stats['routes'].items()))
+    print(f'worst loss ratio to its bound {stats["loss"]:.3f}; worst relative L2 / bound ' + ', '.join(f'{v}: {x:.3f}' for v, x in sorted(stats['l2'].items()))
+          + f'; worst ratio to the float64 rule {stats["l2_64"]:.3f}; {t_dev:.1f} s for the cases (definition included)')
+    if n_cases >= 30:
+        for r in ('k_pe_table_grad', 'k_pe_accum', 'k_pe_grad', 'k_field_basis_grad_part', 'plain torch'):
+            if stats['routes'].get(r, 0) == 0:
+                bad += 1
+                print('UNCOVERED', r)
+    print(f'{n_cases} table cases, {bad} bad')
+    _n = _C.lib().mpc_bounds_check()
+    print('mpc_bounds_check:', _n, _C.lib().mpc_last_error_string().decode() if _n > 0 else '')
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == 'table':
+        return main_table(sys.argv[2:])
     n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     rng = random.Random(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
     dev = torch.device('cuda:0')

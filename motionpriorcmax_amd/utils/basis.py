@@ -88,7 +88,7 @@ def _cached_basis(kind, times, *args):
     if m is None:
         if len(_BASIS_CACHE) > 32:
             _BASIS_CACHE.clear()
-        m = _BASIS_CACHE[key] = (_bernstein_basis_eval if kind == 'bernstein' else _bspline_basis_eval)(t, *args)
+        m = _BASIS_CACHE[key] = _BASIS_EVAL[kind](t, *args)
     return m
 
 
@@ -135,6 +135,13 @@ def _tile_positions(H, W, tile_size, device, dtype):
     return ent
 
 
+def _basis_trains(bm):
+    """Does autograd want the gradient of this basis matrix (the reference's curve_type LEARNED while its basis network trains)?  The
+    fused nodes treat the matrix as a constant (ops.CurveTrajFn, ops.CvxCurveTrajFn, ops.CorrLookupFn return None for it), so such a
+    matrix takes the plain-torch mirrors, where it is an ordinary autograd input."""
+    return torch.is_grad_enabled() and bm.requires_grad
+
+
 def _curve_trajectories(params, bm, tile_size, H, W, scale):
     """pos + scale * (basis x control points), (y, x) order: on the GPU one kernel each way (ops.CurveTrajFn, csrc/curves.hip:
     mpc_curve_traj_fwd / _bwd -- a training step calls this every iteration and a B = 1 step is bound by the host); for CPU tensors
@@ -143,7 +150,7 @@ def _curve_trajectories(params, bm, tile_size, H, W, scale):
     d = c2 // 2
     pos, pos_dev = _tile_positions(H, W, tile_size, params.device, params.dtype)
     assert pos.shape[0] == h * w, 'image shape must be a multiple of the tile size'
-    if params.is_cuda and params.dtype == torch.float32 and d <= 16:
+    if params.is_cuda and params.dtype == torch.float32 and d <= 16 and not _basis_trains(bm):
         from .. import ops
         return ops.CurveTrajFn.apply(params, bm, pos_dev, float(scale)), pos
     flow = torch.einsum('bcdhw,td->btchw', params.view(B, 2, d, h, w), bm) * scale  # [B, n_t, (x, y), h, w]
@@ -171,9 +178,10 @@ _CVX_KERNEL_TILES = (2, 4, 8, 16)
 
 def _cvx_kernels_serve(params, up_mask, bm):
     """The routing rule of `_curve_trajectories`: the kernels take fp32 GPU tensors with d <= 16 and a basis matrix within their
-    48 KB LDS slice; everything else (CPU tensors, other dtypes, d > 16, more times) runs in plain torch."""
+    48 KB LDS slice that is a constant to autograd; everything else (CPU tensors, other dtypes, d > 16, more times, a basis matrix
+    that requires grad) runs in plain torch."""
     return (params.is_cuda and up_mask.is_cuda and params.dtype == torch.float32 and up_mask.dtype == torch.float32
-            and params.shape[1] // 2 <= 16 and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024)
+            and params.shape[1] // 2 <= 16 and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024 and not _basis_trains(bm))
 
 
 def _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale):
@@ -237,6 +245,120 @@ def _bernstein_basis_eval(times, degree):
     return torch.from_numpy(out).float()
 
 
+def _polynomial_basis_eval(times, degree):
+    """t^j for j = 1..d as the reference's PolynomialCurves evaluates it (curves/polynomial.py:55-58): the float64 times rounded to
+    fp32, then an fp32 power (torch on the host)."""
+    t = torch.from_numpy(np.asarray(times, dtype=np.float64).reshape(-1)).float()
+    return t[:, None] ** torch.arange(1, degree + 1)[None, :]
+
+
+def _polynomial_shortcut_basis_eval(times, degree):
+    t = torch.from_numpy(np.asarray(times, dtype=np.float64).reshape(-1))
+    return _shortcut_rows(_polynomial_basis_eval(t.numpy(), degree), t)
+
+
+def _shortcut_rows(bm, t):
+    """The scalar-time shortcuts of `CurveBase.get_flow_from_reference` (curves/base.py:98-106) as rows of the basis matrix: a time
+    of exactly 0.0 gives zeros, a time of exactly 1.0 the last control point -- one-hot on the last column.  `t` holds the times
+    as the caller gave them (the reference compares the Python float, base.py:102-105, BEFORE anything is rounded to fp32: a
+    float64 time of 1 - 1e-12 gets no shortcut although it rounds to 1.0f), on the device of `bm` or the host.  Constants (no
+    gradient reaches the basis network through them); elementwise, nothing is read back."""
+    d = bm.shape[1]
+    last = (torch.arange(d, device=bm.device) == d - 1).to(bm.dtype)          # (an indexed assignment of a scalar would synchronise)
+    bm = torch.where((t == 1).to(bm.device)[:, None], last[None, :], bm)
+    return torch.where((t == 0).to(bm.device)[:, None], torch.zeros((), dtype=bm.dtype, device=bm.device), bm)
+
+
+CURVE_TYPES = ('BEZIER', 'POLYNOMIAL', 'LEARNED')
+
+
+def curve_basis(curve_type, times, degree, basis_network=None, scalar_time_shortcuts=False, device=None):
+    """The [n_t, degree] fp32 basis matrix of one of the reference's three RAFT-spline curve types (`model.curve_type`, reference
+    src/models/raft_spline/curves/__init__.py:13-21), on `device` (default: that of the basis network's parameters for 'LEARNED', of
+    `times` if it is a tensor, else the CPU): flow(t) = sum_j basis[t, j] * P_j.
+
+      'BEZIER'      the Bernstein matrix of `trajectories_from_bezier` (bezier.py:92-113: float64 on the host, then fp32; the same
+                    cached tensor, the same bits)
+      'POLYNOMIAL'  times.float()[:, None] ** arange(1, d + 1), fp32 as curves/polynomial.py:55-58 evaluates it; cached per
+                    timestamps tensor as the Bernstein matrix is (a training step neither synchronises nor uploads)
+      'LEARNED'     basis_network(times.float()[:, None]) (curves/learned.py:76-77): part of the autograd graph, never cached; a
+                    device `times` tensor causes no host synchronisation.  The learned basis is NOT zero at t = 0.
+    Any other `curve_type` raises ValueError.  The cached matrices are shared: do not modify them in place.
+
+    `scalar_time_shortcuts`: `CurveBase.get_flow_from_reference` returns the last control point for a SCALAR time == 1 and zeros
+    for a scalar time == 0 whatever the curve type (curves/base.py:98-106); a list of times gets no shortcut.  For Bezier curves
+    the two agree, for the other two types they do not.  False (the default): the list behaviour -- what the refinement loop
+    (raft.py:178) and the loss evaluate.  True: a row whose time is exactly 0.0 is all zeros and a row whose time is exactly 1.0 is
+    one-hot on the last column (compared as given -- a list or array as float64, a tensor in its own dtype --, before the rounding
+    to fp32, as the reference compares the Python float), constants without gradient -- what `validation_step` evaluates, one scalar at a time
+    (src/modules/raft_spline.py:134-154), and therefore the default of `trajectory_val_metrics` alone."""
+    d = int(degree)
+    if d < 1:
+        raise ValueError(f'degree must be >= 1, got {degree}')
+    if curve_type == 'LEARNED':
+        if basis_network is None:
+            raise ValueError("curve_type 'LEARNED' needs basis_network")
+        if device is None:
+            device = next((p.device for p in basis_network.parameters()), None)
+        # t_in: the times as given (a tensor in its own dtype, anything else as float64), for the shortcut comparison
+        t_in = times.detach().reshape(-1) if torch.is_tensor(times) else torch.from_numpy(np.asarray(times, dtype=np.float64).reshape(-1))
+        t = t_in.to(device=device, dtype=torch.float32)
+        bm = basis_network(t[:, None]).float()
+        if bm.dim() != 2 or tuple(bm.shape) != (t.shape[0], d):
+            raise ValueError(f'basis_network must map [n_t, 1] to [n_t, degree] = {(t.shape[0], d)}, got {tuple(bm.shape)}')
+        return _shortcut_rows(bm, t_in) if scalar_time_shortcuts else bm
+    if curve_type not in CURVE_TYPES:
+        raise ValueError(f'curve_type must be one of {CURVE_TYPES}, got {curve_type!r}')
+    if device is None:
+        device = times.device if torch.is_tensor(times) else torch.device('cpu')
+    if curve_type == 'BEZIER':                  # (the Bernstein rows at t = 0 and t = 1 ARE the shortcut rows: 0 ** 0 == 1)
+        return _device_basis('bernstein', times, (d,), device, torch.float32)
+    return _device_basis('polynomial_shortcuts' if scalar_time_shortcuts else 'polynomial', times, (d,), device, torch.float32)
+
+
+def _curve_matrix(params, times, curve_type, basis_network):
+    """(degree, the basis matrix of `curve_basis` on the device and in the dtype of `params`) for the entry points below."""
+    c2 = params.shape[1]
+    assert params.dim() == 4 and c2 % 2 == 0, params.shape
+    return c2 // 2, curve_basis(curve_type, times, c2 // 2, basis_network, device=params.device).to(params.dtype)
+
+
+def trajectories_from_curves(params, times, tile_size, image_shape, curve_type='BEZIER', basis_network=None, scale=1.0, up_mask=None):
+    """`trajectories_from_bezier` for any of the reference's curve types (`curve_basis`: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the
+    latter with its `basis_network` on the device of `params`): the same contracts, the same routing -- fp32 GPU tensors with
+    d <= 16 (and, with `up_mask`, a basis matrix within 48 KB and a tile size of 2, 4, 8 or 16) run in the fused nodes
+    (ops.CurveTrajFn / ops.CvxCurveTrajFn), everything else in their plain-torch mirrors -- and with 'BEZIER' the same launches
+    and bits.  Times are evaluated as a LIST (no scalar-time shortcut, see `curve_basis`): a learned curve is not zero at t = 0.
+    Differentiable w.r.t. `params`, `up_mask` and, for 'LEARNED', the parameters of `basis_network`.  The fused nodes have no
+    gradient for the basis matrix: a matrix that requires grad (a basis network that trains) takes the plain-torch mirrors, where it
+    is an ordinary autograd input; a polynomial curve, and a learned one whose network is frozen or evaluated under no_grad, run in
+    the fused nodes."""
+    B, c2, h, w = params.shape
+    H, W = (int(v) for v in image_shape)
+    assert c2 % 2 == 0 and (up_mask is not None or (h == H // tile_size and w == W // tile_size)), (params.shape, image_shape, tile_size)
+    d, bm = _curve_matrix(params, times, curve_type, basis_network)
+    if up_mask is not None:
+        return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale)
+    return _curve_trajectories(params, bm, tile_size, H, W, scale)
+
+
+def flows_from_curves(params, times, curve_type='BEZIER', basis_network=None, up_mask=None, scale=1.0):
+    """`flows_from_bezier` for any of the reference's curve types (see `trajectories_from_curves`): [n_t, B, 2, H, W] in (x, y)
+    order, the times evaluated as a LIST (no scalar-time shortcut).  One kernel on the GPU (ops.cvx_flows) when nothing requires
+    grad -- the basis matrix of a learned curve included --, plain torch (differentiable) otherwise."""
+    B, c2, h, w = params.shape
+    d, bm = _curve_matrix(params, times, curve_type, basis_network)
+    if up_mask is not None:
+        if up_mask.dim() != 4 or tuple(up_mask.shape) != (B, 576, h, w):
+            raise ValueError(f'up_mask must be [B, 576, h, w] = {(B, 576, h, w)}, got {tuple(up_mask.shape)}')
+        needs_grad = torch.is_grad_enabled() and (params.requires_grad or up_mask.requires_grad)
+        if not needs_grad and _cvx_kernels_serve(params, up_mask, bm):
+            from .. import ops
+            return ops.cvx_flows(params, up_mask, bm, float(scale))
+        params = _cvx_upsample(params, up_mask)
+    return torch.einsum('bcdhw,td->tbchw', params.reshape(B, 2, d, *params.shape[-2:]), bm) * scale
+
+
 def trajectories_from_bezier(params, times, tile_size, image_shape, scale=1.0, up_mask=None):
     """RAFT-spline adapter: sample Bezier flow curves at the tile centres as `trajectories`
     for `FocusLoss.calc`.
@@ -295,6 +417,11 @@ def _bspline_basis_eval(times, num_ctrl, degree=3):
                 Nn[:, i] += (knots[i + q + 1] - t) / b * N[:, i + 1]
         N = Nn
     return torch.from_numpy(N[:, 1:m]).float()
+
+
+# the host evaluators of `_cached_basis`, by kind
+_BASIS_EVAL = {'bernstein': _bernstein_basis_eval, 'bspline': _bspline_basis_eval, 'polynomial': _polynomial_basis_eval,
+               'polynomial_shortcuts': _polynomial_shortcut_basis_eval}
 
 
 def trajectories_from_bspline(params, times, tile_size, image_shape, scale=1.0, degree=3, up_mask=None):

@@ -12,7 +12,7 @@ grid_sample, cat / permute / reshape) and therefore also the comparator the prob
 import torch
 import torch.nn.functional as F
 
-from .basis import _device_basis
+from .basis import _basis_trains, _device_basis, curve_basis
 
 _KERNEL_MAX_RADIUS, _KERNEL_MAX_TARGETS, _KERNEL_MAX_D, _KERNEL_MAX_LEVELS = 4, 16, 16, 6
 
@@ -216,13 +216,13 @@ class CorrLookup:
             self._descs[key] = desc
         return desc
 
-    def _basis(self, times, d, device, dtype):
+    def _basis(self, times, d, device, dtype, kind='bernstein'):
         if torch.is_tensor(times):
-            return _device_basis('bernstein', times, (int(d),), device, dtype)
-        key = (tuple(float(t) for t in times), int(d), device, dtype)           # (a list: uploaded once per lookup object, not per call)
+            return _device_basis(kind, times, (int(d),), device, dtype)
+        key = (tuple(float(t) for t in times), int(d), device, dtype, kind)     # (a list: uploaded once per lookup object, not per call)
         bm = self._bases.get(key)
         if bm is None:
-            bm = self._bases[key] = _device_basis('bernstein', list(key[0]), (int(d),), device, dtype)
+            bm = self._bases[key] = _device_basis(kind, list(key[0]), (int(d),), device, dtype)
         return bm
 
     # ---- the two calls
@@ -248,6 +248,31 @@ class CorrLookup:
         d = params.shape[1] // 2
         bm = self._basis(times, d, params.device, params.dtype)                  # [T, d]
         if self._kernels_serve(params, d):
+            return self._apply(params, bm)
+        flows = torch.einsum('bcdhw,td->tbchw', params.reshape(self.B, 2, d, self.h, self.w), bm)
+        coords = coords_grid(self.B, self.h, self.w, params.device, params.dtype)[None] + flows
+        return _lookup_mirror(self.levels, self.target_indices, self.radius, coords)
+
+    def lookup_curves(self, params, times, curve_type='BEZIER', basis_network=None):
+        """`lookup_bezier` for any of the reference's curve types (utils.curve_basis: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the latter
+        with its `basis_network` on the device of `params`): the lookup at coords0 + curve.get_flow_from_reference(times) of
+        raft.py:165-180, the times evaluated as a LIST (no scalar-time shortcut).  The same routing as `lookup_bezier`, with
+        'BEZIER' the same launches and bits, `shared_grad=True` included.  For 'LEARNED' the basis matrix is part of the autograd
+        graph, and the fused node has no gradient for it: while the basis network trains (the matrix requires grad) the lookup
+        runs in the plain-torch mirror, where the matrix is an ordinary autograd input -- also when `params` are detached
+        (`detach_bezier`, raft.py:166-167), which is what trains the basis network through the update loop.  A frozen network, or
+        one evaluated under no_grad, runs in the fused node."""
+        T = len(self.num_levels_per_target)
+        if params.dim() != 4 or params.shape[1] % 2 or params.shape[1] < 2 or (params.shape[0], params.shape[2], params.shape[3]) != (self.B, self.h, self.w):
+            raise ValueError(f'params must be [B, 2d, h, w] with (B, h, w) = {(self.B, self.h, self.w)}, got {tuple(params.shape)}')
+        if len(times) != T:
+            raise ValueError(f'{len(times)} times for {T} targets')
+        d = params.shape[1] // 2
+        if curve_type in ('BEZIER', 'POLYNOMIAL'):
+            bm = self._basis(times, d, params.device, params.dtype, 'bernstein' if curve_type == 'BEZIER' else 'polynomial')
+        else:                                    # (the network's output, as it comes: the kernel reads a dense [T, d])
+            bm = curve_basis(curve_type, times, d, basis_network, device=params.device).to(params.dtype).contiguous()
+        if self._kernels_serve(params, d) and not _basis_trains(bm):
             return self._apply(params, bm)
         flows = torch.einsum('bcdhw,td->tbchw', params.reshape(self.B, 2, d, self.h, self.w), bm)
         coords = coords_grid(self.B, self.h, self.w, params.device, params.dtype)[None] + flows

@@ -11,7 +11,7 @@ import torch
 
 from .. import _lib as C
 from ..ops import _call, _f32c, _ptr, _query, _require_gpu
-from .basis import _device_basis
+from .basis import curve_basis
 
 
 def val_metric_keys(num_steps):
@@ -32,7 +32,8 @@ def _bool_bytes(t):
     return (t if t.dtype == torch.bool else t != 0).contiguous()
 
 
-def _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_valid, ev_repr, event_mask):
+def _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_valid, ev_repr, event_mask, curve_type='BEZIER',
+                     basis_network=None, scalar_time_shortcuts=True):
     """Argument checks (all before the first GPU call), then the library call: (values [75] fp32, updated [75] int32, M)."""
     if (params is None) == (flows is None):
         raise ValueError('exactly one prediction source: params (+ up_mask) or flows')
@@ -40,6 +41,8 @@ def _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_va
         raise ValueError('up_mask goes with params')
     if (ev_repr is None) == (event_mask is None):
         raise ValueError('exactly one of ev_repr / event_mask')
+    if curve_type not in ('BEZIER', 'POLYNOMIAL', 'LEARNED') or (curve_type == 'LEARNED' and basis_network is None and params is not None):
+        raise ValueError(f"curve_type must be 'BEZIER', 'POLYNOMIAL' or 'LEARNED' (with basis_network), got {curve_type!r}")
     if isinstance(flow_gt, (list, tuple)):
         M = len(flow_gt)
         gt_shape = (flow_gt[0].shape[0], M) + tuple(flow_gt[0].shape[1:]) if M else ()
@@ -92,7 +95,8 @@ def _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_va
         return values, updated, M
     bm = None
     if params is not None:
-        bm = _f32c(_device_basis('bernstein', timestamps, (int(d),), dev, torch.float32))       # [M, d], float64 on the host, then fp32
+        with torch.no_grad():                    # [M, d]; 'BEZIER': float64 on the host, then fp32 -- the cached matrix
+            bm = _f32c(curve_basis(curve_type, timestamps, int(d), basis_network, scalar_time_shortcuts=scalar_time_shortcuts, device=dev))
         params, up_mask = _f32c(params.detach()), _f32c(up_mask.detach())
     else:
         flows = _f32c(flows.detach())
@@ -108,7 +112,7 @@ def _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_va
 
 
 def trajectory_val_metrics(flow_gt, timestamps, *, params=None, up_mask=None, scale=1.0, flows=None, flow_valid=None, ev_repr=None,
-                           event_mask=None):
+                           event_mask=None, curve_type='BEZIER', basis_network=None, scalar_time_shortcuts=True):
     """Every scalar `RAFTSplineModule.validation_step` logs for one batch (reference src/modules/raft_spline.py:159-194), as
     (values, updated): two dicts over the same keys, a 0-dim fp32 and a 0-dim int32 device tensor each.
 
@@ -120,6 +124,12 @@ def trajectory_val_metrics(flow_gt, timestamps, *, params=None, up_mask=None, sc
                 the kernel (H x W = 8h x 8w; the device functions of `flows_from_bezier`: the same bits), d <= 16
       flows  [M, B, 2, H, W]: any curve type, any H x W, padded or unpadded outputs
       both times `scale`
+    curve_type, basis_network, scalar_time_shortcuts (with params): the curve type of `utils.curve_basis` -- 'BEZIER' (default),
+                'POLYNOMIAL' or 'LEARNED' with its basis network; only the [M, d] matrix handed to the kernel differs.
+                `scalar_time_shortcuts` defaults to True HERE, and here alone: `validation_step` evaluates the curve once per SCALAR
+                timestamp (raft_spline.py:134-154), and `get_flow_from_reference` answers a scalar 1 with the last control point
+                and a scalar 0 with zeros whatever the curve type (curves/base.py:98-106) -- for polynomial and learned curves that
+                is not the value of the basis at those times.  False evaluates every timestamp as the list call does.
     flow_valid  [B, M, H, W] bool (or a list of M [B, H, W]), optional: V_m
     ev_repr [B, C, H, W] (E = any channel != 0, a NaN counts: raft_spline.py:164) or event_mask [B, H, W] bool: exactly one
 
@@ -132,14 +142,16 @@ def trajectory_val_metrics(flow_gt, timestamps, *, params=None, up_mask=None, sc
     every mask is empty; the value is NaN) or raises (`NPE` with an empty mask, utils.py:199: all five singles of that mask are
     NaN / 0 -- this row is UNPINNED, the reference has no value there).  A NaN the reference would add (ae over an empty mask) comes
     with updated = 1.  Nothing synchronises the host.  CPU tensors raise; inputs are detached."""
-    values, updated, M = _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_valid, ev_repr, event_mask)
+    values, updated, M = _val_metrics_raw(flow_gt, timestamps, params, up_mask, scale, flows, flow_valid, ev_repr, event_mask,
+                                          curve_type, basis_network, scalar_time_shortcuts)
     keys = val_metric_keys(M)
     return {k: values[i] for k, i in keys}, {k: updated[i] for k, i in keys}
 
 
 class TrajectoryValMetrics:
     """The epoch accumulator over `trajectory_val_metrics`: the counterpart of the reference's Metric objects (utils.py:335-541) for
-    all keys at once.  `update(**same arguments)` adds every value whose `updated` flag is set to an fp64 sum and the flag to an int64
+    all keys at once.  `update(**same arguments)` (curve_type / basis_network / scalar_time_shortcuts included) adds every value
+    whose `updated` flag is set to an fp64 sum and the flag to an int64
     total, on the device and without a host synchronisation; `compute()` returns sum / total per key as fp32 (`Metric.compute`; a key
     never updated gives NaN where the reference asserts); `state()` returns the two device tensors (sums [75] fp64, totals [75]
     int64) themselves, to be summed across ranks in place (all_reduce) -- the counterpart of dist_reduce_fx="sum".
@@ -156,7 +168,9 @@ class TrajectoryValMetrics:
     def update(self, flow_gt, timestamps, **kwargs):
         values, updated, M = _val_metrics_raw(flow_gt, timestamps, kwargs.pop('params', None), kwargs.pop('up_mask', None),
                                               kwargs.pop('scale', 1.0), kwargs.pop('flows', None), kwargs.pop('flow_valid', None),
-                                              kwargs.pop('ev_repr', None), kwargs.pop('event_mask', None))
+                                              kwargs.pop('ev_repr', None), kwargs.pop('event_mask', None),
+                                              kwargs.pop('curve_type', 'BEZIER'), kwargs.pop('basis_network', None),
+                                              kwargs.pop('scalar_time_shortcuts', True))
         if kwargs:
             raise TypeError(f'unexpected arguments {sorted(kwargs)}')
         if self._sums is None:

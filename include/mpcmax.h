@@ -288,6 +288,58 @@ int mpc_pe_table_basis_grad(const mpc_shape *s, const float *rows, const float *
 int mpc_pe_field_basis_grad(const float *grad_field, const float *coef_rows, const float *grad_out, double *part, float *grad_phim,
                             int32_t B, int32_t G, int32_t k, int32_t nb, void *stream);
 
+/* ---- UNPINNED EXTENSION (FocusLoss.calc_per_event_curves; csrc/pe_curves.hip): the per-event continuous-time warp along RAFT-spline
+ * curves -- control points 1..d (P0 = 0; reference curves/polynomial.py:60-61: x channels first) on the 1/8 grid with the convex-
+ * upsampling mask (raft_spline/utils.py:30-45), or per tile already; every event moves along the curve of its LUT cell at ITS OWN time.
+ * The basis is evaluated in the kernels, in fp32 with one rounding per line (utils.curve_event_basis: the same lines in torch):
+ *   MPC_PEC_BEZIER      u = 1 - t;  tp_1 = t, tp_i = tp_{i-1} * t;  up_0 = 1, up_1 = u, up_i = up_{i-1} * u;  E_i = (C(d,i) * tp_i) * up_{d-i}
+ *   MPC_PEC_POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t
+ *   MPC_PEC_TABLE       table [S + 1][d]:  tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;
+ *                       E_j = T[i][j] + f * (T[i+1][j] - T[i][j])
+ *   phi_j = E_j(t_ref[0]) - E_j(t_event)
+ * mpc_pec_supported     the one copy of the limits: 0 = not served; bit 0: (shape, d, basis, S) is served -- MPC_F_NO_WARP, num_tref == 1,
+ *                       1 <= d <= 16, num_bins <= 64, a table with (S + 1) * d <= mpc_pe_table_limit(); bit 1: mpc_pec_rows_grad also
+ *                       serves an offsets table (one order of a LUT strip's accumulators fits the LDS)
+ * mpc_pec_head_rows     rows [B*G][2][d]:  rows[(b, cell)][0][j] = scale * up_y[j],  rows[(b, cell)][1][j] = scale * up_x[j]  at the tile
+ *                       centres (iy * tile + tile / 2, ix * tile + tile / 2) of the 8h x 8w image, up as for mpc_cvx_traj_fwd; the centre
+ *                       is never added.  mask NULL: params [B][2d][h][w] are per tile already (h x w tiles; tile is ignored).
+ *                       With a mask tile is 2, 4, 8 or 16 and divides 8h and 8w: G = (8h / tile) * (8w / tile).
+ * mpc_pec_head_rows_bwd its adjoint applied to grad_rows: grad_params [B][2d][h][w] and the dense grad_mask [B][576][h][w], every element
+ *                       written, gather form, no float atomics.  (The adjoint of "centre + v" is that of v: with a mask this is
+ *                       mpc_cvx_traj_bwd with the identity as its matrix.)  ws: mpc_pec_head_rows_bwd_workspace_bytes(), with a mask only.
+ * mpc_pec_warp          rows_out [B][M][6] = (y + fy, x + fx, t, p, cell bits, valid), the record of mpc_pe_warp, for mpc_event_splat_fwd
+ *                       with MPC_F_NO_WARP:  cell = the LUT cell of the event's own position;  fy = fx = 0;  for j ascending:
+ *                       fy += rows[cell][0][j] * phi_j,  fx += rows[cell][1][j] * phi_j
+ * mpc_pec_rows_grad     grad_rows[(b, cell)][a][j] = coef * sum over the rows of the cell of phi_j * grad_pos[row][a],  coef = (scal ?
+ *                       scal[MPC_SCAL_GCOEF] : 1) * (grad_out ? grad_out[0] : 1);  rows_warped: what mpc_pec_warp wrote (time and cell
+ *                       are read), grad_pos [B][M][2]: mpc_event_pos_grad's.  offsets (mpc_event_bucket_order): one workgroup per (sample,
+ *                       LUT strip, pass over orders_per_pass orders) sums in LDS in Q33.30 and writes every element once -- bitwise
+ *                       reproducible, each sum below 2^33 / coef in magnitude; at most as many orders per pass as cstrip_rows * wq * 2 * 8
+ *                       bytes per order allow in 150 KB (more: MPC_E_UNSUPPORTED); orders_per_pass 0: the library's choice, the
+ *                       fewest whose workgroups fit the device in one round (the pass is bound by its LDS atomics; same bits).  offsets NULL: grad_rows is zeroed and every
+ *                       row adds with float atomics (any row order; slow, not reproducible).
+ * mpc_pec_rows_grad_passes  the passes that call makes (0: not served with offsets)
+ * mpc_pec_field         field [B*nbm][G][2] = sum_j rows[(b, cell)][a][j] * phim[t][j], j ascending (d <= 16, nbm <= 64): what mpc_lut_smooth takes
+ * mpc_pec_field_adjoint grad_rows[(b, cell)][a][j] += grad_out[0] * sum_t grad_field[(b, t)][cell][a] * phim[t][j]                       */
+#define MPC_PEC_BEZIER     0
+#define MPC_PEC_POLYNOMIAL 1
+#define MPC_PEC_TABLE      2
+int32_t mpc_pec_supported(const mpc_shape *s, int32_t d, int32_t basis, int32_t S);
+int mpc_pec_head_rows(const float *params, const float *mask, float scale, int32_t tile, float *rows,
+                      int32_t B, int32_t d, int32_t h, int32_t w, void *stream);
+int64_t mpc_pec_head_rows_bwd_workspace_bytes(int32_t B, int32_t d, int32_t h, int32_t w, int32_t tile);
+int mpc_pec_head_rows_bwd(const float *grad_rows, const float *params, const float *mask, float scale, int32_t tile,
+                          float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream);
+int mpc_pec_warp(const mpc_shape *s, const float *events, const float *rows, int32_t basis, int32_t d, const float *table, int32_t S,
+                 const float *t_ref, float *rows_out, void *stream);
+int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, const int32_t *offsets, const float *grad_pos, int32_t basis,
+                      int32_t d, const float *table, int32_t S, const float *t_ref, const float *scal, const float *grad_out,
+                      int32_t orders_per_pass, float *grad_rows, void *stream);
+int32_t mpc_pec_rows_grad_passes(const mpc_shape *s, int32_t d, int32_t orders_per_pass);
+int mpc_pec_field(const float *rows, const float *phim, float *field, int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream);
+int mpc_pec_field_adjoint(const float *grad_field, const float *phim, const float *grad_out, float *grad_rows,
+                          int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream);
+
 int mpc_event_splat_bwd(const mpc_shape *s, const float *events, const float *flow_lut,
                         const float *t_ref, const float *grad_iwe, const float *scal,
                         const float *grad_out, float *grad_flow_lut, const float *add_term,

@@ -142,6 +142,15 @@ SIGNATURES = {
     'mpc_pe_table_grad_ordered': (cint, [sp, vp, vp, vp, i32, i32] + [vp] * 5 + [i32, vp, vp]),
     'mpc_pe_table_basis_grad': (cint, [sp, vp, vp, vp, i32, i32] + [vp] * 6),
     'mpc_pe_field_basis_grad': (cint, [vp] * 5 + [i32] * 4 + [vp]),
+    'mpc_pec_supported': (i32, [sp, i32, i32, i32]),
+    'mpc_pec_head_rows': (cint, [vp, vp, f32, i32, vp] + [i32] * 4 + [vp]),
+    'mpc_pec_head_rows_bwd_workspace_bytes': (i64, [i32] * 5),
+    'mpc_pec_head_rows_bwd': (cint, [vp, vp, vp, f32, i32, vp, vp] + [i32] * 4 + [vp, vp]),
+    'mpc_pec_warp': (cint, [sp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    'mpc_pec_rows_grad': (cint, [sp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
+    'mpc_pec_rows_grad_passes': (i32, [sp, i32, i32]),
+    'mpc_pec_field': (cint, [vp, vp, vp] + [i32] * 4 + [vp]),
+    'mpc_pec_field_adjoint': (cint, [vp, vp, vp, vp] + [i32] * 4 + [vp]),
     'mpc_event_splat_bwd': (cint, [sp] + [vp] * 10),
     'mpc_focus_fwd': (cint, [sp, fb, vp, vp]),
     'mpc_focus_bwd': (cint, [sp, fb] + [vp] * 6),

@@ -1,0 +1,550 @@
+// UNPINNED EXTENSION (FocusLoss.calc_per_event_curves; BASELINE.json's north_star and configs[3]): the per-event continuous-time warp
+// along RAFT-spline curves.  The RAFT-spline head produces control points 1..d (P0 = 0) on the 1/8 grid plus the convex-upsampling
+// mask (reference src/models/raft_spline/curves/base.py:35-38, utils.py:30-45, curves/polynomial.py:60-61: x channels first); every
+// event is moved along the curve of its LUT cell evaluated at ITS OWN timestamp -- no time bins, no KNN look-up table, no [B, M, d]
+// basis tensor: the basis is evaluated in registers.
+//   k_pec_head_rows    rows[(b, cell)][0][j] = scale * up_y[j], rows[(b, cell)][1][j] = scale * up_x[j] at the tile centres
+//                      (iy * tile + tile / 2, ix * tile + tile / 2) of the 8h x 8w image (cvx_device.h: cvx_up), or of params themselves
+//                      (no mask: h x w is the tile grid).  The tile centre is never added: (centre + v) - centre is not v in fp32.
+//   k_pec_warp         rows_out = (y + fy, x + fx, t, p, cell bits, valid): the record mpc_pe_warp writes.  cell = LUT cell of the event's
+//                      own position; fy = fx = 0; for j ascending: fy += c[0][j] * phi[j], fx += c[1][j] * phi[j]; phi[j] = E_j(t_ref) - E_j(t)
+//   k_pec_accum        grad_rows[(b, cell)][a][j] = coef * sum over the cell's rows of phi[j] * gpos[row][a] for bucket-ordered rows:
+//                      one workgroup per (sample, LUT strip, pass over a chunk of orders), Q33.30 sums in LDS (ds_add_u64; the scheme
+//                      of k_pe_accum / k_pe_table_grad: bitwise reproducible), every element written once
+//   k_pec_grad_atomic  the same with global float atomics (any row order; slow -- ~20 G atomics/s -- and not reproducible)
+//   k_pec_field        field[(b, t)][cell] = (sum_j rows[.][0][j] phim[t][j], sum_j rows[.][1][j] phim[t][j]), d <= 16
+//   k_pec_field_adj    grad_rows[(b, cell)][a][j] += grad_out * sum_t grad_field[(b, t)][cell][a] * phim[t][j]
+//   k_pec_rows_to_*    the transposes between grad_rows and what the head's adjoint takes
+// The adjoint of "centre + v" is the adjoint of v: the head's backward with a mask IS mpc_cvx_traj_bwd (cvx_curves.hip) with the identity
+// as its basis matrix and grad_rows transposed to [B][d][G][2].
+//
+// E, the basis at a time t, in fp32 with one rounding per line (-ffp-contract=off; utils.curve_event_basis spells the same lines in
+// torch and agrees bit for bit):
+//   BEZIER      u = 1 - t;  tp_1 = t, tp_i = tp_{i-1} * t;  up_0 = 1, up_1 = u, up_i = up_{i-1} * u;  E_i = (C(d, i) * tp_i) * up_{d-i}
+//               (t = 0: every E_i is exactly 0; t = 1: E_d is exactly 1, the others exactly 0 -- the shortcut rows of curves/base.py:102-106)
+//   POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t                                (the lines of pe_phi, events.hip)
+//   TABLE       tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;
+//               E_j = T[i][j] + f * (T[i+1][j] - T[i][j])                 (the lines of pe_tab_locate / utils.table_basis_values)
+#include "common.h"
+#include "cvx_device.h"
+#include "bounds.h"
+
+#define PEC_DMAX 16
+#define PEC_NT 1024            // threads of k_pec_accum
+#define PEC_NIF 4              // rows in flight per thread of k_pec_accum
+#define PEC_LDS_MAX (150 * 1024)
+
+struct PecBasis {
+    int kind, d, S;
+    const float *table;        // [S + 1][d] (MPC_PEC_TABLE)
+    float binom[PEC_DMAX];     // C(d, j + 1), exact in fp32 (d <= 16: at most 12870)
+};
+
+__device__ __forceinline__ void pec_basis(const PecBasis &pb, float t, float E[PEC_DMAX]) {
+    const int d = pb.d;
+    if (pb.kind == MPC_PEC_BEZIER) {
+        const float u = 1.f - t;
+        float tp = t;
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            if (j < d) { E[j] = pb.binom[j] * tp; tp = tp * t; }
+        }
+        float w = 1.f;                                   // up_0, up_1 = 1 * u = u exactly
+#pragma unroll
+        for (int j = PEC_DMAX - 1; j >= 0; --j) {
+            if (j < d) { E[j] = E[j] * w; w = w * u; }
+        }
+    } else if (pb.kind == MPC_PEC_POLYNOMIAL) {
+        float c = t;
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            if (j < d) { E[j] = c; c = c * t; }
+        }
+    } else {
+        const float tc = fminf(fmaxf(t, 0.f), 1.f);
+        const float x = tc * (float)pb.S;
+        const int i = min((int)floorf(x), pb.S - 1);
+        const float f = x - (float)i;
+        const float *r0 = pb.table + (size_t)i * d, *r1 = r0 + d;
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            if (j < d) { const float a = r0[j]; const float df = r1[j] - a; E[j] = a + f * df; }
+        }
+    }
+}
+
+__device__ __forceinline__ void pec_load_row(const float *__restrict__ rows, size_t row, float e[6]) {
+    const float2 *p = reinterpret_cast<const float2 *>(rows + row * 6);
+    const float2 a = p[0], b = p[1], c = p[2];
+    e[0] = a.x; e[1] = a.y; e[2] = b.x; e[3] = b.y; e[4] = c.x; e[5] = c.y;
+}
+
+// ---- head rows ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pec_head_rows(const float *__restrict__ params, const float *__restrict__ mask, float scale, int tile,
+                                                       float *__restrict__ rows, int B, int d, int h, int w, int nty, int ntx) {
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int n = nty * ntx;
+    if (gi >= (long long)B * n) return;
+    const int b = (int)(gi / n), i = (int)(gi - (long long)b * n);
+    const int iy = i / ntx, ix = i - iy * ntx;
+    const size_t plane = (size_t)h * w;
+    const float *pb = params + (size_t)b * 2 * d * plane;
+    float ux[PEC_DMAX], uy[PEC_DMAX];
+    if (mask != nullptr) {
+        cvx_up<PEC_DMAX>(pb, mask + (size_t)b * 576 * plane, d, h, w, (tile >> 1) + iy * tile, (tile >> 1) + ix * tile, ux, uy);
+    } else {
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            ux[j] = j < d ? pb[(size_t)j * plane + i] : 0.f;
+            uy[j] = j < d ? pb[(size_t)(d + j) * plane + i] : 0.f;
+        }
+    }
+    float *o = rows + (size_t)gi * 2 * d;
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j) {
+        if (j < d) { o[j] = scale * uy[j]; o[d + j] = scale * ux[j]; }
+    }
+}
+
+// grad_rows [B*n][2][d] -> grad_traj [B][d][n][2] (what mpc_cvx_traj_bwd takes with T = d), and the identity matrix [d][d] behind it
+__global__ __launch_bounds__(256) void k_pec_rows_to_traj(const float *__restrict__ grows, float *__restrict__ gtraj, float *__restrict__ ident,
+                                                          int B, int d, int n) {
+    const long long total = (long long)B * d * n;
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi < (long long)d * d) ident[gi] = (gi / d == gi % d) ? 1.f : 0.f;
+    if (gi >= total) return;
+    const int i = (int)(gi % n);
+    const long long r = gi / n;
+    const int j = (int)(r % d), b = (int)(r / d);
+    const float *g = grows + ((size_t)b * n + i) * 2 * d;
+    reinterpret_cast<float2 *>(gtraj)[gi] = make_float2(g[j], g[d + j]);
+}
+
+// no mask: grad_params [B][2d][n], channel c < d (x) = scale * grad_rows[.][1][c], channel d + j (y) = scale * grad_rows[.][0][j]
+__global__ __launch_bounds__(256) void k_pec_rows_to_params(const float *__restrict__ grows, float scale, float *__restrict__ gparams,
+                                                            int B, int d, int n) {
+    const long long total = (long long)B * 2 * d * n;
+    const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= total) return;
+    const int i = (int)(gi % n);
+    const long long r = gi / n;
+    const int c = (int)(r % (2 * d)), b = (int)(r / (2 * d));
+    const float *g = grows + ((size_t)b * n + i) * 2 * d;
+    gparams[gi] = scale * (c < d ? g[d + c] : g[c - d]);
+}
+
+// ---- warp -----------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pec_warp(const mpc_shape s, const float *__restrict__ events, const float *__restrict__ coef,
+                                                  const PecBasis pb, const float *__restrict__ t_ref, float *__restrict__ rows_out) {
+    const int d = pb.d;
+    float Er[PEC_DMAX];
+    pec_basis(pb, t_ref[0], Er);
+    const size_t total = (size_t)s.B * s.M;
+    for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
+        const int b = (int)(row / s.M);
+        float e[6];
+        pec_load_row(events, row, e);
+        // the LUT cell of the event's own position, as k_pe_warp computes it (focus.py:186-187)
+        const int iy = min(max((int)floorf(mpc_div_sp(e[0], s.sp)), 0), s.hq - 1), ix = min(max((int)floorf(mpc_div_sp(e[1], s.sp)), 0), s.wq - 1);
+        const int cell = (b * s.hq + iy) * s.wq + ix;
+        const float *c = coef + (size_t)cell * 2 * d;
+        float E[PEC_DMAX];
+        pec_basis(pb, e[2], E);
+        float fy = 0.f, fx = 0.f;
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            if (j < d) { const float ph = Er[j] - E[j]; fy += c[j] * ph; fx += c[d + j] * ph; }
+        }
+        float2 *o = reinterpret_cast<float2 *>(rows_out + row * 6);
+        o[0] = make_float2(e[0] + fy, e[1] + fx);
+        o[1] = make_float2(e[2], e[3]);
+        o[2] = make_float2(__int_as_float(cell), e[5]);
+    }
+}
+
+// ---- row gradient ---------------------------------------------------------------------------------------------------------------
+// Q33.30 of one phi * gradient product, rounded to nearest (pe_to_fixed of events.hip: no bias with small event weights); |v| < 2^31
+__device__ __forceinline__ long long pec_to_fixed(float v) {
+    const float hi = truncf(v);
+    return ((long long)(int)hi << MPC_FIX_SHIFT) + (long long)__float2int_rn((v - hi) * (float)(1 << MPC_FIX_SHIFT));
+}
+
+// coef = scal[MPC_SCAL_GCOEF] (or 1) * grad_out[0] (or 1): gpos holds UNSCALED position gradients where the caller hands both over, so
+// that the fixed-point products are O(event weight x adjoint-image differences) as in k_pe_accum, whatever the loss scale
+__device__ __forceinline__ float pec_coef(const float *__restrict__ scal, const float *__restrict__ grad_out) {
+    return (scal ? scal[MPC_SCAL_GCOEF] : 1.f) * (grad_out ? grad_out[0] : 1.f);
+}
+
+__global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR, int NCS, int KC, int NPASS, const int *__restrict__ offsets,
+                                                      const float *__restrict__ rows, const float2 *__restrict__ gpos, const PecBasis pb,
+                                                      const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                      const float *__restrict__ grad_out, float *__restrict__ grows) {
+    extern __shared__ unsigned long long s_acc[];                // [ncell][2][kc]
+    __shared__ int s_r0[2 * 64 + 1], s_pre[2 * 64 + 1], s_cnt[2 * 64];          // first row / running count / length of the 2 * nb ranges (nb <= 64)
+    const int tid = threadIdx.x, d = pb.d;
+    const int pass = blockIdx.x % NPASS, bs = blockIdx.x / NPASS;
+    const int b = bs / NCS, cst = bs - b * NCS;
+    const int j0 = pass * KC, kc = min(KC, d - j0);
+    const int crow0 = cst * CSR, crow1 = min(crow0 + CSR, s.hq), ncell = max(crow1 - crow0, 0) * s.wq;
+    const int cell0 = (b * s.hq + crow0) * s.wq;
+    const int NK = s.nb * NCS, nrange = 2 * s.nb;
+    const int nacc = ncell * 2 * kc;
+    for (int i = tid; i < nacc; i += PEC_NT) s_acc[MPC_IDX(i, nacc)] = 0ull;
+    // (one lane per range reads its two offsets, then one thread forms the running counts from LDS: read by one thread in turn,
+    // the 2 * nb loads cost a memory latency each -- 160 -> 147 us at 41 bins)
+    for (int j = tid; j < nrange; j += PEC_NT) {
+        const int pol = j / s.nb, it = j - pol * s.nb;
+        const int *o = offsets + (size_t)(b * 2 + pol) * (NK + 1) + it * NCS + cst;
+        // (a table that does not belong to the tensor: clamp into the sample, never read outside it)
+        const int r0 = min(max(o[0], 0), s.M), r1 = min(max(o[1], r0), s.M);
+        s_r0[j] = r0; s_cnt[j] = r1 - r0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int j = 0; j < nrange; ++j) { s_pre[j] = run; run += s_cnt[j]; }
+        s_pre[nrange] = run;
+    }
+    __syncthreads();
+    const int n = s_pre[nrange];
+    float Er[PEC_DMAX];
+    pec_basis(pb, t_ref[0], Er);
+    // (PEC_NIF rows per thread and iteration, their loads issued together: with one row in flight the pass waits out a memory
+    // latency per 1024 rows)
+    for (int q0 = tid; q0 < n; q0 += PEC_NIF * PEC_NT) {
+        float2 g[PEC_NIF];
+        float tt[PEC_NIF];
+        int lc[PEC_NIF];
+#pragma unroll
+        for (int u = 0; u < PEC_NIF; ++u) {
+            const int q = q0 + u * PEC_NT;
+            const bool on = q < n;
+            int lo = 0, hi = nrange;
+            if (on) { while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_pre[mid] <= q) lo = mid; else hi = mid; } }
+            // (n > 0 here, so the sample has a row 0: a lane past the end loads it and drops it)
+            const size_t row = (size_t)b * s.M + (on ? s_r0[lo] + (q - s_pre[lo]) : 0);
+            g[u] = gpos[row];
+            tt[u] = rows[row * 6 + 2];
+            lc[u] = on ? __float_as_int(rows[row * 6 + 4]) - cell0 : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < PEC_NIF; ++u) {
+            if (q0 + u * PEC_NT >= n || (g[u].x == 0.f && g[u].y == 0.f)) continue;
+            MPC_EXPECT(lc[u] >= 0 && lc[u] < ncell);            // (a row outside its strip: the offsets table is not this tensor's)
+            if (lc[u] < 0 || lc[u] >= ncell) continue;
+            float E[PEC_DMAX];
+            pec_basis(pb, tt[u], E);
+            unsigned long long *a = s_acc + (size_t)lc[u] * 2 * kc;
+#pragma unroll
+            for (int j = 0; j < PEC_DMAX; ++j) {
+                if (j >= j0 && j < j0 + kc) {
+                    const float ph = Er[j] - E[j];
+                    atomicAdd(a + MPC_IDX(j - j0, kc), (unsigned long long)pec_to_fixed(ph * g[u].x));
+                    atomicAdd(a + MPC_IDX(kc + j - j0, 2 * kc), (unsigned long long)pec_to_fixed(ph * g[u].y));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const float coef = pec_coef(scal, grad_out);
+    for (int i = tid; i < nacc; i += PEC_NT) {
+        const int lc = i / (2 * kc), r = i - lc * 2 * kc, a = r / kc, jj = r - a * kc;
+        grows[((size_t)(cell0 + lc) * 2 + a) * d + j0 + jj] = coef * mpc_from_fixed((long long)s_acc[MPC_IDX(i, nacc)]);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pec_grad_atomic(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
+                                                         const PecBasis pb, const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                         const float *__restrict__ grad_out, float *__restrict__ grows) {
+    const int d = pb.d;
+    const float coef = pec_coef(scal, grad_out);
+    const int ncell = s.B * s.hq * s.wq;
+    float Er[PEC_DMAX];
+    pec_basis(pb, t_ref[0], Er);
+    const size_t total = (size_t)s.B * s.M;
+    for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
+        float2 g = gpos[row];
+        g.x *= coef; g.y *= coef;
+        if (g.x == 0.f && g.y == 0.f) continue;
+        const float2 tp = reinterpret_cast<const float2 *>(rows + row * 6)[1];
+        const int cell = __float_as_int(rows[row * 6 + 4]);
+        MPC_EXPECT(cell >= 0 && cell < ncell);
+        if (cell < 0 || cell >= ncell) continue;                // (rows that mpc_pec_warp did not write)
+        float E[PEC_DMAX];
+        pec_basis(pb, tp.x, E);
+        float *o = grows + (size_t)cell * 2 * d;
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            if (j < d) { const float ph = Er[j] - E[j]; atomicAdd(o + j, ph * g.x); atomicAdd(o + d + j, ph * g.y); }
+        }
+    }
+}
+
+// ---- smoothness field and its adjoint -------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pec_field(const float *__restrict__ rows, const float *__restrict__ phim, float *__restrict__ field,
+                                                   int B, int G, int d, int nbm) {
+    __shared__ float s_phi[64 * PEC_DMAX];
+    for (int i = threadIdx.x; i < nbm * d; i += 256) s_phi[i] = phim[i];
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (b, cell)
+    if (i >= (long long)B * G) return;
+    const int b = (int)(i / G), cell = (int)(i - (long long)b * G);
+    float cy[PEC_DMAX], cx[PEC_DMAX];
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j) {
+        cy[j] = j < d ? rows[(size_t)i * 2 * d + j] : 0.f;
+        cx[j] = j < d ? rows[(size_t)i * 2 * d + d + j] : 0.f;
+    }
+    for (int t = 0; t < nbm; ++t) {
+        float fy = 0.f, fx = 0.f;
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j)
+            if (j < d) { fy += cy[j] * s_phi[t * d + j]; fx += cx[j] * s_phi[t * d + j]; }
+        reinterpret_cast<float2 *>(field)[((size_t)b * nbm + t) * G + cell] = make_float2(fy, fx);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_pec_field_adj(const float *__restrict__ gfield, const float *__restrict__ phim,
+                                                       const float *__restrict__ gout, float *__restrict__ grows, int B, int G, int d, int nbm) {
+    __shared__ float s_phi[64 * PEC_DMAX];
+    for (int i = threadIdx.x; i < nbm * d; i += 256) s_phi[i] = phim[i];
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (b, cell)
+    if (i >= (long long)B * G) return;
+    const int b = (int)(i / G), cell = (int)(i - (long long)b * G);
+    float gy[PEC_DMAX], gx[PEC_DMAX];
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j) gy[j] = gx[j] = 0.f;
+    for (int t = 0; t < nbm; ++t) {
+        const float2 g = reinterpret_cast<const float2 *>(gfield)[((size_t)b * nbm + t) * G + cell];
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j)
+            if (j < d) { gy[j] += g.x * s_phi[t * d + j]; gx[j] += g.y * s_phi[t * d + j]; }
+    }
+    const float go = gout ? gout[0] : 1.f;
+    float *o = grows + (size_t)i * 2 * d;
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j)
+        if (j < d) { o[j] += go * gy[j]; o[d + j] += go * gx[j]; }
+}
+
+// ---- entry points ---------------------------------------------------------------------------------------------------------------
+static int pec_tile_ok(int tile) { return tile == 2 || tile == 4 || tile == 8 || tile == 16; }
+
+// the tile grid of the head: with a mask the centres of the 8h x 8w image, without one the grid of params itself
+static int pec_head_grid(const char *who, int B, int d, int h, int w, int tile, int has_mask, int *nty, int *ntx) {
+    if (B < 0 || h < 0 || w < 0 || d < 1) { mpc_set_error("%s: bad B / d / h / w", who); return MPC_E_SHAPE; }
+    if (d > PEC_DMAX) { mpc_set_error("%s: more than %d control points per axis", who, PEC_DMAX); return MPC_E_UNSUPPORTED; }
+    if (has_mask) {
+        if (!pec_tile_ok(tile) || (8 * h) % tile || (8 * w) % tile) { mpc_set_error("%s: tile must be 2, 4, 8 or 16 and divide 8h and 8w", who); return MPC_E_SHAPE; }
+        *nty = 8 * h / tile; *ntx = 8 * w / tile;
+    } else {
+        *nty = h; *ntx = w;
+    }
+    if ((long long)B * *nty * *ntx * 2 * d > (1ll << 31) || (long long)h * w > (1ll << 24)) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
+    return 0;
+}
+
+static int pec_make_basis(const char *who, int basis, int d, const float *table, int S, PecBasis *pb) {
+    if (d < 1 || basis < MPC_PEC_BEZIER || basis > MPC_PEC_TABLE) { mpc_set_error("%s: bad degree or basis kind", who); return MPC_E_SHAPE; }
+    if (d > PEC_DMAX) { mpc_set_error("%s: more than %d control points per axis", who, PEC_DMAX); return MPC_E_UNSUPPORTED; }
+    pb->kind = basis; pb->d = d; pb->S = 0; pb->table = nullptr;
+    long long c = 1;
+    for (int j = 0; j < PEC_DMAX; ++j) {
+        if (j < d) c = c * (d - j) / (j + 1);              // C(d, j + 1), exact
+        pb->binom[j] = j < d ? (float)c : 0.f;
+    }
+    if (basis == MPC_PEC_TABLE) {
+        if (!table) { mpc_set_error("%s: the table is null", who); return MPC_E_NULL; }
+        if (S < 1) { mpc_set_error("%s: a table needs samples >= 1", who); return MPC_E_SHAPE; }
+        if ((int64_t)(S + 1) * d > mpc_pe_table_limit()) { mpc_set_error("%s: (samples + 1) * degree exceeds mpc_pe_table_limit()", who); return MPC_E_UNSUPPORTED; }
+        pb->S = S; pb->table = table;
+    }
+    return 0;
+}
+
+// orders per pass of k_pec_accum that fit the LDS beside a strip's cells (0: not even one)
+static int pec_orders_per_pass(const mpc_shape *s, const mpc_ws_layout &L, int d) {
+    if (L.n_cstrips <= 0 || L.cstrip_rows <= 0) return 0;
+    const int64_t per_order = (int64_t)L.cstrip_rows * s->wq * 2 * 8;
+    const int64_t kc = PEC_LDS_MAX / per_order;
+    return (int)(kc < d ? kc : d);
+}
+
+// The library's choice of orders per pass (orders_per_pass = 0).  Every pass is a workgroup of its own, so FEWER orders per pass
+// spread a strip's adds over more CUs at the price of streaming its rows once more per pass: the smallest count whose workgroups
+// still fit the device in one round (all choices write the same bits: integer sums per element).  Measured at the C4 shape
+// (1 x 500 k events, 7 strips, d = 10): 3 orders per pass (28 workgroups) 179 us, 1 order per pass (70 workgroups) 160 us.
+static int pec_cu_count() {
+    static std::atomic<int> ncu_of[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    int ncu = ncu_of[dev & 63].load();
+    if (ncu <= 0) {
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) { (void)hipGetLastError(); ncu = 256; }
+        ncu_of[dev & 63].store(ncu);
+    }
+    return ncu;
+}
+static int pec_choose_orders(const mpc_shape *s, const mpc_ws_layout &L, int d, int kmax) {
+    const int64_t groups = (int64_t)s->B * L.n_cstrips, ncu = pec_cu_count();
+    for (int kc = 1; kc < kmax; ++kc)
+        if (groups * ((d + kc - 1) / kc) <= ncu) return kc;
+    return kmax;
+}
+
+extern "C" int32_t mpc_pec_supported(const mpc_shape *s, int32_t d, int32_t basis, int32_t S) {
+    if (!s || mpc_validate_shape(s)) return 0;
+    if (!(s->flags & MPC_F_NO_WARP) || s->T != 1 || d < 1 || d > PEC_DMAX || s->nb < 1 || s->nb > 64 || s->B < 0) return 0;
+    if (basis < MPC_PEC_BEZIER || basis > MPC_PEC_TABLE) return 0;
+    if (basis == MPC_PEC_TABLE && (S < 1 || (int64_t)(S + 1) * d > mpc_pe_table_limit())) return 0;
+    int32_t r = 1;
+    if (s->B > 0) {
+        const mpc_ws_layout L = mpc_layout(s);
+        if (pec_orders_per_pass(s, L, d) >= 1) r |= 2;
+    }
+    return r;
+}
+
+extern "C" int mpc_pec_head_rows(const float *params, const float *mask, float scale, int32_t tile, float *rows,
+                                 int32_t B, int32_t d, int32_t h, int32_t w, void *stream) {
+    MPC_CHECK_ARG(params && rows, MPC_E_NULL, "null argument");
+    int nty = 0, ntx = 0;
+    int rc = pec_head_grid(__func__, B, d, h, w, tile, mask != nullptr, &nty, &ntx);
+    if (rc) return rc;
+    const long long work = (long long)B * nty * ntx;
+    if (work == 0) return 0;
+    MPC_LAUNCH(k_pec_head_rows, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, mask, scale, tile, rows, B, d, h, w, nty, ntx);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int64_t mpc_pec_head_rows_bwd_workspace_bytes(int32_t B, int32_t d, int32_t h, int32_t w, int32_t tile) {
+    int nty = 0, ntx = 0;
+    int rc = pec_head_grid(__func__, B, d, h, w, tile, 1, &nty, &ntx);
+    if (rc) return rc;
+    const int64_t cvx = mpc_cvx_traj_bwd_workspace_bytes(B, d, d, h, w, tile);
+    if (cvx < 0) return cvx;
+    return mpc_align((int64_t)B * d * nty * ntx * 2 * 4) + mpc_align((int64_t)d * d * 4) + cvx;
+}
+
+extern "C" int mpc_pec_head_rows_bwd(const float *grad_rows, const float *params, const float *mask, float scale, int32_t tile,
+                                     float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream) {
+    MPC_CHECK_ARG(grad_rows && params && grad_params && (!mask || (grad_mask && ws)), MPC_E_NULL, "null argument");
+    int nty = 0, ntx = 0;
+    int rc = pec_head_grid(__func__, B, d, h, w, tile, mask != nullptr, &nty, &ntx);
+    if (rc) return rc;
+    const int n = nty * ntx;
+    hipStream_t st = (hipStream_t)stream;
+    if ((long long)B * h * w == 0) return 0;
+    if (mask == nullptr) {
+        const long long total = (long long)B * 2 * d * n;
+        MPC_LAUNCH(k_pec_rows_to_params, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, grad_rows, scale, grad_params, B, d, n);
+        MPC_CHECK_LAUNCH();
+        return 0;
+    }
+    float *gtraj = (float *)ws;
+    float *ident = (float *)((char *)ws + mpc_align((int64_t)B * d * n * 2 * 4));
+    void *cvx_ws = (char *)ident + mpc_align((int64_t)d * d * 4);
+    long long total = (long long)B * d * n;
+    if (total < (long long)d * d) total = (long long)d * d;
+    MPC_LAUNCH(k_pec_rows_to_traj, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, grad_rows, gtraj, ident, B, d, n);
+    MPC_CHECK_LAUNCH();
+    return mpc_cvx_traj_bwd(gtraj, params, mask, ident, scale, grad_params, grad_mask, B, d, d, h, w, tile, cvx_ws, stream);
+}
+
+#define PEC_SHAPE_CHECKS()                                                                                                                   \
+    MPC_CHECK_ARG((s->flags & MPC_F_NO_WARP) && s->T == 1, MPC_E_UNSUPPORTED, "takes MPC_F_NO_WARP shapes with num_tref == 1");                \
+    { int rc__ = mpc_validate_shape(s); if (rc__) return rc__; }
+
+extern "C" int mpc_pec_warp(const mpc_shape *s, const float *events, const float *rows, int32_t basis, int32_t d, const float *table, int32_t S,
+                            const float *t_ref, float *rows_out, void *stream) {
+    MPC_CHECK_ARG(s && rows && t_ref && rows_out && (events || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PEC_SHAPE_CHECKS();
+    PecBasis pb;
+    int rc = pec_make_basis(__func__, basis, d, table, S, &pb);
+    if (rc) return rc;
+    const int64_t total = (int64_t)s->B * s->M;
+    if (total == 0) return 0;
+    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    MPC_LAUNCH(k_pec_warp, dim3(grid), dim3(256), 0, (hipStream_t)stream, *s, events, rows, pb, t_ref, rows_out);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, const int32_t *offsets, const float *grad_pos, int32_t basis,
+                                 int32_t d, const float *table, int32_t S, const float *t_ref, const float *scal, const float *grad_out,
+                                 int32_t orders_per_pass, float *grad_rows, void *stream) {
+    MPC_CHECK_ARG(s && t_ref && grad_rows && ((rows_warped && grad_pos) || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PEC_SHAPE_CHECKS();
+    PecBasis pb;
+    int rc = pec_make_basis(__func__, basis, d, table, S, &pb);
+    if (rc) return rc;
+    MPC_CHECK_ARG(orders_per_pass >= 0, MPC_E_SHAPE, "orders_per_pass < 0");
+    if (s->B == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t out_bytes = (size_t)s->B * s->hq * s->wq * 2 * d * sizeof(float);
+    if (offsets == nullptr) {
+        const int e0 = mpc_zero_async(grad_rows, out_bytes, st);
+        if (e0) return e0;
+        const int64_t total = (int64_t)s->B * s->M;
+        if (total == 0) return 0;
+        const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+        MPC_LAUNCH(k_pec_grad_atomic, dim3(grid), dim3(256), 0, st, *s, rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal,
+                   grad_out, grad_rows);
+        MPC_CHECK_LAUNCH();
+        return 0;
+    }
+    MPC_CHECK_ARG(s->nb <= 64, MPC_E_UNSUPPORTED, "num_bins > 64");
+    const mpc_ws_layout L = mpc_layout(s);
+    const int kmax = pec_orders_per_pass(s, L, d);
+    MPC_CHECK_ARG(kmax >= 1, MPC_E_UNSUPPORTED, "a LUT strip's accumulators of one order do not fit the LDS (pass no offsets)");
+    const int kc = orders_per_pass == 0 ? pec_choose_orders(s, L, d, kmax) : (orders_per_pass < d ? orders_per_pass : d);
+    MPC_CHECK_ARG(kc <= kmax, MPC_E_UNSUPPORTED, "orders_per_pass beyond what the LDS holds");
+    const int npass = (d + kc - 1) / kc;
+    const size_t lds = (size_t)L.cstrip_rows * s->wq * 2 * kc * 8;
+    static mpc_device_once attr_once;
+    if (attr_once.need()) {
+        // (the kernel has 1 KB of static LDS of its own)
+        hipError_t e = hipFuncSetAttribute((const void *)k_pec_accum, hipFuncAttributeMaxDynamicSharedMemorySize, PEC_LDS_MAX + 2048);
+        if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
+        attr_once.mark();
+    }
+    MPC_LAUNCH(k_pec_accum, dim3(s->B * L.n_cstrips * npass), dim3(PEC_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, kc, npass, offsets, rows_warped,
+               reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal, grad_out, grad_rows);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int32_t mpc_pec_rows_grad_passes(const mpc_shape *s, int32_t d, int32_t orders_per_pass) {
+    if (!s || mpc_validate_shape(s) || d < 1 || d > PEC_DMAX || s->B <= 0) return 0;
+    const mpc_ws_layout L = mpc_layout(s);
+    const int kmax = pec_orders_per_pass(s, L, d);
+    if (kmax < 1) return 0;
+    const int kc = orders_per_pass <= 0 ? pec_choose_orders(s, L, d, kmax) : (orders_per_pass < d ? orders_per_pass : d);
+    return kc <= kmax ? (d + kc - 1) / kc : 0;
+}
+
+extern "C" int mpc_pec_field(const float *rows, const float *phim, float *field, int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream) {
+    MPC_CHECK_ARG(rows && phim && field, MPC_E_NULL, "null argument");
+    MPC_CHECK_ARG(B >= 0 && G >= 0 && d >= 1 && nbm >= 1, MPC_E_SHAPE, "bad shape");
+    MPC_CHECK_ARG(d <= PEC_DMAX && nbm <= 64, MPC_E_UNSUPPORTED, "more than 16 orders or 64 field times");
+    if ((long long)B * G == 0) return 0;
+    MPC_LAUNCH(k_pec_field, dim3((unsigned)(((long long)B * G + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, phim, field, B, G, d, nbm);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mpc_pec_field_adjoint(const float *grad_field, const float *phim, const float *grad_out, float *grad_rows,
+                                     int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream) {
+    MPC_CHECK_ARG(grad_field && phim && grad_rows, MPC_E_NULL, "null argument");
+    MPC_CHECK_ARG(B >= 0 && G >= 0 && d >= 1 && nbm >= 1, MPC_E_SHAPE, "bad shape");
+    MPC_CHECK_ARG(d <= PEC_DMAX && nbm <= 64, MPC_E_UNSUPPORTED, "more than 16 orders or 64 field times");
+    if ((long long)B * G == 0) return 0;
+    MPC_LAUNCH(k_pec_field_adj, dim3((unsigned)(((long long)B * G + 255) / 256)), dim3(256), 0, (hipStream_t)stream, grad_field, phim, grad_out,
+               grad_rows, B, G, d, nbm);
+    MPC_CHECK_LAUNCH();
+    return 0;
+}
+
+MPC_BOUNDS_UNIT("pe_curves.hip")

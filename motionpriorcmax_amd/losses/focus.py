@@ -268,7 +268,113 @@ class FocusLoss(base.TrajectoryLossBase):
         iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
         return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
 
-    AUTO_STATIC_MAX_EVENTS = 150_000      # B * M up to which the captured plan wins (C2: 0.16 against 0.20 ms; C4, 500k events: it loses)
+    PEC_TILES = (2, 4, 8, 16)
+
+    def _curve_tile_grid(self, params, up_mask, scale):
+        """The checks of calc_per_event_curves that need no device: -> (d, tile).  Every rule raises a ValueError that names it."""
+        if self.num_tref != 1:
+            raise ValueError('calc_per_event_curves needs num_tref == 1')
+        if not torch.is_tensor(params) or params.dim() != 4 or params.shape[1] % 2 or params.shape[1] < 2:
+            raise ValueError(f'params must be [B, 2d, h, w] (control points 1..d, x channels first), got {tuple(getattr(params, "shape", ()))}')
+        B, c2, h, w = params.shape
+        sp, scale = self.lut_superpixel_size, float(scale)
+        if not scale > 0:
+            raise ValueError(f'scale must be positive, got {scale}')
+        tile = int(round(sp / scale))
+        if tile not in self.PEC_TILES or abs(tile * scale - sp) > 1e-6 * sp:
+            raise ValueError(f'tile = lut_superpixel_size / scale = {sp} / {scale} must be one of {self.PEC_TILES}')
+        hq, wq = self._cfg.lut_grid
+        if up_mask is not None:
+            if not torch.is_tensor(up_mask) or tuple(up_mask.shape) != (B, 576, h, w):
+                raise ValueError(f'up_mask must be [B, 576, h, w] = {(B, 576, h, w)}, got {tuple(getattr(up_mask, "shape", ()))}')
+            if (8 * h) % tile or (8 * w) % tile or (8 * h // tile, 8 * w // tile) != (hq, wq):
+                raise ValueError(f'the tile grid of the 8h x 8w = {8 * h} x {8 * w} image at tile {tile} must equal the look-up-table grid {hq} x {wq}')
+        elif (h, w) != (hq, wq):
+            raise ValueError(f'without up_mask the grid of params is the tile grid and must equal the look-up-table grid {hq} x {wq}, got {h} x {w}')
+        return c2 // 2, tile
+
+    def calc_per_event_curves(self, params, t_ref, batch, *, up_mask=None, curve_type='BEZIER', basis_table=None, scale=1.0, fused=True):
+        """UNPINNED EXTENSION (BASELINE.json's north_star and configs[3]): the per-event continuous-time warp along RAFT-spline
+        curves.  Every event moves along the curve of the tile it lies in, evaluated at ITS OWN timestamp -- no time bins, no KNN
+        look-up table, time not piecewise constant (`trajectories_from_bezier(up_mask=)` + `calc` is that route).
+
+        params [B, 2d, h, w]: control points 1..d, x in the first d channels, y in the next d (reference curves/polynomial.py:60-61;
+        P0 = 0).  With up_mask [B, 576, h, w] they live on the 1/8 grid and are upsampled as reference raft_spline/utils.py:30-45
+        does; without it they are per tile already (h x w = the tile grid).  t_ref scalar tensor / float, batch as for `calc`.
+          rows[(b, cell)][0][j] = scale * up_y[j],  rows[(b, cell)][1][j] = scale * up_x[j]   at the tile centres
+              (iy * tile + tile // 2, ix * tile + tile // 2) of the 8h x 8w image; tile = lut_superpixel_size / scale, one of 2, 4, 8,
+              16; the tile grid must equal the look-up-table grid (EVIMO2: 384 x 512 net, 480 x 640 events, scale 1.25, sp 5, tile 4)
+          warped = (y, x) + sum_j rows[cell(y, x)][:, j] * phi_j,   phi_j = E_j(t_ref) - E_j(t_event)      (j ascending)
+        with E of `utils.curve_event_basis`: curve_type 'BEZIER' (1 <= d), 'POLYNOMIAL', or 'TABLE' with basis_table [S + 1, d] (a
+        constant: e.g. the cubic B-spline `bspline_basis(knots, d + 1)` or a frozen learned basis).  Then the reference's weights,
+        vote, blur and objective; the smoothness term is the reference's Charbonnier term on rows x phim with
+        phim[t] = E(t_ref) - E(t_mid[t]) ('on_flow_to_tref') or E(t_mid[t + 1]) - E(t_mid[t]) ('on_flow_to_next').
+        Returns the triple of `calc`.  Gradients go to params and up_mask only.
+
+        fused=True: one autograd node (ops.PerEventCurvesFn, csrc/pe_curves.hip), the basis evaluated in registers; with a
+        bucket-ordered batch (`event_offsets`) the backward sums per LUT strip in LDS fixed point, bitwise reproducible, in
+        ceil(d / orders per pass) passes; without the table it uses global float atomics (slow, not reproducible).
+        fused=False, and whatever the library refuses (d > 16, a table past mpc_pe_table_limit(), num_bins > 64, a CPU basis_table):
+        phi [B, M, d] and the rows in plain torch around the existing per-event nodes (the cross-check).  No graph capture."""
+        from ..utils import curve_event_basis, curve_head_rows
+        from ..utils.basis import CURVE_EVENT_TYPES
+        d, tile = self._curve_tile_grid(params, up_mask, scale)
+        if curve_type not in CURVE_EVENT_TYPES:
+            raise ValueError(f'curve_type must be one of {CURVE_EVENT_TYPES}, got {curve_type!r}')
+        if (curve_type == 'TABLE') != (basis_table is not None):
+            raise ValueError("curve_type='TABLE' and basis_table go together")
+        if basis_table is not None and not (torch.is_tensor(basis_table) and basis_table.dim() == 2 and basis_table.dtype == torch.float32
+                                            and basis_table.shape[0] >= 2 and basis_table.shape[1] == d):
+            raise ValueError(f'basis_table must be a 2-D float32 tensor [samples + 1, d = {d}]')
+        events = batch['events']
+        if events.shape[0] != params.shape[0]:
+            raise ValueError(f'params hold {params.shape[0]} samples, the events {events.shape[0]}')
+        num_pos_events = batch['num_pos_events'] if 'num_pos_events' in batch else -1
+        assert not self.polarity_aware_batching or num_pos_events > -1
+        dev = events.device
+        h, w = self._cfg.image_shape
+        hq, wq = self._cfg.lut_grid
+        B = events.shape[0]
+        if torch.is_tensor(t_ref):
+            t_ref = t_ref.to(device=dev, dtype=torch.float32).reshape(1)
+        else:
+            t_ref = torch.full((1,), float(t_ref), dtype=torch.float32, device=dev)
+        offsets = batch['event_offsets'] if 'event_offsets' in batch else None
+        if fused and basis_table is not None and basis_table.device != dev:
+            fused = False
+        if fused and not ops.pec_supported(self._cfg, events, int(num_pos_events), d, curve_type,
+                                           basis_table.shape[0] - 1 if basis_table is not None else 0) & 1:
+            fused = False
+        if basis_table is not None:
+            basis_table = basis_table.detach().to(dev)
+        phim = None
+        if self.smooth_weight > 0:
+            from ..utils.synth import bin_mid_times
+            tm = self._tmid_dev.get(dev)
+            if tm is None:
+                tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
+            with torch.no_grad():
+                bv = curve_event_basis(torch.cat((t_ref, tm)), d, curve_type, basis_table)
+                phim = (bv[2:] - bv[1:-1]) if self.smooth_type == 'on_flow_to_next' else (bv[:1] - bv[1:])
+            if phim.shape[0] == 0:
+                phim = None
+        if fused:
+            loss, focus, smooth, iwes = ops.PerEventCurvesFn.apply(params, up_mask, events, t_ref, phim, self._cfg, int(num_pos_events), offsets,
+                                                                   curve_type, basis_table, float(scale), tile)
+        else:
+            with torch.no_grad():
+                phi = curve_event_basis(t_ref, d, curve_type, basis_table) - curve_event_basis(events[..., 2], d, curve_type, basis_table)
+            c_rows = curve_head_rows(params, up_mask, scale, tile)
+            focus, iwes = ops.PerEventBasisFocusFn.apply(c_rows, events, phi, t_ref, self._cfg, int(num_pos_events), offsets)
+            smooth = torch.zeros((), device=dev)
+            if phim is not None:
+                field = ops.BasisFieldFn.apply(c_rows, phim, B, hq, wq)
+                smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
+            loss = focus + smooth
+        iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
+        return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
+
+    AUTO_STATIC_MAX_EVENTS = 150_000     # B * M up to which the captured plan wins (C2: 0.16 against 0.20 ms; C4, 500k events: it loses)
     AUTO_STATIC_AFTER = 3                 # consecutive calcs of one shape before it is captured
 
     def _auto_static(self, trajectories, events, num_pos_events, offsets):

@@ -1103,6 +1103,127 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         return (g_grid, None, None, g_phim) + (None,) * 6 + (g_table,)
 
 
+PEC_BASIS = {'BEZIER': 0, 'POLYNOMIAL': 1, 'TABLE': 2}        # include/mpcmax.h: MPC_PEC_*
+PEC_ROWS_GRAD_TAP = None       # diagnostics (tests): a list that receives a copy of every grad_rows [B*G, 2d] PerEventCurvesFn computes
+
+
+def _pec_shape(cfg, events, num_pos):
+    B, M, Mp = _check_events(events, cfg, num_pos)
+    return make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+
+
+def pec_supported(cfg, events, num_pos, d, curve_type, samples=0):
+    """mpc_pec_supported for this batch: 0 = the curve kernels (csrc/pe_curves.hip) do not serve it, bit 0 = they do, bit 1 = the
+    row gradient also takes an offsets table.  The library's answer: the limits live there only."""
+    if not (torch.is_tensor(events) and events.is_cuda) or curve_type not in PEC_BASIS:
+        return 0
+    shape = _pec_shape(cfg, events, num_pos)
+    return _query('mpc_pec_supported', events.device, ctypes.byref(shape), int(d), PEC_BASIS[curve_type], int(samples))
+
+
+class PerEventCurvesFn(torch.autograd.Function):
+    """UNPINNED extension (FocusLoss.calc_per_event_curves): the per-event continuous-time warp along RAFT-spline curves as ONE
+    autograd node of library calls on the current stream (csrc/pe_curves.hip):
+    head rows (mpc_pec_head_rows) -> warp (mpc_pec_warp) -> vote (mpc_event_splat_fwd, MPC_F_NO_WARP) -> blur + objective
+    (mpc_contrast_fwd) [-> field (mpc_pec_field) -> Charbonnier term (mpc_lut_smooth)] -> scalars (mpc_finalize), and back:
+    mpc_event_pos_grad -> mpc_pec_rows_grad [-> mpc_pec_field_adjoint] -> mpc_pec_head_rows_bwd.
+    params [B, 2d, h, w] (x channels first), up_mask [B, 576, h, w] or None, phim [nbm, d] or None (no smoothness term), table
+    [S + 1, d] or None.  Returns (loss, focus, smooth, iwes_blurred); differentiable w.r.t. params and up_mask through `loss`.
+    No host synchronisation.  The position gradient is taken UNSCALED (a `scal` of ones) and the loss scale applied after the
+    fixed-point sums, as k_pe_accum does: the sums' resolution does not depend on grad_out."""
+
+    @staticmethod
+    def forward(ctx, params, up_mask, events, t_ref, phim, cfg: PathConfig, num_pos: int, offsets, curve_type: str, table, scale: float,
+                tile: int, orders_per_pass: int = 0):
+        _require_gpu(params, 'params')
+        B, M, Mp = _check_events(events, cfg, num_pos)
+        dev = params.device
+        p = _f32c(params.detach())
+        m = None
+        if up_mask is not None:
+            _require_gpu(up_mask, 'up_mask')
+            m = _f32c(up_mask.detach())
+        ev = _f32c(events.detach())
+        pm = _f32c(phim.detach()) if phim is not None else None
+        tr = _f32c(t_ref.detach().to(dev))
+        tab = None
+        if table is not None:
+            _require_gpu(table, 'basis_table')
+            tab = _f32c(table.detach())
+        Bp, c2, h, w = p.shape
+        d, kind, S = c2 // 2, PEC_BASIS[curve_type], (tab.shape[0] - 1 if tab is not None else 0)
+        shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+        hq, wq = shape.hq, shape.wq
+        G = hq * wq
+        grid = (8 * h // tile, 8 * w // tile) if m is not None else (h, w)
+        if Bp != B or c2 != 2 * d or grid != (hq, wq) or (m is not None and tuple(m.shape) != (B, 576, h, w)) or \
+                (tab is not None and (tab.dim() != 2 or tab.shape[1] != d)) or (pm is not None and (pm.dim() != 2 or pm.shape[1] != d)):
+            raise ValueError(f'params {tuple(p.shape)} / up_mask / basis_table / phim do not match [B={B}, 2d, h, w] with the tile grid {(hq, wq)}')
+        sup = _query('mpc_pec_supported', dev, ctypes.byref(shape), d, kind, S)
+        if not sup & 1:
+            raise ValueError(f'the curve kernels do not serve d={d}, {curve_type}, samples={S}, num_bins={cfg.num_bins} (mpc_pec_supported)')
+        need_grad = params.requires_grad or (up_mask is not None and up_mask.requires_grad)
+        c_rows = torch.empty((B * G, 2 * d), dtype=torch.float32, device=dev)
+        _call('mpc_pec_head_rows', dev, _ptr(p), _ptr(m), float(scale), int(tile), _ptr(c_rows), B, d, h, w)
+        ws = alloc_workspace(shape, dev)
+        rows = torch.empty_like(ev)
+        if B * M > 0:                                 # (an empty tensor has no pointer to hand over)
+            _call('mpc_pec_warp', dev, ctypes.byref(shape), _ptr(ev), _ptr(c_rows), kind, d, _ptr(tab), S, _ptr(tr), _ptr(rows))
+        raw = event_splat_fwd(shape, rows, None, tr, ws)
+        blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
+        g_field, s_nimg = None, 0
+        if pm is not None and cfg.smooth_weight > 0 and pm.shape[0] > 0:
+            nbm = pm.shape[0]
+            field = torch.empty((B * nbm, hq, wq, 2), dtype=torch.float32, device=dev)
+            _call('mpc_pec_field', dev, _ptr(c_rows), _ptr(pm), _ptr(field), B, G, d, nbm)
+            s_nimg = B * nbm
+            g_field = lut_smooth(shape, field, s_nimg, 2, cfg.smooth_weight, ws, need_grad)
+        scal = finalize(shape, s_nimg, 2 if s_nimg else 0, cfg.smooth_weight if s_nimg else 0.0, ws, dev)
+        offs = _check_offsets(offsets, cfg, shape, dev) if (offsets is not None and sup & 2) else None
+        ctx.shape, ctx.dims = shape, (B, d, h, w, kind, S, float(scale), int(tile), int(orders_per_pass))
+        ctx.has = (m is not None, g_field is not None, offs is not None, tab is not None)
+        ctx.set_materialize_grads(False)
+        none = tr
+        ctx.save_for_backward(p, m if m is not None else none, rows, tr, gimg if gimg is not None else none, scal,
+                              offs if offs is not None else none, g_field if g_field is not None else none,
+                              pm if pm is not None else none, tab if tab is not None else none)
+        out = scal[:3].clone()
+        loss, focus, smooth = out[C.SCAL_LOSS], out[C.SCAL_FOCUS], out[C.SCAL_SMOOTH]
+        ctx.mark_non_differentiable(focus, smooth, blur)
+        return loss, focus, smooth, blur
+
+    @staticmethod
+    def backward(ctx, g_loss, g_focus, g_smooth, g_blur):
+        if g_loss is None:
+            return (None,) * 13
+        p, m, rows, tr, gimg, scal, offs, g_field, pm, tab = ctx.saved_tensors
+        has_mask, has_smooth, has_offs, has_tab = ctx.has
+        shape = ctx.shape
+        B, d, h, w, kind, S, scale, tile, opp = ctx.dims
+        G = shape.hq * shape.wq
+        dev = rows.device
+        go = _f32c(g_loss.reshape(1))
+        gpos = None
+        if shape.B * shape.M > 0:
+            unit = torch.ones(C.SCAL_COUNT, dtype=torch.float32, device=dev)
+            gpos = event_pos_grad(shape, rows, tr, gimg, unit, None)
+        g_rows = torch.empty((B * G, 2 * d), dtype=torch.float32, device=dev)
+        _call('mpc_pec_rows_grad', dev, ctypes.byref(shape), _ptr(rows) if gpos is not None else None, _ptr(offs) if has_offs else None, _ptr(gpos),
+              kind, d, _ptr(tab) if has_tab else None, S, _ptr(tr), _ptr(scal), _ptr(go), opp, _ptr(g_rows))
+        if has_smooth:
+            _call('mpc_pec_field_adjoint', dev, _ptr(g_field), _ptr(pm), _ptr(go), _ptr(g_rows), B, G, d, pm.shape[0])
+        if PEC_ROWS_GRAD_TAP is not None:
+            PEC_ROWS_GRAD_TAP.append(g_rows.clone())
+        gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
+        gm = ws = None
+        if has_mask:
+            gm = torch.empty((B, 576, h, w), dtype=torch.float32, device=dev)          # (every element is written)
+            ws = torch.empty(max(_query('mpc_pec_head_rows_bwd_workspace_bytes', dev, B, d, h, w, tile), 256), dtype=torch.uint8, device=dev)
+        _call('mpc_pec_head_rows_bwd', dev, _ptr(g_rows), _ptr(p), _ptr(m) if has_mask else None, scale, tile, _ptr(gp), _ptr(gm), B, d, h, w,
+              _ptr(ws))
+        return (gp, gm) + (None,) * 11
+
+
 class TileCoeffRowsFn(torch.autograd.Function):
     """coeff_grid [B, S, 2k, H, W] -> the coefficients at the tile centres (offset tile // 2, row-major: trajectories.py:3-52),
     scales summed, one row per tile: [B*hq*wq, 2k].  One autograd node with a strided copy each way instead of the half dozen

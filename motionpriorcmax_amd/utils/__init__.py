@@ -1,5 +1,5 @@
 from .trajectories import get_optical_flow_tile_mask, coeffs_grid_to_list  # noqa: F401
-from .basis import compute_basis, basis_values, basis_table, table_basis_values, bernstein_basis, trajectories_from_bezier, bspline_basis, trajectories_from_bspline, flows_from_bezier, curve_basis, trajectories_from_curves, flows_from_curves  # noqa: F401
+from .basis import compute_basis, basis_values, basis_table, table_basis_values, bernstein_basis, trajectories_from_bezier, bspline_basis, trajectories_from_bspline, flows_from_bezier, curve_basis, trajectories_from_curves, flows_from_curves, curve_event_basis, curve_head_rows  # noqa: F401
 from .event_image_converter import EventImageConverter  # noqa: F401
 from .voxel_grid import VoxelGrid, voxel_grids  # noqa: F401
 from .ingest import ingest_events, ingest_raw_events  # noqa: F401

@@ -61,6 +61,64 @@ def table_basis_values(table, times):
     return lo + f[..., None] * (table[i + 1] - lo)
 
 
+CURVE_EVENT_TYPES = ('BEZIER', 'POLYNOMIAL', 'TABLE')
+
+
+def curve_event_basis(times, d, curve_type, basis_table=None):
+    """The basis E of FocusLoss.calc_per_event_curves at arbitrary times: times [...] -> [..., d] in fp32, on the device of `times`,
+    nothing read back.  This is the DEFINITION and the lines are those of the kernels (csrc/pe_curves.hip: pec_basis), one fp32
+    operation each, so that the two agree bit for bit:
+      'BEZIER'      u = 1 - t;  tp_1 = t, tp_i = tp_{i-1} * t;  up_0 = 1, up_1 = u, up_i = up_{i-1} * u;
+                    E_i = (C(d, i) * tp_i) * up_{d-i}, i = 1..d (P0 = 0: reference curves/bezier.py:92-113).  At t = 0 every E_i is
+                    exactly 0; at t = 1, E_d is exactly 1 and the others exactly 0 (the shortcut rows of curves/base.py:102-106).
+                    The binomials are exact fp32 constants up to d = 26 (the kernels serve d <= 16).
+      'POLYNOMIAL'  E_1 = t, E_i = E_{i-1} * t (the lines of pe_phi, csrc/events.hip; curves/polynomial.py:55-58 up to the rounding
+                    of pow)
+      'TABLE'       `table_basis_values(basis_table, t)`: basis_table [S + 1, d] sampled at the knots i / S, interpolated linearly
+                    (e.g. the cubic B-spline: bspline_basis(knots, d + 1), or a frozen learned basis)."""
+    d = int(d)
+    if d < 1:
+        raise ValueError(f'degree must be >= 1, got {d}')
+    if curve_type not in CURVE_EVENT_TYPES:
+        raise ValueError(f'curve_type must be one of {CURVE_EVENT_TYPES}, got {curve_type!r}')
+    if (curve_type == 'TABLE') != (basis_table is not None):
+        raise ValueError("curve_type='TABLE' and basis_table go together")
+    t = times.to(torch.float32)
+    if curve_type == 'TABLE':
+        if basis_table.dim() != 2 or basis_table.shape[1] != d or basis_table.dtype != torch.float32:
+            raise ValueError(f'basis_table must be float32 [samples + 1, {d}], got {tuple(basis_table.shape)} {basis_table.dtype}')
+        return table_basis_values(basis_table.detach().to(t.device), t)
+    if curve_type == 'POLYNOMIAL':
+        cols = [t]
+        for _ in range(1, d):
+            cols.append(cols[-1] * t)
+        return torch.stack(cols, dim=-1)
+    u = 1 - t
+    tp = [t]                                   # tp[i - 1] = t^i
+    for _ in range(1, d):
+        tp.append(tp[-1] * t)
+    up = [torch.ones_like(t), u]               # up[i] = u^i
+    for _ in range(2, d):
+        up.append(up[-1] * u)
+    return torch.stack([(float(math.comb(d, i)) * tp[i - 1]) * up[d - i] for i in range(1, d + 1)], dim=-1)
+
+
+def curve_head_rows(params, up_mask, scale, tile):
+    """The tile rows of FocusLoss.calc_per_event_curves in plain torch (the mirror of mpc_pec_head_rows): params [B, 2d, h, w] (x
+    channels first) -> [B * G, 2d] with rows[(b, cell)][j] = scale * up_y[j], rows[(b, cell)][d + j] = scale * up_x[j], `up` the
+    convex upsampling (`_cvx_upsample`) read at the tile centres (iy * tile + tile // 2, ix * tile + tile // 2) of the 8h x 8w
+    image, or `params` themselves without a mask (h x w is the tile grid then).  The tile centre is never added.  Differentiable."""
+    B, c2, h, w = params.shape
+    d = c2 // 2
+    if up_mask is not None:
+        up = _cvx_upsample(params, up_mask)[:, :, tile // 2::tile, tile // 2::tile]
+    else:
+        up = params
+    up = float(scale) * up
+    G = up.shape[2] * up.shape[3]
+    return torch.cat((up[:, d:], up[:, :d]), dim=1).reshape(B, c2, G).permute(0, 2, 1).reshape(B * G, c2)
+
+
 def basis_table(basis_type, num_basis, samples, basis_network=None, device=None):
     """The table of `table_basis_values` for one of the bases of `basis_values`: its values at the samples + 1 knots i / samples,
     [samples + 1, num_basis] fp32, plain torch and differentiable through `basis_network`.  Training the reference's learned basis

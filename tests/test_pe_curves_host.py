@@ -1,0 +1,231 @@
+"""FocusLoss.calc_per_event_curves, host side: the fp32 basis mirror utils.curve_event_basis against float64, its exact end points,
+the reduction of the definition to the per-event basis warp for polynomial curves, the head-rows mirror, the share of tiles the
+gradient accounting may excuse for every GPU case, the routing rules and the interface's errors.  (GPU side:
+tests/test_gpu_pe_curves.py.)"""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import pe_curves_cases as PC
+from oracle import focus_oracle as O
+
+
+def _times(n, seed):
+    g = torch.Generator().manual_seed(seed)
+    named = torch.tensor([0.0, 1.0, 2.0 ** -20, 1.0 - 2.0 ** -24], dtype=torch.float32)
+    return torch.cat((named, torch.rand(n, generator=g)))
+
+
+@pytest.mark.parametrize('d', [1, 3, 10, 16])
+def test_bezier_mirror_against_float64_bernstein(d):
+    """Every E_i within 2d * 2^-24 * E_i of its float64 value: i - 1 products for tp, 2 (d - i) roundings for u and its powers, 2
+    for the final products -- at most 2d roundings of 2^-24 relative each.  (Measured over 400 000 uniform times: 3.9, 13.9 and
+    21.8 units of 2^-24 at d = 3, 10, 16.)  That count holds in fp32's normal range.  Below it (2^-126) a rounding errs by up to
+    2^-150 ABSOLUTE instead, and an intermediate may underflow altogether: at t = 2^-20, d = 16, tp_8 = 2^-160 is 0 in fp32 while
+    C(16, 8) tp_8 = 2^-146.3 is a subnormal number -- so each of the 2d roundings adds 2^-150, scaled by at most C(d, i), to the
+    bound.  For every value above 2^-100 the bound is the relative one."""
+    from motionpriorcmax_amd.utils import curve_event_basis
+    t = _times(20000, d)
+    got = curve_event_basis(t, d, 'BEZIER')
+    assert got.dtype == torch.float32 and tuple(got.shape) == (t.numel(), d)
+    want = O.bernstein_matrix(t.double().numpy(), d).double()
+    binom = torch.tensor([float(math.comb(d, i)) for i in range(1, d + 1)], dtype=torch.float64)
+    bound = 2 * d * 2.0 ** -24 * want + 2 * d * 2.0 ** -150 * binom
+    err = (got.double() - want).abs()
+    worst = float((err / want.clamp(min=1e-30))[want > 2.0 ** -100].max() / 2.0 ** -24)
+    print(f'd={d}: worst error {worst:.1f} units of 2^-24 (bound {2 * d})')
+    assert (err <= bound).all(), float((err - bound).max())
+    # the end points are exact: the shortcut rows of the reference's curves
+    assert torch.equal(got[0], torch.zeros(d))
+    assert torch.equal(got[1], (torch.arange(d) == d - 1).float())
+
+
+def test_polynomial_and_table_mirrors():
+    """The POLYNOMIAL mirror is the lines of pe_phi (csrc/events.hip), bit for bit: that is what makes the curve kernels equal
+    calc_per_event_basis(basis_type='polynomial') and the fused=False route bitwise.  Against `basis_values(..., 'polynomial')`,
+    which raises t to the power j in one call, it is bit-equal for j = 1 only: an iterated product rounds j - 1 times and pow is
+    not correctly rounded either (the figures are printed: a few units of 2^-24 on a minority of the times) -- so the higher
+    orders are held to (j - 1) roundings of 2^-24 plus one unit in the last place (2^-23) for pow, relative."""
+    from motionpriorcmax_amd.utils import curve_event_basis, basis_values, table_basis_values
+    t = _times(5000, 1)
+    tr = torch.tensor([0.41])
+    for d in (1, 3, 9):
+        E, Er = curve_event_basis(t, d, 'POLYNOMIAL'), curve_event_basis(tr, d, 'POLYNOMIAL')
+        # the lines of pe_phi: a = t_ref, c = t; phi_j = a - c; a *= t_ref; c *= t
+        a, c = tr.clone(), t.clone()
+        for j in range(d):
+            assert torch.equal((Er - E)[:, j], a - c)
+            a, c = a * tr, c * t
+        Pw, Pr = basis_values(t, d, 'polynomial'), basis_values(tr, d, 'polynomial')
+        assert torch.equal((Er - E)[:, :1], (Pr - Pw)[:, :1]), d
+        j = torch.arange(d, dtype=torch.float64) + 1.5      # (order j + 1: j roundings of the running product, one unit in the last place for pow)
+        for got, want in ((E, Pw), (Er, Pr)):
+            err = (got.double() - want.double()).abs()
+            print(f'd={d}: iterated product against pow: {int((err > 0).sum())} of {err.numel()} differ, worst '
+                  f'{float((err / want.double().clamp(min=1e-30)).max() / 2.0 ** -24):.2f} units of 2^-24')
+            assert (err <= (j + 0.5) * 2.0 ** -24 * want.double() + 2.0 ** -149).all()
+    tab = PC.bspline_table(7)
+    assert torch.equal(curve_event_basis(t, 7, 'TABLE', tab), table_basis_values(tab, t))
+    # the cubic B-spline of 8 control points at 65 knots: a partition of unity with N_0, zero at t = 0, the last one 1 at t = 1
+    assert torch.equal(tab[0], torch.zeros(7)) and torch.equal(tab[-1], (torch.arange(7) == 6).float())
+
+
+def test_definition_reduces_to_the_per_event_basis_warp_for_polynomial_curves():
+    """Same loss and same row gradient in float64: rows [cell][(y, x)][j] ARE the tile coefficients of calc_per_event_basis."""
+    d, t_ref = 3, 0.41
+    shape, B, M, nb, sp = (32, 40), 2, 1500, 5, 4
+    hq, wq = shape[0] // sp, shape[1] // sp
+    cfg = PC.loss_cfg('l2', 'on_flow_to_tref', image_shape=shape)
+    ev, num_pos = O.synth_events(B, M, shape, nb, seed=2, pad_frac=0.1)
+    params = torch.randn(B, 2 * d, hq, wq, generator=torch.Generator().manual_seed(1), dtype=torch.float64) * 2
+    r = PC.definition(cfg, ev, num_pos, params, None, t_ref, 'POLYNOMIAL')
+    r['loss'].backward()
+    # the same coefficients on a dense grid, y channels first, at the tile centres
+    grid = torch.zeros(B, 1, 2 * d, *shape, dtype=torch.float64)
+    grid[:, 0, :, sp // 2::sp, sp // 2::sp] = torch.cat((params[:, d:], params[:, :d]), dim=1)
+    grid.requires_grad_(True)
+    lo, _, mo = O.FocusLossOracle(**cfg).calc_per_event_basis(grid, t_ref, {'events': ev.double(), 'num_pos_events': num_pos}, d, 'polynomial')
+    lo.backward()
+    assert abs(float(lo.detach()) - float(r['loss'].detach())) <= 1e-12 * abs(float(lo.detach()))
+    assert (mo['iwes'].reshape(r['iwes'].shape) - r['iwes']).abs().max() <= 1e-12 * r['iwes'].abs().max()
+    want = grid.grad[:, 0, :, sp // 2::sp, sp // 2::sp].permute(0, 2, 3, 1).reshape(B, hq, wq, 2, d)
+    assert (r['rows'].grad - want).abs().max() <= 1e-10 * want.abs().max()
+
+
+@pytest.mark.parametrize('scale,tile,hw', [(1.0, 4, (3, 4)), (1.25, 4, (4, 4)), (1.0, 8, (2, 3)), (1.0, 2, (2, 2)), (0.25, 16, (2, 4))])
+def test_head_rows_mirror_is_the_upsampled_control_points_at_the_tile_centres(scale, tile, hw):
+    from motionpriorcmax_amd.utils import curve_head_rows
+    from motionpriorcmax_amd.utils.basis import _cvx_upsample
+    g = torch.Generator().manual_seed(tile)
+    d, Bn = 3, 2
+    h, w = hw
+    p = torch.randn(Bn, 2 * d, h, w, generator=g)
+    m = torch.randn(Bn, 576, h, w, generator=g)
+    rows = curve_head_rows(p, m, scale, tile)
+    up = _cvx_upsample(p, m)
+    nty, ntx = 8 * h // tile, 8 * w // tile
+    assert tuple(rows.shape) == (Bn * nty * ntx, 2 * d)
+    r = rows.reshape(Bn, nty, ntx, 2, d)
+    for iy in (0, nty - 1):
+        for ix in (0, ntx // 2, ntx - 1):
+            y, x = iy * tile + tile // 2, ix * tile + tile // 2
+            assert torch.equal(r[:, iy, ix, 0], scale * up[:, d:, y, x]) and torch.equal(r[:, iy, ix, 1], scale * up[:, :d, y, x])
+    # ... and the test definition's own formula (F.unfold) in float64
+    want = PC.rows_of(p.double(), m.double(), scale, tile)
+    assert (r.double() - want).abs().max() <= 1e-5 * want.abs().max()
+    # without a mask the control points are per tile already
+    r0 = curve_head_rows(p, None, scale, tile).reshape(Bn, h, w, 2, d)
+    assert torch.equal(r0[..., 0, :], (scale * p[:, d:]).permute(0, 2, 3, 1)) and torch.equal(r0[..., 1, :], (scale * p[:, :d]).permute(0, 2, 3, 1))
+
+
+@pytest.mark.parametrize('name', list(PC.CASES))
+def test_the_accounting_excuses_a_minority_of_the_tiles(name):
+    """From the definition's positions alone, before anything runs on a GPU: the explained share of every case is below the 25 %
+    cap of assert_accountable."""
+    cfg, ev, num_pos, *_ = PC.case_inputs(name)
+    ref = PC.reference(name)
+    tiles, _ = PC.explained_tiles(cfg, ev, num_pos, ref['warped'], ref['iwes'])
+    share = float(tiles.float().mean())
+    print(f'{name}: explained share {100 * share:.2f} %')
+    assert share < 0.25
+    assert np.isfinite(ref['loss']) and float(ref['g_rows'].abs().max()) > 0
+    # some events leave the image, most stay
+    w = ref['warped'][:, 0]
+    out = ((w[..., 0] < 0) | (w[..., 0] > PC.SHAPE[0]) | (w[..., 1] < 0) | (w[..., 1] > PC.SHAPE[1])).float().mean()
+    assert 0 < float(out) < 0.5
+
+
+def _loss(**over):
+    from motionpriorcmax_amd import LossFactory
+    return LossFactory.get_loss_calculator('FOCUS', PC.loss_cfg(**over))
+
+
+def test_every_rule_raises_a_value_error_that_names_it():
+    L = _loss()
+    ev, num_pos = O.synth_events(2, 100, PC.SHAPE, PC.NB, seed=1)
+    batch = {'events': ev, 'num_pos_events': num_pos}
+    p = torch.zeros(2, 6, PC.HQ, PC.WQ)
+    p8, m8 = torch.zeros(2, 6, 12, 16), torch.zeros(2, 576, 12, 16)
+    with pytest.raises(ValueError, match='num_tref == 1'):
+        _loss(num_tref=2, scale_iwe_by_dt=False, polarity_aware_batching=False).calc_per_event_curves(p, 0.4, batch)
+    with pytest.raises(ValueError, match=r'\[B, 2d, h, w\]'):
+        L.calc_per_event_curves(torch.zeros(2, 5, PC.HQ, PC.WQ), 0.4, batch)
+    with pytest.raises(ValueError, match='lut_superpixel_size / scale'):
+        L.calc_per_event_curves(p, 0.4, batch, scale=1.25)             # tile 3.2
+    with pytest.raises(ValueError, match='lut_superpixel_size / scale'):
+        L.calc_per_event_curves(p, 0.4, batch, scale=4.0)              # tile 1
+    with pytest.raises(ValueError, match='look-up-table grid'):
+        L.calc_per_event_curves(torch.zeros(2, 6, PC.HQ, PC.WQ + 1), 0.4, batch)
+    with pytest.raises(ValueError, match='look-up-table grid'):
+        L.calc_per_event_curves(torch.zeros(2, 6, 12, 15), 0.4, batch, up_mask=torch.zeros(2, 576, 12, 15))
+    with pytest.raises(ValueError, match='look-up-table grid'):
+        L.calc_per_event_curves(p8, 0.4, batch, up_mask=m8, scale=0.5)   # tile 8: 12 x 16 tiles against 24 x 32 cells
+    with pytest.raises(ValueError, match='up_mask must be'):
+        L.calc_per_event_curves(p8, 0.4, batch, up_mask=torch.zeros(2, 575, 12, 16))
+    with pytest.raises(ValueError, match='curve_type'):
+        L.calc_per_event_curves(p, 0.4, batch, curve_type='LEARNED')
+    with pytest.raises(ValueError, match='go together'):
+        L.calc_per_event_curves(p, 0.4, batch, curve_type='TABLE')
+    with pytest.raises(ValueError, match='go together'):
+        L.calc_per_event_curves(p, 0.4, batch, basis_table=torch.zeros(9, 3))
+    with pytest.raises(ValueError, match='basis_table must be'):
+        L.calc_per_event_curves(p, 0.4, batch, curve_type='TABLE', basis_table=torch.zeros(9, 4))
+    with pytest.raises(ValueError, match='samples'):
+        L.calc_per_event_curves(torch.zeros(3, 6, PC.HQ, PC.WQ), 0.4, batch)
+    from motionpriorcmax_amd.utils import curve_event_basis
+    with pytest.raises(ValueError, match='degree'):
+        curve_event_basis(torch.zeros(3), 0, 'BEZIER')
+    with pytest.raises(ValueError, match='curve_type'):
+        curve_event_basis(torch.zeros(3), 2, 'DCT')
+    with pytest.raises(ValueError, match='go together'):
+        curve_event_basis(torch.zeros(3), 2, 'TABLE')
+
+
+def test_routing(monkeypatch):
+    """fused=True runs ops.PerEventCurvesFn where the library serves the case; fused=False, and whatever mpc_pec_supported refuses
+    (d > 16, a table past its limit) or cannot read (a CPU table beside GPU events), takes the existing per-event nodes with phi
+    [B, M, d] from the mirror."""
+    from motionpriorcmax_amd import ops
+    L = _loss(smooth_weight=0.0)
+    ev, num_pos = O.synth_events(2, 50, PC.SHAPE, PC.NB, seed=1)
+    batch = {'events': ev, 'num_pos_events': num_pos}
+    seen = []
+
+    class Fused:
+        @staticmethod
+        def apply(params, up_mask, events, t_ref, phim, cfg, num_pos, offsets, curve_type, table, scale, tile):
+            seen.append(('fused', curve_type, tile, params.shape[1] // 2))
+            z = torch.zeros(())
+            return z, z, z, torch.zeros(2, 2, *PC.SHAPE)
+
+    class Unfused:
+        @staticmethod
+        def apply(c_rows, events, phi, t_ref, cfg, num_pos, offsets=None):
+            seen.append(('unfused', tuple(c_rows.shape), tuple(phi.shape)))
+            return torch.zeros(()), torch.zeros(2, 2, *PC.SHAPE)
+
+    asked = []
+
+    def supported(cfg, events, num_pos, d, curve_type, samples=0):
+        asked.append((d, curve_type, samples))
+        return 0 if (d > 16 or (samples + 1) * d > 8192) else 3
+
+    monkeypatch.setattr(ops, 'PerEventCurvesFn', Fused)
+    monkeypatch.setattr(ops, 'PerEventBasisFocusFn', Unfused)
+    monkeypatch.setattr(ops, 'pec_supported', supported)
+    G = PC.HQ * PC.WQ
+    L.calc_per_event_curves(torch.zeros(2, 20, PC.HQ, PC.WQ), 0.4, batch)
+    assert seen[-1] == ('fused', 'BEZIER', 4, 10)
+    L.calc_per_event_curves(torch.zeros(2, 20, PC.HQ, PC.WQ), 0.4, batch, fused=False)
+    assert seen[-1] == ('unfused', (2 * G, 20), (2, 50, 10))
+    L.calc_per_event_curves(torch.zeros(2, 34, PC.HQ, PC.WQ), 0.4, batch)                     # d = 17
+    assert seen[-1] == ('unfused', (2 * G, 34), (2, 50, 17)) and asked[-1] == (17, 'BEZIER', 0)
+    L.calc_per_event_curves(torch.zeros(2, 6, PC.HQ, PC.WQ), 0.4, batch, curve_type='TABLE', basis_table=torch.zeros(4097, 3))
+    assert seen[-1][0] == 'unfused' and asked[-1] == (3, 'TABLE', 4096)
+    L.calc_per_event_curves(torch.zeros(2, 6, PC.HQ, PC.WQ), 0.4, batch, curve_type='TABLE', basis_table=torch.zeros(65, 3))
+    assert seen[-1] == ('fused', 'TABLE', 4, 3)
+    # the library itself refuses CPU events (no launch, no answer): nothing is served
+    monkeypatch.undo()
+    assert ops.pec_supported(L._cfg, ev, num_pos, 10, 'BEZIER') == 0

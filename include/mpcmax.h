@@ -748,6 +748,35 @@ int mpc_corr_pyramid_fwd(const mpc_corr_desc *desc, int D, const float *fmap1, c
 int mpc_corr_pyramid_bwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, float *grad_fmap1,
                          float *grad_fmap2, void *ws, void *stream);
 
+/* Same extension, several references (additive, still version 107): the events-plus-frames pyramid of the reference's default model.
+ * Reference: corr.py:221-225 (CorrComputation.__add__: the flat target list is the concatenation of the references' targets, events
+ * then frames in raft.py:131-144), corr.py:246-260 (_corr_dot_prod_M_to_N), corr.py:282-302 (the merged volume, pooled).
+ *   reference r: fmap1[r] [B][D][h][w], fmap2[r] [n_r][B][D][h][w], n_r = first_target[r + 1] - first_target[r] >= 1; flat target
+ *   t = first_target[r] + k is target k of reference r; first_target[0] = 0, first_target[R] = desc->T.  All references share B, D,
+ *   h, w.  `desc` describes the merged pyramid exactly as above (within a level the slots of one reference are contiguous):
+ *   level_l[slot][b*h*w + i][j] = (sum_c fmap1[ref(t)][b][c][i] * P_l(fmap2[ref(t)][k][b])[c][j]) / sqrt(D).
+ * The feature maps are read where they lie (no concatenated copy on the device) and grad_fmap1[r] / grad_fmap2[r]
+ * (mpc_corr_pyramid_multi_bwd only; NULL drops that gradient, a reference with both NULL launches nothing of its own) are written
+ * straight into their own tensors, every element by a kernel.  Launches: those of the single-reference call of the merged target list -- the forward one
+ * GEMM after the pools, the backward at most one grad_fmap1 GEMM (over reference, split, sample, tile), one reduce, one gP GEMM, one
+ * gather.  Every reference keeps the k split of the single-reference problem of that reference alone: the call equals the R
+ * single-reference calls bit for bit (levels sliced by slot range, gradients per reference).
+ * mpc_corr_pyramid_multi_workspace_bytes: the sum of mpc_corr_pyramid_workspace_bytes over the references taken alone.
+ * Limits: those above on the merged list, and R in [1, MPC_CORR_MAX_REFS] (else MPC_E_UNSUPPORTED; the per-reference plans travel
+ * to the kernels by value); a first_target that does not rise from 0 to desc->T: MPC_E_SHAPE.
+ * mpc_corr_pyramid_multi_supported: these checks on the host alone.  */
+#define MPC_CORR_MAX_REFS 4
+typedef struct mpc_corr_refs {
+    int32_t R;
+    int32_t first_target[MPC_CORR_MAX_REFS + 1];
+    const float *fmap1[MPC_CORR_MAX_REFS], *fmap2[MPC_CORR_MAX_REFS];
+    float *grad_fmap1[MPC_CORR_MAX_REFS], *grad_fmap2[MPC_CORR_MAX_REFS];      /* mpc_corr_pyramid_multi_bwd only */
+} mpc_corr_refs;
+long long mpc_corr_pyramid_multi_workspace_bytes(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, int backward);
+int mpc_corr_pyramid_multi_supported(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs);
+int mpc_corr_pyramid_multi_fwd(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream);
+int mpc_corr_pyramid_multi_bwd(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream);
+
 /* ---- the ground-truth flow targets of the EVIMO2 / MultiFlow configurations (what mpc_val_metrics takes as flow_gt / flow_valid)
  * from the raw multi-step flow, as one launch.
  * Reference: src/loader/evimo2/datasubset.py:171-188 (mode 0), src/loader/multiflow/sample.py:108-139 with downsample=True (mode 1).

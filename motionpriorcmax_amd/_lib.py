@@ -84,6 +84,15 @@ class CorrDesc(ctypes.Structure):
                 ('level', ctypes.c_void_p * CORR_MAX_LEVELS), ('grad_level', ctypes.c_void_p * CORR_MAX_LEVELS)]
 
 
+CORR_MAX_REFS = 4                                       # include/mpcmax.h: MPC_CORR_MAX_REFS
+
+
+class CorrRefs(ctypes.Structure):
+    """include/mpcmax.h: struct mpc_corr_refs (the references of mpc_corr_pyramid_multi_*)."""
+    _fields_ = [('R', ctypes.c_int32), ('first_target', ctypes.c_int32 * (CORR_MAX_REFS + 1))] + \
+               [(k, ctypes.c_void_p * CORR_MAX_REFS) for k in ('fmap1', 'fmap2', 'grad_fmap1', 'grad_fmap2')]
+
+
 TARGETS_EVIMO2, TARGETS_MULTIFLOW = 0, 1        # include/mpcmax.h: mpc_targets_shape.mode
 
 
@@ -99,6 +108,7 @@ VAL_MULTI_KEYS = ('epe_multi', 'ae_multi', 'T3PE', 'TEPE', 'TAE')          # the
 
 vp, i32, i64, f32, cint = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_int
 sp, fb, vsp, isp, wsp, cdp, tsp = (ctypes.POINTER(t) for t in (Shape, FocusBuffers, VoxShape, IngestShape, WindowShape, CorrDesc, TargetsShape))
+crp = ctypes.POINTER(CorrRefs)
 fsp, esp, rsp, vlp = (ctypes.POINTER(t) for t in (FlowShape, ErrShape, ReprShape, ValShape))
 
 # The whole binding: every export of include/mpcmax.h -> (restype, argtypes), in the header's order.  lib() applies the table and
@@ -199,6 +209,10 @@ SIGNATURES = {
     'mpc_corr_pyramid_supported': (cint, [cdp, cint]),
     'mpc_corr_pyramid_fwd': (cint, [cdp, cint] + [vp] * 4),
     'mpc_corr_pyramid_bwd': (cint, [cdp, cint] + [vp] * 6),
+    'mpc_corr_pyramid_multi_workspace_bytes': (ctypes.c_longlong, [cdp, cint, crp, cint]),
+    'mpc_corr_pyramid_multi_supported': (cint, [cdp, cint, crp]),
+    'mpc_corr_pyramid_multi_fwd': (cint, [cdp, cint, crp, vp, vp]),
+    'mpc_corr_pyramid_multi_bwd': (cint, [cdp, cint, crp, vp, vp]),
     'mpc_flow_targets_supported': (cint, [tsp]),
     'mpc_flow_targets': (cint, [tsp] + [vp] * 6),
     'mpc_dsec_flow_decode': (cint, [vp, vp, vp, i32, i32, i32, vp]),

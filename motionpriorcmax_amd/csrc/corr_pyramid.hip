@@ -23,6 +23,12 @@
 //   k_corr_pyr_gather   grad_fmap2 from the gP_l (their partials in index order, levels ascending); writes every element (0 where
 //                       no level reaches); four x per thread and 16-byte accesses where w % 4 == 0.
 // No atomics, every sum in one fixed order: bitwise reproducible.  Volume offsets are 64-bit.
+// Several references (corr.py:221-225, 246-260: CorrComputation.__add__ / _corr_dot_prod_M_to_N, events then frames): the flat target
+// list is the concatenation of the references' targets, the problem is block-diagonal, and the same launches serve it -- a slot
+// reads the fmap1 / fmap2 of its target's reference where they lie and writes its gradient into that reference's tensors.  Every
+// reference keeps the split (S1, S, kblocks) of the single-reference problem of that reference alone and gemm<2> runs over (reference,
+// split, sample, tile) with k = that reference's (level, slot, j): the call equals the single-reference calls bit for bit.  The
+// single-reference entry points are the same code with one reference.
 #include <algorithm>
 #include <math.h>
 #include "common.h"
@@ -37,13 +43,30 @@
 
 typedef float cp_f32x16 __attribute__((ext_vector_type(16)));
 
-// sub-buffers of the workspace, in floats: P_l (l >= 1), gP_l (backward), split-k partials (backward)
+// sub-buffers of the workspace, in floats: P_l (l >= 1) of all slots, then per reference gP_l (backward) and its split-k partials
 struct cp_plan {
-    long long p_off[MPC_CORR_MAX_LEVELS], gp_off[MPC_CORR_MAX_LEVELS], part_off, total;
+    long long p_off[MPC_CORR_MAX_LEVELS], total;
     int pitch[MPC_CORR_MAX_LEVELS];
-    int D, S, kblocks;                     // grad_fmap1: S ranges of the kblocks k blocks of the concatenation
-    int S1;                                // gP: S1 ranges of the k blocks of i; gP_l is [S1][n_l][B][D][pitch_l]
+    int D;
     float sq;                              // sqrt(D) in fp32, as torch.sqrt(torch.tensor(D).float()) gives it
+};
+
+// one reference: its tensors, its flat targets [t0, t0 + level_n[0]), its slots [slot0[l], slot0[l] + level_n[l]) of level l
+// (contiguous: the targets of a level ascend), and the split of its two backward products
+struct cp_ref {
+    const float *fmap1, *fmap2;
+    float *grad_fmap1, *grad_fmap2;
+    long long gp_off[MPC_CORR_MAX_LEVELS], part_off;
+    int t0, num_levels;
+    int slot0[MPC_CORR_MAX_LEVELS], level_n[MPC_CORR_MAX_LEVELS];
+    int S, kblocks;                        // grad_fmap1: S ranges of the kblocks k blocks of the concatenation
+    int S1;                                // gP: S1 ranges of the k blocks of i; gP_l is [S1][level_n[l]][B][D][pitch_l]
+};
+
+struct cp_refs {
+    int R;
+    unsigned char ref_of[MPC_CORR_MAX_TARGETS];        // flat target -> reference
+    cp_ref r[MPC_CORR_MAX_REFS];
 };
 
 struct cp_operand {
@@ -174,19 +197,22 @@ __device__ __forceinline__ void cp_write(const cp_f32x16 (&acc)[2][2], float *c,
 
 __device__ __forceinline__ bool cp_al16(const void *p) { return (((uintptr_t)p) & 15) == 0; }
 
-// the operand P_l of (level l, slot k, sample b): fmap2 itself at level 0, the workspace above
-__device__ __forceinline__ const float *cp_pooled(const mpc_corr_desc &D, const cp_plan &P, const float *fmap2, const float *ws, int l,
+// the operand P_l of (level l, slot k, sample b): the fmap2 of the slot's reference itself at level 0, the workspace above
+__device__ __forceinline__ const float *cp_pooled(const mpc_corr_desc &D, const cp_plan &P, const cp_refs &M, const float *ws, int l,
                                                   int k, int b, long long &ld) {
     const long long hw = (long long)D.h * D.w;
-    if (l == 0) { ld = hw; return fmap2 + ((long long)D.level_target[0][k] * D.B + b) * P.D * hw; }
+    if (l == 0) {
+        const int t = D.level_target[0][k];
+        const cp_ref &R = M.r[MPC_IDX(M.ref_of[MPC_IDX(t, D.T)], M.R)];
+        ld = hw;
+        return R.fmap2 + ((long long)MPC_IDX(t - R.t0, R.level_n[0]) * D.B + b) * P.D * hw;
+    }
     ld = P.pitch[l];
     return ws + P.p_off[l] + ((long long)k * D.B + b) * P.D * ld;
 }
 
 template <int MODE>
-__global__ __launch_bounds__(256) void k_corr_pyr_gemm(const mpc_corr_desc D, const cp_plan P, const float *__restrict__ fmap1,
-                                                       const float *__restrict__ fmap2, float *__restrict__ ws,
-                                                       float *__restrict__ out) {
+__global__ __launch_bounds__(256) void k_corr_pyr_gemm(const mpc_corr_desc D, const cp_plan P, const cp_refs M, float *__restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) float s_cp[];          // [CP_TILE] A | [CP_TILE] B
     float *sA = s_cp, *sB = s_cp + CP_TILE;
     const long long hw = (long long)D.h * D.w;
@@ -199,14 +225,14 @@ __global__ __launch_bounds__(256) void k_corr_pyr_gemm(const mpc_corr_desc D, co
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
     long long bid = blockIdx.x;
-    if (MODE == 0 || MODE == 1) {
-        // (level, slot, sample, tile m, tile n), n fastest.  forward: m = i, n = j, k = c; gP: m = c, n = j, k = i
-        const int tm = MODE == 0 ? (int)((hw + CP_BM - 1) / CP_BM) : (Dm + CP_BM - 1) / CP_BM;
-        int l = 0, tn = 1, s = 0;
+    if (MODE == 0) {
+        // (level, slot, sample, tile m, tile n), n fastest: m = i, n = j, k = c
+        const int tm = (int)((hw + CP_BM - 1) / CP_BM);
+        int l = 0, tn = 1;
         for (; l < D.num_levels; ++l) {
             tn = (D.level_h[l] * D.level_w[l] + CP_BM - 1) / CP_BM;
-            const long long per = (long long)D.level_n[l] * D.B * tm * tn, cnt = MODE == 0 ? per : D.grad_level[l] ? per * P.S1 : 0;
-            if (bid < cnt) { s = (int)(bid / per); bid -= s * per; break; }
+            const long long cnt = (long long)D.level_n[l] * D.B * tm * tn;
+            if (bid < cnt) break;
             bid -= cnt;
         }
         MPC_EXPECT(l < D.num_levels);
@@ -215,63 +241,98 @@ __global__ __launch_bounds__(256) void k_corr_pyr_gemm(const mpc_corr_desc D, co
         const int im = (int)(bid % tm); bid /= tm;
         const int b = (int)(bid % D.B), k = (int)(bid / D.B);
         const int N = D.level_h[l] * D.level_w[l], m0 = im * CP_BM, n0 = in * CP_BM;
-        if (MODE == 0) {
-            long long ldb;
-            const float *pb = cp_pooled(D, P, fmap2, ws, l, k, b, ldb);
-            const cp_operand A = {fmap1 + (long long)b * Dm * hw + m0, hw, (int)(hw - m0), (hw & 3) == 0 && cp_al16(fmap1)};
-            const cp_operand B = {pb + n0, ldb, N - n0, (ldb & 3) == 0 && cp_al16(pb)};
-            cp_gemm_range<false, false>(acc, A, B, 0, Dm, sA, sB);
-            const long long row0 = (long long)k * D.B * hw + (long long)b * hw + m0;
-            const long long ext = ((long long)D.level_n[l] * D.B * hw - row0) * N - n0;
-            cp_write(acc, const_cast<float *>(D.level[l]) + row0 * N + n0, N, (int)(hw - m0), N - n0, true, P.sq, ext);
-        } else {
-            const float *g = D.grad_level[l] + ((long long)k * D.B + b) * hw * N;
-            const cp_operand A = {fmap1 + ((long long)b * Dm + m0) * hw, hw, Dm - m0, (hw & 3) == 0 && cp_al16(fmap1)};
-            const cp_operand B = {g + n0, N, N - n0, (N & 3) == 0 && cp_al16(g)};
-            const int nkb = (int)((hw + CP_BK - 1) / CP_BK);
-            const int kb0 = (int)((long long)s * nkb / P.S1), kb1 = (int)((long long)(s + 1) * nkb / P.S1);
-            cp_gemm_range<true, false>(acc, A, B, kb0 * CP_BK, min((long long)kb1 * CP_BK, hw), sA, sB);
-            const long long ld = P.pitch[l], row0 = (((long long)s * D.level_n[l] + k) * D.B + b) * Dm + m0;
-            const long long ext = ((long long)P.S1 * D.level_n[l] * D.B * Dm - row0) * ld - n0;
-            cp_write(acc, ws + P.gp_off[l] + row0 * ld + n0, ld, Dm - m0, N - n0, true, P.sq, ext);
+        const float *fmap1 = M.r[MPC_IDX(M.ref_of[MPC_IDX(D.level_target[l][MPC_IDX(k, D.level_n[l])], D.T)], M.R)].fmap1;
+        long long ldb;
+        const float *pb = cp_pooled(D, P, M, ws, l, k, b, ldb);
+        const cp_operand A = {fmap1 + (long long)b * Dm * hw + m0, hw, (int)(hw - m0), (hw & 3) == 0 && cp_al16(fmap1)};
+        const cp_operand B = {pb + n0, ldb, N - n0, (ldb & 3) == 0 && cp_al16(pb)};
+        cp_gemm_range<false, false>(acc, A, B, 0, Dm, sA, sB);
+        const long long row0 = (long long)k * D.B * hw + (long long)b * hw + m0;
+        const long long ext = ((long long)D.level_n[l] * D.B * hw - row0) * N - n0;
+        cp_write(acc, const_cast<float *>(D.level[l]) + row0 * N + n0, N, (int)(hw - m0), N - n0, true, P.sq, ext);
+    } else if (MODE == 1) {
+        // (level with a cotangent, reference that wants grad_fmap2, split, slot of the reference, sample, tile m, tile n), n fastest:
+        // m = c, n = j, k = i in the reference's own S1 ranges
+        const int tm = (Dm + CP_BM - 1) / CP_BM;
+        int l = 0, tn = 1, s = 0, ri = 0;
+        bool found = false;
+        for (; l < D.num_levels; ++l) {
+            if (!D.grad_level[l]) continue;
+            tn = (D.level_h[l] * D.level_w[l] + CP_BM - 1) / CP_BM;
+            for (ri = 0; ri < M.R; ++ri) {
+                if (!M.r[ri].grad_fmap2 || l >= M.r[ri].num_levels) continue;
+                const long long per = (long long)M.r[ri].level_n[l] * D.B * tm * tn, cnt = per * M.r[ri].S1;
+                if (bid < cnt) { s = (int)(bid / per); bid -= s * per; found = true; break; }
+                bid -= cnt;
+            }
+            if (found) break;
         }
+        MPC_EXPECT(found);
+        if (!found) return;
+        const cp_ref &R = M.r[MPC_IDX(ri, M.R)];
+        const int in = (int)(bid % tn); bid /= tn;
+        const int im = (int)(bid % tm); bid /= tm;
+        const int b = (int)(bid % D.B), kr = (int)(bid / D.B), k = R.slot0[l] + MPC_IDX(kr, R.level_n[l]);
+        const int N = D.level_h[l] * D.level_w[l], m0 = im * CP_BM, n0 = in * CP_BM;
+        const float *g = D.grad_level[l] + ((long long)MPC_IDX(k, D.level_n[l]) * D.B + b) * hw * N;
+        const cp_operand A = {R.fmap1 + ((long long)b * Dm + m0) * hw, hw, Dm - m0, (hw & 3) == 0 && cp_al16(R.fmap1)};
+        const cp_operand B = {g + n0, N, N - n0, (N & 3) == 0 && cp_al16(g)};
+        const int nkb = (int)((hw + CP_BK - 1) / CP_BK);
+        const int kb0 = (int)((long long)s * nkb / R.S1), kb1 = (int)((long long)(s + 1) * nkb / R.S1);
+        cp_gemm_range<true, false>(acc, A, B, kb0 * CP_BK, min((long long)kb1 * CP_BK, hw), sA, sB);
+        const long long ld = P.pitch[l], row0 = (((long long)s * R.level_n[l] + kr) * D.B + b) * Dm + m0;
+        const long long ext = ((long long)R.S1 * R.level_n[l] * D.B * Dm - row0) * ld - n0;
+        cp_write(acc, ws + R.gp_off[l] + row0 * ld + n0, ld, Dm - m0, N - n0, true, P.sq, ext);
     } else {
-        // (split, sample, tile m, tile n), n fastest: m = c, n = i, k = (level, slot, j) in k blocks [kb0, kb1) of the concatenation
+        // (reference that wants grad_fmap1, split, sample, tile m, tile n), n fastest: m = c, n = i, k = (level, slot of the reference, j)
+        // in k blocks [kb0, kb1) of the reference's concatenation
         const int tm = (Dm + CP_BM - 1) / CP_BM, tn = (int)((hw + CP_BM - 1) / CP_BM);
+        int ri = 0;
+        for (; ri < M.R; ++ri) {
+            if (!M.r[ri].grad_fmap1) continue;
+            const long long cnt = (long long)M.r[ri].S * D.B * tm * tn;
+            if (bid < cnt) break;
+            bid -= cnt;
+        }
+        MPC_EXPECT(ri < M.R);
+        if (ri >= M.R) return;
+        const cp_ref &R = M.r[ri];
         const int in = (int)(bid % tn); bid /= tn;
         const int im = (int)(bid % tm); bid /= tm;
         const int b = (int)(bid % D.B), s = (int)(bid / D.B);
         const int m0 = im * CP_BM, n0 = in * CP_BM;
-        const int kb0 = (int)((long long)s * P.kblocks / P.S), kb1 = (int)((long long)(s + 1) * P.kblocks / P.S);
+        const int kb0 = (int)((long long)s * R.kblocks / R.S), kb1 = (int)((long long)(s + 1) * R.kblocks / R.S);
         int first = 0;
-        for (int l = 0; l < D.num_levels; ++l) {
+        for (int l = 0; l < R.num_levels; ++l) {
             if (!D.grad_level[l]) continue;
             const int N = D.level_h[l] * D.level_w[l], nkb = (N + CP_BK - 1) / CP_BK;
-            for (int k = 0; k < D.level_n[l]; ++k, first += nkb) {
+            for (int kr = 0; kr < R.level_n[l]; ++kr, first += nkb) {
                 const int lo = max(kb0, first) - first, hi = min(kb1, first + nkb) - first;
                 if (lo >= hi) continue;
+                const int k = R.slot0[l] + kr;
                 long long lda;
-                const float *pa = cp_pooled(D, P, fmap2, ws, l, k, b, lda);
-                const float *g = D.grad_level[l] + (((long long)k * D.B + b) * hw + n0) * N;
+                const float *pa = cp_pooled(D, P, M, ws, l, k, b, lda);
+                const float *g = D.grad_level[l] + (((long long)MPC_IDX(k, D.level_n[l]) * D.B + b) * hw + n0) * N;
                 const cp_operand A = {pa + (long long)m0 * lda, lda, Dm - m0, (lda & 3) == 0 && cp_al16(pa)};
                 const cp_operand B = {g, N, (int)(hw - n0), (N & 3) == 0 && cp_al16(D.grad_level[l])};
                 cp_gemm_range<true, true>(acc, A, B, lo * CP_BK, min(hi * CP_BK, N), sA, sB);
             }
         }
         const long long row0 = (long long)b * Dm + m0;
-        if (P.S == 1) {
-            cp_write(acc, out + row0 * hw + n0, hw, Dm - m0, (int)(hw - n0), true, P.sq, ((long long)D.B * Dm - row0) * hw - n0);
+        if (R.S == 1) {
+            cp_write(acc, R.grad_fmap1 + row0 * hw + n0, hw, Dm - m0, (int)(hw - n0), true, P.sq, ((long long)D.B * Dm - row0) * hw - n0);
         } else {
             const long long prow0 = (long long)s * D.B * Dm + row0;
-            cp_write(acc, ws + P.part_off + prow0 * hw + n0, hw, Dm - m0, (int)(hw - n0), false, 1.f,
-                     ((long long)P.S * D.B * Dm - prow0) * hw - n0);
+            cp_write(acc, ws + R.part_off + prow0 * hw + n0, hw, Dm - m0, (int)(hw - n0), false, 1.f,
+                     ((long long)R.S * D.B * Dm - prow0) * hw - n0);
         }
     }
 }
 
-// P_l [n_l][B][D][pitch_l] from P_(l-1) (fmap2 [T][B][D][hw] at l = 1): a thread per element, the pad of a row included
-__global__ __launch_bounds__(256) void k_corr_pyr_pool(const mpc_corr_desc D, const cp_plan P, const float *__restrict__ fmap2,
-                                                       float *__restrict__ ws, int l) {
+// P_l [n_l][B][D][pitch_l] from P_(l-1) (the fmap2 [n_r][B][D][hw] of the slot's reference at l = 1): a thread per element, the pad
+// of a row included
+__global__ __launch_bounds__(256) void k_corr_pyr_pool(const mpc_corr_desc D, const cp_plan P, const cp_refs M, float *__restrict__ ws,
+                                                       int l) {
     const int pitch = P.pitch[l], wl = D.level_w[l], N = D.level_h[l] * wl;
     const long long rows = (long long)D.level_n[l] * D.B * P.D, total = rows * pitch;
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -288,7 +349,13 @@ __global__ __launch_bounds__(256) void k_corr_pyr_pool(const mpc_corr_desc D, co
         const int ws_ = D.level_w[l - 1];
         const float *src;
         if (l == 1) {
-            src = fmap2 + (((long long)t * D.B + b) * P.D + c) * ((long long)D.h * D.w);
+            // the reference of target t by selects over the table (uniform reads): a per-thread index into it would cost loads
+            const float *f2 = M.r[0].fmap2;
+            [[maybe_unused]] int nr = M.r[0].level_n[0];           // (the extent of the checked index)
+            int t0 = 0;
+            for (int ri = 1; ri < M.R; ++ri)
+                if (t >= M.r[ri].t0) { f2 = M.r[ri].fmap2; t0 = M.r[ri].t0; nr = M.r[ri].level_n[0]; }
+            src = f2 + (((long long)MPC_IDX(t - t0, nr) * D.B + b) * P.D + c) * ((long long)D.h * D.w);
         } else {
             src = ws + P.p_off[l - 1] + MPC_IDX(((long long)u * D.B + b) * P.D + c, (long long)D.level_n[l - 1] * D.B * P.D) * P.pitch[l - 1];
         }
@@ -299,38 +366,64 @@ __global__ __launch_bounds__(256) void k_corr_pyr_pool(const mpc_corr_desc D, co
     ws[P.p_off[l] + MPC_IDX(e, total)] = v;
 }
 
-__global__ __launch_bounds__(256) void k_corr_pyr_reduce(const cp_plan P, const float *__restrict__ ws, float *__restrict__ out, long long n) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+// grad_fmap1 of every reference whose S > 1 (and that wants it), n = B * D * hw elements and ceil(n / 256) workgroups each (the
+// reference is the workgroup's: its table entry is read once, uniformly): partial_0 + partial_1 + ... / sqrt(D)
+__global__ __launch_bounds__(256) void k_corr_pyr_reduce(const cp_plan P, const cp_refs M, const float *__restrict__ ws, long long n) {
+    const long long per = (n + 255) / 256;
+    long long bid = blockIdx.x;
+    int ri = 0;
+    for (; ri < M.R; ++ri) {
+        if (!M.r[ri].grad_fmap1 || M.r[ri].S <= 1) continue;
+        if (bid < per) break;
+        bid -= per;
+    }
+    MPC_EXPECT(ri < M.R);
+    if (ri >= M.R) return;
+    const cp_ref &R = M.r[ri];
+    const long long e = bid * 256 + threadIdx.x;
     if (e >= n) return;
-    const float *part = ws + P.part_off;
-    float v = part[MPC_IDX(e, n * P.S)];
-    for (int s = 1; s < P.S; ++s) v = v + part[MPC_IDX((long long)s * n + e, n * P.S)];
-    out[e] = v / P.sq;
+    const float *part = ws + R.part_off;
+    float v = part[MPC_IDX(e, n * R.S)];
+    for (int s = 1; s < R.S; ++s) v = v + part[MPC_IDX((long long)s * n + e, n * R.S)];
+    R.grad_fmap1[e] = v / P.sq;
 }
 
+// a thread per element (V of them) of the grad_fmap2 of every reference that wants it, whole workgroups per reference (its table
+// entry is read uniformly)
 template <int V>
-__global__ __launch_bounds__(256) void k_corr_pyr_gather(const mpc_corr_desc D, const cp_plan P, const float *__restrict__ ws,
-                                                         float *__restrict__ grad_fmap2) {
-    const long long hw = (long long)D.h * D.w, total = (long long)D.T * D.B * P.D * hw;
-    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * V;          // V = 4: w % 4 == 0, the V elements share a row
+__global__ __launch_bounds__(256) void k_corr_pyr_gather(const mpc_corr_desc D, const cp_plan P, const cp_refs M, const float *__restrict__ ws) {
+    const long long hw = (long long)D.h * D.w;
+    long long bid = blockIdx.x;
+    int ri = 0;
+    for (; ri < M.R; ++ri) {
+        if (!M.r[ri].grad_fmap2) continue;
+        const long long cnt = ((long long)M.r[ri].level_n[0] * D.B * P.D * hw / V + 255) / 256;
+        if (bid < cnt) break;
+        bid -= cnt;
+    }
+    MPC_EXPECT(ri < M.R);
+    if (ri >= M.R) return;
+    const cp_ref &R = M.r[ri];
+    const long long total = (long long)R.level_n[0] * D.B * P.D * hw;
+    const long long e = (bid * 256 + threadIdx.x) * V;                            // V = 4: w % 4 == 0, the V elements share a row
     if (e >= total) return;
-    const long long row = e / hw;                      // (t * B + b) * D + c
+    const long long row = e / hw;                      // (k * B + b) * D + c, k the reference's own target
     const int pix = (int)(e - row * hw), y = pix / D.w, x = pix - y * D.w;
     const long long tb = row / P.D;
-    const int c = (int)(row - tb * P.D), b = (int)(tb % D.B), t = (int)(tb / D.B);
+    const int c = (int)(row - tb * P.D), b = (int)(tb % D.B), t = R.t0 + (int)(tb / D.B);
     float v[V];
 #pragma unroll
     for (int u = 0; u < V; ++u) v[u] = 0.f;
     float wgt = 1.f;
-    for (int l = 0; l < D.num_levels; ++l, wgt *= 0.25f) {
+    for (int l = 0; l < R.num_levels; ++l, wgt *= 0.25f) {
         if (!D.grad_level[l]) continue;
         int k = -1;
-        for (int u = 0; u < D.level_n[l]; ++u) if (D.level_target[l][u] == t) k = u;
+        for (int u = 0; u < R.level_n[l]; ++u) if (D.level_target[l][MPC_IDX(R.slot0[l] + u, D.level_n[l])] == t) k = u;
         const int yl = y >> l, wl = D.level_w[l];
         if (k < 0 || yl >= D.level_h[l]) continue;
-        const long long rows = (long long)D.level_n[l] * D.B * P.D;
-        for (int s = 0; s < P.S1; ++s) {
-            const float *gp = ws + P.gp_off[l] + MPC_IDX(s * rows + ((long long)k * D.B + b) * P.D + c, rows * P.S1) * P.pitch[l] + yl * wl;
+        const long long rows = (long long)R.level_n[l] * D.B * P.D;
+        for (int s = 0; s < R.S1; ++s) {
+            const float *gp = ws + R.gp_off[l] + MPC_IDX(s * rows + ((long long)k * D.B + b) * P.D + c, rows * R.S1) * P.pitch[l] + yl * wl;
             if (V == 4 && l == 0) {
                 const float4 q = *reinterpret_cast<const float4 *>(gp + MPC_IDX(x, wl - 3));
                 v[0] = v[0] + q.x; v[1 % V] = v[1 % V] + q.y; v[2 % V] = v[2 % V] + q.z; v[3 % V] = v[3 % V] + q.w;
@@ -343,8 +436,9 @@ __global__ __launch_bounds__(256) void k_corr_pyr_gather(const mpc_corr_desc D, 
             }
         }
     }
-    if (V == 4) *reinterpret_cast<float4 *>(grad_fmap2 + e) = make_float4(v[0], v[1 % V], v[2 % V], v[3 % V]);
-    else grad_fmap2[e] = v[0];
+    float *out = R.grad_fmap2 + MPC_IDX(e, total - (V - 1));
+    if (V == 4) *reinterpret_cast<float4 *>(out) = make_float4(v[0], v[1 % V], v[2 % V], v[3 % V]);
+    else out[0] = v[0];
 }
 
 // ---- host
@@ -380,37 +474,96 @@ static int cp_check(const char *who, const mpc_corr_desc *D, int Dm) {
     return 0;
 }
 
-// `all_levels`: size for a cotangent at every level (the workspace query); else by desc->grad_level
-static cp_plan cp_make_plan(const mpc_corr_desc *D, int Dm, int backward, bool all_levels) {
+static int cp_check_refs(const char *who, const mpc_corr_desc *D, const mpc_corr_refs *refs) {
+    if (!refs) { mpc_set_error("%s: null references", who); return MPC_E_NULL; }
+    if (refs->R < 1 || refs->R > MPC_CORR_MAX_REFS) {
+        mpc_set_error("%s: %d references, 1 to %d are served", who, refs->R, MPC_CORR_MAX_REFS); return MPC_E_UNSUPPORTED;
+    }
+    bool ok = refs->first_target[0] == 0 && refs->first_target[refs->R] == D->T;
+    for (int r = 0; r < refs->R; ++r) ok = ok && refs->first_target[r] < refs->first_target[r + 1];
+    if (!ok) {
+        mpc_set_error("%s: first_target does not cover the %d targets: it must rise from 0 to T, a target or more per reference", who, D->T);
+        return MPC_E_SHAPE;
+    }
+    return 0;
+}
+
+// The workspace layout and every reference's split.  A reference's split is that of the single-reference problem of the reference
+// alone, from its sizes only (S1: as if every level had a cotangent), so that equal calls -- and the single-reference call of the
+// same reference -- sum in equal order.  `all_levels`: size for a cotangent at every level (the workspace query); else by
+// desc->grad_level.  Pointers are not set here.
+static cp_plan cp_make_plan(const mpc_corr_desc *D, int Dm, const mpc_corr_refs *refs, int backward, bool all_levels, cp_refs &M) {
     cp_plan P = {};
+    M = {};
     const long long hw = (long long)D->h * D->w;
-    P.D = Dm; P.S = 1; P.S1 = 1;
+    P.D = Dm;
     P.sq = sqrtf((float)Dm);
     long long off = 0;
     for (int l = 0; l < D->num_levels; ++l) {
         P.pitch[l] = (D->level_h[l] * D->level_w[l] + 3) / 4 * 4;
         if (l >= 1) { P.p_off[l] = off; off += (long long)D->level_n[l] * D->B * Dm * P.pitch[l]; }
     }
-    if (backward) {
-        // the two backward products have few tiles at batch 1: split k until about three workgroups per CU, at least four k
-        // blocks each -- from the sizes alone (S1: as if every level had a cotangent), so that equal calls sum in equal order
-        long long tiles1 = 0;
-        for (int l = 0; l < D->num_levels; ++l)
-            tiles1 += (long long)D->level_n[l] * std::max(D->B, 1) * ((Dm + CP_BM - 1) / CP_BM) * ((D->level_h[l] * D->level_w[l] + CP_BM - 1) / CP_BM);
-        P.S1 = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(CP_MAX_SPLIT, (768 + tiles1 - 1) / tiles1), (hw + CP_BK - 1) / CP_BK / 4));
+    M.R = refs->R;
+    for (int r = 0; r < refs->R; ++r) {
+        cp_ref &R = M.r[r];
+        const int t0 = refs->first_target[r], t1 = refs->first_target[r + 1];
+        R.t0 = t0; R.S = 1; R.S1 = 1;
+        for (int t = t0; t < t1; ++t) M.ref_of[t] = (unsigned char)r;
         for (int l = 0; l < D->num_levels; ++l) {
-            P.gp_off[l] = off; off += (long long)P.S1 * D->level_n[l] * D->B * Dm * P.pitch[l];
-            if (all_levels || D->grad_level[l]) P.kblocks += D->level_n[l] * ((D->level_h[l] * D->level_w[l] + CP_BK - 1) / CP_BK);
+            int first = -1, n = 0;
+            for (int s = 0; s < D->level_n[l]; ++s) {
+                const int t = D->level_target[l][s];
+                if (t >= t0 && t < t1) { if (first < 0) first = s; ++n; }
+            }
+            R.slot0[l] = std::max(first, 0); R.level_n[l] = n;
+            if (n > 0) R.num_levels = l + 1;
+        }
+        if (!backward) continue;
+        // the two backward products have few tiles at batch 1: split k until about three workgroups per CU, at least four k
+        // blocks each
+        long long tiles1 = 0;
+        for (int l = 0; l < R.num_levels; ++l)
+            tiles1 += (long long)R.level_n[l] * std::max(D->B, 1) * ((Dm + CP_BM - 1) / CP_BM) * ((D->level_h[l] * D->level_w[l] + CP_BM - 1) / CP_BM);
+        R.S1 = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(CP_MAX_SPLIT, (768 + tiles1 - 1) / tiles1), (hw + CP_BK - 1) / CP_BK / 4));
+        for (int l = 0; l < R.num_levels; ++l) {
+            R.gp_off[l] = off; off += (long long)R.S1 * R.level_n[l] * D->B * Dm * P.pitch[l];
+            if (all_levels || D->grad_level[l]) R.kblocks += R.level_n[l] * ((D->level_h[l] * D->level_w[l] + CP_BK - 1) / CP_BK);
         }
         const long long tiles = (long long)std::max(D->B, 1) * ((Dm + CP_BM - 1) / CP_BM) * ((hw + CP_BM - 1) / CP_BM);
         long long S = std::min<long long>(CP_MAX_SPLIT, (768 + tiles - 1) / tiles);
-        S = std::max<long long>(1, std::min<long long>(S, P.kblocks / 4));
-        P.S = (int)S;
-        P.part_off = off;
-        if (P.S > 1) off += (long long)P.S * D->B * Dm * hw;
+        S = std::max<long long>(1, std::min<long long>(S, R.kblocks / 4));
+        R.S = (int)S;
+        R.part_off = off;
+        if (R.S > 1) off += (long long)R.S * D->B * Dm * hw;
     }
     P.total = off;
     return P;
+}
+
+static mpc_corr_refs cp_one_ref(const mpc_corr_desc *D, const float *fmap1, const float *fmap2, float *grad_fmap1, float *grad_fmap2) {
+    mpc_corr_refs refs = {};
+    refs.R = 1;
+    refs.first_target[1] = D ? D->T : 0;
+    refs.fmap1[0] = fmap1; refs.fmap2[0] = fmap2; refs.grad_fmap1[0] = grad_fmap1; refs.grad_fmap2[0] = grad_fmap2;
+    return refs;
+}
+
+// the descriptor of reference r alone: what the single-reference entry points take for it
+static mpc_corr_desc cp_ref_desc(const mpc_corr_desc *D, const cp_refs &M, int r) {
+    mpc_corr_desc d = *D;
+    const cp_ref &R = M.r[r];
+    d.T = R.level_n[0]; d.num_levels = R.num_levels;
+    for (int l = 0; l < MPC_CORR_MAX_LEVELS; ++l) {
+        d.level_n[l] = l < R.num_levels ? R.level_n[l] : 0;
+        for (int s = 0; s < MPC_CORR_MAX_TARGETS; ++s)
+            d.level_target[l][s] = l < R.num_levels && s < R.level_n[l] ? (uint8_t)(D->level_target[l][R.slot0[l] + s] - R.t0) : 0;
+    }
+    return d;
+}
+
+static long long cp_workspace_bytes(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, int backward) {
+    cp_refs M;
+    return std::max<long long>(16, cp_make_plan(desc, D, refs, backward, true, M).total * (long long)sizeof(float));
 }
 
 extern "C" int mpc_corr_pyramid_supported(const mpc_corr_desc *desc, int D) { return cp_check(__func__, desc, D); }
@@ -418,77 +571,141 @@ extern "C" int mpc_corr_pyramid_supported(const mpc_corr_desc *desc, int D) { re
 extern "C" long long mpc_corr_pyramid_workspace_bytes(const mpc_corr_desc *desc, int D, int backward) {
     const int rc = cp_check(__func__, desc, D);
     if (rc) return rc;
-    return std::max<long long>(16, cp_make_plan(desc, D, backward, true).total * (long long)sizeof(float));
+    const mpc_corr_refs one = cp_one_ref(desc, nullptr, nullptr, nullptr, nullptr);
+    return cp_workspace_bytes(desc, D, &one, backward);
 }
 
-static int cp_pool_levels(const mpc_corr_desc *desc, const cp_plan &P, const float *fmap2, float *ws, hipStream_t st) {
+extern "C" int mpc_corr_pyramid_multi_supported(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs) {
+    const int rc = cp_check(__func__, desc, D);
+    return rc ? rc : cp_check_refs(__func__, desc, refs);
+}
+
+// the sum of what the single-reference query gives for every reference alone (each at least 16 bytes); the layout needs no more
+extern "C" long long mpc_corr_pyramid_multi_workspace_bytes(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, int backward) {
+    int rc = cp_check(__func__, desc, D);
+    if (!rc) rc = cp_check_refs(__func__, desc, refs);
+    if (rc) return rc;
+    cp_refs M;
+    cp_make_plan(desc, D, refs, 0, true, M);
+    long long bytes = 0;
+    for (int r = 0; r < refs->R; ++r) {
+        const mpc_corr_desc d = cp_ref_desc(desc, M, r);
+        const mpc_corr_refs one = cp_one_ref(&d, nullptr, nullptr, nullptr, nullptr);
+        bytes += cp_workspace_bytes(&d, D, &one, backward);
+    }
+    return bytes;
+}
+
+static int cp_pool_levels(const mpc_corr_desc *desc, const cp_plan &P, const cp_refs &M, float *ws, hipStream_t st) {
     for (int l = 1; l < desc->num_levels; ++l) {
         const long long total = (long long)desc->level_n[l] * desc->B * P.D * P.pitch[l];
-        MPC_LAUNCH(k_corr_pyr_pool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *desc, P, fmap2, ws, l);
+        MPC_LAUNCH(k_corr_pyr_pool, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, *desc, P, M, ws, l);
     }
     return 0;
-}
-
-static long long cp_gemm_blocks(const mpc_corr_desc *D, int Dm, int mode, int split) {
-    const long long hw = (long long)D->h * D->w, tm = mode == 0 ? (hw + CP_BM - 1) / CP_BM : (Dm + CP_BM - 1) / CP_BM;
-    long long nb = 0;
-    for (int l = 0; l < D->num_levels; ++l)
-        if (mode == 0 || D->grad_level[l])
-            nb += (long long)split * D->level_n[l] * D->B * tm * ((D->level_h[l] * D->level_w[l] + CP_BM - 1) / CP_BM);
-    return nb;
 }
 
 #define CP_LDS (2 * CP_TILE * sizeof(float))
 
-extern "C" int mpc_corr_pyramid_fwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, void *ws, void *stream) {
-    int rc = cp_check(__func__, desc, D);
-    if (rc) return rc;
+static int cp_fwd(const char *who, const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream) {
     if (desc->B == 0) return 0;
-    if (!fmap1 || !fmap2 || !ws || (((uintptr_t)ws) & 15)) { mpc_set_error("%s: null argument (or a workspace that is not 16-byte aligned)", __func__); return MPC_E_NULL; }
-    for (int l = 0; l < desc->num_levels; ++l) if (!desc->level[l]) { mpc_set_error("%s: level %d is null", __func__, l); return MPC_E_NULL; }
-    const cp_plan P = cp_make_plan(desc, D, 0, true);
+    bool null = !ws || (((uintptr_t)ws) & 15);
+    for (int r = 0; r < refs->R; ++r) null = null || !refs->fmap1[r] || !refs->fmap2[r];
+    if (null) { mpc_set_error("%s: null argument (or a workspace that is not 16-byte aligned)", who); return MPC_E_NULL; }
+    for (int l = 0; l < desc->num_levels; ++l) if (!desc->level[l]) { mpc_set_error("%s: level %d is null", who, l); return MPC_E_NULL; }
+    cp_refs M;
+    const cp_plan P = cp_make_plan(desc, D, refs, 0, true, M);
+    for (int r = 0; r < refs->R; ++r) { M.r[r].fmap1 = refs->fmap1[r]; M.r[r].fmap2 = refs->fmap2[r]; }
     const hipStream_t st = (hipStream_t)stream;
-    cp_pool_levels(desc, P, fmap2, (float *)ws, st);
-    const long long nb = cp_gemm_blocks(desc, D, 0, 1);
-    if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
-    MPC_LAUNCH(k_corr_pyr_gemm<0>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, fmap1, fmap2, (float *)ws, (float *)nullptr);
+    cp_pool_levels(desc, P, M, (float *)ws, st);
+    const long long hw = (long long)desc->h * desc->w;
+    long long nb = 0;
+    for (int l = 0; l < desc->num_levels; ++l)
+        nb += (long long)desc->level_n[l] * desc->B * ((hw + CP_BM - 1) / CP_BM) * ((desc->level_h[l] * desc->level_w[l] + CP_BM - 1) / CP_BM);
+    if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
+    MPC_LAUNCH(k_corr_pyr_gemm<0>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, M, (float *)ws);
     MPC_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int mpc_corr_pyramid_bwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, float *grad_fmap1,
-                                    float *grad_fmap2, void *ws, void *stream) {
-    int rc = cp_check(__func__, desc, D);
-    if (rc) return rc;
-    if (desc->B == 0 || (!grad_fmap1 && !grad_fmap2)) return 0;
-    if (!fmap1 || !fmap2 || !ws || (((uintptr_t)ws) & 15)) { mpc_set_error("%s: null argument (or a workspace that is not 16-byte aligned)", __func__); return MPC_E_NULL; }
-    const cp_plan P = cp_make_plan(desc, D, 1, false);
+static int cp_bwd(const char *who, const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream) {
+    bool want1 = false, want2 = false;
+    for (int r = 0; r < refs->R; ++r) { want1 = want1 || refs->grad_fmap1[r]; want2 = want2 || refs->grad_fmap2[r]; }
+    if (desc->B == 0 || (!want1 && !want2)) return 0;
+    bool null = !ws || (((uintptr_t)ws) & 15);
+    for (int r = 0; r < refs->R; ++r) null = null || !refs->fmap1[r] || !refs->fmap2[r];
+    if (null) { mpc_set_error("%s: null argument (or a workspace that is not 16-byte aligned)", who); return MPC_E_NULL; }
+    cp_refs M;
+    const cp_plan P = cp_make_plan(desc, D, refs, 1, false, M);
+    for (int r = 0; r < refs->R; ++r) {
+        M.r[r].fmap1 = refs->fmap1[r]; M.r[r].fmap2 = refs->fmap2[r];
+        M.r[r].grad_fmap1 = refs->grad_fmap1[r]; M.r[r].grad_fmap2 = refs->grad_fmap2[r];
+    }
     const hipStream_t st = (hipStream_t)stream;
-    const long long hw = (long long)desc->h * desc->w;
-    if (grad_fmap1) {
+    const long long hw = (long long)desc->h * desc->w, tm = (D + CP_BM - 1) / CP_BM;
+    if (want1) {
+        // the pooled feature maps, where a slot of a reference that wants grad_fmap1 reads one
         bool pooled = false;
-        for (int l = 1; l < desc->num_levels; ++l) pooled = pooled || desc->grad_level[l];
-        if (pooled) cp_pool_levels(desc, P, fmap2, (float *)ws, st);
-        const long long nb = (long long)P.S * desc->B * ((D + CP_BM - 1) / CP_BM) * ((hw + CP_BM - 1) / CP_BM);
-        if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
-        MPC_LAUNCH(k_corr_pyr_gemm<2>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, fmap1, fmap2, (float *)ws, grad_fmap1);
-        if (P.S > 1) {
+        for (int r = 0; r < refs->R; ++r)
+            for (int l = 1; l < M.r[r].num_levels; ++l) pooled = pooled || (refs->grad_fmap1[r] && desc->grad_level[l]);
+        if (pooled) cp_pool_levels(desc, P, M, (float *)ws, st);
+        long long nb = 0, reduced = 0;
+        for (int r = 0; r < refs->R; ++r)
+            if (refs->grad_fmap1[r]) { nb += (long long)M.r[r].S * desc->B * tm * ((hw + CP_BM - 1) / CP_BM); reduced += M.r[r].S > 1; }
+        if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
+        MPC_LAUNCH(k_corr_pyr_gemm<2>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, M, (float *)ws);
+        if (reduced) {
             const long long n = (long long)desc->B * D * hw;
-            MPC_LAUNCH(k_corr_pyr_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, P, (const float *)ws, grad_fmap1, n);
+            MPC_LAUNCH(k_corr_pyr_reduce, dim3((unsigned)(reduced * ((n + 255) / 256))), dim3(256), 0, st, P, M, (const float *)ws, n);
         }
     }
-    if (grad_fmap2) {
-        const long long nb = cp_gemm_blocks(desc, D, 1, P.S1);
-        if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
-        if (nb > 0) MPC_LAUNCH(k_corr_pyr_gemm<1>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, fmap1, fmap2, (float *)ws, (float *)nullptr);
-        const long long n = (long long)desc->T * desc->B * D * hw;
-        if ((desc->w & 3) == 0 && (((uintptr_t)grad_fmap2) & 15) == 0)
-            MPC_LAUNCH(k_corr_pyr_gather<4>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, st, *desc, P, (const float *)ws, grad_fmap2);
-        else
-            MPC_LAUNCH(k_corr_pyr_gather<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, *desc, P, (const float *)ws, grad_fmap2);
+    if (want2) {
+        long long nb = 0;
+        bool al16 = true;
+        for (int r = 0; r < refs->R; ++r) {
+            if (!refs->grad_fmap2[r]) continue;
+            al16 = al16 && (((uintptr_t)refs->grad_fmap2[r]) & 15) == 0;
+            for (int l = 0; l < M.r[r].num_levels; ++l)
+                if (desc->grad_level[l])
+                    nb += (long long)M.r[r].S1 * M.r[r].level_n[l] * desc->B * tm * ((desc->level_h[l] * desc->level_w[l] + CP_BM - 1) / CP_BM);
+        }
+        if (nb > 0x7fffffffll) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
+        if (nb > 0) MPC_LAUNCH(k_corr_pyr_gemm<1>, dim3((unsigned)nb), dim3(256), CP_LDS, st, *desc, P, M, (float *)ws);
+        const int V = (desc->w & 3) == 0 && al16 ? 4 : 1;
+        long long gb = 0;                                       // whole workgroups per reference that wants grad_fmap2
+        for (int r = 0; r < refs->R; ++r)
+            if (refs->grad_fmap2[r]) gb += ((long long)M.r[r].level_n[0] * desc->B * D * hw / V + 255) / 256;
+        if (V == 4) MPC_LAUNCH(k_corr_pyr_gather<4>, dim3((unsigned)gb), dim3(256), 0, st, *desc, P, M, (const float *)ws);
+        else MPC_LAUNCH(k_corr_pyr_gather<1>, dim3((unsigned)gb), dim3(256), 0, st, *desc, P, M, (const float *)ws);
     }
     MPC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int mpc_corr_pyramid_fwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, void *ws, void *stream) {
+    const int rc = cp_check(__func__, desc, D);
+    if (rc) return rc;
+    const mpc_corr_refs one = cp_one_ref(desc, fmap1, fmap2, nullptr, nullptr);
+    return cp_fwd(__func__, desc, D, &one, ws, stream);
+}
+
+extern "C" int mpc_corr_pyramid_bwd(const mpc_corr_desc *desc, int D, const float *fmap1, const float *fmap2, float *grad_fmap1,
+                                    float *grad_fmap2, void *ws, void *stream) {
+    const int rc = cp_check(__func__, desc, D);
+    if (rc) return rc;
+    const mpc_corr_refs one = cp_one_ref(desc, fmap1, fmap2, grad_fmap1, grad_fmap2);
+    return cp_bwd(__func__, desc, D, &one, ws, stream);
+}
+
+extern "C" int mpc_corr_pyramid_multi_fwd(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream) {
+    int rc = cp_check(__func__, desc, D);
+    if (!rc) rc = cp_check_refs(__func__, desc, refs);
+    return rc ? rc : cp_fwd(__func__, desc, D, refs, ws, stream);
+}
+
+extern "C" int mpc_corr_pyramid_multi_bwd(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream) {
+    int rc = cp_check(__func__, desc, D);
+    if (!rc) rc = cp_check_refs(__func__, desc, refs);
+    return rc ? rc : cp_bwd(__func__, desc, D, refs, ws, stream);
 }
 
 MPC_BOUNDS_UNIT("corr_pyramid.hip")

@@ -1663,6 +1663,73 @@ class CorrPyramidFn(torch.autograd.Function):
         return g1, g2, None
 
 
+def corr_pyramid_refs(counts):
+    """The C descriptor (include/mpcmax.h: mpc_corr_refs) of references with `counts` targets each, without tensor pointers."""
+    refs = C.CorrRefs(R=len(counts))
+    for r, n in enumerate(counts[:C.CORR_MAX_REFS]):
+        refs.first_target[r + 1] = refs.first_target[r] + int(n)
+    return refs
+
+
+class CorrPyramidMultiFn(torch.autograd.Function):
+    """CorrPyramidFn over several references (utils.corr_pyramid_fused in list form; reference corr.py:221-225, 246-260, 282-302:
+    the events-plus-frames pyramid): `num_levels` the host list of R lists of level counts, then fmap1[0..R) [B, D, h, w] and
+    fmap2[0..R) [n_r, B, D, h, w] (fp32, contiguous, on one GPU) -> the levels of the merged target list as a tuple, one autograd
+    node with the launches of the single-reference node (csrc/corr_pyramid.hip: a slot reads the feature maps of its reference where
+    they lie).  The backward computes only the requested ones of the 2R gradients, each written straight into its own tensor, every
+    element by a kernel; a missing level cotangent is zero.  Equal, bit for bit, to the R single-reference nodes."""
+
+    @staticmethod
+    def forward(ctx, num_levels, *fmaps):
+        R = len(fmaps) // 2
+        for i, t in enumerate(fmaps):
+            _require_gpu(t, f'fmap{1 + i // R}[{i % R}]')
+        B, D, h, w = fmaps[0].shape
+        dev = fmaps[0].device
+        nl = [int(v) for ref in num_levels for v in ref]
+        desc, tix = corr_pyramid_desc(B, h, w, nl)
+        levels = [torch.empty((len(ts), B * h * w, 1, h >> l, w >> l), dtype=torch.float32, device=dev) for l, ts in enumerate(tix)]
+        fm = [t.detach() for t in fmaps]
+        if B > 0:
+            for l, lv in enumerate(levels):
+                desc.level[l] = lv.data_ptr()
+            refs = corr_pyramid_refs([len(ref) for ref in num_levels])
+            for r in range(R):
+                refs.fmap1[r], refs.fmap2[r] = fm[r].data_ptr(), fm[R + r].data_ptr()
+            nws = _query('mpc_corr_pyramid_multi_workspace_bytes', dev, ctypes.byref(desc), D, ctypes.byref(refs), 0)
+            ws = torch.empty((nws + 3) // 4, dtype=torch.float32, device=dev)
+            _call('mpc_corr_pyramid_multi_fwd', dev, ctypes.byref(desc), D, ctypes.byref(refs), _ptr(ws))
+        ctx.num_levels = [[int(v) for v in ref] for ref in num_levels]
+        ctx.set_materialize_grads(False)                              # (an unused level arrives as None, not as a volume of zeros)
+        ctx.save_for_backward(*fm)
+        return tuple(levels)
+
+    @staticmethod
+    def backward(ctx, *gl):
+        fm = ctx.saved_tensors
+        R = len(fm) // 2
+        B, D, h, w = fm[0].shape
+        dev = fm[0].device
+        want = ctx.needs_input_grad[1:]
+        if not any(want):
+            return (None,) * (1 + 2 * R)
+        grads = [torch.empty_like(t) if wanted else None for t, wanted in zip(fm, want)]          # (every element is written by a kernel)
+        if B > 0:
+            desc, _ = corr_pyramid_desc(B, h, w, [v for ref in ctx.num_levels for v in ref])
+            gl = [None if g is None else _f32c(g) for g in gl]
+            for l, g in enumerate(gl):
+                desc.grad_level[l] = None if g is None else g.data_ptr()
+            refs = corr_pyramid_refs([len(ref) for ref in ctx.num_levels])
+            for r in range(R):
+                refs.fmap1[r], refs.fmap2[r] = fm[r].data_ptr(), fm[R + r].data_ptr()
+                refs.grad_fmap1[r] = None if grads[r] is None else grads[r].data_ptr()
+                refs.grad_fmap2[r] = None if grads[R + r] is None else grads[R + r].data_ptr()
+            nws = _query('mpc_corr_pyramid_multi_workspace_bytes', dev, ctypes.byref(desc), D, ctypes.byref(refs), 1)
+            ws = torch.empty((nws + 3) // 4, dtype=torch.float32, device=dev)
+            _call('mpc_corr_pyramid_multi_bwd', dev, ctypes.byref(desc), D, ctypes.byref(refs), _ptr(ws))
+        return (None, *grads)
+
+
 class GridTrajFn(torch.autograd.Function):
     """The network's coefficient grid [B, S, 2k, H, W] -> `trajectories` [B, n_t, n, 2] (y, x) at the tile centres (row A3 of SURVEY.md
     8(a): reference trajectory_net.py:57-119): one kernel forward, one backward (two when `dphi` needs a gradient), csrc/grid_traj.hip,

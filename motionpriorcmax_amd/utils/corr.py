@@ -4,7 +4,8 @@ the loop that calls it: raft.py:165-189).
 `corr_pyramid` is the reference's batched matmul, division and average pools in plain torch: the mirror, the CPU path and the comparator.
 `corr_pyramid_fused` builds the same pyramid on the GPU as one autograd node (ops.CorrPyramidFn, csrc/corr_pyramid.hip): every level
 is its own fp32-MFMA GEMM against the pooled feature map, written once; inputs the kernels do not take -- CPU tensors, other dtypes,
-non-contiguous tensors, D that is no multiple of 4 or above 512, more than 16 targets or 6 levels -- go to `corr_pyramid`.
+non-contiguous tensors, D that is no multiple of 4 or above 512, more than 16 targets or 6 levels -- go to `corr_pyramid`.  Both take
+one reference (tensors) or several (lists: the events-plus-frames pyramid of the reference's default model, ops.CorrPyramidMultiFn).
 `CorrLookup` is the network's one gather, 12 times per forward: on the GPU one kernel each way (ops.CorrLookupFn, csrc/corr_lookup.hip); everything the kernels do not take --
 CPU tensors, other dtypes, non-contiguous tensors, radius > 4, more than 16 targets or control points, more than 6 levels -- runs the
 plain-torch mirror below, which is written as the reference's own operator chain (coordinate tensor, normalisation to [-1, 1],
@@ -32,21 +33,10 @@ def level_target_indices(num_levels_per_target):
     return [[t for t, v in enumerate(nl) if v >= l + 1] for l in range(max(nl))]
 
 
-def corr_pyramid(fmap1, fmap2, num_levels_per_target):
-    """fmap1 [B, D, h, w], fmap2 [n, B, D, h, w] (or [B, D, h, w] for one target) -> (levels, target_indices): levels[l]
-    [n_l, B*h*w, 1, h_l, w_l] = fmap1^T @ fmap2 / sqrt(D), 2 x 2 average-pooled l times (the pool drops an odd last row / column), for
-    the targets of `level_target_indices` -- the reference's CorrComputation.get_correlation_volume and CorrData.get_downsampled
-    (corr.py:262-270, 106-123) operator for operator.  target_indices are host lists."""
-    nl = _levels_list(num_levels_per_target)
-    if fmap2.dim() == 4:
-        fmap2 = fmap2[None]
-    n, B, D, h, w = fmap2.shape
-    if tuple(fmap1.shape) != (B, D, h, w) or len(nl) != n:
-        raise ValueError(f'fmap1 {tuple(fmap1.shape)}, fmap2 {tuple(fmap2.shape)} and {len(nl)} level counts do not belong together')
-    corr = fmap1.reshape(B, D, h * w).transpose(-1, -2) @ fmap2.reshape(n, B, D, h * w)
-    corr = corr / torch.sqrt(torch.tensor(D, device=corr.device).float())
+def _pool_levels(corr, nl, B, h, w):
+    """CorrData.get_downsampled per level (corr.py:106-123, 296-302) over the volume corr [n, B, h*w, h*w]."""
     tix = level_target_indices(nl)
-    levels = [corr.reshape(n, B * h * w, 1, h, w)]
+    levels = [corr.reshape(len(nl), B * h * w, 1, h, w)]
     for l in range(1, len(tix)):
         prev = levels[-1]
         pick = [tix[l - 1].index(t) for t in tix[l]]
@@ -56,11 +46,83 @@ def corr_pyramid(fmap1, fmap2, num_levels_per_target):
     return levels, tix
 
 
+def _references(fmap1, fmap2, num_levels_per_target):
+    """The list form checked: R tensors fmap1[r] [B, D, h, w], R tensors fmap2[r] [n_r, B, D, h, w] (4 dimensions: one target), R
+    entries of level counts (an int or n_r ints) -> (fmap1, fmap2 as 5 dimensions, level counts as R lists).  All references
+    share B, D, h, w (corr.py:171, 183)."""
+    if not isinstance(fmap2, (list, tuple)) or not isinstance(num_levels_per_target, (list, tuple)) or \
+            not len(fmap1) == len(fmap2) == len(num_levels_per_target) or not len(fmap1):
+        raise ValueError('the list form takes as many fmap2 tensors and level-count entries as fmap1 tensors, one or more')
+    f2s = [f[None] if f.dim() == 4 else f for f in fmap2]
+    nls = [_levels_list(v) for v in num_levels_per_target]
+    shape = tuple(fmap1[0].shape)
+    for r, (f1, f2, nl) in enumerate(zip(fmap1, f2s, nls)):
+        if f1.dim() != 4 or f2.dim() != 5 or tuple(f1.shape) != shape or tuple(f2.shape[1:]) != shape or len(nl) != f2.shape[0]:
+            raise ValueError(f'reference {r}: fmap1 {tuple(f1.shape)}, fmap2 {tuple(f2.shape)} and {len(nl)} level counts do not belong '
+                             f'together, or to the [B, D, h, w] = {shape} of reference 0')
+    return list(fmap1), f2s, nls
+
+
+def corr_pyramid(fmap1, fmap2, num_levels_per_target):
+    """fmap1 [B, D, h, w], fmap2 [n, B, D, h, w] (or [B, D, h, w] for one target) -> (levels, target_indices): levels[l]
+    [n_l, B*h*w, 1, h_l, w_l] = fmap1^T @ fmap2 / sqrt(D), 2 x 2 average-pooled l times (the pool drops an odd last row / column), for
+    the targets of `level_target_indices` -- the reference's CorrComputation.get_correlation_volume and CorrData.get_downsampled
+    (corr.py:262-270, 106-123) operator for operator.  target_indices are host lists.
+    The list form -- fmap1 a list of R tensors, fmap2 a list of R tensors, num_levels_per_target a list of R entries (an int or a
+    list of ints each) -- is the events-plus-frames pyramid (CorrComputation.__add__ and _corr_dot_prod_M_to_N, corr.py:221-225,
+    246-260; events then frames in raft.py:131-144): the flat target list is the concatenation in the order given, and the volume
+    the reference's expand / cat, one batched matmul and the division.  A list of one reference is the tensor form."""
+    if isinstance(fmap1, (list, tuple)):
+        f1s, f2s, nls = _references(fmap1, fmap2, num_levels_per_target)
+        if len(f1s) == 1:
+            return corr_pyramid(f1s[0], f2s[0], nls[0])
+        B, D, h, w = f1s[0].shape
+        nl = [v for ref in nls for v in ref]
+        a = torch.cat([x.expand(len(ref), -1, -1, -1, -1) for x, ref in zip(f1s, nls)], dim=0)
+        b = torch.cat(f2s, dim=0)
+        corr = a.view(len(nl), B, D, h * w).transpose(-1, -2) @ b.view(len(nl), B, D, h * w)
+        corr = corr / torch.sqrt(torch.tensor(D, device=corr.device).float())
+        return _pool_levels(corr, nl, B, h, w)
+    nl = _levels_list(num_levels_per_target)
+    if fmap2.dim() == 4:
+        fmap2 = fmap2[None]
+    n, B, D, h, w = fmap2.shape
+    if tuple(fmap1.shape) != (B, D, h, w) or len(nl) != n:
+        raise ValueError(f'fmap1 {tuple(fmap1.shape)}, fmap2 {tuple(fmap2.shape)} and {len(nl)} level counts do not belong together')
+    corr = fmap1.reshape(B, D, h * w).transpose(-1, -2) @ fmap2.reshape(n, B, D, h * w)
+    corr = corr / torch.sqrt(torch.tensor(D, device=corr.device).float())
+    return _pool_levels(corr, nl, B, h, w)
+
+
+def _corr_pyramid_fused_refs(fmap1, fmap2, num_levels_per_target):
+    f1s, f2s, nls = _references(fmap1, fmap2, num_levels_per_target)
+    if len(f1s) == 1:
+        return corr_pyramid_fused(f1s[0], f2s[0], nls[0])
+    B, D, h, w = f1s[0].shape
+    dev = f1s[0].device
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in f1s + f2s):
+        return corr_pyramid(f1s, f2s, nls)
+    import ctypes
+    from .. import ops, _lib as C
+    nl = [v for ref in nls for v in ref]
+    if len(f1s) > C.CORR_MAX_REFS or len(nl) > C.CORR_MAX_TARGETS or max(nl) > C.CORR_MAX_LEVELS:
+        return corr_pyramid(f1s, f2s, nls)
+    desc, tix = ops.corr_pyramid_desc(B, h, w, nl)
+    refs = ops.corr_pyramid_refs([len(ref) for ref in nls])
+    if C.lib().mpc_corr_pyramid_multi_supported(ctypes.byref(desc), D, ctypes.byref(refs)) != 0:
+        return corr_pyramid(f1s, f2s, nls)
+    return list(ops.CorrPyramidMultiFn.apply(nls, *f1s, *f2s)), tix
+
+
 def corr_pyramid_fused(fmap1, fmap2, num_levels_per_target):
     """`corr_pyramid` with the same arguments, checks, level shapes and target_indices, built on the GPU by ops.CorrPyramidFn where the
     kernels serve the inputs (fp32, contiguous, CUDA, D a multiple of 4 up to 512, at most 16 targets and 6 levels): one autograd
     node with gradients to fmap1 and fmap2, no host synchronisation, bitwise reproducible.  Everything else returns
-    `corr_pyramid(...)`.  Only the single-reference form (fmap1 [B, D, h, w]: corr.py:235-260, _corr_dot_prod_1_to_N)."""
+    `corr_pyramid(...)`.  The list form (several references: events plus frames) goes to ops.CorrPyramidMultiFn under the same
+    conditions on every tensor and on the merged target list, and at most 4 references (MPC_CORR_MAX_REFS): one node with the same
+    launches, gradients to all 2R feature maps, equal bit for bit to the R single-reference nodes."""
+    if isinstance(fmap1, (list, tuple)):
+        return _corr_pyramid_fused_refs(fmap1, fmap2, num_levels_per_target)
     nl = _levels_list(num_levels_per_target)
     f2 = fmap2[None] if fmap2.dim() == 4 else fmap2
     if f2.dim() != 5:
@@ -174,8 +236,12 @@ class CorrLookup:
     @classmethod
     def from_fmaps(cls, fmap1, fmap2, num_levels_per_target, radius=4, shared_grad=False):
         """The lookup over the pyramid of `corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)`: what raft.py:129 / :161 build
-        from the two feature maps (single-reference form), with the pyramid as one autograd node back to the feature maps."""
+        from the two feature maps, with the pyramid as one autograd node back to the feature maps.  In list form (fmap1, fmap2 and
+        num_levels_per_target lists of R entries: raft.py:131-144 with boundary images, events then frames) the lookup is over the
+        merged level counts."""
         levels, _ = corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)
+        if isinstance(fmap1, (list, tuple)):
+            num_levels_per_target = [v for ref in num_levels_per_target for v in _levels_list(ref)]
         return cls(levels, num_levels_per_target, radius=radius, shared_grad=shared_grad)
 
     # ---- routing

@@ -10,7 +10,12 @@ The bar: on both legs and both batch sizes the fused median lies below the mirro
 (the larger of the two variants' max - min).  Per-kernel times from the library's own events (mpc_profile_start / _stop), and the
 fp32 FLOP/s the three GEMM launches achieve over the operations their shapes need (2 * B * D * hw * sum_l n_l h_l w_l each), beside
 the 157.3 TF fp32 matrix peak.  Writes profiles/corr_pyramid.json (tagged with build.source_hash()):
-    python tools/corr_pyramid_probe.py [out.json]"""
+    python tools/corr_pyramid_probe.py [out.json]
+With --multi the reference's default model (raft-spline.yaml: use_boundary_images, a 384 x 512 input, so the same 48 x 64 grid and
+D = 256): two references in list form, events [1, 2, 3, 4] plus frames [4] (ops.CorrPyramidMultiFn), against the list-form mirror --
+the expand / cat, batched matmul, division and pool chain, which is what a caller had for this model before.  The same legs, bar
+and per-kernel times, and per mode the peak rise of allocated device memory over one call.  Writes profiles/corr_pyramid_multi.json:
+    python tools/corr_pyramid_probe.py --multi [out.json]"""
 import ctypes
 import json
 import os
@@ -26,6 +31,7 @@ from motionpriorcmax_amd import utils, build, _lib as C  # noqa: E402
 
 BLOCKS, CALLS, WARM = 7, 10, 2
 H, W, D_FEAT, LEVELS = 48, 64, 256, [1, 1, 1, 1, 4]
+LEVELS_MULTI = [[1, 2, 3, 4], [4]]                      # events, then frames
 PEAK_TF = 157.3
 GEMMS = {'k_corr_pyr_gemm<0>': 'forward', 'k_corr_pyr_gemm<1>': 'grad_pooled_fmap2', 'k_corr_pyr_gemm<2>': 'grad_fmap1'}
 dev = torch.device('cuda:0')
@@ -59,24 +65,41 @@ def kernel_times(fn, reps):
     return out
 
 
-def gemm_flops(B):
-    tix = utils.level_target_indices(LEVELS)
+def peak_rise(fn):
+    """Bytes by which the allocator's peak exceeds what is allocated before one call of fn (the results are dropped first)."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    before = torch.cuda.memory_allocated(dev)
+    fn()
+    torch.cuda.synchronize()
+    return int(torch.cuda.max_memory_allocated(dev) - before)
+
+
+def gemm_flops(B, levels):
+    tix = utils.level_target_indices([v for ref in levels for v in ref] if isinstance(levels[0], list) else levels)
     return 2 * B * D_FEAT * H * W * sum(len(t) * (H >> l) * (W >> l) for l, t in enumerate(tix))
 
 
-def main(out_path):
+def main(out_path, levels=LEVELS):
+    multi = isinstance(levels[0], list)
     if not torch.cuda.is_available():
         raise SystemExit('corr_pyramid_probe: no GPU; a timing on the CPU says nothing')
     res = {'source_hash': build.source_hash(), 'method': f'one process, variants alternating, median of {BLOCKS} blocks x {CALLS} calls after '
            f'{WARM} warm-up calls; host clock ending in torch.cuda.synchronize(); per-kernel: mpc_profile_start / mpc_profile_stop',
-           'shape': dict(grid=[H, W], feature_dim=D_FEAT, num_levels_per_target=LEVELS), 'fp32_matrix_peak_TF': PEAK_TF, 'batches': {}}
+           'shape': dict(grid=[H, W], feature_dim=D_FEAT, num_levels_per_target=levels), 'fp32_matrix_peak_TF': PEAK_TF, 'batches': {}}
     for B in (1, 6):
         g = torch.Generator().manual_seed(256 + B)
-        f1 = torch.randn(B, D_FEAT, H, W, generator=g).to(dev).requires_grad_(True)
-        f2 = torch.randn(len(LEVELS), B, D_FEAT, H, W, generator=g).to(dev).requires_grad_(True)
+        if multi:
+            f1 = [torch.randn(B, D_FEAT, H, W, generator=g).to(dev).requires_grad_(True) for _ in levels]
+            f2 = [torch.randn(len(ref), B, D_FEAT, H, W, generator=g).to(dev).requires_grad_(True) for ref in levels]
+            leaves = f1 + f2
+        else:
+            f1 = torch.randn(B, D_FEAT, H, W, generator=g).to(dev).requires_grad_(True)
+            f2 = torch.randn(len(levels), B, D_FEAT, H, W, generator=g).to(dev).requires_grad_(True)
+            leaves = [f1, f2]
         with torch.no_grad():
-            want, _ = utils.corr_pyramid(f1, f2, LEVELS)
-            got, _ = utils.corr_pyramid_fused(f1, f2, LEVELS)
+            want, _ = utils.corr_pyramid(f1, f2, levels)
+            got, _ = utils.corr_pyramid_fused(f1, f2, levels)
             cots = [torch.randn(lv.shape, device=dev) for lv in want]
             fwd_diff = [float((a - b).abs().max()) for a, b in zip(got, want)]
             level_bytes = 4 * sum(lv.numel() for lv in want)
@@ -85,12 +108,12 @@ def main(out_path):
         def fwd(f):
             def run():
                 with torch.no_grad():
-                    f(f1, f2, LEVELS)
+                    f(f1, f2, levels)
             return run
 
         def fwd_bwd(f):
             def run():
-                return torch.autograd.grad(f(f1, f2, LEVELS)[0], [f1, f2], cots)
+                return torch.autograd.grad(f(f1, f2, levels)[0], leaves, cots)
             return run
 
         modes = {'forward_mirror': fwd(utils.corr_pyramid), 'forward_fused': fwd(utils.corr_pyramid_fused),
@@ -110,11 +133,16 @@ def main(out_path):
              for k, v in samples.items()}
         kt = kernel_times(modes['fwd_bwd_fused'], 5)
         r['kernels_us'] = {k: round(v, 2) for k, v in sorted(kt.items())}
-        flops = gemm_flops(B)
+        if multi:
+            r['peak_rise_bytes'] = {k: peak_rise(fn) for k, fn in modes.items()}
+        flops = gemm_flops(B, levels)
         r['gemm_flops_each'] = flops
         r['gemm_achieved_TF'] = {GEMMS[k]: round(flops / (v * 1e-6) / 1e12, 1) for k, v in kt.items() if k in GEMMS}
         r['level_bytes'] = level_bytes
-        r['max_abs_diff_to_mirror'] = dict(levels=fwd_diff, grad_fmap1=grad_diff[0], grad_fmap2=grad_diff[1], max_abs_grad=grad_max)
+        if multi:
+            r['max_abs_diff_to_mirror'] = dict(levels=fwd_diff, grad_fmap1=grad_diff[:len(levels)], grad_fmap2=grad_diff[len(levels):], max_abs_grad=grad_max)
+        else:
+            r['max_abs_diff_to_mirror'] = dict(levels=fwd_diff, grad_fmap1=grad_diff[0], grad_fmap2=grad_diff[1], max_abs_grad=grad_max)
         r['bar'] = {}
         for leg in ('forward', 'fwd_bwd'):
             a, m = r[leg + '_fused'], r[leg + '_mirror']
@@ -124,7 +152,7 @@ def main(out_path):
         res['batches'][f'B{B}'] = r
         print(f'B={B}', json.dumps({k: r[k]['median_ms'] for k in modes}), json.dumps(r['kernels_us']), json.dumps(r['gemm_achieved_TF']),
               json.dumps(r['bar']), json.dumps(r['max_abs_diff_to_mirror']), flush=True)
-        del cots, modes, f1, f2
+        del cots, modes, f1, f2, leaves
         torch.cuda.empty_cache()
     res['bar_met_on_every_leg'] = all(leg['met'] for b in res['batches'].values() for leg in b['bar'].values())
     with open(out_path, 'w') as f:
@@ -134,4 +162,8 @@ def main(out_path):
 
 
 if __name__ == '__main__':
-    main(sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'profiles', 'corr_pyramid.json'))
+    argv = [a for a in sys.argv[1:] if a != '--multi']
+    if '--multi' in sys.argv[1:]:
+        main(argv[0] if argv else os.path.join(ROOT, 'profiles', 'corr_pyramid_multi.json'), LEVELS_MULTI)
+    else:
+        main(argv[0] if argv else os.path.join(ROOT, 'profiles', 'corr_pyramid.json'))

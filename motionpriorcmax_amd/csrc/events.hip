@@ -4,10 +4,9 @@
 //   backward: SURVEY.md 8a row A11
 // Arithmetic follows SURVEY.md Appendix A op for op (fp32, no FMA contraction: this file is
 // compiled with -ffp-contract=off).
-#include "common.h"
+#include "pe_device.h"
 #include "ev_count_device.h"
 #include "knn_device.h"
-#include "bounds.h"
 #include "diag/stamps.h"
 
 struct EvParams {
@@ -864,34 +863,24 @@ int mpc_event_splat_bwd_job(const mpc_shape *s, const float *events, const int32
 // ---- UNPINNED EXTENSION, fused form (FocusLoss.calc_per_event_basis): the per-event continuous-time basis warp itself and the
 // chain from the position gradient back to the tile coefficients, one pass over the events each.
 //   k_pe_warp : rows_out[b][i] = (y + sum_k c[cell][0][k] phi[b][i][k], x + sum_k c[cell][1][k] phi[b][i][k], t, p, cell, valid)
-//               cell = LUT cell of the event's own position (focus.py:186-187), kept in column 4 (its bits) for the backward --
-//               with MPC_F_NO_WARP nothing else reads that column; coef [B*hq*wq][2][k], phi [B][M][k] (basis_k(t_ref) - basis_k(t))
+//               cell = LUT cell of the event's own position (pe_device.h: pe_own_cell, pe_write_row; the RAFT-spline curves of
+//               pe_curves.hip write the same record); coef [B*hq*wq][2][k], phi [B][M][k] (basis_k(t_ref) - basis_k(t))
 //   k_pe_grad : grad_coef[cell][d][k] += phi[b][i][k] * d objective / d warped position_d  (float atomics: the gradient of this
 //               extension is not bitwise reproducible; the forward is)
-#define PE_KMAX 8          // orders held in registers (beyond: the generic instantiation reads phi per use)
 // phi[j] = basis_j(t_ref) - basis_j(t), j < k, from the tensor, or -- phi == nullptr: the polynomial basis t^(j+1) (basis.py:26-27) --
 // worked out here (one multiply per order instead of 4 k bytes of traffic per event and kernel)
 // A third source (TAB; FocusLoss.calc_per_event_basis(basis_type='table')): a table T [S + 1][k] of samples of the basis at the knots
-// i / S, interpolated linearly -- the DEFINITION is these five fp32 operations, one per line, nothing fused (utils.table_basis_values
-// spells the same lines in torch and must agree bit for bit):
-//   tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;  B_j = T[i][j] + f * (T[i+1][j] - T[i][j])
-// (t == 1 lands in the last interval with f == 1).  The table is read THROUGH THE CACHE in all three kernels: a time-sorted batch puts
-// the 64 lanes of a wavefront on one or two knots (a broadcast load), a bucket-ordered one on the knots of one time bin, and an LDS
-// copy of up to 64 KB per workgroup would cost k_pe_warp / k_pe_grad their occupancy and does not fit beside k_pe_accum's strip
-// accumulators (up to 150 KB).
-__device__ __forceinline__ void pe_tab_locate(float t, int S, int &i, float &f) {
-    const float tc = fminf(fmaxf(t, 0.f), 1.f);
-    const float x = tc * (float)S;
-    i = min((int)floorf(x), S - 1);
-    f = x - (float)i;
-}
+// i / S, interpolated linearly (pe_device.h: pe_tab_locate / pe_tab_lerp, with the definition).  The table is read THROUGH THE
+// CACHE in all three kernels: a time-sorted batch puts the 64 lanes of a wavefront on one or two knots (a broadcast load), a
+// bucket-ordered one on the knots of one time bin, and an LDS copy of up to 64 KB per workgroup would cost k_pe_warp / k_pe_grad
+// their occupancy and does not fit beside k_pe_accum's strip accumulators (up to 150 KB).
 template <int KB>
 __device__ __forceinline__ void pe_tab_basis(const float *__restrict__ table, int S, int k, float t, float *out /* [KB or min(k, 8)] */) {
     const int kk = KB > 0 ? KB : min(k, PE_KMAX);
     int i; float f;
     pe_tab_locate(t, S, i, f);
     const float *r0 = table + (size_t)i * k, *r1 = r0 + k;
-    for (int j = 0; j < kk; ++j) { const float a = r0[j]; const float d = r1[j] - a; out[j] = a + f * d; }
+    for (int j = 0; j < kk; ++j) out[j] = pe_tab_lerp(r0[j], r1[j], f);
 }
 // the table the TAB instantiations read (appended to the kernels' arguments: the other instantiations never load them); bref =
 // B(t_ref), formed once per thread before its loop over the rows
@@ -928,8 +917,7 @@ __global__ __launch_bounds__(256) void k_pe_warp(const mpc_shape s, const float 
         const int b = (int)(row / p.M);
         float e[6];
         load_event(events, row, e);
-        const int iy = min(max((int)floorf(mpc_div_sp(e[0], p.sp)), 0), p.hq - 1), ix = min(max((int)floorf(mpc_div_sp(e[1], p.sp)), 0), p.wq - 1);
-        const int cell = (b * p.hq + iy) * p.wq + ix;
+        const int cell = pe_own_cell(b, e[0], e[1], p.sp, p.hq, p.wq);
         const float *c = coef + (size_t)cell * 2 * k;
         float fy = 0.f, fx = 0.f;
         float ph[KB > 0 ? KB : PE_KMAX];
@@ -940,10 +928,7 @@ __global__ __launch_bounds__(256) void k_pe_warp(const mpc_shape s, const float 
         } else {
             for (int j = 0; j < k; ++j) { const float f = j < PE_KMAX ? ph[j] : phi[row * k + j]; fy += c[j] * f; fx += c[k + j] * f; }
         }
-        float2 *o = reinterpret_cast<float2 *>(rows_out + row * 6);
-        o[0] = make_float2(e[0] + fy, e[1] + fx);
-        o[1] = make_float2(e[2], e[3]);
-        o[2] = make_float2(__int_as_float(cell), e[5]);
+        pe_write_row(rows_out, row, e, fy, fx, cell);
     }
 }
 
@@ -989,13 +974,8 @@ __global__ __launch_bounds__(256) void k_pe_grad(const mpc_shape s, const float 
 //               2 * nb row ranges of its strip, gathers the adjoint-image taps of every row and adds phi * gradient to the strip's
 //               [cell][2][k] accumulators in LDS -- 64-bit fixed point like k_lut_accum: integer sums, bitwise reproducible -- and
 //               writes every cell of the strip once (global float atomics ran at ~20 G/s on this chip: 0.83 ms for the 17 M of a C3 step)
+//               (pe_device.h: pe_to_fixed, pe_strip, pe_range_of -- shared with k_pec_accum of pe_curves.hip)
 #define PE_NT 1024
-// Q33.30 of one phi * gradient product, rounded to NEAREST: at most 2^-31 per row added, and no bias (with small event weights a
-// product is a few units of 2^-30, and a conversion that truncates towards zero shrinks every sum by half a unit per row)
-__device__ __forceinline__ long long pe_to_fixed(float v) {         // |v| < 2^31
-    const float hi = truncf(v);
-    return ((long long)(int)hi << MPC_FIX_SHIFT) + (long long)__float2int_rn((v - hi) * (float)(1 << MPC_FIX_SHIFT));
-}
 #define PE_NIF 4
 // (TAB with gpos: the unscaled (gy, gx) of every row that contributes is stored for k_pe_table_grad; the caller zeroes gpos first --
 // rows outside every range of the offsets table, and rows this kernel skips, then read as zeros)
@@ -1013,8 +993,8 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
     // B * NCS workgroups -- 98 at the DSEC batch -- left most of the CUs idle)
     const int part = blockIdx.x % SPLIT, bs = blockIdx.x / SPLIT;
     const int b = bs / NCS, cst = bs - b * NCS;
-    const int crow0 = cst * CSR, crow1 = min(crow0 + CSR, p.hq), ncell = (crow1 - crow0) * p.wq;
-    const int cell0 = (b * p.hq + crow0) * p.wq;
+    const PeStrip strip = pe_strip(b, cst, CSR, p.hq, p.wq);
+    const int ncell = strip.ncell, cell0 = strip.cell0;
     const int NK = p.nb * NCS, nrange = 2 * p.nb;
     for (int i = tid; i < ncell * 2 * kk; i += PE_NT) s_pacc[i] = 0ull;
     if (tid == 0) {
@@ -1043,7 +1023,7 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
             const int q = q0 + u * PE_NT;
             on[u] = q < n;
             int j = 0;
-            if (on[u]) { int lo = 0, hi = nrange; while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_pre[mid] <= q) lo = mid; else hi = mid; } j = lo; }
+            if (on[u]) j = pe_range_of(s_pre, nrange, q);
             const int row = on[u] ? s_r0[j] + (q - s_pre[j]) : 0;
             pol[u] = (p.P == 2) ? (row >= p.Mp ? 1 : 0) : 0;
             grow[u] = (size_t)b * p.M + row;
@@ -1079,29 +1059,35 @@ __global__ __launch_bounds__(PE_NT) void k_pe_accum(const mpc_shape s, int CSR, 
     for (int i = tid; i < ncell * 2 * kk; i += PE_NT) dst[i] = coef * mpc_from_fixed((long long)s_pacc[i]);
 }
 
-extern "C" int mpc_pe_warp(const mpc_shape *s, const float *events, const float *coef_rows, const float *phi, int32_t k,
-                           const float *t_ref, float *rows_out, void *stream) {
-    MPC_CHECK_ARG(s && coef_rows && (phi || t_ref) && rows_out && (events || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG(k >= 1 && k <= 64 && (phi || k <= PE_KMAX), MPC_E_SHAPE, "1 <= num_basis <= 64 (<= 8 for the built-in polynomial basis)");
+// ---- entry points.  Every operation has ONE implementation that takes (phi, PeTab, gpos) and launches the TAB instantiation where
+// there is a table; the public functions of the two families keep what differs between them -- their own pointers and the limits
+// on k and S -- in the order they always had, and hand over.
+#define PE_DISPATCH(kern, TAB, grid, block, lds, st, ...)                                        \
+    do {                                                                                         \
+        if (k == 1) MPC_LAUNCH((kern<1, TAB>), grid, block, lds, st, __VA_ARGS__);               \
+        else if (k == 3) MPC_LAUNCH((kern<3, TAB>), grid, block, lds, st, __VA_ARGS__);          \
+        else MPC_LAUNCH((kern<0, TAB>), grid, block, lds, st, __VA_ARGS__);                      \
+    } while (0)
+#define PE_DISPATCH_TB(kern, grid, block, lds, st, ...)                                          \
+    do {                                                                                         \
+        if (tb.table) PE_DISPATCH(kern, true, grid, block, lds, st, __VA_ARGS__);                \
+        else PE_DISPATCH(kern, false, grid, block, lds, st, __VA_ARGS__);                        \
+    } while (0)
+static const PeTab PE_NO_TAB{nullptr, 0};
+
+static int pe_warp_impl(const mpc_shape *s, const float *events, const float *coef_rows, const float *phi, int k, const PeTab tb,
+                        const float *t_ref, float *rows_out, void *stream) {
     int rc = mpc_validate_shape(s);
     if (rc) return rc;
     const int64_t total = (int64_t)s->B * s->M;
     if (total == 0) return 0;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipStream_t st = (hipStream_t)stream;
-    if (k == 1) MPC_LAUNCH(k_pe_warp<1>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, PeTab{nullptr, 0});
-    else if (k == 3) MPC_LAUNCH(k_pe_warp<3>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, PeTab{nullptr, 0});
-    else MPC_LAUNCH(k_pe_warp<0>, dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, PeTab{nullptr, 0});
+    PE_DISPATCH_TB(k_pe_warp, dim3(pe_row_grid(total)), dim3(256), 0, (hipStream_t)stream, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
     MPC_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int mpc_pe_grad(const mpc_shape *s, const float *rows, const float *phi, int32_t k, const float *t_ref, const float *grad_iwe,
-                           const float *scal, const float *grad_out, float *grad_coef_rows, void *stream) {
-    MPC_CHECK_ARG(s && (phi || t_ref) && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG((s->flags & MPC_F_NO_WARP) && s->T == 1, MPC_E_UNSUPPORTED, "mpc_pe_grad takes the rows of mpc_pe_warp (MPC_F_NO_WARP), num_tref == 1");
-    MPC_CHECK_ARG(t_ref, MPC_E_NULL, "t_ref is null");
-    MPC_CHECK_ARG(k >= 1 && k <= 64 && (phi || k <= PE_KMAX), MPC_E_SHAPE, "1 <= num_basis <= 64 (<= 8 for the built-in polynomial basis)");
+static int pe_grad_impl(const mpc_shape *s, const float *rows, const float *phi, int k, const PeTab tb, const float *t_ref,
+                        const float *grad_iwe, const float *scal, const float *grad_out, float *grad_coef_rows, float2 *gpos, void *stream) {
     int rc = mpc_validate_shape(s);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -1109,10 +1095,7 @@ extern "C" int mpc_pe_grad(const mpc_shape *s, const float *rows, const float *p
     if (e0) return e0;
     const int64_t total = (int64_t)s->B * s->M;
     if (total == 0) return 0;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    if (k == 1) MPC_LAUNCH(k_pe_grad<1>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
-    else if (k == 3) MPC_LAUNCH(k_pe_grad<3>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
-    else MPC_LAUNCH(k_pe_grad<0>, dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    PE_DISPATCH_TB(k_pe_grad, dim3(pe_row_grid(total)), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
     MPC_CHECK_LAUNCH();
     return 0;
 }
@@ -1124,41 +1107,70 @@ extern "C" int32_t mpc_pe_grad_ordered_supported(const mpc_shape *s, int32_t k) 
     if (!(s->flags & MPC_F_NO_WARP) || s->T != 1 || k < 1 || k > 64 || s->nb > 64 || s->B <= 0) return 0;
     const mpc_ws_layout L = mpc_layout(s);
     if (L.n_cstrips <= 0) return 0;
-    return (size_t)L.cstrip_rows * s->wq * 2 * k * 8 <= 150 * 1024 ? 1 : 0;
+    return (size_t)L.cstrip_rows * s->wq * 2 * k * 8 <= PE_LDS_MAX ? 1 : 0;
 }
 
-extern "C" int mpc_pe_grad_ordered(const mpc_shape *s, const float *rows, const int32_t *offsets, const float *phi, int32_t k,
-                                   const float *t_ref, const float *grad_iwe, const float *scal, const float *grad_out,
-                                   float *grad_coef_rows, int32_t split, void *stream) {
-    MPC_CHECK_ARG(s && offsets && (phi || t_ref) && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG((s->flags & MPC_F_NO_WARP) && s->T == 1, MPC_E_UNSUPPORTED, "mpc_pe_grad_ordered takes the rows of mpc_pe_warp (MPC_F_NO_WARP), num_tref == 1");
-    MPC_CHECK_ARG(t_ref, MPC_E_NULL, "t_ref is null");
-    MPC_CHECK_ARG(k >= 1 && k <= 64 && (phi || k <= PE_KMAX) && s->nb <= 64, MPC_E_SHAPE, "1 <= num_basis <= 64 (<= 8 built-in polynomial), num_bins <= 64");
+// (gpos: zeroed here first -- rows outside every range of the offsets table, and rows the kernel skips, carry no gradient)
+static int pe_grad_ordered_impl(const mpc_shape *s, const float *rows, const int32_t *offsets, const float *phi, int k, const PeTab tb,
+                                const float *t_ref, const float *grad_iwe, const float *scal, const float *grad_out, float *grad_coef_rows,
+                                int split, float2 *gpos, void *stream) {
     int rc = mpc_validate_shape(s);
     if (rc) return rc;
     if (s->B == 0) return 0;
     const mpc_ws_layout L = mpc_layout(s);
     MPC_CHECK_ARG(L.n_cstrips > 0, MPC_E_UNSUPPORTED, "no bucketed event layout for this shape");
     const size_t lds = (size_t)L.cstrip_rows * s->wq * 2 * k * 8;
-    MPC_CHECK_ARG(lds <= 150 * 1024, MPC_E_UNSUPPORTED, "a LUT strip's accumulators do not fit the LDS (use mpc_pe_grad)");
+    MPC_CHECK_ARG(lds <= PE_LDS_MAX, MPC_E_UNSUPPORTED, "a LUT strip's accumulators do not fit the LDS (use the atomic gradient)");
+    MPC_CHECK_ARG(split >= 1 && split <= 16, MPC_E_SHAPE, "1 <= split <= 16");
     hipStream_t st = (hipStream_t)stream;
     static mpc_device_once attr_once;
     if (attr_once.need()) {
         // (these kernels have 1 KB of static LDS of their own: the cap of set_max_lds_ev would pass the CU's 160 KB)
-        const void *fns[3] = {(const void *)k_pe_accum<1>, (const void *)k_pe_accum<3>, (const void *)k_pe_accum<0>};
+        const void *fns[6] = {(const void *)k_pe_accum<1, false>, (const void *)k_pe_accum<3, false>, (const void *)k_pe_accum<0, false>,
+                              (const void *)k_pe_accum<1, true>, (const void *)k_pe_accum<3, true>, (const void *)k_pe_accum<0, true>};
         for (const void *fn : fns) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
+            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PE_LDS_MAX + 2048);
             if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
         }
         attr_once.mark();
     }
-    MPC_CHECK_ARG(split >= 1 && split <= 16, MPC_E_SHAPE, "1 <= split <= 16");
-    const dim3 grid(s->B * L.n_cstrips * split);
-    if (k == 1) MPC_LAUNCH(k_pe_accum<1>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
-    else if (k == 3) MPC_LAUNCH(k_pe_accum<3>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
-    else MPC_LAUNCH(k_pe_accum<0>, grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, PeTab{nullptr, 0}, (float2 *)nullptr);
+    if (gpos != nullptr && (int64_t)s->B * s->M > 0) {
+        const int e0 = mpc_zero_async(gpos, (size_t)s->B * s->M * 2 * sizeof(float), st);
+        if (e0) return e0;
+    }
+    PE_DISPATCH_TB(k_pe_accum, dim3(s->B * L.n_cstrips * split), dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k,
+                   t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
     MPC_CHECK_LAUNCH();
     return 0;
+}
+
+#define PE_PHI_K_MSG "1 <= num_basis <= 64 (<= 8 for the built-in polynomial basis)"
+#define PE_ROWS_CHECK() MPC_CHECK_ARG((s->flags & MPC_F_NO_WARP) && s->T == 1, MPC_E_UNSUPPORTED, "takes the rows of the per-event warp (MPC_F_NO_WARP), num_tref == 1")
+
+extern "C" int mpc_pe_warp(const mpc_shape *s, const float *events, const float *coef_rows, const float *phi, int32_t k,
+                           const float *t_ref, float *rows_out, void *stream) {
+    MPC_CHECK_ARG(s && coef_rows && (phi || t_ref) && rows_out && (events || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    MPC_CHECK_ARG(k >= 1 && k <= 64 && (phi || k <= PE_KMAX), MPC_E_SHAPE, PE_PHI_K_MSG);
+    return pe_warp_impl(s, events, coef_rows, phi, k, PE_NO_TAB, t_ref, rows_out, stream);
+}
+
+extern "C" int mpc_pe_grad(const mpc_shape *s, const float *rows, const float *phi, int32_t k, const float *t_ref, const float *grad_iwe,
+                           const float *scal, const float *grad_out, float *grad_coef_rows, void *stream) {
+    MPC_CHECK_ARG(s && (phi || t_ref) && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PE_ROWS_CHECK();
+    MPC_CHECK_ARG(t_ref, MPC_E_NULL, "t_ref is null");
+    MPC_CHECK_ARG(k >= 1 && k <= 64 && (phi || k <= PE_KMAX), MPC_E_SHAPE, PE_PHI_K_MSG);
+    return pe_grad_impl(s, rows, phi, k, PE_NO_TAB, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, nullptr, stream);
+}
+
+extern "C" int mpc_pe_grad_ordered(const mpc_shape *s, const float *rows, const int32_t *offsets, const float *phi, int32_t k,
+                                   const float *t_ref, const float *grad_iwe, const float *scal, const float *grad_out,
+                                   float *grad_coef_rows, int32_t split, void *stream) {
+    MPC_CHECK_ARG(s && offsets && (phi || t_ref) && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PE_ROWS_CHECK();
+    MPC_CHECK_ARG(t_ref, MPC_E_NULL, "t_ref is null");
+    MPC_CHECK_ARG(k >= 1 && k <= 64 && (phi || k <= PE_KMAX) && s->nb <= 64, MPC_E_SHAPE, PE_PHI_K_MSG ", num_bins <= 64");
+    return pe_grad_ordered_impl(s, rows, offsets, phi, k, PE_NO_TAB, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, split, nullptr, stream);
 }
 
 // ---- the table basis (basis_type='table'): the three kernels above as TAB instantiations, and the gradient w.r.t. the table ----
@@ -1186,7 +1198,7 @@ __device__ __forceinline__ long long pe_wave_sum_ll(long long v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
-template <int KB>
+template <int KB, bool TAB = true>          // (TAB: the name PE_DISPATCH gives an instantiation; there is no other)
 __global__ __launch_bounds__(PT_NT) void k_pe_table_grad(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
                                                          const float *__restrict__ coef, int S, int k,
                                                          unsigned long long *__restrict__ acc) {
@@ -1272,19 +1284,7 @@ extern "C" int mpc_pe_table_warp(const mpc_shape *s, const float *events, const 
                                  const float *t_ref, float *rows_out, void *stream) {
     MPC_CHECK_ARG(s && coef_rows && table && t_ref && rows_out && (events || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
     PE_TABLE_CHECKS("mpc_pe_table_warp");
-    int rc = mpc_validate_shape(s);
-    if (rc) return rc;
-    const int64_t total = (int64_t)s->B * s->M;
-    if (total == 0) return 0;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    hipStream_t st = (hipStream_t)stream;
-    const PeTab tb{table, S};
-    const float *phi = nullptr;
-    if (k == 1) MPC_LAUNCH((k_pe_warp<1, true>), dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
-    else if (k == 3) MPC_LAUNCH((k_pe_warp<3, true>), dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
-    else MPC_LAUNCH((k_pe_warp<0, true>), dim3(grid), dim3(256), 0, st, *s, events, coef_rows, phi, k, t_ref, rows_out, tb);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    return pe_warp_impl(s, events, coef_rows, nullptr, k, PeTab{table, S}, t_ref, rows_out, stream);
 }
 
 extern "C" int mpc_pe_table_grad(const mpc_shape *s, const float *rows, const float *table, int32_t S, int32_t k, const float *t_ref,
@@ -1292,22 +1292,8 @@ extern "C" int mpc_pe_table_grad(const mpc_shape *s, const float *rows, const fl
                                  void *stream) {
     MPC_CHECK_ARG(s && table && t_ref && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
     PE_TABLE_CHECKS("mpc_pe_table_grad");
-    int rc = mpc_validate_shape(s);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int e0 = mpc_zero_async(grad_coef_rows, (size_t)s->B * s->hq * s->wq * 2 * k * sizeof(float), st);
-    if (e0) return e0;
-    const int64_t total = (int64_t)s->B * s->M;
-    if (total == 0) return 0;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
-    const PeTab tb{table, S};
-    const float *phi = nullptr;
-    float2 *gpos = reinterpret_cast<float2 *>(grad_pos);
-    if (k == 1) MPC_LAUNCH((k_pe_grad<1, true>), dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
-    else if (k == 3) MPC_LAUNCH((k_pe_grad<3, true>), dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
-    else MPC_LAUNCH((k_pe_grad<0, true>), dim3(grid), dim3(256), 0, st, *s, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    return pe_grad_impl(s, rows, nullptr, k, PeTab{table, S}, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, reinterpret_cast<float2 *>(grad_pos),
+                        stream);
 }
 
 extern "C" int mpc_pe_table_grad_ordered(const mpc_shape *s, const float *rows, const int32_t *offsets, const float *table, int32_t S, int32_t k,
@@ -1315,38 +1301,8 @@ extern "C" int mpc_pe_table_grad_ordered(const mpc_shape *s, const float *rows, 
                                          float *grad_coef_rows, int32_t split, float *grad_pos, void *stream) {
     MPC_CHECK_ARG(s && offsets && table && t_ref && grad_iwe && scal && grad_coef_rows && (rows || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
     PE_TABLE_CHECKS("mpc_pe_table_grad_ordered");
-    int rc = mpc_validate_shape(s);
-    if (rc) return rc;
-    if (s->B == 0) return 0;
-    const mpc_ws_layout L = mpc_layout(s);
-    MPC_CHECK_ARG(L.n_cstrips > 0, MPC_E_UNSUPPORTED, "no bucketed event layout for this shape");
-    const size_t lds = (size_t)L.cstrip_rows * s->wq * 2 * k * 8;
-    MPC_CHECK_ARG(lds <= 150 * 1024, MPC_E_UNSUPPORTED, "a LUT strip's accumulators do not fit the LDS (use mpc_pe_table_grad)");
-    MPC_CHECK_ARG(split >= 1 && split <= 16, MPC_E_SHAPE, "1 <= split <= 16");
-    hipStream_t st = (hipStream_t)stream;
-    static mpc_device_once attr_once;
-    if (attr_once.need()) {
-        const void *fns[3] = {(const void *)k_pe_accum<1, true>, (const void *)k_pe_accum<3, true>, (const void *)k_pe_accum<0, true>};
-        for (const void *fn : fns) {
-            hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-            if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
-        }
-        attr_once.mark();
-    }
-    if (grad_pos != nullptr && (int64_t)s->B * s->M > 0) {
-        // (rows outside every range of the table, and rows the kernel skips, carry no gradient)
-        const int e0 = mpc_zero_async(grad_pos, (size_t)s->B * s->M * 2 * sizeof(float), st);
-        if (e0) return e0;
-    }
-    const dim3 grid(s->B * L.n_cstrips * split);
-    const PeTab tb{table, S};
-    const float *phi = nullptr;
-    float2 *gpos = reinterpret_cast<float2 *>(grad_pos);
-    if (k == 1) MPC_LAUNCH((k_pe_accum<1, true>), grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
-    else if (k == 3) MPC_LAUNCH((k_pe_accum<3, true>), grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
-    else MPC_LAUNCH((k_pe_accum<0, true>), grid, dim3(PE_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, split, offsets, rows, phi, k, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, tb, gpos);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    return pe_grad_ordered_impl(s, rows, offsets, nullptr, k, PeTab{table, S}, t_ref, grad_iwe, scal, grad_out, grad_coef_rows, split,
+                                reinterpret_cast<float2 *>(grad_pos), stream);
 }
 
 extern "C" int mpc_pe_table_basis_grad(const mpc_shape *s, const float *rows, const float *grad_pos, const float *coef_rows, int32_t S, int32_t k,
@@ -1376,9 +1332,7 @@ extern "C" int mpc_pe_table_basis_grad(const mpc_shape *s, const float *rows, co
         const int grid = (int)((total + PT_NT - 1) / PT_NT < 256 ? (total + PT_NT - 1) / PT_NT : 256);
         unsigned long long *a = reinterpret_cast<unsigned long long *>(acc);
         const float2 *gpos = reinterpret_cast<const float2 *>(grad_pos);
-        if (k == 1) MPC_LAUNCH(k_pe_table_grad<1>, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
-        else if (k == 3) MPC_LAUNCH(k_pe_table_grad<3>, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
-        else MPC_LAUNCH(k_pe_table_grad<0>, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
+        PE_DISPATCH(k_pe_table_grad, true, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
         MPC_CHECK_LAUNCH();
     }
     MPC_LAUNCH(k_pe_table_finish, dim3((nent + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(acc), S, k, t_ref, scal,
@@ -1396,7 +1350,7 @@ extern "C" int mpc_event_pos_grad(const mpc_shape *s, const float *events, const
     if (rc) return rc;
     const int64_t total = (int64_t)s->B * s->M;
     if (total == 0) return 0;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const int grid = pe_row_grid(total);
     MPC_LAUNCH(k_event_pos_grad, dim3(grid), dim3(256), 0, (hipStream_t)stream, *s, events, t_ref, grad_iwe, scal, grad_out,
                reinterpret_cast<float2 *>(grad_pos));
     MPC_CHECK_LAUNCH();

@@ -6,13 +6,13 @@
 //   k_pec_head_rows    rows[(b, cell)][0][j] = scale * up_y[j], rows[(b, cell)][1][j] = scale * up_x[j] at the tile centres
 //                      (iy * tile + tile / 2, ix * tile + tile / 2) of the 8h x 8w image (cvx_device.h: cvx_up), or of params themselves
 //                      (no mask: h x w is the tile grid).  The tile centre is never added: (centre + v) - centre is not v in fp32.
-//   k_pec_warp         rows_out = (y + fy, x + fx, t, p, cell bits, valid): the record mpc_pe_warp writes.  cell = LUT cell of the event's
-//                      own position; fy = fx = 0; for j ascending: fy += c[0][j] * phi[j], fx += c[1][j] * phi[j]; phi[j] = E_j(t_ref) - E_j(t)
+//   k_pec_warp         rows_out = (y + fy, x + fx, t, p, cell bits, valid) (pe_device.h: pe_own_cell, pe_write_row -- mpc_pe_warp's);
+//                      fy = fx = 0; for j ascending: fy += c[0][j] * phi[j], fx += c[1][j] * phi[j]; phi[j] = E_j(t_ref) - E_j(t)
 //   k_pec_accum        grad_rows[(b, cell)][a][j] = coef * sum over the cell's rows of phi[j] * gpos[row][a] for bucket-ordered rows:
-//                      one workgroup per (sample, LUT strip, pass over a chunk of orders), Q33.30 sums in LDS (ds_add_u64; the scheme
-//                      of k_pe_accum / k_pe_table_grad: bitwise reproducible), every element written once
+//                      one workgroup per (sample, LUT strip, pass over a chunk of orders), Q33.30 sums in LDS (ds_add_u64, pe_to_fixed;
+//                      strip and ranges as in k_pe_accum -- pe_device.h: bitwise reproducible), every element written once
 //   k_pec_grad_atomic  the same with global float atomics (any row order; slow -- ~20 G atomics/s -- and not reproducible)
-//   k_pec_field        field[(b, t)][cell] = (sum_j rows[.][0][j] phim[t][j], sum_j rows[.][1][j] phim[t][j]), d <= 16
+//   mpc_pec_field      k_basis_field<16> (pe_device.h)
 //   k_pec_field_adj    grad_rows[(b, cell)][a][j] += grad_out * sum_t grad_field[(b, t)][cell][a] * phim[t][j]
 //   k_pec_rows_to_*    the transposes between grad_rows and what the head's adjoint takes
 // The adjoint of "centre + v" is the adjoint of v: the head's backward with a mask IS mpc_cvx_traj_bwd (cvx_curves.hip) with the identity
@@ -23,16 +23,12 @@
 //   BEZIER      u = 1 - t;  tp_1 = t, tp_i = tp_{i-1} * t;  up_0 = 1, up_1 = u, up_i = up_{i-1} * u;  E_i = (C(d, i) * tp_i) * up_{d-i}
 //               (t = 0: every E_i is exactly 0; t = 1: E_d is exactly 1, the others exactly 0 -- the shortcut rows of curves/base.py:102-106)
 //   POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t                                (the lines of pe_phi, events.hip)
-//   TABLE       tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;
-//               E_j = T[i][j] + f * (T[i+1][j] - T[i][j])                 (the lines of pe_tab_locate / utils.table_basis_values)
-#include "common.h"
+//   TABLE       pe_tab_locate / pe_tab_lerp (pe_device.h, with the definition)
+#include "pe_device.h"
 #include "cvx_device.h"
-#include "bounds.h"
 
-#define PEC_DMAX 16
 #define PEC_NT 1024            // threads of k_pec_accum
 #define PEC_NIF 4              // rows in flight per thread of k_pec_accum
-#define PEC_LDS_MAX (150 * 1024)
 
 struct PecBasis {
     int kind, d, S;
@@ -61,14 +57,12 @@ __device__ __forceinline__ void pec_basis(const PecBasis &pb, float t, float E[P
             if (j < d) { E[j] = c; c = c * t; }
         }
     } else {
-        const float tc = fminf(fmaxf(t, 0.f), 1.f);
-        const float x = tc * (float)pb.S;
-        const int i = min((int)floorf(x), pb.S - 1);
-        const float f = x - (float)i;
+        int i; float f;
+        pe_tab_locate(t, pb.S, i, f);
         const float *r0 = pb.table + (size_t)i * d, *r1 = r0 + d;
 #pragma unroll
         for (int j = 0; j < PEC_DMAX; ++j) {
-            if (j < d) { const float a = r0[j]; const float df = r1[j] - a; E[j] = a + f * df; }
+            if (j < d) E[j] = pe_tab_lerp(r0[j], r1[j], f);
         }
     }
 }
@@ -144,9 +138,7 @@ __global__ __launch_bounds__(256) void k_pec_warp(const mpc_shape s, const float
         const int b = (int)(row / s.M);
         float e[6];
         pec_load_row(events, row, e);
-        // the LUT cell of the event's own position, as k_pe_warp computes it (focus.py:186-187)
-        const int iy = min(max((int)floorf(mpc_div_sp(e[0], s.sp)), 0), s.hq - 1), ix = min(max((int)floorf(mpc_div_sp(e[1], s.sp)), 0), s.wq - 1);
-        const int cell = (b * s.hq + iy) * s.wq + ix;
+        const int cell = pe_own_cell(b, e[0], e[1], s.sp, s.hq, s.wq);
         const float *c = coef + (size_t)cell * 2 * d;
         float E[PEC_DMAX];
         pec_basis(pb, e[2], E);
@@ -155,20 +147,11 @@ __global__ __launch_bounds__(256) void k_pec_warp(const mpc_shape s, const float
         for (int j = 0; j < PEC_DMAX; ++j) {
             if (j < d) { const float ph = Er[j] - E[j]; fy += c[j] * ph; fx += c[d + j] * ph; }
         }
-        float2 *o = reinterpret_cast<float2 *>(rows_out + row * 6);
-        o[0] = make_float2(e[0] + fy, e[1] + fx);
-        o[1] = make_float2(e[2], e[3]);
-        o[2] = make_float2(__int_as_float(cell), e[5]);
+        pe_write_row(rows_out, row, e, fy, fx, cell);
     }
 }
 
 // ---- row gradient ---------------------------------------------------------------------------------------------------------------
-// Q33.30 of one phi * gradient product, rounded to nearest (pe_to_fixed of events.hip: no bias with small event weights); |v| < 2^31
-__device__ __forceinline__ long long pec_to_fixed(float v) {
-    const float hi = truncf(v);
-    return ((long long)(int)hi << MPC_FIX_SHIFT) + (long long)__float2int_rn((v - hi) * (float)(1 << MPC_FIX_SHIFT));
-}
-
 // coef = scal[MPC_SCAL_GCOEF] (or 1) * grad_out[0] (or 1): gpos holds UNSCALED position gradients where the caller hands both over, so
 // that the fixed-point products are O(event weight x adjoint-image differences) as in k_pe_accum, whatever the loss scale
 __device__ __forceinline__ float pec_coef(const float *__restrict__ scal, const float *__restrict__ grad_out) {
@@ -185,8 +168,8 @@ __global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR
     const int pass = blockIdx.x % NPASS, bs = blockIdx.x / NPASS;
     const int b = bs / NCS, cst = bs - b * NCS;
     const int j0 = pass * KC, kc = min(KC, d - j0);
-    const int crow0 = cst * CSR, crow1 = min(crow0 + CSR, s.hq), ncell = max(crow1 - crow0, 0) * s.wq;
-    const int cell0 = (b * s.hq + crow0) * s.wq;
+    const PeStrip strip = pe_strip(b, cst, CSR, s.hq, s.wq);
+    const int ncell = strip.ncell, cell0 = strip.cell0;
     const int NK = s.nb * NCS, nrange = 2 * s.nb;
     const int nacc = ncell * 2 * kc;
     for (int i = tid; i < nacc; i += PEC_NT) s_acc[MPC_IDX(i, nacc)] = 0ull;
@@ -219,8 +202,8 @@ __global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR
         for (int u = 0; u < PEC_NIF; ++u) {
             const int q = q0 + u * PEC_NT;
             const bool on = q < n;
-            int lo = 0, hi = nrange;
-            if (on) { while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_pre[mid] <= q) lo = mid; else hi = mid; } }
+            int lo = 0;
+            if (on) lo = pe_range_of(s_pre, nrange, q);
             // (n > 0 here, so the sample has a row 0: a lane past the end loads it and drops it)
             const size_t row = (size_t)b * s.M + (on ? s_r0[lo] + (q - s_pre[lo]) : 0);
             g[u] = gpos[row];
@@ -239,8 +222,8 @@ __global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR
             for (int j = 0; j < PEC_DMAX; ++j) {
                 if (j >= j0 && j < j0 + kc) {
                     const float ph = Er[j] - E[j];
-                    atomicAdd(a + MPC_IDX(j - j0, kc), (unsigned long long)pec_to_fixed(ph * g[u].x));
-                    atomicAdd(a + MPC_IDX(kc + j - j0, 2 * kc), (unsigned long long)pec_to_fixed(ph * g[u].y));
+                    atomicAdd(a + MPC_IDX(j - j0, kc), (unsigned long long)pe_to_fixed(ph * g[u].x));
+                    atomicAdd(a + MPC_IDX(kc + j - j0, 2 * kc), (unsigned long long)pe_to_fixed(ph * g[u].y));
                 }
             }
         }
@@ -281,29 +264,6 @@ __global__ __launch_bounds__(256) void k_pec_grad_atomic(const mpc_shape s, cons
 }
 
 // ---- smoothness field and its adjoint -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pec_field(const float *__restrict__ rows, const float *__restrict__ phim, float *__restrict__ field,
-                                                   int B, int G, int d, int nbm) {
-    __shared__ float s_phi[64 * PEC_DMAX];
-    for (int i = threadIdx.x; i < nbm * d; i += 256) s_phi[i] = phim[i];
-    __syncthreads();
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (b, cell)
-    if (i >= (long long)B * G) return;
-    const int b = (int)(i / G), cell = (int)(i - (long long)b * G);
-    float cy[PEC_DMAX], cx[PEC_DMAX];
-#pragma unroll
-    for (int j = 0; j < PEC_DMAX; ++j) {
-        cy[j] = j < d ? rows[(size_t)i * 2 * d + j] : 0.f;
-        cx[j] = j < d ? rows[(size_t)i * 2 * d + d + j] : 0.f;
-    }
-    for (int t = 0; t < nbm; ++t) {
-        float fy = 0.f, fx = 0.f;
-#pragma unroll
-        for (int j = 0; j < PEC_DMAX; ++j)
-            if (j < d) { fy += cy[j] * s_phi[t * d + j]; fx += cx[j] * s_phi[t * d + j]; }
-        reinterpret_cast<float2 *>(field)[((size_t)b * nbm + t) * G + cell] = make_float2(fy, fx);
-    }
-}
-
 __global__ __launch_bounds__(256) void k_pec_field_adj(const float *__restrict__ gfield, const float *__restrict__ phim,
                                                        const float *__restrict__ gout, float *__restrict__ grows, int B, int G, int d, int nbm) {
     __shared__ float s_phi[64 * PEC_DMAX];
@@ -367,7 +327,7 @@ static int pec_make_basis(const char *who, int basis, int d, const float *table,
 static int pec_orders_per_pass(const mpc_shape *s, const mpc_ws_layout &L, int d) {
     if (L.n_cstrips <= 0 || L.cstrip_rows <= 0) return 0;
     const int64_t per_order = (int64_t)L.cstrip_rows * s->wq * 2 * 8;
-    const int64_t kc = PEC_LDS_MAX / per_order;
+    const int64_t kc = PE_LDS_MAX / per_order;
     return (int)(kc < d ? kc : d);
 }
 
@@ -466,7 +426,7 @@ extern "C" int mpc_pec_warp(const mpc_shape *s, const float *events, const float
     if (rc) return rc;
     const int64_t total = (int64_t)s->B * s->M;
     if (total == 0) return 0;
-    const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const int grid = pe_row_grid(total);
     MPC_LAUNCH(k_pec_warp, dim3(grid), dim3(256), 0, (hipStream_t)stream, *s, events, rows, pb, t_ref, rows_out);
     MPC_CHECK_LAUNCH();
     return 0;
@@ -489,7 +449,7 @@ extern "C" int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, c
         if (e0) return e0;
         const int64_t total = (int64_t)s->B * s->M;
         if (total == 0) return 0;
-        const int grid = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+        const int grid = pe_row_grid(total);
         MPC_LAUNCH(k_pec_grad_atomic, dim3(grid), dim3(256), 0, st, *s, rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal,
                    grad_out, grad_rows);
         MPC_CHECK_LAUNCH();
@@ -506,7 +466,7 @@ extern "C" int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, c
     static mpc_device_once attr_once;
     if (attr_once.need()) {
         // (the kernel has 1 KB of static LDS of its own)
-        hipError_t e = hipFuncSetAttribute((const void *)k_pec_accum, hipFuncAttributeMaxDynamicSharedMemorySize, PEC_LDS_MAX + 2048);
+        hipError_t e = hipFuncSetAttribute((const void *)k_pec_accum, hipFuncAttributeMaxDynamicSharedMemorySize, PE_LDS_MAX + 2048);
         if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
         attr_once.mark();
     }
@@ -526,13 +486,7 @@ extern "C" int32_t mpc_pec_rows_grad_passes(const mpc_shape *s, int32_t d, int32
 }
 
 extern "C" int mpc_pec_field(const float *rows, const float *phim, float *field, int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream) {
-    MPC_CHECK_ARG(rows && phim && field, MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG(B >= 0 && G >= 0 && d >= 1 && nbm >= 1, MPC_E_SHAPE, "bad shape");
-    MPC_CHECK_ARG(d <= PEC_DMAX && nbm <= 64, MPC_E_UNSUPPORTED, "more than 16 orders or 64 field times");
-    if ((long long)B * G == 0) return 0;
-    MPC_LAUNCH(k_pec_field, dim3((unsigned)(((long long)B * G + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, phim, field, B, G, d, nbm);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    return pe_field_run<PEC_DMAX>(__func__, "more than 16 orders or 64 field times", rows, phim, field, B, G, d, nbm, stream);
 }
 
 extern "C" int mpc_pec_field_adjoint(const float *grad_field, const float *phim, const float *grad_out, float *grad_rows,

@@ -6,11 +6,11 @@
 // bound by the host (0.74-0.97 ms).  Four kernels; every global access coalesced over the tiles / pixels.
 //   k_tile_rows        rows[(b, iy, ix)][c]      = sum_s grid[b][s][c][iy * tile + tile / 2][ix * tile + tile / 2]
 //   k_tile_rows_bwd    ggrid[b][s][c][y][x]      = grows[(b, y / tile, x / tile)][c] at a tile centre, else 0  (EVERY element written)
-//   k_basis_field      field[(b, t)][cell][d]    = sum_j rows[(b, cell)][d][j] phim[t][j]            (the layout mpc_lut_smooth takes)
+//   k_basis_field<8>   field[(b, t)][cell][d]    = sum_j rows[(b, cell)][d][j] phim[t][j]            (pe_device.h: the curves' field is <16>)
 //   k_rows_grad_finish out[(b, cell)][d][j]      = sum_split gp[split][(b, cell)][d][j] + gout * sum_t gfield[(b, t)][cell][d] phim[t][j]
-#include "common.h"
+#include "pe_device.h"
 
-#define TILE_KMAX 8            // basis orders per axis (mpc_pe_warp's register variant holds as many)
+#define TILE_KMAX PE_KMAX      // basis orders per axis (mpc_pe_warp's register variant holds as many)
 
 __global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ grid, float *__restrict__ rows, int B, int S, int c2, int H, int W,
                                                    int tile, int hq, int wq) {
@@ -54,29 +54,6 @@ __global__ __launch_bounds__(256) void k_tile_rows_bwd(const float *__restrict__
         if ((W & 3) == 0) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
         else
             for (int u = 0; u < 4 && 4 * x4 + u < W; ++u) dst[u] = v[u];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_basis_field(const float *__restrict__ rows, const float *__restrict__ phim, float *__restrict__ field,
-                                                     int B, int G, int k, int nb) {
-    __shared__ float s_phi[64 * TILE_KMAX];
-    for (int i = threadIdx.x; i < nb * k; i += 256) s_phi[i] = phim[i];
-    __syncthreads();
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // (b, cell)
-    if (i >= (long long)B * G) return;
-    const int b = (int)(i / G), cell = (int)(i - (long long)b * G);
-    float cy[TILE_KMAX], cx[TILE_KMAX];
-#pragma unroll
-    for (int j = 0; j < TILE_KMAX; ++j) {
-        cy[j] = j < k ? rows[(size_t)i * 2 * k + j] : 0.f;
-        cx[j] = j < k ? rows[(size_t)i * 2 * k + k + j] : 0.f;
-    }
-    for (int t = 0; t < nb; ++t) {
-        float fy = 0.f, fx = 0.f;
-#pragma unroll
-        for (int j = 0; j < TILE_KMAX; ++j)
-            if (j < k) { fy += cy[j] * s_phi[t * k + j]; fx += cx[j] * s_phi[t * k + j]; }
-        reinterpret_cast<float2 *>(field)[((size_t)b * nb + t) * G + cell] = make_float2(fy, fx);
     }
 }
 
@@ -186,13 +163,7 @@ extern "C" int mpc_pe_tile_rows_bwd(const float *grad_rows, float *grad_grid, in
 }
 
 extern "C" int mpc_pe_basis_field(const float *rows, const float *phim, float *field, int32_t B, int32_t G, int32_t k, int32_t nb, void *stream) {
-    MPC_CHECK_ARG(rows && phim && field, MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG(B >= 0 && G >= 0 && k >= 1 && nb >= 1, MPC_E_SHAPE, "bad shape");
-    MPC_CHECK_ARG(k <= TILE_KMAX && nb <= 64, MPC_E_UNSUPPORTED, "more than 8 basis orders or 64 time bins");
-    if ((long long)B * G == 0) return 0;
-    MPC_LAUNCH(k_basis_field, dim3((unsigned)(((long long)B * G + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, phim, field, B, G, k, nb);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    return pe_field_run<TILE_KMAX>(__func__, "more than 8 basis orders or 64 time bins", rows, phim, field, B, G, k, nb, stream);
 }
 
 extern "C" int mpc_pe_rows_grad_finish(const float *grad_parts, int32_t split, const float *grad_field, const float *phim, const float *grad_out,

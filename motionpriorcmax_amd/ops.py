@@ -904,17 +904,40 @@ def pe_table_supported(cfg, events, num_pos, k, samples):
     return _query('mpc_pe_table_supported', events.device, ctypes.byref(shape), int(k), int(samples)) == 1
 
 
-def _pe_fwd(shape, ev, coef_rows, ph, k, tr, ws, need_grad, tab=None):
-    """The per-event forward core: mpc_pe_warp (`tab` [S + 1, k]: mpc_pe_table_warp) -> mpc_event_splat_fwd (MPC_F_NO_WARP) ->
-    mpc_contrast_fwd -> (warped rows, blurred images, adjoint images or None)."""
+def _pe_tail(cfg, shape, rows, tr, ws, need_grad, field=None):
+    """What every fused per-event node runs on its warped rows: mpc_event_splat_fwd (MPC_F_NO_WARP) -> mpc_contrast_fwd
+    [-> `field` = (entry point, tile rows, phim [nbm, k], k): the smoothness field -> mpc_lut_smooth] -> mpc_finalize ->
+    (blurred images, adjoint images or None, gradient of the field or None, scalars)."""
+    raw = event_splat_fwd(shape, rows, None, tr, ws)
+    blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
+    g_field, s_nimg = None, 0
+    if field is not None:
+        name, c_rows, pm, k = field
+        nbm = pm.shape[0]
+        s_nimg = shape.B * nbm
+        fld = torch.empty((s_nimg, shape.hq, shape.wq, 2), dtype=torch.float32, device=rows.device)
+        _call(name, rows.device, _ptr(c_rows), _ptr(pm), _ptr(fld), shape.B, shape.hq * shape.wq, k, nbm)
+        g_field = lut_smooth(shape, fld, s_nimg, 2, cfg.smooth_weight, ws, need_grad)
+    scal = finalize(shape, s_nimg, 2 if s_nimg else 0, cfg.smooth_weight if s_nimg else 0.0, ws, rows.device)
+    return blur, gimg, g_field, scal
+
+
+def _pe_outputs(ctx, scal, blur):
+    """(loss, focus, smooth, blur) of a fused per-event node from the scalars of _pe_tail: one copy of three floats."""
+    out = scal[:3].clone()
+    loss, focus, smooth = out[C.SCAL_LOSS], out[C.SCAL_FOCUS], out[C.SCAL_SMOOTH]
+    ctx.mark_non_differentiable(focus, smooth, blur)
+    return loss, focus, smooth, blur
+
+
+def _pe_fwd(cfg, shape, ev, coef_rows, ph, k, tr, ws, need_grad, tab=None, field=None):
+    """The per-event forward core: mpc_pe_warp (`tab` [S + 1, k]: mpc_pe_table_warp) -> _pe_tail -> (warped rows, *its results)."""
     rows = torch.empty_like(ev)
     if shape.B * shape.M > 0 and tab is not None:
         _call('mpc_pe_table_warp', ev.device, ctypes.byref(shape), _ptr(ev), _ptr(coef_rows), _ptr(tab), tab.shape[0] - 1, k, _ptr(tr), _ptr(rows))
     elif shape.B * shape.M > 0:               # (an empty tensor has no pointer to hand over)
         _call('mpc_pe_warp', ev.device, ctypes.byref(shape), _ptr(ev), _ptr(coef_rows), _ptr(ph), k, _ptr(tr), _ptr(rows))
-    raw = event_splat_fwd(shape, rows, None, tr, ws)
-    blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
-    return rows, blur, gimg
+    return (rows,) + _pe_tail(cfg, shape, rows, tr, ws, need_grad, field)
 
 
 def _pe_ordered_offsets(offsets, cfg, shape, k, dev):
@@ -975,8 +998,7 @@ class PerEventBasisFocusFn(torch.autograd.Function):
         if tuple(cr.shape) != (B * shape.hq * shape.wq, 2 * k) or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coef_rows {tuple(cr.shape)} / phi do not match [B*hq*wq, 2k] / [B, M, k] (k <= 8 without phi)')
         ws = alloc_workspace(shape, dev)
-        rows, blur, gimg = _pe_fwd(shape, ev, cr, ph, k, tr, ws, need_grad)
-        scal = finalize(shape, 0, 0, 0.0, ws, dev)
+        rows, blur, gimg, _, scal = _pe_fwd(cfg, shape, ev, cr, ph, k, tr, ws, need_grad)
         ctx.shape, ctx.k = shape, k
         offs = _pe_ordered_offsets(offsets, cfg, shape, k, dev)
         ctx.has_offs = offs is not None
@@ -1033,22 +1055,14 @@ class PerEventBasisCalcFn(torch.autograd.Function):
             need_grad = need_grad or table.requires_grad or (phim is not None and phim.requires_grad)
         Bc, S, c2, H, W = cg.shape
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
-        hq, wq = shape.hq, shape.wq
-        G = hq * wq
+        G = shape.hq * shape.wq
         if Bc != B or c2 != 2 * k or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coeff_grid {tuple(cg.shape)} / phi do not match [B, S, 2k, H, W] / [B, M, k] (k <= 8 without phi)')
         c_rows = torch.empty((B * G, 2 * k), dtype=torch.float32, device=dev)
         _call('mpc_pe_tile_rows', dev, _ptr(cg), _ptr(c_rows), B, S, c2, H, W, tile)
         ws = alloc_workspace(shape, dev)
-        rows, blur, gimg = _pe_fwd(shape, ev, c_rows, ph, k, tr, ws, need_grad, tab)
-        g_field, s_nimg = None, 0
-        if pm is not None and cfg.smooth_weight > 0:
-            nb = pm.shape[0]
-            field = torch.empty((B * nb, hq, wq, 2), dtype=torch.float32, device=dev)
-            _call('mpc_pe_basis_field', dev, _ptr(c_rows), _ptr(pm), _ptr(field), B, G, k, nb)
-            s_nimg = B * nb
-            g_field = lut_smooth(shape, field, s_nimg, 2, cfg.smooth_weight, ws, need_grad)
-        scal = finalize(shape, s_nimg, 2 if s_nimg else 0, cfg.smooth_weight if s_nimg else 0.0, ws, dev)
+        field = ('mpc_pe_basis_field', c_rows, pm, k) if pm is not None and cfg.smooth_weight > 0 else None
+        rows, blur, gimg, g_field, scal = _pe_fwd(cfg, shape, ev, c_rows, ph, k, tr, ws, need_grad, tab, field)
         offs = _pe_ordered_offsets(offsets, cfg, shape, k, dev)
         ctx.shape, ctx.k, ctx.tile, ctx.grid_shape = shape, k, tile, (B, S, c2, H, W)
         ctx.has = (ph is not None, pm is not None and g_field is not None, offs is not None)
@@ -1059,10 +1073,7 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         ctx.save_for_backward(rows, ph if ph is not None else none, tr, gimg if gimg is not None else none, scal,
                               offs if offs is not None else none, g_field if g_field is not None else none, pm if pm is not None else none,
                               tab if tab is not None else none, c_rows if tab is not None else none)
-        out = scal[:3].clone()
-        loss, focus, smooth = out[C.SCAL_LOSS], out[C.SCAL_FOCUS], out[C.SCAL_SMOOTH]
-        ctx.mark_non_differentiable(focus, smooth, blur)
-        return loss, focus, smooth, blur
+        return _pe_outputs(ctx, scal, blur)
 
     @staticmethod
     def backward(ctx, g_loss, g_focus, g_smooth, g_blur):
@@ -1169,16 +1180,8 @@ class PerEventCurvesFn(torch.autograd.Function):
         rows = torch.empty_like(ev)
         if B * M > 0:                                 # (an empty tensor has no pointer to hand over)
             _call('mpc_pec_warp', dev, ctypes.byref(shape), _ptr(ev), _ptr(c_rows), kind, d, _ptr(tab), S, _ptr(tr), _ptr(rows))
-        raw = event_splat_fwd(shape, rows, None, tr, ws)
-        blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
-        g_field, s_nimg = None, 0
-        if pm is not None and cfg.smooth_weight > 0 and pm.shape[0] > 0:
-            nbm = pm.shape[0]
-            field = torch.empty((B * nbm, hq, wq, 2), dtype=torch.float32, device=dev)
-            _call('mpc_pec_field', dev, _ptr(c_rows), _ptr(pm), _ptr(field), B, G, d, nbm)
-            s_nimg = B * nbm
-            g_field = lut_smooth(shape, field, s_nimg, 2, cfg.smooth_weight, ws, need_grad)
-        scal = finalize(shape, s_nimg, 2 if s_nimg else 0, cfg.smooth_weight if s_nimg else 0.0, ws, dev)
+        field = ('mpc_pec_field', c_rows, pm, d) if pm is not None and cfg.smooth_weight > 0 and pm.shape[0] > 0 else None
+        blur, gimg, g_field, scal = _pe_tail(cfg, shape, rows, tr, ws, need_grad, field)
         offs = _check_offsets(offsets, cfg, shape, dev) if (offsets is not None and sup & 2) else None
         ctx.shape, ctx.dims = shape, (B, d, h, w, kind, S, float(scale), int(tile), int(orders_per_pass))
         ctx.has = (m is not None, g_field is not None, offs is not None, tab is not None)
@@ -1187,10 +1190,7 @@ class PerEventCurvesFn(torch.autograd.Function):
         ctx.save_for_backward(p, m if m is not None else none, rows, tr, gimg if gimg is not None else none, scal,
                               offs if offs is not None else none, g_field if g_field is not None else none,
                               pm if pm is not None else none, tab if tab is not None else none)
-        out = scal[:3].clone()
-        loss, focus, smooth = out[C.SCAL_LOSS], out[C.SCAL_FOCUS], out[C.SCAL_SMOOTH]
-        ctx.mark_non_differentiable(focus, smooth, blur)
-        return loss, focus, smooth, blur
+        return _pe_outputs(ctx, scal, blur)
 
     @staticmethod
     def backward(ctx, g_loss, g_focus, g_smooth, g_blur):

@@ -152,6 +152,60 @@ def test_polynomial_curves_equal_the_per_event_basis_warp_bit_for_bit(d):
     assert (gp - want).abs().max() <= 1e-5 * want.abs().max()
 
 
+@pytest.mark.parametrize('S', [1, 4])
+@pytest.mark.parametrize('k', [1, 3, 5])
+def test_table_curves_equal_the_table_basis_warp_bit_for_bit(k, S):
+    """TABLE curves against the tabulated basis warp through the C entry points, on the same bucket-ordered events, tile rows,
+    table and t_ref: both families interpolate the table with pe_tab_locate / pe_tab_lerp and accumulate with pe_to_fixed
+    (csrc/pe_device.h), so the warped rows and the tile gradients agree bit for bit.  k: one per KB instantiation of the basis
+    kernels; the event times include 0, 1, every knot i / S and one value just below a knot.  The gradients: mpc_pec_rows_grad
+    on the position gradient that mpc_pe_table_grad_ordered (split = 1, grad_out = 1) leaves behind from the same adjoint image."""
+    from motionpriorcmax_amd import _lib as C, ops
+    dev = _dev()
+    shape, sp, Bn, M = (16, 24), 4, 2, 400
+    L = _loss(PC.loss_cfg('l2', image_shape=shape, lut_superpixel_size=sp))
+    ev, num_pos = PC.O.synth_events(Bn, M, shape, PC.NB, seed=13, pad_frac=0.1)
+    knots = [i / S for i in range(S + 1)]
+    below = float(torch.nextafter(torch.tensor(knots[-1] if S == 1 else knots[S // 2]), torch.tensor(0.0)))
+    for blk in (0, num_pos):                                      # (both polarities)
+        for i, t in enumerate(knots + [below]):
+            ev[:, blk + 3 * i, 2] = t
+    ev[..., 4] = torch.clamp(torch.floor(ev[..., 2] * PC.NB), 0, PC.NB - 1) * ev[..., 5]
+    ob = L.order_events({'events': ev.to(dev), 'num_pos_events': num_pos})
+    evd, offs = ob['events'], ob['event_offsets']
+    times = set(evd[..., 2][evd[..., 5] != 0].tolist())
+    assert {0.0, 1.0, below} | set(float(torch.tensor(t, dtype=torch.float32)) for t in knots) <= times
+    sh = ops._pec_shape(L._cfg, evd, num_pos)
+    assert ops._query('mpc_pe_grad_ordered_supported', dev, ctypes.byref(sh), k) == 1 and ops._lut_strips(sh, dev) >= 1
+    n = sh.B * sh.hq * sh.wq
+    g = torch.Generator().manual_seed(100 * k + S)
+    rows = (torch.randn(n, 2 * k, generator=g) * 3).to(dev)
+    table = torch.randn(S + 1, k, generator=g).to(dev)
+    tr = torch.full((1,), 0.41, dtype=torch.float32, device=dev)
+    out_c, out_t = torch.empty_like(evd), torch.empty_like(evd)
+    ops._call('mpc_pec_warp', dev, ctypes.byref(sh), ops._ptr(evd), ops._ptr(rows), ops.PEC_BASIS['TABLE'], k, ops._ptr(table), S, ops._ptr(tr),
+              ops._ptr(out_c))
+    ops._call('mpc_pe_table_warp', dev, ctypes.byref(sh), ops._ptr(evd), ops._ptr(rows), ops._ptr(table), S, k, ops._ptr(tr), ops._ptr(out_t))
+    print(f'k={k} S={S}: warped rows differ in {int((out_c.view(torch.int32) != out_t.view(torch.int32)).sum())} of {out_c.numel()} elements')
+    assert torch.equal(out_c.view(torch.int32), out_t.view(torch.int32))          # (bit patterns: column 4 holds the cell index)
+    assert float((out_t[..., :2] - evd[..., :2]).abs().max()) > 0
+    # the gradients, from one adjoint image (two polarity planes per sample)
+    gimg = torch.randn(Bn * 2, *shape, generator=g).to(dev)
+    scal = torch.ones(C.SCAL_COUNT, dtype=torch.float32, device=dev)
+    one = torch.ones(1, dtype=torch.float32, device=dev)
+    g_t = torch.empty(1, n, 2 * k, device=dev)
+    gpos = torch.empty(Bn, M, 2, device=dev)
+    ops._call('mpc_pe_table_grad_ordered', dev, ctypes.byref(sh), ops._ptr(out_t), ops._ptr(offs), ops._ptr(table), S, k, ops._ptr(tr), ops._ptr(gimg),
+              ops._ptr(scal), ops._ptr(one), ops._ptr(g_t), 1, ops._ptr(gpos))
+    g_c = torch.empty(n, 2 * k, device=dev)
+    ops._call('mpc_pec_rows_grad', dev, ctypes.byref(sh), ops._ptr(out_c), ops._ptr(offs), ops._ptr(gpos), ops.PEC_BASIS['TABLE'], k, ops._ptr(table), S,
+              ops._ptr(tr), ops._ptr(scal), ops._ptr(one), 0, ops._ptr(g_c))
+    print(f'k={k} S={S}: tile gradients differ in {int((g_c != g_t[0]).sum())} of {g_c.numel()} elements, '
+          f'largest |difference| {float((g_c - g_t[0]).abs().max()):.3e} of {float(g_t.abs().max()):.3e}')
+    assert float(g_t.abs().max()) > 0 and int((gpos != 0).any(-1).sum()) > M // 2
+    assert torch.equal(g_c, g_t[0])
+
+
 def test_ordered_backward_is_reproducible():
     dev = _dev()
     name = 'bezier10'

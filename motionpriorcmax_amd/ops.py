@@ -1443,7 +1443,8 @@ class CvxCurveTrajFn(torch.autograd.Function):
         nty, ntx = ((v - s + tile - 1) // tile if v > s else 0 for v in (8 * h, 8 * w))          # (the count of the tile mask's centres)
         n = nty * ntx
         traj = torch.empty((B, T, n, 2), dtype=torch.float32, device=dev)
-        _call('mpc_cvx_traj_fwd', dev, _ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile)
+        if B * n > 0:                                 # (an empty tensor has no pointer to hand over: 8h or 8w within half a tile)
+            _call('mpc_cvx_traj_fwd', dev, _ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile)
         ctx.save_for_backward(p, m, bm)
         ctx.dims = (B, d, T, h, w, tile, float(scale))
         return traj
@@ -1455,6 +1456,9 @@ class CvxCurveTrajFn(torch.autograd.Function):
         g = _f32c(g)
         dev = g.device
         gp = gm = ws = None
+        if g.numel() == 0:                            # no tile centre (or B = 0): no cotangent to hand over, and nothing reaches the inputs
+            return (torch.zeros_like(p) if ctx.needs_input_grad[0] else None, torch.zeros_like(m) if ctx.needs_input_grad[1] else None,
+                    None, None, None)
         if ctx.needs_input_grad[0]:
             gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
             ws = torch.empty(max(_query('mpc_cvx_traj_bwd_workspace_bytes', dev, B, d, T, h, w, tile), 4) // 4, dtype=torch.float32, device=dev)

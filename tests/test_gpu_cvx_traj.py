@@ -3,7 +3,12 @@ utils.flows_from_bezier -> ops.cvx_flows (csrc/cvx_curves.hip: mpc_cvx_traj_fwd 
 fixtures of the unmodified reference (tools/gen_golden_cvx.py), at the tolerance rule of tests/test_cvx_traj_host.py: for every
 tensor max |X_gpu - X_fp64| <= max(4 * err_X, 2^-22 * max |X_fp64|) with err_X the reference's own fp32 error from the fixture;
 `traj` gets half an ulp of its largest coordinate on top of the flows' tolerance for its one add.  Every figure is printed before
-it is asserted (pytest -s shows them)."""
+it is asserted (pytest -s shows them).
+
+These bounds are one figure per tensor on five small inputs.  The kernels are held per element -- bit for bit on exact inputs, per
+element under a counted rounding bound on weighted ones, at the fill chunks, tiles, basis sizes and template edges the fixtures do
+not reach -- by tests/test_gpu_cvx_cases.py with tests/cvx_cases.py (cases, references, a restatement of the index arithmetic) and
+tests/test_cvx_cases_host.py (census and mutants, on the CPU)."""
 import ctypes
 
 import numpy as np

@@ -296,9 +296,22 @@ int mpc_pe_field_basis_grad(const float *grad_field, const float *coef_rows, con
  *   MPC_PEC_POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t
  *   MPC_PEC_TABLE       table [S + 1][d]:  tc = min(max(t, 0), 1);  x = tc * (float)S;  i = min((int)floorf(x), S - 1);  f = x - (float)i;
  *                       E_j = T[i][j] + f * (T[i+1][j] - T[i][j])
+ *   MPC_PEC_BSPLINE     the clamped (open-uniform) cubic B-spline of d + 1 control points (P0 = 0), L = d - 2 spans, 3 <= d; no table:
+ *                         tc = min(max(t, 0), 1);  x = tc * (float)L;  s = min((int)floorf(x), L - 1)
+ *                         u(k) = (float)min(max(s + k, 0), L)          scaled knots, exact small integers, k = -2..3
+ *                         N_0 = 1
+ *                         for j = 1..3:  saved = 0
+ *                             for r = 0..j-1:
+ *                                 right = u(r+1) - x;   left = x - u(1-j+r);   den = u(r+1) - u(1-j+r)      (den is 1, 2 or 3, never 0)
+ *                                 temp = N_r / den;     N_r = saved + right * temp;     saved = left * temp
+ *                             N_j = saved
+ *                         E_{s-1+q} = N_q, q = 0..3   (index -1 is P0 and is dropped);   every other E_j = +0
+ *                       (the division correctly rounded.)  t = 0: every E_j is exactly 0; t = 1: E_d is exactly 1, the others exactly 0;
+ *                       at most 4 of the d are non-zero: mpc_pec_warp reads only the coefficient pairs whose phi_j is not 0 (at most 8;
+ *                       the same bits as the dense sum for finite coefficients), mpc_pec_rows_grad adds nothing for the others.
  *   phi_j = E_j(t_ref[0]) - E_j(t_event)
  * mpc_pec_supported     the one copy of the limits: 0 = not served; bit 0: (shape, d, basis, S) is served -- MPC_F_NO_WARP, num_tref == 1,
- *                       1 <= d <= 16, num_bins <= 64, a table with (S + 1) * d <= mpc_pe_table_limit(); bit 1: mpc_pec_rows_grad also
+ *                       1 <= d <= 16 (MPC_PEC_BSPLINE: 3 <= d <= 16), num_bins <= 64, a table with (S + 1) * d <= mpc_pe_table_limit(); bit 1: mpc_pec_rows_grad also
  *                       serves an offsets table (one order of a LUT strip's accumulators fits the LDS)
  * mpc_pec_head_rows     rows [B*G][2][d]:  rows[(b, cell)][0][j] = scale * up_y[j],  rows[(b, cell)][1][j] = scale * up_x[j]  at the tile
  *                       centres (iy * tile + tile / 2, ix * tile + tile / 2) of the 8h x 8w image, up as for mpc_cvx_traj_fwd; the centre
@@ -324,6 +337,7 @@ int mpc_pe_field_basis_grad(const float *grad_field, const float *coef_rows, con
 #define MPC_PEC_BEZIER     0
 #define MPC_PEC_POLYNOMIAL 1
 #define MPC_PEC_TABLE      2
+#define MPC_PEC_BSPLINE    3
 int32_t mpc_pec_supported(const mpc_shape *s, int32_t d, int32_t basis, int32_t S);
 int mpc_pec_head_rows(const float *params, const float *mask, float scale, int32_t tile, float *rows,
                       int32_t B, int32_t d, int32_t h, int32_t w, void *stream);

@@ -12,6 +12,8 @@
 //                      one workgroup per (sample, LUT strip, pass over a chunk of orders), Q33.30 sums in LDS (ds_add_u64, pe_to_fixed;
 //                      strip and ranges as in k_pe_accum -- pe_device.h: bitwise reproducible), every element written once
 //   k_pec_grad_atomic  the same with global float atomics (any row order; slow -- ~20 G atomics/s -- and not reproducible)
+//   k_pec_*_bsp        the three kernels above for the cubic B-spline (the same bodies, instantiated without the other kinds: those
+//                      run exactly the code they ran before the B-spline existed)
 //   mpc_pec_field      k_basis_field<16> (pe_device.h)
 //   k_pec_field_adj    grad_rows[(b, cell)][a][j] += grad_out * sum_t grad_field[(b, t)][cell][a] * phim[t][j]
 //   k_pec_rows_to_*    the transposes between grad_rows and what the head's adjoint takes
@@ -24,6 +26,21 @@
 //               (t = 0: every E_i is exactly 0; t = 1: E_d is exactly 1, the others exactly 0 -- the shortcut rows of curves/base.py:102-106)
 //   POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t                                (the lines of pe_phi, events.hip)
 //   TABLE       pe_tab_locate / pe_tab_lerp (pe_device.h, with the definition)
+//   BSPLINE     the clamped (open-uniform) cubic B-spline of d + 1 control points (P0 = 0), L = d - 2 spans, d >= 3 (pec_bspline):
+//                 tc = min(max(t, 0), 1);  x = tc * (float)L;  s = min((int)floorf(x), L - 1)
+//                 u(k) = (float)min(max(s + k, 0), L)          scaled knots, exact small integers, k = -2..3
+//                 N_0 = 1
+//                 for j = 1..3:  saved = 0
+//                     for r = 0..j-1:
+//                         right = u(r+1) - x;   left = x - u(1-j+r);   den = u(r+1) - u(1-j+r)      (den is 1, 2 or 3, never 0)
+//                         temp = N_r / den;     N_r = saved + right * temp;     saved = left * temp
+//                     N_j = saved
+//                 E_{s-1+q} = N_q, q = 0..3   (index -1 is P0 and is dropped);   every other E_j = +0
+//               (the division is the correctly rounded one: hipcc's default for fp32.  t = 0: every E_j is exactly 0 -- left = 0 in
+//               every `saved`; t = 1: right = 0 everywhere, E_d is exactly 1, the others exactly 0.)  At most 4 of the d are non-zero,
+//               so phi_j is exactly +0 outside the windows of t_ref and t: k_pec_warp reads the coefficient pairs of the others only
+//               (c * 0 added to a sum that starts at +0 never changes it for finite c: the same bits as the dense sum), the two
+//               gradient kernels add nothing for them (a zero in the integer sums; +-0 in the float atomics).
 #include "pe_device.h"
 #include "cvx_device.h"
 
@@ -36,9 +53,44 @@ struct PecBasis {
     float binom[PEC_DMAX];     // C(d, j + 1), exact in fp32 (d <= 16: at most 12870)
 };
 
+// the four non-zero functions s .. s + 3 (of the d + 1; function 0 belongs to P0) of the cubic B-spline at t; returns the span s
+__device__ __forceinline__ int pec_bspline(int d, float t, float N[4]) {
+    const int L = d - 2;
+    const float tc = fminf(fmaxf(t, 0.f), 1.f);
+    const float x = tc * (float)L;
+    const int s = min((int)floorf(x), L - 1);
+    float u[6];                                          // u[k + 2] = u(k)
+#pragma unroll
+    for (int k = -2; k <= 3; ++k) u[k + 2] = (float)min(max(s + k, 0), L);
+    N[0] = 1.f;
+#pragma unroll
+    for (int j = 1; j <= 3; ++j) {
+        float saved = 0.f;
+#pragma unroll
+        for (int r = 0; r < j; ++r) {
+            const float right = u[r + 3] - x, left = x - u[3 - j + r], den = u[r + 3] - u[3 - j + r];
+            const float temp = N[r] / den;
+            N[r] = saved + right * temp;
+            saved = left * temp;
+        }
+        N[j] = saved;
+    }
+    return s;
+}
+
+// BSP: the B-spline has kernels of its own (k_pec_*_bsp), so that the three other kinds run the code they ran before it existed
+template <bool BSP>
 __device__ __forceinline__ void pec_basis(const PecBasis &pb, float t, float E[PEC_DMAX]) {
     const int d = pb.d;
-    if (pb.kind == MPC_PEC_BEZIER) {
+    if constexpr (BSP) {
+        float N[4];
+        const int s = pec_bspline(d, t, N);
+#pragma unroll
+        for (int j = 0; j < PEC_DMAX; ++j) {
+            const int q = j + 1 - s;                     // (s + 3 <= d: every j >= d gets 0)
+            E[j] = q == 0 ? N[0] : q == 1 ? N[1] : q == 2 ? N[2] : q == 3 ? N[3] : 0.f;
+        }
+    } else if (pb.kind == MPC_PEC_BEZIER) {
         const float u = 1.f - t;
         float tp = t;
 #pragma unroll
@@ -128,11 +180,25 @@ __global__ __launch_bounds__(256) void k_pec_rows_to_params(const float *__restr
 }
 
 // ---- warp -----------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pec_warp(const mpc_shape s, const float *__restrict__ events, const float *__restrict__ coef,
-                                                  const PecBasis pb, const float *__restrict__ t_ref, float *__restrict__ rows_out) {
+// the flow of one event, j ascending.  SPARSE (the B-spline): an order whose phi_j is exactly 0 is not read -- at most 8 of d remain
+template <bool SPARSE>
+__device__ __forceinline__ void pec_flow(const float *__restrict__ c, int d, const float Er[PEC_DMAX], const float E[PEC_DMAX], float &fy, float &fx) {
+    fy = 0.f; fx = 0.f;
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j) {
+        if (j < d) {
+            const float ph = Er[j] - E[j];
+            if (!SPARSE || ph != 0.f) { fy += c[j] * ph; fx += c[d + j] * ph; }
+        }
+    }
+}
+
+template <bool BSP>
+__device__ __forceinline__ void pec_warp_body(const mpc_shape &s, const float *__restrict__ events, const float *__restrict__ coef,
+                                              const PecBasis &pb, const float *__restrict__ t_ref, float *__restrict__ rows_out) {
     const int d = pb.d;
     float Er[PEC_DMAX];
-    pec_basis(pb, t_ref[0], Er);
+    pec_basis<BSP>(pb, t_ref[0], Er);
     const size_t total = (size_t)s.B * s.M;
     for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
         const int b = (int)(row / s.M);
@@ -141,14 +207,19 @@ __global__ __launch_bounds__(256) void k_pec_warp(const mpc_shape s, const float
         const int cell = pe_own_cell(b, e[0], e[1], s.sp, s.hq, s.wq);
         const float *c = coef + (size_t)cell * 2 * d;
         float E[PEC_DMAX];
-        pec_basis(pb, e[2], E);
-        float fy = 0.f, fx = 0.f;
-#pragma unroll
-        for (int j = 0; j < PEC_DMAX; ++j) {
-            if (j < d) { const float ph = Er[j] - E[j]; fy += c[j] * ph; fx += c[d + j] * ph; }
-        }
+        pec_basis<BSP>(pb, e[2], E);
+        float fy, fx;
+        pec_flow<BSP>(c, d, Er, E, fy, fx);
         pe_write_row(rows_out, row, e, fy, fx, cell);
     }
+}
+__global__ __launch_bounds__(256) void k_pec_warp(const mpc_shape s, const float *__restrict__ events, const float *__restrict__ coef,
+                                                  const PecBasis pb, const float *__restrict__ t_ref, float *__restrict__ rows_out) {
+    pec_warp_body<false>(s, events, coef, pb, t_ref, rows_out);
+}
+__global__ __launch_bounds__(256) void k_pec_warp_bsp(const mpc_shape s, const float *__restrict__ events, const float *__restrict__ coef,
+                                                      const PecBasis pb, const float *__restrict__ t_ref, float *__restrict__ rows_out) {
+    pec_warp_body<true>(s, events, coef, pb, t_ref, rows_out);
 }
 
 // ---- row gradient ---------------------------------------------------------------------------------------------------------------
@@ -158,10 +229,38 @@ __device__ __forceinline__ float pec_coef(const float *__restrict__ scal, const 
     return (scal ? scal[MPC_SCAL_GCOEF] : 1.f) * (grad_out ? grad_out[0] : 1.f);
 }
 
-__global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR, int NCS, int KC, int NPASS, const int *__restrict__ offsets,
-                                                      const float *__restrict__ rows, const float2 *__restrict__ gpos, const PecBasis pb,
-                                                      const float *__restrict__ t_ref, const float *__restrict__ scal,
-                                                      const float *__restrict__ grad_out, float *__restrict__ grows) {
+// one row's adds of the orders j0 .. j0 + kc - 1 into its cell's sums a [2][kc].  SPARSE (the B-spline): an order whose phi_j is exactly
+// 0 -- decided from the row's own time, never from its bin -- would add the integer 0 (+-0 in k_pec_grad_atomic): skipped, the same bits
+template <bool SPARSE>
+__device__ __forceinline__ void pec_accum_row(unsigned long long *a, int j0, int kc, const float Er[PEC_DMAX], const float E[PEC_DMAX], float2 g) {
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j) {
+        if (j >= j0 && j < j0 + kc) {
+            const float ph = Er[j] - E[j];
+            if (SPARSE && ph == 0.f) continue;
+            atomicAdd(a + MPC_IDX(j - j0, kc), (unsigned long long)pe_to_fixed(ph * g.x));
+            atomicAdd(a + MPC_IDX(kc + j - j0, 2 * kc), (unsigned long long)pe_to_fixed(ph * g.y));
+        }
+    }
+}
+
+template <bool SPARSE>
+__device__ __forceinline__ void pec_atomic_row(float *o, int d, const float Er[PEC_DMAX], const float E[PEC_DMAX], float2 g) {
+#pragma unroll
+    for (int j = 0; j < PEC_DMAX; ++j) {
+        if (j < d) {
+            const float ph = Er[j] - E[j];
+            if (SPARSE && ph == 0.f) continue;
+            atomicAdd(o + j, ph * g.x); atomicAdd(o + d + j, ph * g.y);
+        }
+    }
+}
+
+template <bool BSP>
+__device__ __forceinline__ void pec_accum_body(const mpc_shape &s, int CSR, int NCS, int KC, int NPASS, const int *__restrict__ offsets,
+                                               const float *__restrict__ rows, const float2 *__restrict__ gpos, const PecBasis &pb,
+                                               const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                               const float *__restrict__ grad_out, float *__restrict__ grows) {
     extern __shared__ unsigned long long s_acc[];                // [ncell][2][kc]
     __shared__ int s_r0[2 * 64 + 1], s_pre[2 * 64 + 1], s_cnt[2 * 64];          // first row / running count / length of the 2 * nb ranges (nb <= 64)
     const int tid = threadIdx.x, d = pb.d;
@@ -191,7 +290,7 @@ __global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR
     __syncthreads();
     const int n = s_pre[nrange];
     float Er[PEC_DMAX];
-    pec_basis(pb, t_ref[0], Er);
+    pec_basis<BSP>(pb, t_ref[0], Er);
     // (PEC_NIF rows per thread and iteration, their loads issued together: with one row in flight the pass waits out a memory
     // latency per 1024 rows)
     for (int q0 = tid; q0 < n; q0 += PEC_NIF * PEC_NT) {
@@ -216,16 +315,9 @@ __global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR
             MPC_EXPECT(lc[u] >= 0 && lc[u] < ncell);            // (a row outside its strip: the offsets table is not this tensor's)
             if (lc[u] < 0 || lc[u] >= ncell) continue;
             float E[PEC_DMAX];
-            pec_basis(pb, tt[u], E);
+            pec_basis<BSP>(pb, tt[u], E);
             unsigned long long *a = s_acc + (size_t)lc[u] * 2 * kc;
-#pragma unroll
-            for (int j = 0; j < PEC_DMAX; ++j) {
-                if (j >= j0 && j < j0 + kc) {
-                    const float ph = Er[j] - E[j];
-                    atomicAdd(a + MPC_IDX(j - j0, kc), (unsigned long long)pe_to_fixed(ph * g[u].x));
-                    atomicAdd(a + MPC_IDX(kc + j - j0, 2 * kc), (unsigned long long)pe_to_fixed(ph * g[u].y));
-                }
-            }
+            pec_accum_row<BSP>(a, j0, kc, Er, E, g[u]);
         }
     }
     __syncthreads();
@@ -235,15 +327,28 @@ __global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR
         grows[((size_t)(cell0 + lc) * 2 + a) * d + j0 + jj] = coef * mpc_from_fixed((long long)s_acc[MPC_IDX(i, nacc)]);
     }
 }
+__global__ __launch_bounds__(PEC_NT) void k_pec_accum(const mpc_shape s, int CSR, int NCS, int KC, int NPASS, const int *__restrict__ offsets,
+                                                      const float *__restrict__ rows, const float2 *__restrict__ gpos, const PecBasis pb,
+                                                      const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                      const float *__restrict__ grad_out, float *__restrict__ grows) {
+    pec_accum_body<false>(s, CSR, NCS, KC, NPASS, offsets, rows, gpos, pb, t_ref, scal, grad_out, grows);
+}
+__global__ __launch_bounds__(PEC_NT) void k_pec_accum_bsp(const mpc_shape s, int CSR, int NCS, int KC, int NPASS, const int *__restrict__ offsets,
+                                                          const float *__restrict__ rows, const float2 *__restrict__ gpos, const PecBasis pb,
+                                                          const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                          const float *__restrict__ grad_out, float *__restrict__ grows) {
+    pec_accum_body<true>(s, CSR, NCS, KC, NPASS, offsets, rows, gpos, pb, t_ref, scal, grad_out, grows);
+}
 
-__global__ __launch_bounds__(256) void k_pec_grad_atomic(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
-                                                         const PecBasis pb, const float *__restrict__ t_ref, const float *__restrict__ scal,
-                                                         const float *__restrict__ grad_out, float *__restrict__ grows) {
+template <bool BSP>
+__device__ __forceinline__ void pec_grad_atomic_body(const mpc_shape &s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
+                                                     const PecBasis &pb, const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                     const float *__restrict__ grad_out, float *__restrict__ grows) {
     const int d = pb.d;
     const float coef = pec_coef(scal, grad_out);
     const int ncell = s.B * s.hq * s.wq;
     float Er[PEC_DMAX];
-    pec_basis(pb, t_ref[0], Er);
+    pec_basis<BSP>(pb, t_ref[0], Er);
     const size_t total = (size_t)s.B * s.M;
     for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
         float2 g = gpos[row];
@@ -254,13 +359,20 @@ __global__ __launch_bounds__(256) void k_pec_grad_atomic(const mpc_shape s, cons
         MPC_EXPECT(cell >= 0 && cell < ncell);
         if (cell < 0 || cell >= ncell) continue;                // (rows that mpc_pec_warp did not write)
         float E[PEC_DMAX];
-        pec_basis(pb, tp.x, E);
+        pec_basis<BSP>(pb, tp.x, E);
         float *o = grows + (size_t)cell * 2 * d;
-#pragma unroll
-        for (int j = 0; j < PEC_DMAX; ++j) {
-            if (j < d) { const float ph = Er[j] - E[j]; atomicAdd(o + j, ph * g.x); atomicAdd(o + d + j, ph * g.y); }
-        }
+        pec_atomic_row<BSP>(o, d, Er, E, g);
     }
+}
+__global__ __launch_bounds__(256) void k_pec_grad_atomic(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
+                                                         const PecBasis pb, const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                         const float *__restrict__ grad_out, float *__restrict__ grows) {
+    pec_grad_atomic_body<false>(s, rows, gpos, pb, t_ref, scal, grad_out, grows);
+}
+__global__ __launch_bounds__(256) void k_pec_grad_atomic_bsp(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
+                                                             const PecBasis pb, const float *__restrict__ t_ref, const float *__restrict__ scal,
+                                                             const float *__restrict__ grad_out, float *__restrict__ grows) {
+    pec_grad_atomic_body<true>(s, rows, gpos, pb, t_ref, scal, grad_out, grows);
 }
 
 // ---- smoothness field and its adjoint -------------------------------------------------------------------------------------------
@@ -306,8 +418,9 @@ static int pec_head_grid(const char *who, int B, int d, int h, int w, int tile, 
 }
 
 static int pec_make_basis(const char *who, int basis, int d, const float *table, int S, PecBasis *pb) {
-    if (d < 1 || basis < MPC_PEC_BEZIER || basis > MPC_PEC_TABLE) { mpc_set_error("%s: bad degree or basis kind", who); return MPC_E_SHAPE; }
+    if (d < 1 || basis < MPC_PEC_BEZIER || basis > MPC_PEC_BSPLINE) { mpc_set_error("%s: bad degree or basis kind", who); return MPC_E_SHAPE; }
     if (d > PEC_DMAX) { mpc_set_error("%s: more than %d control points per axis", who, PEC_DMAX); return MPC_E_UNSUPPORTED; }
+    if (basis == MPC_PEC_BSPLINE && d < 3) { mpc_set_error("%s: the cubic B-spline needs degree >= 3 (d + 1 >= 4 control points)", who); return MPC_E_SHAPE; }
     pb->kind = basis; pb->d = d; pb->S = 0; pb->table = nullptr;
     long long c = 1;
     for (int j = 0; j < PEC_DMAX; ++j) {
@@ -356,7 +469,7 @@ static int pec_choose_orders(const mpc_shape *s, const mpc_ws_layout &L, int d, 
 extern "C" int32_t mpc_pec_supported(const mpc_shape *s, int32_t d, int32_t basis, int32_t S) {
     if (!s || mpc_validate_shape(s)) return 0;
     if (!(s->flags & MPC_F_NO_WARP) || s->T != 1 || d < 1 || d > PEC_DMAX || s->nb < 1 || s->nb > 64 || s->B < 0) return 0;
-    if (basis < MPC_PEC_BEZIER || basis > MPC_PEC_TABLE) return 0;
+    if (basis < MPC_PEC_BEZIER || basis > MPC_PEC_BSPLINE || (basis == MPC_PEC_BSPLINE && d < 3)) return 0;
     if (basis == MPC_PEC_TABLE && (S < 1 || (int64_t)(S + 1) * d > mpc_pe_table_limit())) return 0;
     int32_t r = 1;
     if (s->B > 0) {
@@ -427,7 +540,8 @@ extern "C" int mpc_pec_warp(const mpc_shape *s, const float *events, const float
     const int64_t total = (int64_t)s->B * s->M;
     if (total == 0) return 0;
     const int grid = pe_row_grid(total);
-    MPC_LAUNCH(k_pec_warp, dim3(grid), dim3(256), 0, (hipStream_t)stream, *s, events, rows, pb, t_ref, rows_out);
+    if (basis == MPC_PEC_BSPLINE) MPC_LAUNCH(k_pec_warp_bsp, dim3(grid), dim3(256), 0, (hipStream_t)stream, *s, events, rows, pb, t_ref, rows_out);
+    else MPC_LAUNCH(k_pec_warp, dim3(grid), dim3(256), 0, (hipStream_t)stream, *s, events, rows, pb, t_ref, rows_out);
     MPC_CHECK_LAUNCH();
     return 0;
 }
@@ -450,8 +564,12 @@ extern "C" int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, c
         const int64_t total = (int64_t)s->B * s->M;
         if (total == 0) return 0;
         const int grid = pe_row_grid(total);
-        MPC_LAUNCH(k_pec_grad_atomic, dim3(grid), dim3(256), 0, st, *s, rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal,
-                   grad_out, grad_rows);
+        if (basis == MPC_PEC_BSPLINE)
+            MPC_LAUNCH(k_pec_grad_atomic_bsp, dim3(grid), dim3(256), 0, st, *s, rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal,
+                       grad_out, grad_rows);
+        else
+            MPC_LAUNCH(k_pec_grad_atomic, dim3(grid), dim3(256), 0, st, *s, rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal,
+                       grad_out, grad_rows);
         MPC_CHECK_LAUNCH();
         return 0;
     }
@@ -467,11 +585,16 @@ extern "C" int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, c
     if (attr_once.need()) {
         // (the kernel has 1 KB of static LDS of its own)
         hipError_t e = hipFuncSetAttribute((const void *)k_pec_accum, hipFuncAttributeMaxDynamicSharedMemorySize, PE_LDS_MAX + 2048);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_pec_accum_bsp, hipFuncAttributeMaxDynamicSharedMemorySize, PE_LDS_MAX + 2048);
         if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
         attr_once.mark();
     }
-    MPC_LAUNCH(k_pec_accum, dim3(s->B * L.n_cstrips * npass), dim3(PEC_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, kc, npass, offsets, rows_warped,
-               reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal, grad_out, grad_rows);
+    if (basis == MPC_PEC_BSPLINE)
+        MPC_LAUNCH(k_pec_accum_bsp, dim3(s->B * L.n_cstrips * npass), dim3(PEC_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, kc, npass, offsets,
+                   rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal, grad_out, grad_rows);
+    else
+        MPC_LAUNCH(k_pec_accum, dim3(s->B * L.n_cstrips * npass), dim3(PEC_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, kc, npass, offsets, rows_warped,
+                   reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal, grad_out, grad_rows);
     MPC_CHECK_LAUNCH();
     return 0;
 }

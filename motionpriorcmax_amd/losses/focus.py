@@ -70,6 +70,7 @@ class FocusLoss(base.TrajectoryLossBase):
         self._auto_key, self._auto_run = None, 0
         self._auto_never = set()              # shapes whose plan could not be captured: eager from then on
         self._tmid_dev = {}                   # bin mid-times per device (calc_per_event_basis)
+        self._pec_mid_basis = {}              # (device, curve_type, d) -> curve_event_basis at the bin mid-times (calc_per_event_curves)
         # num_tref > 1 (not in the shipped yaml files): the T reference times of a sample as T samples of the num_tref == 1 path
         # (_calc_trefs_as_samples); False: the general kernels (one launch for all reference times, global-atomic event path)
         self.trefs_as_samples = bool(trefs_as_samples)
@@ -305,8 +306,9 @@ class FocusLoss(base.TrajectoryLossBase):
               (iy * tile + tile // 2, ix * tile + tile // 2) of the 8h x 8w image; tile = lut_superpixel_size / scale, one of 2, 4, 8,
               16; the tile grid must equal the look-up-table grid (EVIMO2: 384 x 512 net, 480 x 640 events, scale 1.25, sp 5, tile 4)
           warped = (y, x) + sum_j rows[cell(y, x)][:, j] * phi_j,   phi_j = E_j(t_ref) - E_j(t_event)      (j ascending)
-        with E of `utils.curve_event_basis`: curve_type 'BEZIER' (1 <= d), 'POLYNOMIAL', or 'TABLE' with basis_table [S + 1, d] (a
-        constant: e.g. the cubic B-spline `bspline_basis(knots, d + 1)` or a frozen learned basis).  Then the reference's weights,
+        with E of `utils.curve_event_basis`: curve_type 'BEZIER' (1 <= d), 'POLYNOMIAL', 'BSPLINE' (the clamped cubic B-spline of
+        d + 1 control points, evaluated exactly: 3 <= d, ValueError below; at most 8 of the d coefficient pairs are read per event),
+        or 'TABLE' with basis_table [S + 1, d] (a constant, e.g. a frozen learned basis).  Then the reference's weights,
         vote, blur and objective; the smoothness term is the reference's Charbonnier term on rows x phim with
         phim[t] = E(t_ref) - E(t_mid[t]) ('on_flow_to_tref') or E(t_mid[t + 1]) - E(t_mid[t]) ('on_flow_to_next').
         Returns the triple of `calc`.  Gradients go to params and up_mask only.
@@ -317,12 +319,14 @@ class FocusLoss(base.TrajectoryLossBase):
         fused=False, and whatever the library refuses (d > 16, a table past mpc_pe_table_limit(), num_bins > 64, a CPU basis_table):
         phi [B, M, d] and the rows in plain torch around the existing per-event nodes (the cross-check).  No graph capture."""
         from ..utils import curve_event_basis, curve_head_rows
-        from ..utils.basis import CURVE_EVENT_TYPES
+        from ..utils.basis import CURVE_EVENT_TYPES, BSPLINE_MIN_DEGREE
         d, tile = self._curve_tile_grid(params, up_mask, scale)
         if curve_type not in CURVE_EVENT_TYPES:
             raise ValueError(f'curve_type must be one of {CURVE_EVENT_TYPES}, got {curve_type!r}')
         if (curve_type == 'TABLE') != (basis_table is not None):
             raise ValueError("curve_type='TABLE' and basis_table go together")
+        if curve_type == 'BSPLINE' and d < BSPLINE_MIN_DEGREE:
+            raise ValueError(f"curve_type='BSPLINE' is cubic: it needs d >= {BSPLINE_MIN_DEGREE} control points per axis beside P0, got {d}")
         if basis_table is not None and not (torch.is_tensor(basis_table) and basis_table.dim() == 2 and basis_table.dtype == torch.float32
                                             and basis_table.shape[0] >= 2 and basis_table.shape[1] == d):
             raise ValueError(f'basis_table must be a 2-D float32 tensor [samples + 1, d = {d}]')
@@ -354,8 +358,17 @@ class FocusLoss(base.TrajectoryLossBase):
             if tm is None:
                 tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
             with torch.no_grad():
-                bv = curve_event_basis(torch.cat((t_ref, tm)), d, curve_type, basis_table)
-                phim = (bv[2:] - bv[1:-1]) if self.smooth_type == 'on_flow_to_next' else (bv[:1] - bv[1:])
+                # (the basis at the bin mid-times is a constant of (curve, d): kept -- the torch lines of the B-spline are ~80 small
+                # launches, 0.3 ms of host time per step; a table is the caller's and may change between calls)
+                key = (dev, curve_type, d)
+                em = self._pec_mid_basis.get(key) if basis_table is None else None
+                if em is None:
+                    em = curve_event_basis(tm, d, curve_type, basis_table)
+                    if basis_table is None:
+                        if len(self._pec_mid_basis) >= 16:
+                            self._pec_mid_basis.clear()
+                        self._pec_mid_basis[key] = em
+                phim = (em[1:] - em[:-1]) if self.smooth_type == 'on_flow_to_next' else (curve_event_basis(t_ref, d, curve_type, basis_table) - em)
             if phim.shape[0] == 0:
                 phim = None
         if fused:

@@ -1114,7 +1114,7 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         return (g_grid, None, None, g_phim) + (None,) * 6 + (g_table,)
 
 
-PEC_BASIS = {'BEZIER': 0, 'POLYNOMIAL': 1, 'TABLE': 2}        # include/mpcmax.h: MPC_PEC_*
+PEC_BASIS = {'BEZIER': 0, 'POLYNOMIAL': 1, 'TABLE': 2, 'BSPLINE': 3}        # include/mpcmax.h: MPC_PEC_*
 PEC_ROWS_GRAD_TAP = None       # diagnostics (tests): a list that receives a copy of every grad_rows [B*G, 2d] PerEventCurvesFn computes
 
 

@@ -61,7 +61,30 @@ def table_basis_values(table, times):
     return lo + f[..., None] * (table[i + 1] - lo)
 
 
-CURVE_EVENT_TYPES = ('BEZIER', 'POLYNOMIAL', 'TABLE')
+CURVE_EVENT_TYPES = ('BEZIER', 'POLYNOMIAL', 'TABLE', 'BSPLINE')
+BSPLINE_MIN_DEGREE = 3
+
+
+def _bspline_event_basis(t, d):
+    """'BSPLINE' of `curve_event_basis`, its lines one by one (t fp32 [...] -> [..., d])."""
+    L = d - 2
+    tc = t.clamp(min=0).clamp(max=1)
+    x = tc * float(L)
+    s = x.floor().to(torch.int64).clamp(min=0, max=L - 1)
+    u = {k: (s + k).clamp(min=0, max=L).to(torch.float32) for k in range(-2, 4)}       # scaled knots: exact small integers
+    N = [torch.ones_like(x), None, None, None]
+    for j in range(1, 4):
+        saved = torch.zeros_like(x)
+        for r in range(j):
+            right, left, den = u[r + 1] - x, x - u[1 - j + r], u[r + 1] - u[1 - j + r]
+            temp = N[r] / den                   # (tensor / tensor: a division, correctly rounded; never by a Python scalar)
+            N[r] = saved + right * temp
+            saved = left * temp
+        N[j] = saved
+    # E_{s-1+q} = N_q: scattered into the d + 1 functions of the spline (s + q <= L + 2 = d), then function 0 (P0 = 0) is dropped
+    E = torch.zeros(t.shape + (d + 1,), dtype=torch.float32, device=t.device)
+    E.scatter_(-1, torch.stack([s + q for q in range(4)], dim=-1), torch.stack(N, dim=-1))
+    return E[..., 1:]
 
 
 def curve_event_basis(times, d, curve_type, basis_table=None):
@@ -75,7 +98,21 @@ def curve_event_basis(times, d, curve_type, basis_table=None):
       'POLYNOMIAL'  E_1 = t, E_i = E_{i-1} * t (the lines of pe_phi, csrc/events.hip; curves/polynomial.py:55-58 up to the rounding
                     of pow)
       'TABLE'       `table_basis_values(basis_table, t)`: basis_table [S + 1, d] sampled at the knots i / S, interpolated linearly
-                    (e.g. the cubic B-spline: bspline_basis(knots, d + 1), or a frozen learned basis)."""
+                    (a frozen learned basis, say; the cubic B-spline has a kind of its own)
+      'BSPLINE'     the clamped (open-uniform) cubic B-spline of `bspline_basis` with d + 1 control points (P0 = 0), L = d - 2 spans,
+                    d >= 3, exactly -- no table:
+                      tc = min(max(t, 0), 1);  x = tc * (float)L;  s = min((int)floorf(x), L - 1)
+                      u(k) = (float)min(max(s + k, 0), L)          scaled knots, exact small integers, k = -2..3
+                      N_0 = 1
+                      for j = 1..3:  saved = 0
+                          for r = 0..j-1:
+                              right = u(r+1) - x;   left = x - u(1-j+r);   den = u(r+1) - u(1-j+r)      (den is 1, 2 or 3, never 0)
+                              temp = N_r / den;     N_r = saved + right * temp;     saved = left * temp
+                          N_j = saved
+                      E_{s-1+q} = N_q, q = 0..3   (index -1 is P0 and is dropped);   every other E_j = +0
+                    (The NURBS Book's BasisFuns on the knots scaled by L; the division is correctly rounded.)  At t = 0 every E_j is
+                    exactly 0, at t = 1 E_d is exactly 1 and the others exactly 0; at most 4 of the d are non-zero; d = 3 is the cubic
+                    Bezier curve."""
     d = int(d)
     if d < 1:
         raise ValueError(f'degree must be >= 1, got {d}')
@@ -84,6 +121,10 @@ def curve_event_basis(times, d, curve_type, basis_table=None):
     if (curve_type == 'TABLE') != (basis_table is not None):
         raise ValueError("curve_type='TABLE' and basis_table go together")
     t = times.to(torch.float32)
+    if curve_type == 'BSPLINE':
+        if d < BSPLINE_MIN_DEGREE:
+            raise ValueError(f"curve_type='BSPLINE' is cubic: it needs d >= {BSPLINE_MIN_DEGREE} control points per axis beside P0, got {d}")
+        return _bspline_event_basis(t, d)
     if curve_type == 'TABLE':
         if basis_table.dim() != 2 or basis_table.shape[1] != d or basis_table.dtype != torch.float32:
             raise ValueError(f'basis_table must be float32 [samples + 1, {d}], got {tuple(basis_table.shape)} {basis_table.dtype}')
@@ -327,12 +368,12 @@ def _shortcut_rows(bm, t):
     return torch.where((t == 0).to(bm.device)[:, None], torch.zeros((), dtype=bm.dtype, device=bm.device), bm)
 
 
-CURVE_TYPES = ('BEZIER', 'POLYNOMIAL', 'LEARNED')
+CURVE_TYPES = ('BEZIER', 'POLYNOMIAL', 'LEARNED', 'BSPLINE')
 
 
 def curve_basis(curve_type, times, degree, basis_network=None, scalar_time_shortcuts=False, device=None):
     """The [n_t, degree] fp32 basis matrix of one of the reference's three RAFT-spline curve types (`model.curve_type`, reference
-    src/models/raft_spline/curves/__init__.py:13-21), on `device` (default: that of the basis network's parameters for 'LEARNED', of
+    src/models/raft_spline/curves/__init__.py:13-21) or of the cubic B-spline, on `device` (default: that of the basis network's parameters for 'LEARNED', of
     `times` if it is a tensor, else the CPU): flow(t) = sum_j basis[t, j] * P_j.
 
       'BEZIER'      the Bernstein matrix of `trajectories_from_bezier` (bezier.py:92-113: float64 on the host, then fp32; the same
@@ -341,6 +382,9 @@ def curve_basis(curve_type, times, degree, basis_network=None, scalar_time_short
                     timestamps tensor as the Bernstein matrix is (a training step neither synchronises nor uploads)
       'LEARNED'     basis_network(times.float()[:, None]) (curves/learned.py:76-77): part of the autograd graph, never cached; a
                     device `times` tensor causes no host synchronisation.  The learned basis is NOT zero at t = 0.
+      'BSPLINE'     the cubic B-spline matrix of `trajectories_from_bspline` (`bspline_basis(times, degree + 1)`: float64 on the
+                    host, then fp32; the same cached tensor, the same bits; degree >= 3) -- UNPINNED EXTENSION, the curve that
+                    FocusLoss.calc_per_event_curves(curve_type='BSPLINE') evaluates per event
     Any other `curve_type` raises ValueError.  The cached matrices are shared: do not modify them in place.
 
     `scalar_time_shortcuts`: `CurveBase.get_flow_from_reference` returns the last control point for a SCALAR time == 1 and zeros
@@ -371,6 +415,10 @@ def curve_basis(curve_type, times, degree, basis_network=None, scalar_time_short
         device = times.device if torch.is_tensor(times) else torch.device('cpu')
     if curve_type == 'BEZIER':                  # (the Bernstein rows at t = 0 and t = 1 ARE the shortcut rows: 0 ** 0 == 1)
         return _device_basis('bernstein', times, (d,), device, torch.float32)
+    if curve_type == 'BSPLINE':                 # (clamped ends: its rows at t = 0 and t = 1 are the shortcut rows too)
+        if d < BSPLINE_MIN_DEGREE:
+            raise ValueError(f"curve_type='BSPLINE' is cubic: it needs degree >= {BSPLINE_MIN_DEGREE} control points per axis beside P0, got {d}")
+        return _device_basis('bspline', times, (d + 1, 3), device, torch.float32)
     return _device_basis('polynomial_shortcuts' if scalar_time_shortcuts else 'polynomial', times, (d,), device, torch.float32)
 
 
@@ -383,7 +431,7 @@ def _curve_matrix(params, times, curve_type, basis_network):
 
 def trajectories_from_curves(params, times, tile_size, image_shape, curve_type='BEZIER', basis_network=None, scale=1.0, up_mask=None):
     """`trajectories_from_bezier` for any of the reference's curve types (`curve_basis`: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the
-    latter with its `basis_network` on the device of `params`): the same contracts, the same routing -- fp32 GPU tensors with
+    latter with its `basis_network` on the device of `params`) and for 'BSPLINE' (the bits of `trajectories_from_bspline`): the same contracts, the same routing -- fp32 GPU tensors with
     d <= 16 (and, with `up_mask`, a basis matrix within 48 KB and a tile size of 2, 4, 8 or 16) run in the fused nodes
     (ops.CurveTrajFn / ops.CvxCurveTrajFn), everything else in their plain-torch mirrors -- and with 'BEZIER' the same launches
     and bits.  Times are evaluated as a LIST (no scalar-time shortcut, see `curve_basis`): a learned curve is not zero at t = 0.

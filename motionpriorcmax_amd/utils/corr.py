@@ -321,7 +321,7 @@ class CorrLookup:
 
     def lookup_curves(self, params, times, curve_type='BEZIER', basis_network=None):
         """`lookup_bezier` for any of the reference's curve types (utils.curve_basis: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the latter
-        with its `basis_network` on the device of `params`): the lookup at coords0 + curve.get_flow_from_reference(times) of
+        with its `basis_network` on the device of `params`; also 'BSPLINE', the cubic B-spline): the lookup at coords0 + curve.get_flow_from_reference(times) of
         raft.py:165-180, the times evaluated as a LIST (no scalar-time shortcut).  The same routing as `lookup_bezier`, with
         'BEZIER' the same launches and bits, `shared_grad=True` included.  For 'LEARNED' the basis matrix is part of the autograd
         graph, and the fused node has no gradient for it: while the basis network trains (the matrix requires grad) the lookup

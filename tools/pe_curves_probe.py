@@ -12,7 +12,13 @@ Median of `--steps` steps per route (forward + backward), the routes ALTERNATING
 timed from the host with a device synchronisation on both sides; then the per-kernel times of 3 steps from ops.KernelTimer, and
 the passes of the ordered row gradient (mpc_pec_rows_grad_passes).
 
-    python tools/pe_curves_probe.py [--out profiles/pe_curves.json] [--steps 15] [--workloads C4,C4b6]"""
+--curve BEZIER (the default) is the above, written to profiles/pe_curves.json.  --curve BSPLINE and --curve TABLE time the cubic
+B-spline of 11 control points instead, written to profiles/pe_curves_bspline.json: `fused` is the named kind -- 'BSPLINE', exact and
+in registers, or 'TABLE', the same basis sampled at S = 1024 (bspline_basis) and interpolated --, `fused_other` the other of the two
+in the same alternation, `lut` trajectories_from_curves(curve_type='BSPLINE') + calc; `unfused` only with --routes.  With a
+B-spline kind the bucket-ordered layout also times k_pec_accum at 1 and 3 orders per pass beside the library's choice.
+
+    python tools/pe_curves_probe.py [--curve BEZIER] [--out FILE] [--steps 15] [--workloads C4,C4b6] [--routes fused,lut]"""
 import argparse
 import ctypes
 import json
@@ -31,12 +37,47 @@ from motionpriorcmax_amd.build import source_hash  # noqa: E402
 from motionpriorcmax_amd.utils.synth import synth_events, bin_mid_times  # noqa: E402
 
 
+TABLE_SAMPLES = 1024
+
+
+class _OrdersPerPass:
+    """ops.PerEventCurvesFn with `orders_per_pass` fixed (FocusLoss.calc_per_event_curves always takes the library's choice)."""
+
+    def __init__(self, fn, k):
+        self.fn, self.k = fn, k
+
+    def apply(self, *a):
+        return self.fn.apply(*a, self.k)
+
+
+def orders_per_pass_sweep(sh, d, step, clear, rounds=5):
+    """k_pec_accum per step (us, median of `rounds` alternating rounds) at the library's choice (0), 1 and 3 orders per pass."""
+    real = ops.PerEventCurvesFn
+    got = {k: [] for k in (0, 1, 3)}
+    try:
+        for _ in range(rounds):
+            for k in got:
+                ops.PerEventCurvesFn = _OrdersPerPass(real, k)
+                with ops.KernelTimer() as kt:
+                    step()
+                    clear()
+                got[k].append(sum(v['total_us'] for n, v in kt.summary().items() if n.startswith('k_pec_accum')))          # (k_pec_accum_bsp)
+    finally:
+        ops.PerEventCurvesFn = real
+    return {str(k): {'median_us': round(statistics.median(v), 1), 'min_us': round(min(v), 1), 'max_us': round(max(v), 1),
+                     'passes': int(C.lib().mpc_pec_rows_grad_passes(ctypes.byref(sh), d, k))} for k, v in got.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'pe_curves.json'))
+    ap.add_argument('--curve', choices=('BEZIER', 'BSPLINE', 'TABLE'), default='BEZIER')
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--routes', default=None, help='comma list out of fused, fused_other, unfused, lut (default: all of the curve)')
     ap.add_argument('--steps', type=int, default=15)
     ap.add_argument('--workloads', default='C4,C4b6')
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'pe_curves.json' if args.curve == 'BEZIER' else 'pe_curves_bspline.json')
     dev = torch.device('cuda:0')
     result = {'steps': args.steps, 'source_hash': source_hash(), 'device': torch.cuda.get_device_name(0), 'workloads': {}}
     for wname in args.workloads.split(','):
@@ -53,6 +94,14 @@ def main():
         sorted_b = {'events': ev.to(dev), 'num_pos_events': npos}
         batches = {'time_sorted': sorted_b, 'bucket_ordered': L.order_events(sorted_b)}
         sh = ops._pec_shape(L._cfg, sorted_b['events'], npos)
+        table = None
+        if args.curve != 'BEZIER':
+            result['curve'], result['table_samples'] = args.curve, TABLE_SAMPLES
+            table = utils.bspline_basis(torch.arange(TABLE_SAMPLES + 1, dtype=torch.float64) / TABLE_SAMPLES, d + 1).float().to(dev)
+        kinds = {'BEZIER': ('BEZIER', None), 'BSPLINE': ('BSPLINE', 'TABLE'), 'TABLE': ('TABLE', 'BSPLINE')}[args.curve]
+
+        def curve_kw(kind):
+            return dict(curve_type=kind, basis_table=table if kind == 'TABLE' else None)
         out_w = {'desc': wl['desc'] + '; control points on the 1/8 grid + up_mask', 'sp': bench.SP, 'd': d,
                  'row_gradient_passes_ordered': int(C.lib().mpc_pec_rows_grad_passes(ctypes.byref(sh), d, 0)), 'layouts': {}}
 
@@ -62,15 +111,27 @@ def main():
 
         for lname, b in batches.items():
             def r_fused():
-                L.calc_per_event_curves(params, t_ref, b, up_mask=mask)[0].backward()
+                L.calc_per_event_curves(params, t_ref, b, up_mask=mask, **curve_kw(kinds[0]))[0].backward()
+
+            def r_fused_other():
+                L.calc_per_event_curves(params, t_ref, b, up_mask=mask, **curve_kw(kinds[1]))[0].backward()
 
             def r_unfused():
-                L.calc_per_event_curves(params, t_ref, b, up_mask=mask, fused=False)[0].backward()
+                L.calc_per_event_curves(params, t_ref, b, up_mask=mask, fused=False, **curve_kw(kinds[0]))[0].backward()
 
             def r_lut():
-                traj, _ = utils.trajectories_from_bezier(params, times, bench.PATCH, (H, W), up_mask=mask)
+                if args.curve == 'BEZIER':
+                    traj, _ = utils.trajectories_from_bezier(params, times, bench.PATCH, (H, W), up_mask=mask)
+                else:
+                    traj, _ = utils.trajectories_from_curves(params, times, bench.PATCH, (H, W), curve_type='BSPLINE', up_mask=mask)
                 L.calc(traj, times, b)[0].backward()
-            routes = {'fused': r_fused, 'unfused': r_unfused, 'lut': r_lut}
+            if args.curve == 'BEZIER':
+                routes = {'fused': r_fused, 'unfused': r_unfused, 'lut': r_lut}
+            else:
+                routes = {'fused': r_fused, 'fused_other': r_fused_other, 'lut': r_lut}
+            if args.routes:
+                every = {'fused': r_fused, 'fused_other': r_fused_other, 'unfused': r_unfused, 'lut': r_lut}
+                routes = {n: every[n] for n in args.routes.split(',') if n != 'fused_other' or kinds[1]}
             times_ms = {n: [] for n in routes}
             for fn in routes.values():
                 for _ in range(2):
@@ -97,6 +158,10 @@ def main():
                           'library_kernels_us_per_step': ks, 'library_kernels_total_us': round(sum(ks.values()), 1)}
                 print(f'{wname} {lname} {n}: median {out[n]["median_ms"]} ms (min {out[n]["min_ms"]}, p90 {out[n]["p90_ms"]}); library kernels '
                       f'{out[n]["library_kernels_total_us"]} us: ' + ' '.join(f'{a}={v}' for a, v in list(ks.items())[:8]), flush=True)
+            if args.curve != 'BEZIER' and lname == 'bucket_ordered' and 'fused' in routes:
+                out['fused']['k_pec_accum_us_by_orders_per_pass'] = orders_per_pass_sweep(sh, d, r_fused, clear)
+                print(f'{wname} {lname} k_pec_accum by orders per pass (0 = the library\'s choice): '
+                      f'{out["fused"]["k_pec_accum_us_by_orders_per_pass"]}', flush=True)
             out_w['layouts'][lname] = out
         result['workloads'][wname] = out_w
         del batches, sorted_b, params, mask

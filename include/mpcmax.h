@@ -333,7 +333,20 @@ int mpc_pe_field_basis_grad(const float *grad_field, const float *coef_rows, con
  *                       row adds with float atomics (any row order; slow, not reproducible).
  * mpc_pec_rows_grad_passes  the passes that call makes (0: not served with offsets)
  * mpc_pec_field         field [B*nbm][G][2] = sum_j rows[(b, cell)][a][j] * phim[t][j], j ascending (d <= 16, nbm <= 64): what mpc_lut_smooth takes
- * mpc_pec_field_adjoint grad_rows[(b, cell)][a][j] += grad_out[0] * sum_t grad_field[(b, t)][cell][a] * phim[t][j]                       */
+ * mpc_pec_field_adjoint grad_rows[(b, cell)][a][j] += grad_out[0] * sum_t grad_field[(b, t)][cell][a] * phim[t][j]
+ * A table that TRAINS (additive, still version 107; served wherever mpc_pec_supported answers bit 0 for MPC_PEC_TABLE):
+ * mpc_pec_table_basis_grad  grad_table [S + 1][d] = scal[MPC_SCAL_GCOEF] * grad_out[0] * d objective / d table through the events.
+ *                       rows_warped: what mpc_pec_warp wrote (time and cell bits are read); grad_pos [B][M][2]: the UNSCALED position
+ *                       gradients of mpc_event_pos_grad (a scal of ones, no grad_out); rows: mpc_pec_head_rows'.  With
+ *                       G_j = gy * rows[cell][0][j] + gx * rows[cell][1][j] and (i, f) of the row's time, (ir, fr) of t_ref[0]:
+ *                       grad[i][j] -= (1 - f) G_j, grad[i + 1][j] -= f G_j, grad[ir][j] += (1 - fr) G_j, grad[ir + 1][j] += fr G_j; rows
+ *                       with (gy, gx) == (0, 0) add nothing.  One streaming pass, sums in 64-bit fixed point (Q33.30) in LDS: bitwise
+ *                       the same for any row order, any grid and either event layout; |G_j| < 2^31 and a knot's sum over the batch
+ *                       below 2^33.  1 <= d <= 16, S >= 1, (S + 1) * d <= mpc_pe_table_limit() (beyond: MPC_E_UNSUPPORTED, no launch).
+ *                       acc: scratch of (S + 2) * d int64 (zeroed here).  The kernel body is mpc_pe_table_basis_grad's.
+ * mpc_pec_field_basis_grad  the adjoint of mpc_pec_field w.r.t. phim: grad_phim [nbm][d] = grad_out[0] * sum over (b, cell, a) of
+ *                       grad_field[(b, t)][cell][a] * rows[(b, cell)][a][j]; fp64 sums in a fixed order, bitwise reproducible; part:
+ *                       scratch of nbm * 64 * d doubles; d <= 16, nbm <= 64                                                        */
 #define MPC_PEC_BEZIER     0
 #define MPC_PEC_POLYNOMIAL 1
 #define MPC_PEC_TABLE      2
@@ -353,6 +366,10 @@ int32_t mpc_pec_rows_grad_passes(const mpc_shape *s, int32_t d, int32_t orders_p
 int mpc_pec_field(const float *rows, const float *phim, float *field, int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream);
 int mpc_pec_field_adjoint(const float *grad_field, const float *phim, const float *grad_out, float *grad_rows,
                           int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream);
+int mpc_pec_table_basis_grad(const mpc_shape *s, const float *rows_warped, const float *grad_pos, const float *rows, int32_t d, int32_t S,
+                             const float *t_ref, const float *scal, const float *grad_out, int64_t *acc, float *grad_table, void *stream);
+int mpc_pec_field_basis_grad(const float *grad_field, const float *rows, const float *grad_out, double *part, float *grad_phim,
+                             int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream);
 
 int mpc_event_splat_bwd(const mpc_shape *s, const float *events, const float *flow_lut,
                         const float *t_ref, const float *grad_iwe, const float *scal,

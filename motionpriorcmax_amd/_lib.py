@@ -161,6 +161,8 @@ SIGNATURES = {
     'mpc_pec_rows_grad_passes': (i32, [sp, i32, i32]),
     'mpc_pec_field': (cint, [vp, vp, vp] + [i32] * 4 + [vp]),
     'mpc_pec_field_adjoint': (cint, [vp, vp, vp, vp] + [i32] * 4 + [vp]),
+    'mpc_pec_table_basis_grad': (cint, [sp, vp, vp, vp, i32, i32] + [vp] * 6),
+    'mpc_pec_field_basis_grad': (cint, [vp] * 5 + [i32] * 4 + [vp]),
     'mpc_event_splat_bwd': (cint, [sp] + [vp] * 10),
     'mpc_focus_fwd': (cint, [sp, fb, vp, vp]),
     'mpc_focus_bwd': (cint, [sp, fb] + [vp] * 6),

@@ -1174,90 +1174,21 @@ extern "C" int mpc_pe_grad_ordered(const mpc_shape *s, const float *rows, const 
 }
 
 // ---- the table basis (basis_type='table'): the three kernels above as TAB instantiations, and the gradient w.r.t. the table ----
-//   k_pe_table_grad : ONE streaming pass over the rows' (t, cell), the stored unscaled (gy, gx) and the tile rows (cache-resident,
-//               cell-coherent in the ordered layout).  G_j = gy c[cell][0][j] + gx c[cell][1][j];  acc[i][j] += (1 - f) G_j,
-//               acc[i + 1][j] += f G_j, sum[j] += G_j, with (i, f) of the row's time (pe_tab_locate).  The accumulators
-//               [(S + 1) k knot entries + k sums] live in LDS as Q33.30 (pe_to_fixed: round to nearest; ds_add_u64), every workgroup
-//               adds its non-zero entries to the global 64-bit accumulators at the end: integer sums, so the result is bitwise
-//               the same for any order of the rows, any grid and either event layout.
-//               BOUNDS: pe_to_fixed takes |G_j| < 2^31 -- G is (event weight) x (a difference of adjoint-image values, O(1) in the
-//               unscaled units of MPC_SCAL_GCOEF) x (a tile coefficient: a displacement in pixels); a knot's sum over the WHOLE batch
-//               must stay below 2^33 in magnitude (S = 1 puts every event on two knots: 2.8 M events x a mean |G| of 3000).
-//               A time-sorted batch (the DSEC loader's) puts the 64 lanes of a wavefront on one or two neighbouring intervals,
-//               i.e. 64 adds to the same two or three LDS words.  Every live lane adds by itself all the same: summing the knots'
-//               integers across the lanes with shuffles first (lane 0 adding once) was measured and is no faster -- 75 against
-//               68 us on a time-sorted C3 batch, 46 against 47 us on a bucket-ordered one -- the pass is
-//               bound by its gathers of tile rows, not by the LDS.  The sums over ALL events stay in registers and are added once
-//               per wavefront (every lane of every wavefront would hit the same k words).
-//   k_pe_table_finish : grad_table[i][j] = scal[GCOEF] grad_out (-acc[i][j] + [i == ir] (1 - fr) sum[j] + [i == ir + 1] fr sum[j]),
-//               (ir, fr) of t_ref: phi_j = B_j(t_ref) - B_j(t_event), products unscaled until here
-#define PT_NT 1024
-#define PE_TABLE_MAX_ENTRIES 16384          // (S + 1) * k: 128 KB of 64-bit accumulators (+ k sums) in the CU's 160 KB
-__device__ __forceinline__ long long pe_wave_sum_ll(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+//   k_pe_table_grad / k_pe_table_finish : pe_table_grad_body<KB, PE_KMAX> / pe_table_finish_one (pe_device.h, with the comment on
+//               bounds and on time-sorted batches): the body is shared with the curves' k_pec_table_grad, which holds 16 orders
+#define PT_NT PE_TAB_NT
 template <int KB, bool TAB = true>          // (TAB: the name PE_DISPATCH gives an instantiation; there is no other)
 __global__ __launch_bounds__(PT_NT) void k_pe_table_grad(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
                                                          const float *__restrict__ coef, int S, int k,
                                                          unsigned long long *__restrict__ acc) {
-    extern __shared__ unsigned long long s_tacc[];          // [(S + 1) * kk] knots, then [kk] sums
     const EvParams p = make_params(s);
-    const int tid = threadIdx.x, kk = KB > 0 ? KB : min(k, PE_KMAX);
-    const int nent = (S + 1) * kk, nall = nent + kk;
-    for (int i = tid; i < nall; i += PT_NT) s_tacc[MPC_IDX(i, nall)] = 0ull;
-    __syncthreads();
-    const size_t total = (size_t)p.B * p.M;
-    const int ncell = p.B * p.hq * p.wq;
-    long long sg[KB > 0 ? KB : PE_KMAX];
-    for (int j = 0; j < kk; ++j) sg[j] = 0;
-    for (size_t base = (size_t)blockIdx.x * PT_NT; base < total; base += (size_t)gridDim.x * PT_NT) {
-        const size_t row = base + tid;
-        float2 g = make_float2(0.f, 0.f);
-        if (row < total) g = gpos[row];
-        if (g.x == 0.f && g.y == 0.f) continue;                 // (a row of weight 0, or past the end: contributes nothing)
-        const float2 tp = *reinterpret_cast<const float2 *>(rows + row * 6 + 2);         // (t, p)
-        const int cell = min(max(__float_as_int(rows[row * 6 + 4]), 0), ncell - 1);     // (rows of mpc_pe_table_warp; never outside coef)
-        int i; float f;
-        pe_tab_locate(tp.x, S, i, f);
-        const float one_f = 1.f - f;
-        const float *c = coef + (size_t)cell * 2 * k;
-        for (int j = 0; j < kk; ++j) {
-            const float py = g.x * c[j], px = g.y * c[k + j];
-            const float G = py + px;
-            // (0 <= i <= S - 1: both knots lie inside the [S + 1] rows)
-            atomicAdd(&s_tacc[MPC_IDX((size_t)i * kk + j, nent)], (unsigned long long)pe_to_fixed(one_f * G));
-            atomicAdd(&s_tacc[MPC_IDX((size_t)(i + 1) * kk + j, nent)], (unsigned long long)pe_to_fixed(f * G));
-            sg[j] += pe_to_fixed(G);
-        }
-    }
-    for (int j = 0; j < kk; ++j) {
-        const long long v = pe_wave_sum_ll(sg[j]);
-        if ((tid & 63) == 0 && v != 0) atomicAdd(&s_tacc[MPC_IDX(nent + j, nall)], (unsigned long long)v);
-    }
-    __syncthreads();
-    for (int i = tid; i < nall; i += PT_NT) {
-        const unsigned long long v = s_tacc[MPC_IDX(i, nall)];
-        if (v != 0ull) atomicAdd(acc + i, v);
-    }
+    pe_table_grad_body<KB, PE_KMAX>((size_t)p.B * p.M, p.B * p.hq * p.wq, rows, gpos, coef, S, k, acc);
 }
 
 __global__ __launch_bounds__(256) void k_pe_table_finish(const unsigned long long *__restrict__ acc, int S, int k, const float *__restrict__ t_ref,
                                                          const float *__restrict__ scal, const float *__restrict__ grad_out,
                                                          float *__restrict__ gtable) {
-    const int idx = blockIdx.x * 256 + threadIdx.x, nent = (S + 1) * k;
-    if (idx >= nent) return;
-    const int i = idx / k, j = idx - i * k;
-    const float coef = scal[MPC_SCAL_GCOEF] * (grad_out ? grad_out[0] : 1.f);
-    int ir; float fr;
-    pe_tab_locate(t_ref[0], S, ir, fr);
-    const double unit = 1.0 / (double)(1 << MPC_FIX_SHIFT);
-    const double sum = (double)(long long)acc[nent + j] * unit;
-    double v = -((double)(long long)acc[idx] * unit);
-    if (i == ir) v += (double)(1.f - fr) * sum;
-    if (i == ir + 1) v += (double)fr * sum;
-    gtable[idx] = v == 0.0 ? 0.f : coef * (float)v;            // (no contribution stays 0 where the objective's scale is not finite: no events)
+    pe_table_finish_one(blockIdx.x * 256 + threadIdx.x, acc, S, k, t_ref, scal, grad_out, gtable);
 }
 
 static bool pe_table_ok(const mpc_shape *s, int32_t k, int32_t S) {
@@ -1313,32 +1244,16 @@ extern "C" int mpc_pe_table_basis_grad(const mpc_shape *s, const float *rows, co
     int rc = mpc_validate_shape(s);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int nent = (S + 1) * k, nall = nent + k;
-    const int e0 = mpc_zero_async(acc, (size_t)nall * 8, st);
-    if (e0) return e0;
-    const int64_t total = (int64_t)s->B * s->M;
-    if (total > 0) {
-        const size_t lds = (size_t)nall * 8;
-        static mpc_device_once attr_once;
-        if (attr_once.need()) {
-            const void *fns[3] = {(const void *)k_pe_table_grad<1>, (const void *)k_pe_table_grad<3>, (const void *)k_pe_table_grad<0>};
-            for (const void *fn : fns) {
-                hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (PE_TABLE_MAX_ENTRIES + PE_KMAX) * 8);
-                if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
-            }
-            attr_once.mark();
-        }
-        // (one workgroup per CU and 1024 rows per trip; a batch of more than 256 Ki rows makes further trips)
-        const int grid = (int)((total + PT_NT - 1) / PT_NT < 256 ? (total + PT_NT - 1) / PT_NT : 256);
-        unsigned long long *a = reinterpret_cast<unsigned long long *>(acc);
-        const float2 *gpos = reinterpret_cast<const float2 *>(grad_pos);
-        PE_DISPATCH(k_pe_table_grad, true, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a);
-        MPC_CHECK_LAUNCH();
-    }
-    MPC_LAUNCH(k_pe_table_finish, dim3((nent + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(acc), S, k, t_ref, scal,
-               grad_out, grad_table);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    static mpc_device_once attr_once;
+    const float2 *gpos = reinterpret_cast<const float2 *>(grad_pos);
+    return pe_table_basis_grad_run<PE_KMAX>(
+        __func__, s, S, k, acc, st, attr_once,
+        {(const void *)k_pe_table_grad<1>, (const void *)k_pe_table_grad<3>, (const void *)k_pe_table_grad<0>},
+        [&](int grid, size_t lds, unsigned long long *a) { PE_DISPATCH(k_pe_table_grad, true, dim3(grid), dim3(PT_NT), lds, st, *s, rows, gpos, coef_rows, S, k, a); },
+        [&](int nent) {
+            MPC_LAUNCH(k_pe_table_finish, dim3((nent + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(acc), S, k, t_ref, scal,
+                       grad_out, grad_table);
+        });
 }
 
 extern "C" int mpc_event_pos_grad(const mpc_shape *s, const float *events, const float *t_ref, const float *grad_iwe,

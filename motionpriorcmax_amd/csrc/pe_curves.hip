@@ -17,6 +17,9 @@
 //   mpc_pec_field      k_basis_field<16> (pe_device.h)
 //   k_pec_field_adj    grad_rows[(b, cell)][a][j] += grad_out * sum_t grad_field[(b, t)][cell][a] * phim[t][j]
 //   k_pec_rows_to_*    the transposes between grad_rows and what the head's adjoint takes
+//   k_pec_table_grad   d loss / d table through the events (a table that trains): pe_table_grad_body<., 16> (pe_device.h), one streaming
+//                      pass, Q33.30 sums in LDS, bitwise reproducible in either layout; k_pec_table_finish: the t_ref knots and the scale
+//   mpc_pec_field_basis_grad  k_field_basis_grad_part / _sum <16> (pe_device.h): the adjoint of the field w.r.t. phim, fp64 in a fixed order
 // The adjoint of "centre + v" is the adjoint of v: the head's backward with a mask IS mpc_cvx_traj_bwd (cvx_curves.hip) with the identity
 // as its basis matrix and grad_rows transposed to [B][d][G][2].
 //
@@ -400,6 +403,21 @@ __global__ __launch_bounds__(256) void k_pec_field_adj(const float *__restrict__
         if (j < d) { o[j] += go * gy[j]; o[d + j] += go * gx[j]; }
 }
 
+// ---- the gradient w.r.t. a tabulated basis (a table that trains: FocusLoss.calc_per_event_curves with basis_table.requires_grad) ----
+// Through the events: pe_table_grad_body / pe_table_finish_one (pe_device.h -- the ONE implementation, events.hip's k_pe_table_grad is
+// its <KB, 8> instantiation; the comment on the fixed-point bounds and on time-sorted batches is there) with 16 orders: `coef` are the
+// tile rows of k_pec_head_rows, the records those of k_pec_warp.  <10>: the shipped curve degree, its loops unrolled; <0>: any other d.
+template <int KB>
+__global__ __launch_bounds__(PE_TAB_NT) void k_pec_table_grad(const mpc_shape s, const float *__restrict__ rows, const float2 *__restrict__ gpos,
+                                                              const float *__restrict__ coef, int S, int d, unsigned long long *__restrict__ acc) {
+    pe_table_grad_body<KB, PEC_DMAX>((size_t)s.B * s.M, s.B * s.hq * s.wq, rows, gpos, coef, S, d, acc);
+}
+__global__ __launch_bounds__(256) void k_pec_table_finish(const unsigned long long *__restrict__ acc, int S, int d, const float *__restrict__ t_ref,
+                                                          const float *__restrict__ scal, const float *__restrict__ grad_out,
+                                                          float *__restrict__ gtable) {
+    pe_table_finish_one(blockIdx.x * 256 + threadIdx.x, acc, S, d, t_ref, scal, grad_out, gtable);
+}
+
 // ---- entry points ---------------------------------------------------------------------------------------------------------------
 static int pec_tile_ok(int tile) { return tile == 2 || tile == 4 || tile == 8 || tile == 16; }
 
@@ -622,6 +640,34 @@ extern "C" int mpc_pec_field_adjoint(const float *grad_field, const float *phim,
                grad_rows, B, G, d, nbm);
     MPC_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int mpc_pec_table_basis_grad(const mpc_shape *s, const float *rows_warped, const float *grad_pos, const float *rows, int32_t d, int32_t S,
+                                        const float *t_ref, const float *scal, const float *grad_out, int64_t *acc, float *grad_table, void *stream) {
+    MPC_CHECK_ARG(s && rows && t_ref && scal && acc && grad_table && ((rows_warped && grad_pos) || s->M == 0 || s->B == 0), MPC_E_NULL, "null argument");
+    PEC_SHAPE_CHECKS();
+    MPC_CHECK_ARG(d >= 1 && S >= 1, MPC_E_SHAPE, "degree >= 1, samples >= 1");
+    MPC_CHECK_ARG(d <= PEC_DMAX, MPC_E_UNSUPPORTED, "more than 16 control points per axis");
+    MPC_CHECK_ARG((int64_t)(S + 1) * d <= mpc_pe_table_limit(), MPC_E_UNSUPPORTED, "(samples + 1) * degree exceeds mpc_pe_table_limit()");
+    hipStream_t st = (hipStream_t)stream;
+    static mpc_device_once attr_once;
+    const float2 *gpos = reinterpret_cast<const float2 *>(grad_pos);
+    return pe_table_basis_grad_run<PEC_DMAX>(
+        __func__, s, S, d, acc, st, attr_once, {(const void *)k_pec_table_grad<10>, (const void *)k_pec_table_grad<0>},
+        [&](int grid, size_t lds, unsigned long long *a) {
+            if (d == 10) MPC_LAUNCH(k_pec_table_grad<10>, dim3(grid), dim3(PE_TAB_NT), lds, st, *s, rows_warped, gpos, rows, S, d, a);
+            else MPC_LAUNCH(k_pec_table_grad<0>, dim3(grid), dim3(PE_TAB_NT), lds, st, *s, rows_warped, gpos, rows, S, d, a);
+        },
+        [&](int nent) {
+            MPC_LAUNCH(k_pec_table_finish, dim3((nent + 255) / 256), dim3(256), 0, st, reinterpret_cast<const unsigned long long *>(acc), S, d, t_ref, scal,
+                       grad_out, grad_table);
+        });
+}
+
+extern "C" int mpc_pec_field_basis_grad(const float *grad_field, const float *rows, const float *grad_out, double *part, float *grad_phim,
+                                        int32_t B, int32_t G, int32_t d, int32_t nbm, void *stream) {
+    return pe_field_basis_grad_run<PEC_DMAX>(__func__, "more than 16 orders or 64 field times", grad_field, rows, grad_out, part, grad_phim,
+                                             B, G, d, nbm, stream);
 }
 
 MPC_BOUNDS_UNIT("pe_curves.hip")

@@ -92,45 +92,7 @@ __global__ __launch_bounds__(256) void k_rows_grad_finish(const float *__restric
         if (j < k) { out[(size_t)i * 2 * k + j] = gy[j]; out[(size_t)i * 2 * k + k + j] = gx[j]; }
 }
 
-// The adjoint of k_basis_field with respect to phim (a basis that is differentiable: the table route of calc_per_event_basis):
-//   gphim[t][j] = gout * sum_{b, cell, d} gfield[(b, t)][cell][d] * rows[(b, cell)][d][j]
-// Workgroup (part, t) sums every FB_PARTS-th block of 256 cells in fp64 -- per thread, then block_sum_d: a fixed order -- into
-// part[t][part][j]; k_field_basis_grad_sum adds the parts in order.  Bitwise reproducible.
-#define FB_PARTS 64
-__global__ __launch_bounds__(256) void k_field_basis_grad_part(const float *__restrict__ gfield, const float *__restrict__ rows,
-                                                               double *__restrict__ part, int B, int G, int k, int nb, int P) {
-    __shared__ double s_red[256 / 64];
-    const int pt = blockIdx.x, t = blockIdx.y;
-    const long long n = (long long)B * G;
-    double a[TILE_KMAX];
-#pragma unroll
-    for (int j = 0; j < TILE_KMAX; ++j) a[j] = 0.0;
-    for (long long i = (long long)pt * 256 + threadIdx.x; i < n; i += (long long)P * 256) {
-        const int b = (int)(i / G), cell = (int)(i - (long long)b * G);
-        const float2 g = reinterpret_cast<const float2 *>(gfield)[((size_t)b * nb + t) * G + cell];
-        const float *c = rows + (size_t)i * 2 * k;
-#pragma unroll
-        for (int j = 0; j < TILE_KMAX; ++j)
-            if (j < k) a[j] += (double)g.x * (double)c[j] + (double)g.y * (double)c[k + j];
-    }
-#pragma unroll
-    for (int j = 0; j < TILE_KMAX; ++j) {
-        if (j < k) {                                               // (k is uniform: every thread takes the same branches)
-            const double v = block_sum_d<256>(a[j], s_red);
-            if (threadIdx.x == 0) part[((size_t)t * P + pt) * k + j] = v;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_field_basis_grad_sum(const double *__restrict__ part, const float *__restrict__ gout,
-                                                              float *__restrict__ gphim, int k, int nb, int P) {
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= nb * k) return;
-    const int t = idx / k, j = idx - t * k;
-    double v = 0.0;
-    for (int q = 0; q < P; ++q) v += part[((size_t)t * P + q) * k + j];
-    gphim[idx] = (float)((double)(gout ? gout[0] : 1.f) * v);
-}
+// (the adjoint of k_basis_field with respect to phim -- k_field_basis_grad_part / _sum -- is in pe_device.h: the curves hold 16 orders)
 
 static int tile_args(int B, int S, int c2, int H, int W, int tile, const char *who) {
     if (B < 0 || S < 1 || c2 < 2 || (c2 & 1) || H < 1 || W < 1 || tile < 1) { mpc_set_error("%s: bad shape", who); return MPC_E_SHAPE; }
@@ -180,17 +142,6 @@ extern "C" int mpc_pe_rows_grad_finish(const float *grad_parts, int32_t split, c
 
 extern "C" int mpc_pe_field_basis_grad(const float *grad_field, const float *coef_rows, const float *grad_out, double *part, float *grad_phim,
                                        int32_t B, int32_t G, int32_t k, int32_t nb, void *stream) {
-    MPC_CHECK_ARG(grad_field && coef_rows && part && grad_phim, MPC_E_NULL, "null argument");
-    MPC_CHECK_ARG(B >= 0 && G >= 0 && k >= 1 && nb >= 1, MPC_E_SHAPE, "bad shape");
-    MPC_CHECK_ARG(k <= TILE_KMAX && nb <= 64, MPC_E_UNSUPPORTED, "more than 8 basis orders or 64 time bins");
-    hipStream_t st = (hipStream_t)stream;
-    const long long n = (long long)B * G;
-    const int P = (int)((n + 255) / 256 < FB_PARTS ? (n + 255) / 256 : FB_PARTS);
-    if (P > 0) {
-        MPC_LAUNCH(k_field_basis_grad_part, dim3(P, nb), dim3(256), 0, st, grad_field, coef_rows, part, B, G, k, nb, P);
-        MPC_CHECK_LAUNCH();
-    }
-    MPC_LAUNCH(k_field_basis_grad_sum, dim3((nb * k + 255) / 256), dim3(256), 0, st, part, grad_out, grad_phim, k, nb, P);
-    MPC_CHECK_LAUNCH();
-    return 0;
+    return pe_field_basis_grad_run<TILE_KMAX>(__func__, "more than 8 basis orders or 64 time bins", grad_field, coef_rows, grad_out, part, grad_phim,
+                                              B, G, k, nb, stream);
 }

@@ -294,7 +294,8 @@ class FocusLoss(base.TrajectoryLossBase):
             raise ValueError(f'without up_mask the grid of params is the tile grid and must equal the look-up-table grid {hq} x {wq}, got {h} x {w}')
         return c2 // 2, tile
 
-    def calc_per_event_curves(self, params, t_ref, batch, *, up_mask=None, curve_type='BEZIER', basis_table=None, scale=1.0, fused=True):
+    def calc_per_event_curves(self, params, t_ref, batch, *, up_mask=None, curve_type='BEZIER', basis_table=None, scale=1.0, fused=True,
+                              basis_network=None, table_samples=1024):
         """UNPINNED EXTENSION (BASELINE.json's north_star and configs[3]): the per-event continuous-time warp along RAFT-spline
         curves.  Every event moves along the curve of the tile it lies in, evaluated at ITS OWN timestamp -- no time bins, no KNN
         look-up table, time not piecewise constant (`trajectories_from_bezier(up_mask=)` + `calc` is that route).
@@ -308,19 +309,47 @@ class FocusLoss(base.TrajectoryLossBase):
           warped = (y, x) + sum_j rows[cell(y, x)][:, j] * phi_j,   phi_j = E_j(t_ref) - E_j(t_event)      (j ascending)
         with E of `utils.curve_event_basis`: curve_type 'BEZIER' (1 <= d), 'POLYNOMIAL', 'BSPLINE' (the clamped cubic B-spline of
         d + 1 control points, evaluated exactly: 3 <= d, ValueError below; at most 8 of the d coefficient pairs are read per event),
-        or 'TABLE' with basis_table [S + 1, d] (a constant, e.g. a frozen learned basis).  Then the reference's weights,
+        or 'TABLE' with basis_table [S + 1, d] (a frozen learned basis, say -- or one that trains: below).  Then the reference's weights,
         vote, blur and objective; the smoothness term is the reference's Charbonnier term on rows x phim with
         phim[t] = E(t_ref) - E(t_mid[t]) ('on_flow_to_tref') or E(t_mid[t + 1]) - E(t_mid[t]) ('on_flow_to_next').
-        Returns the triple of `calc`.  Gradients go to params and up_mask only.
+        Returns the triple of `calc`.  Gradients go to params and up_mask -- and to basis_table where it requires grad (and grad
+        mode is on): d loss / d T through the events, where with (gy, gx) the position gradient of a row, G_j = gy * rows[cell][0][j]
+        + gx * rows[cell][1][j], (i, f) the interval of the row's time and (ir, fr) that of t_ref, T's gradient gets -(1 - f) G_j at
+        [i][j], -f G_j at [i + 1][j], +(1 - fr) G_j at [ir][j] and +fr G_j at [ir + 1][j] (rows of weight 0 add nothing), and through
+        the smoothness term, whose phim is then built inside the graph with `utils.table_basis_values`.  A table that does not
+        require grad is a constant and runs exactly what it ran before.
+        curve_type='LEARNED', basis_network=net, table_samples=S (default 1024): the reference's learned curve (curves/learned.py:
+        76-77) tabulated -- shorthand for curve_type='TABLE', basis_table=utils.curve_basis('LEARNED', arange(S + 1) / S, d, net): the
+        network runs at the S + 1 knots inside the graph, and autograd carries the table's gradient into its parameters.
+        The fused node serves (S + 1) * d <= mpc_pe_table_limit() = 16384: at d = 16 the default table_samples = 1024 is ONE knot
+        past it (16400) and takes the plain-torch route, roughly 10 to 40 times slower -- pass table_samples <= 1023 there (d = 10: up to
+        1637).  The table is moved to the events' device; a caller's own basis_table on another device is not, and leaves the node.
 
         fused=True: one autograd node (ops.PerEventCurvesFn, csrc/pe_curves.hip), the basis evaluated in registers; with a
         bucket-ordered batch (`event_offsets`) the backward sums per LUT strip in LDS fixed point, bitwise reproducible, in
         ceil(d / orders per pass) passes; without the table it uses global float atomics (slow, not reproducible).
         fused=False, and whatever the library refuses (d > 16, a table past mpc_pe_table_limit(), num_bins > 64, a CPU basis_table):
-        phi [B, M, d] and the rows in plain torch around the existing per-event nodes (the cross-check).  No graph capture."""
-        from ..utils import curve_event_basis, curve_head_rows
+        phi [B, M, d] and the rows in plain torch around the existing per-event nodes (the cross-check).  A table that trains is
+        served by the fused node wherever a constant one is (mpc_pec_table_basis_grad: one more streaming pass, Q33.30 sums, bitwise
+        reproducible in either event layout; |G_j| < 2^31 and a knot's sum over the batch below 2^33); elsewhere phi stays in the
+        graph and plain torch around the vote / objective kernels delivers the same three gradients.  No graph capture."""
+        from ..utils import curve_event_basis, curve_head_rows, curve_basis, table_basis_values
         from ..utils.basis import CURVE_EVENT_TYPES, BSPLINE_MIN_DEGREE
         d, tile = self._curve_tile_grid(params, up_mask, scale)
+        if curve_type == 'LEARNED':
+            if basis_table is not None:
+                raise ValueError("curve_type='LEARNED' builds its own table from basis_network: pass no basis_table")
+            if basis_network is None:
+                raise ValueError("curve_type='LEARNED' needs basis_network")
+            S = int(table_samples)
+            if S < 1:
+                raise ValueError(f'table_samples must be >= 1, got {table_samples}')
+            net_dev = next((p.device for p in basis_network.parameters()), batch['events'].device)
+            # (the network at the knots i / S, inside the graph; a wrong output width raises in curve_basis)
+            basis_table = curve_basis('LEARNED', torch.arange(S + 1, dtype=torch.float32, device=net_dev) / float(S), d, basis_network)
+            # (a network on another device than the events: the table moves, inside the graph, and the fused node still serves it)
+            basis_table = basis_table.to(batch['events'].device)
+            curve_type = 'TABLE'
         if curve_type not in CURVE_EVENT_TYPES:
             raise ValueError(f'curve_type must be one of {CURVE_EVENT_TYPES}, got {curve_type!r}')
         if (curve_type == 'TABLE') != (basis_table is not None):
@@ -349,31 +378,61 @@ class FocusLoss(base.TrajectoryLossBase):
         if fused and not ops.pec_supported(self._cfg, events, int(num_pos_events), d, curve_type,
                                            basis_table.shape[0] - 1 if basis_table is not None else 0) & 1:
             fused = False
+        # a table that TRAINS stays in the graph; any other is the constant it was
+        trains = basis_table is not None and basis_table.requires_grad and torch.is_grad_enabled()
         if basis_table is not None:
-            basis_table = basis_table.detach().to(dev)
+            basis_table = basis_table.to(dev) if trains else basis_table.detach().to(dev)
         phim = None
         if self.smooth_weight > 0:
             from ..utils.synth import bin_mid_times
             tm = self._tmid_dev.get(dev)
             if tm is None:
                 tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
-            with torch.no_grad():
-                # (the basis at the bin mid-times is a constant of (curve, d): kept -- the torch lines of the B-spline are ~80 small
-                # launches, 0.3 ms of host time per step; a table is the caller's and may change between calls)
-                key = (dev, curve_type, d)
-                em = self._pec_mid_basis.get(key) if basis_table is None else None
-                if em is None:
-                    em = curve_event_basis(tm, d, curve_type, basis_table)
-                    if basis_table is None:
-                        if len(self._pec_mid_basis) >= 16:
-                            self._pec_mid_basis.clear()
-                        self._pec_mid_basis[key] = em
-                phim = (em[1:] - em[:-1]) if self.smooth_type == 'on_flow_to_next' else (curve_event_basis(t_ref, d, curve_type, basis_table) - em)
+            if trains:
+                # (in the graph: the lines of curve_event_basis('TABLE'), the same bits)
+                if self.smooth_type == 'on_flow_to_next':
+                    em = table_basis_values(basis_table, tm)
+                    phim = em[1:] - em[:-1]
+                else:
+                    bv = table_basis_values(basis_table, torch.cat((t_ref, tm)))    # (one evaluation for t_ref and the mid-times)
+                    phim = bv[:1] - bv[1:]
+            else:
+                with torch.no_grad():
+                    # (the basis at the bin mid-times is a constant of (curve, d): kept -- the torch lines of the B-spline are ~80 small
+                    # launches, 0.3 ms of host time per step; a table is the caller's and may change between calls)
+                    key = (dev, curve_type, d)
+                    em = self._pec_mid_basis.get(key) if basis_table is None else None
+                    if em is None:
+                        em = curve_event_basis(tm, d, curve_type, basis_table)
+                        if basis_table is None:
+                            if len(self._pec_mid_basis) >= 16:
+                                self._pec_mid_basis.clear()
+                            self._pec_mid_basis[key] = em
+                    phim = (em[1:] - em[:-1]) if self.smooth_type == 'on_flow_to_next' else (curve_event_basis(t_ref, d, curve_type, basis_table) - em)
             if phim.shape[0] == 0:
                 phim = None
         if fused:
             loss, focus, smooth, iwes = ops.PerEventCurvesFn.apply(params, up_mask, events, t_ref, phim, self._cfg, int(num_pos_events), offsets,
                                                                    curve_type, basis_table, float(scale), tile)
+        elif trains:
+            # plain torch around the vote / objective kernels with phi INSIDE the graph (autograd carries its gradient to the table):
+            # the chain of calc_per_event_basis for a table the library does not serve, and the cross-check of the fused node
+            sp, G, M = self.lut_superpixel_size, hq * wq, events.shape[1]
+            phi = table_basis_values(basis_table, t_ref) - table_basis_values(basis_table, events[..., 2])
+            c_rows = curve_head_rows(params, up_mask, scale, tile)
+            with torch.no_grad():
+                iy = torch.div(events[..., 0], sp, rounding_mode='floor').long().clamp_(0, hq - 1)      # focus.py:186-187
+                ix = torch.div(events[..., 1], sp, rounding_mode='floor').long().clamp_(0, wq - 1)
+                idx = (torch.arange(B, device=dev).view(-1, 1) * G + iy * wq + ix).reshape(-1)
+            ce = ops.GatherRowsFn.apply(c_rows, idx).view(B, M, 2, d)
+            warped = events[..., :2] + (ce * phi[:, :, None, :]).sum(-1)                              # [B, M, 2]  (y, x)
+            focus, iwes = ops.PrewarpedFocusFn.apply(warped, events, t_ref, self._cfg, int(num_pos_events))
+            smooth = torch.zeros((), device=dev)
+            if phim is not None:
+                nbm = phim.shape[0]
+                field = (c_rows.reshape(B * G * 2, d) @ phim.t()).view(B, G, 2, nbm).permute(0, 3, 1, 2).reshape(B * nbm, hq, wq, 2)
+                smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
+            loss = focus + smooth
         else:
             with torch.no_grad():
                 phi = curve_event_basis(t_ref, d, curve_type, basis_table) - curve_event_basis(events[..., 2], d, curve_type, basis_table)

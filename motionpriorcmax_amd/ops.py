@@ -1140,6 +1140,11 @@ class PerEventCurvesFn(torch.autograd.Function):
     mpc_event_pos_grad -> mpc_pec_rows_grad [-> mpc_pec_field_adjoint] -> mpc_pec_head_rows_bwd.
     params [B, 2d, h, w] (x channels first), up_mask [B, 576, h, w] or None, phim [nbm, d] or None (no smoothness term), table
     [S + 1, d] or None.  Returns (loss, focus, smooth, iwes_blurred); differentiable w.r.t. params and up_mask through `loss`.
+    A table that requires grad trains as well: through the events by mpc_pec_table_basis_grad (one streaming pass over the warped
+    records, the position gradients the backward has anyway and the tile rows; Q33.30 sums, bitwise reproducible in either event
+    layout), through the smoothness term by returning the gradient of `phim` (mpc_pec_field_basis_grad), which torch chains into
+    the table through utils.table_basis_values.  The tile rows are kept for that only: with a constant table (and phim) the node
+    makes the calls it made before the table could train, the same launches and the same bits.
     No host synchronisation.  The position gradient is taken UNSCALED (a `scal` of ones) and the loss scale applied after the
     fixed-point sums, as k_pe_accum does: the sums' resolution does not depend on grad_out."""
 
@@ -1174,6 +1179,9 @@ class PerEventCurvesFn(torch.autograd.Function):
         if not sup & 1:
             raise ValueError(f'the curve kernels do not serve d={d}, {curve_type}, samples={S}, num_bins={cfg.num_bins} (mpc_pec_supported)')
         need_grad = params.requires_grad or (up_mask is not None and up_mask.requires_grad)
+        # (inputs 9 and 4: the table and phim -- a table that trains reaches the loss through both)
+        basis_trains = (tab is not None and ctx.needs_input_grad[9]) or (pm is not None and ctx.needs_input_grad[4])
+        need_grad = need_grad or basis_trains
         c_rows = torch.empty((B * G, 2 * d), dtype=torch.float32, device=dev)
         _call('mpc_pec_head_rows', dev, _ptr(p), _ptr(m), float(scale), int(tile), _ptr(c_rows), B, d, h, w)
         ws = alloc_workspace(shape, dev)
@@ -1189,14 +1197,14 @@ class PerEventCurvesFn(torch.autograd.Function):
         none = tr
         ctx.save_for_backward(p, m if m is not None else none, rows, tr, gimg if gimg is not None else none, scal,
                               offs if offs is not None else none, g_field if g_field is not None else none,
-                              pm if pm is not None else none, tab if tab is not None else none)
+                              pm if pm is not None else none, tab if tab is not None else none, c_rows if basis_trains else none)
         return _pe_outputs(ctx, scal, blur)
 
     @staticmethod
     def backward(ctx, g_loss, g_focus, g_smooth, g_blur):
         if g_loss is None:
             return (None,) * 13
-        p, m, rows, tr, gimg, scal, offs, g_field, pm, tab = ctx.saved_tensors
+        p, m, rows, tr, gimg, scal, offs, g_field, pm, tab, c_rows = ctx.saved_tensors
         has_mask, has_smooth, has_offs, has_tab = ctx.has
         shape = ctx.shape
         B, d, h, w, kind, S, scale, tile, opp = ctx.dims
@@ -1212,6 +1220,17 @@ class PerEventCurvesFn(torch.autograd.Function):
               kind, d, _ptr(tab) if has_tab else None, S, _ptr(tr), _ptr(scal), _ptr(go), opp, _ptr(g_rows))
         if has_smooth:
             _call('mpc_pec_field_adjoint', dev, _ptr(g_field), _ptr(pm), _ptr(go), _ptr(g_rows), B, G, d, pm.shape[0])
+        g_table = g_phim = None
+        if has_tab and ctx.needs_input_grad[9]:
+            acc = torch.empty(((S + 2) * d,), dtype=torch.int64, device=dev)
+            g_table = torch.empty_like(tab)
+            _call('mpc_pec_table_basis_grad', dev, ctypes.byref(shape), _ptr(rows) if gpos is not None else None, _ptr(gpos), _ptr(c_rows), d, S,
+                  _ptr(tr), _ptr(scal), _ptr(go), _ptr(acc), _ptr(g_table))
+        if has_smooth and ctx.needs_input_grad[4]:
+            nbm = pm.shape[0]
+            part = torch.empty((nbm * 64 * d,), dtype=torch.float64, device=dev)
+            g_phim = torch.empty_like(pm)
+            _call('mpc_pec_field_basis_grad', dev, _ptr(g_field), _ptr(c_rows), _ptr(go), _ptr(part), _ptr(g_phim), B, G, d, nbm)
         if PEC_ROWS_GRAD_TAP is not None:
             PEC_ROWS_GRAD_TAP.append(g_rows.clone())
         gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
@@ -1221,7 +1240,7 @@ class PerEventCurvesFn(torch.autograd.Function):
             ws = torch.empty(max(_query('mpc_pec_head_rows_bwd_workspace_bytes', dev, B, d, h, w, tile), 256), dtype=torch.uint8, device=dev)
         _call('mpc_pec_head_rows_bwd', dev, _ptr(g_rows), _ptr(p), _ptr(m) if has_mask else None, scale, tile, _ptr(gp), _ptr(gm), B, d, h, w,
               _ptr(ws))
-        return (gp, gm) + (None,) * 11
+        return (gp, gm, None, None, g_phim) + (None,) * 4 + (g_table,) + (None,) * 3
 
 
 class TileCoeffRowsFn(torch.autograd.Function):

@@ -136,6 +136,14 @@ bool mpc_knn_uses_far_list(const mpc_shape *s);
 __device__ __forceinline__ float mpc_div_sp(float v, int sp) {
     return ((sp & (sp - 1)) == 0) ? v * (1.f / (float)sp) : v / (float)sp;
 }
+// Issue priority of the calling wavefront (0 .. 3; VALU issue on a SIMD is arbitrated by priority, then by age).  Scalar, ignores EXEC: only
+// in control flow that is uniform over the workgroup.  Expands to nothing unless a kernel's priority switch (tuning.h) is on, so that a
+// build with every switch at 0 holds no such instruction -- the builtin also fences the compiler's scheduler.
+#if KS_PRIO || KNN_BW_PRIO
+#define MPC_PRIO(n) __builtin_amdgcn_s_setprio(n)
+#else
+#define MPC_PRIO(n) ((void)0)
+#endif
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

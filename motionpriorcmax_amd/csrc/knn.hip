@@ -974,6 +974,11 @@ __global__ __launch_bounds__(256, NEXT ? KNN_BW_OCC_NEXT : (IWD ? KNN_BW_OCC_IWD
                                                       int gx, int gy, int bd, int *far_next, const float *__restrict__ gnext_scale KB_STAMP_PARAM) {
     constexpr int TS = 16;
     KB_STAMP_BEGIN
+    // (KNN_BW_PRIO, tuning.h) the phases before the window loop -- reach, row ranges, staging: a chain of dependent round trips -- issue
+    // ahead of the older workgroups' window arithmetic.  Measured zero-sum, the switch is off (profiles/issue_prio_runs.md).  Every MPC_PRIO
+    // of this kernel sits at its top level or at that of the loop over rounds of points (behind the `continue` of a wavefront without
+    // points, a wave-uniform branch), never in a per-lane branch: the instruction is scalar and ignores EXEC.
+    if (KNN_BW_PRIO) MPC_PRIO(1);
     extern __shared__ __align__(16) unsigned char s_dyn[];
     if (blockIdx.x == 0 && threadIdx.x == 0 && far_next != nullptr) *far_next = 0;       // (k_knn_bwd_far, the next launch: its dynamic items)
     __shared__ int s_rowbase[KNN_TROWS + 1];
@@ -1143,6 +1148,7 @@ __global__ __launch_bounds__(256, NEXT ? KNN_BW_OCC_NEXT : (IWD ? KNN_BW_OCC_IWD
         const int g = act ? s_rowg[lo] + (pi - s_rowbase[lo]) : 0;
         const float2 pt = sp_[MPC_IDX(g, p.n)];
         const int i = si_[MPC_IDX(g, p.n)];
+        if (KNN_BW_PRIO) MPC_PRIO(0);                 // (the cells are staged, the point is requested: the window loop runs at priority 0)
         // query cells within reach: |q - p| <= R per axis (R carries a 0.01 px + 1e-4 relative margin, which dominates
         // the rounding of these expressions)
         int y0 = (int)ceilf((pt.x - R - p.off) * inv_sp), y1 = (int)floorf((pt.x + R - p.off) * inv_sp);
@@ -1216,6 +1222,7 @@ __global__ __launch_bounds__(256, NEXT ? KNN_BW_OCC_NEXT : (IWD ? KNN_BW_OCC_IWD
                 }
             }
         }
+        if (KNN_BW_PRIO == 2) MPC_PRIO(1);            // (the final stores; a further round of points drops it again above)
         if (act) {
             // no flow_to_next term: d traj(t_mid)[t] = -g goes straight to its place in the trajectory gradient (the value
             // k_knn_bwd_combine would write: -g + 0 - 0); k_knn_bwd_combine_direct then only adds the bins up

@@ -56,6 +56,9 @@
 #ifndef KS_RETRY_BLOCKS
 #define KS_RETRY_BLOCKS (256 * KS_MORE_OCC)   // strip workgroups of the tail launch
 #endif
+// (256 = the CUs of an MI355X.  The figure only says among how many workgroups the strip work is dealt out: forward progress rests on
+// tail_fallback_blocks, which asks the device.  As a launch argument worked out from the queried CU count it cost k_knn_tail<2, true,
+// false, false> two more spilled registers, 16 -> 18 -- the kernel has no scalar register to spare: it stays a constant.)
 static_assert(KNN_FAR_WS * KNN_FAR_TH == KS_NT, "a block of queries of the second launch = one workgroup");
 static_assert(KNN_RCAP <= 6, "the packed chord widths of the main launch");
 static_assert(KNN_MARGIN > KNN_RCAP, "the strip kernel must not reach the outermost ring of the bucket grid");
@@ -111,6 +114,10 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
 #define KS_SYNC() __syncthreads()
     KS_STP_DECL
     KS_STP();
+    // (KS_PRIO, tuning.h) main launch: the load phases -- radius from the table, row table, staging: few instructions, each at the head of
+    // a dependent round trip -- issue ahead of the older workgroups' search arithmetic.  Every MPC_PRIO of this body sits at its top
+    // level (workgroup-uniform); the early return of an overflowed strip needs none: the priority dies with the wave.
+    if (MODE == 0 && KS_PRIO) MPC_PRIO(KS_PRIO == 2 ? 2 : 1);
     constexpr int MAXCH = FARK ? KS_MAXCH_FAR : (L1 ? KS_MAXCH_L1 : KS_MAXCH);      // words of four slots per query
     (void)SPLIT;
     constexpr int RC = FARK ? KNN_RFAR : KNN_RCAP;
@@ -461,6 +468,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
         }
         KS_SYNC();
         KS_STP();    // 4: staged
+        if (MODE == 0 && KS_PRIO) MPC_PRIO(0);
 
         // ---- search --------------------------------------------------------------------------------------
         const float qy = (float)(cy * p.sp) + p.off, qx = (float)(cx * p.sp) + p.off;
@@ -746,6 +754,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             }
         }
         // ---- outputs ---------------------------------------------------------------------------------------
+        if (MODE == 0 && KS_PRIO == 2) MPC_PRIO(1);      // (a finished workgroup gives up its slot sooner)
         if (live) {
             const size_t BQ = (size_t)p.B * p.nb * p.G;
             float2 ov; float norm = 0.f;
@@ -1355,14 +1364,26 @@ bool mpc_knn_strip_counts_events(const mpc_shape *s, const EvCountArgs *evc) {
 // Fallback workgroups of a tail launch: as many as KS_FB_BLOCKS, but at least 32 workgroup slots fewer than the chip holds
 // workgroups of this kernel at once (see k_knn_tail: a fallback workgroup may spin until the strip workgroups are done, and those
 // must always find a free slot), and no fewer than `min_fb` (the event-count prefix of mpc_focus_fwd rides in the first B of them).
-static int tail_fallback_blocks(const void *kernel, size_t lds_tail, int min_fb) {
-    int dev = 0, ncu = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, KS_NT, lds_tail) != hipSuccess) {
-        (void)hipGetLastError();
-        mpc_set_error("mpc_knn_strip_launch: occupancy query failed");
-        return MPC_E_UNSUPPORTED;
+// The CU count of the device and the occupancy of instantiation `inst` (0 .. 7) of k_knn_tail come from ONE query
+// per device, instantiation and LDS size, kept in a word -- LDS size + 1 | CUs << 32 | workgroups per CU << 48 -- that later launches read
+// (the three runtime calls per launch were host time of every step).  Two threads (forward and autograd thread) may both run the query,
+// which is harmless: it is idempotent and the word is written whole.
+static int tail_fallback_blocks(const void *kernel, int inst, size_t lds_tail, int min_fb) {
+    static std::atomic<uint64_t> cache[64][8];
+    std::atomic<uint64_t> &slot = cache[mpc_device_once::dev()][inst];
+    uint64_t c = slot.load(std::memory_order_acquire);
+    if ((uint32_t)c != (uint32_t)lds_tail + 1u) {
+        int dev = 0, ncu_q = 0, per_cu_q = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu_q, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_q, kernel, KS_NT, lds_tail) != hipSuccess || ncu_q < 1 || ncu_q > 0xffff || per_cu_q < 0) {
+            (void)hipGetLastError();
+            mpc_set_error("mpc_knn_strip_launch: occupancy query failed");
+            return MPC_E_UNSUPPORTED;
+        }
+        c = (uint64_t)((uint32_t)lds_tail + 1u) | ((uint64_t)ncu_q << 32) | ((uint64_t)(per_cu_q & 0xffff) << 48);
+        slot.store(c, std::memory_order_release);
     }
+    const int ncu = (int)((c >> 32) & 0xffff), per_cu = (int)(c >> 48);
     const long long slots = (long long)ncu * per_cu;
     // (32 slots -- one per group of 8 CUs -- stay free of spinners whatever happens: enough for forward progress in ANY dispatch order;
     // with the hardware's usual order the strip workgroups hold their slots before a fallback workgroup starts, and what counts is how
@@ -1400,7 +1421,8 @@ int mpc_knn_strip_launch(const mpc_shape *s, const float *traj, const knn_cs_t *
     do {                                                                                                                  \
         MPC_LAUNCH((k_knn_strip<WS, L1_, NEXT_, IWD_>), grid, dim3(KS_NT), lds, st, p, traj, cell_start, sat, spos, sidx, \
                            flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy, ec, n_evc, evc_stride);   \
-        const int fb_ = tail_fallback_blocks((const void *)k_knn_tail<WS, L1_, NEXT_, IWD_>, lds_tail, ec.events ? ec.B : 0); \
+        const int fb_ = tail_fallback_blocks((const void *)k_knn_tail<WS, L1_, NEXT_, IWD_>, (L1_ ? 4 : 0) | (NEXT_ ? 2 : 0) | (IWD_ ? 1 : 0), \
+                                             lds_tail, ec.events ? ec.B : 0);                                             \
         if (fb_ < 0) return fb_;                                                                                          \
         MPC_LAUNCH((k_knn_tail<WS, L1_, NEXT_, IWD_>), dim3(KS_RETRY_BLOCKS + fb_), dim3(KS_NT), lds_tail, st, p, traj, cell_start, sat, spos, sidx, \
                            flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy, ec);                      \

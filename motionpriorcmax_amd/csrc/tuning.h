@@ -85,7 +85,24 @@
 #define KNN_FAR_BLOCKS 4096     // (2048: 237 us against 218 at a 48 px contraction band)
 #endif
 
+#ifndef KNN_BW_PRIO
+#define KNN_BW_PRIO 0         // k_knn_bwd_tile: issue priority (MPC_PRIO) of its phases.  0: none, the kernel as it was; 1: raised from entry to the window
+                              // loop (reach, row ranges, staging), 0 in the loop; 2: as 1 and raised again for the final stores.
+                              // Measured, not kept (profiles/issue_prio_runs.md): the phase before the loop falls from 4.5 to 2.9 us of a workgroup and
+                              // the loop grows by as much -- lifetime 10.3 -> 10.4 us; k_knn_bwd_tile at C3, kernel trace, medians of two runs each:
+                              // 0: 106.9 / 104.9 us, 1: 106.5 / 105.4, 2: 108.2 / 106.4 (2 also spills three more registers with flow_to_next + 'iwd')
+#endif
+
 // ---- knn_strip.hip -------------------------------------------------------------------------------------------------
+#ifndef KS_PRIO
+#define KS_PRIO 1                   // k_knn_strip (main launch only; the tail's strip workgroups run with few waves per SIMD): issue priority (MPC_PRIO)
+                                    // of its phases.  0: none, the kernel as it was; 1: raised from the start of the body to the "staged" barrier, 0 from
+                                    // pass 1 on; 2: priority 2 up to that barrier, 0 from pass 1 through the ranking of the K-th level, 1 from the outputs on.
+                                    // k_knn_strip at C3, kernel trace, medians of two runs each (profiles/issue_prio_runs.md): 0: 214.6 / 215.9 us,
+                                    // 1: 204.5 / 205.5; in the visit before, with 2 beside them: 0: 222.1 / 215.1, 1: 210.9 / 205.3, 2: 211.7 / 205.7.
+                                    // A workgroup's phases (white noise): before the search 11.4 -> 7.4 us, search 8.7 -> 11.9, lifetime 20.1 -> 19.3:
+                                    // most of what the load phases gain the search gives back, the rest is the 10 us.  2 buys nothing over 1.
+#endif
 #ifndef KS_MORE_MIN
 #define KS_MORE_MIN 16               // a strip goes to the second launch for its unfinished queries if it has more than this many (or far queries)
 #endif

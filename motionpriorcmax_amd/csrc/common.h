@@ -154,6 +154,30 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
 }
+// Inclusive scan of `v` over the wavefront (every lane active).
+__device__ __forceinline__ int wave_scan_incl(int v) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if ((tid & 63) >= o) v += t; }
+    return v;
+}
+// Exclusive prefix of src[0 .. n) into dst[0 .. n), starting at `base`, by a workgroup of 256 threads: a contiguous segment of
+// the array per thread, the 256 segment sums scanned per wavefront and carried over the four wave sums (s_wsum: 4 ints of LDS;
+// one barrier inside, none behind the stores).  Returns the prefix behind the thread's own segment: in thread 255, base + the total.
+__device__ __forceinline__ int block_prefix_excl(const int *src, int *dst, int n, int *s_wsum, int base = 0) {
+    const int tid = threadIdx.x;
+    const int per = (n + 255) >> 8;
+    const int i0 = min(tid * per, n), i1 = min(i0 + per, n);
+    int local = 0;
+    for (int i = i0; i < i1; ++i) local += src[i];
+    const int incl = wave_scan_incl(local);
+    if ((tid & 63) == 63) s_wsum[tid >> 6] = incl;
+    __syncthreads();
+    int run = base + incl - local;
+    for (int w = 0; w < (tid >> 6); ++w) run += s_wsum[w];
+    for (int i = i0; i < i1; ++i) { dst[i] = run; run += src[i]; }
+    return run;
+}
 // Sum of `v` over a workgroup of NT threads (NT multiple of 64); result valid in thread 0.
 template <int NT>
 __device__ __forceinline__ double block_sum_d(double v, double *lds /* NT/64 doubles */) {

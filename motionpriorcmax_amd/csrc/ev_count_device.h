@@ -6,7 +6,7 @@
 // The counting pass reads the events once (67 MB at C3).  In the fused forward it rides in spare workgroups of the KNN
 // strip kernel (VALU bound, HBM idle); stand-alone it is k_ev_count (events.hip).
 #pragma once
-#include "common.h"
+#include "ev_key_device.h"
 
 struct EvCountArgs {
     const float *events;   // [B][M][6]; null: nothing to count
@@ -31,7 +31,7 @@ __device__ __forceinline__ void ev_count_block(const EvCountArgs &a, int blk, in
     const int nk = a.nb * a.NCS;
     for (int i = tid; i < nk; i += 256) s_cnt[i] = 0;
     __syncthreads();
-    const float inv_CSR = 1.f / (float)a.CSR;
+    const float inv_CSR = ev_strip_inv(a.CSR);
     const int r0 = chunk * EV_COUNT_ROWS, r1 = min(r0 + EV_COUNT_ROWS, a.M);
     // columns 0 (y) and 4 (bin) of the row: two 8-byte loads of the three that make up a row; eight rows of a thread in
     // flight together (the workgroup holds a slot of the kernel it rides in: it has to be short)
@@ -45,13 +45,8 @@ __device__ __forceinline__ void ev_count_block(const EvCountArgs &a, int blk, in
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             if (i0 + u * 256 >= r1) continue;
-            // the cell exactly as warp_cell (events.hip) computes it
-            int it = (int)bn[u].x;
-            int iy = (int)floorf(mpc_div_sp(ya[u].x, a.sp));
-            it = min(max(it, 0), a.nb - 1);
-            iy = min(max(iy, 0), a.hq - 1);
-            const int cst = (int)(((float)iy + 0.5f) * inv_CSR);
-            atomicAdd(&s_cnt[it * a.NCS + cst], 1);
+            const int it = (int)bn[u].x, iy = ev_cell_raw(ya[u].x, a.sp);
+            atomicAdd(&s_cnt[ev_clamp(it, a.nb) * a.NCS + ev_strip(ev_clamp(iy, a.hq), inv_CSR)], 1);
         }
     }
     __syncthreads();
@@ -64,21 +59,9 @@ __device__ __forceinline__ void ev_count_block(const EvCountArgs &a, int blk, in
 // first record of every backward bucket of sample b = exclusive prefix of its capacities (once the counting is complete:
 // a later kernel).  256 threads; s_tmp: 4 ints of LDS
 __device__ __forceinline__ void ev_prefix_block(const EvCountArgs &a, int b, int *s_tmp) {
-    const int tid = threadIdx.x, nk = a.nb * a.NCS;
+    const int nk = a.nb * a.NCS;
     const int *cap = a.cap + (size_t)b * nk;
-    int *start = a.cap + (size_t)a.B * nk + (size_t)b * nk;
-    const int per = (nk + 255) >> 8;
-    const int i0 = min(tid * per, nk), i1 = min(i0 + per, nk);
-    int local = 0;
-    for (int i = i0; i < i1; ++i) local += cap[i];
-    int incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += v; }
-    if ((tid & 63) == 63) s_tmp[tid >> 6] = incl;
-    __syncthreads();
-    int run = incl - local;
-    for (int w = 0; w < (tid >> 6); ++w) run += s_tmp[w];
-    for (int i = i0; i < i1; ++i) { start[i] = run; run += cap[i]; }
+    block_prefix_excl(cap, a.cap + (size_t)a.B * nk + (size_t)b * nk, nk, s_tmp);
     __syncthreads();
 }
 #endif

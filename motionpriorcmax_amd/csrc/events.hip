@@ -33,17 +33,11 @@ __device__ __forceinline__ EvParams make_params(const mpc_shape s) {
 
 // Warp one event for reference time `tr`.  `e` = the 6 columns of the event row.
 // Returns false if the event contributes nothing (weight exactly 0).
-// LUT cell of an event (focus.py:184-191): it = int(bin), iy = int(y // sp), ix = int(x // sp)
+// LUT cell of an event (ev_key_device.h)
 __device__ __forceinline__ void warp_cell(const EvParams &p, const float e[6], int b, int tr, Warped &o) {
-    int it = (int)e[4];
-    int iy = (int)floorf(mpc_div_sp(e[0], p.sp));
-    int ix = (int)floorf(mpc_div_sp(e[1], p.sp));
-    // torch indexing would raise on out-of-range indices; clamp instead of faulting
-    it = min(max(it, 0), p.nb - 1);
-    iy = min(max(iy, 0), p.hq - 1);
-    ix = min(max(ix, 0), p.wq - 1);
-    o.it = it; o.iy = iy; o.ix = ix;
-    o.lut = (((b * p.nb + it) * p.hq + iy) * p.wq + ix) * p.T + tr;
+    const int it = (int)e[4], iy = ev_cell_raw(e[0], p.sp), ix = ev_cell_raw(e[1], p.sp);
+    o.it = ev_clamp(it, p.nb); o.iy = ev_clamp(iy, p.hq); o.ix = ev_clamp(ix, p.wq);
+    o.lut = (((b * p.nb + o.it) * p.hq + o.iy) * p.wq + o.ix) * p.T + tr;
 }
 
 // Warp with the flow `f` of the event's LUT cell already at hand (warp_cell + a read of the table).
@@ -296,7 +290,7 @@ __global__ __launch_bounds__(256) void k_ev_bin(const mpc_shape s, const BinLayo
     for (int i = tid; i < nloc; i += 256) s_cnt[i] = 0;
     __syncthreads();
     const float tref = (p.flags & MPC_F_SCALE_BY_DT) ? t_ref[0] : 0.f;
-    const float inv_SR = 1.f / (float)L.SR, inv_CSR = 1.f / (float)L.CSR;
+    const float inv_SR = 1.f / (float)L.SR, inv_CSR = ev_strip_inv(L.CSR);
 
     float ry[EV_PER_THREAD], rx[EV_PER_THREAD], rw[EV_PER_THREAD];
     int f0[EV_PER_THREAD], f1[EV_PER_THREAD], bk[EV_PER_THREAD];     // local bucket ids (-1: none)
@@ -336,7 +330,7 @@ __global__ __launch_bounds__(256) void k_ev_bin(const mpc_shape s, const BinLayo
         if (s0 >= 0) { f0[k] = pol * L.NS + s0; r0[k] = atomicAdd(&s_cnt[MPC_IDX(f0[k], nf_loc)], 1); }
         if (s1 >= 0 && s1 != s0) { f1[k] = pol * L.NS + s1; r1[k] = atomicAdd(&s_cnt[MPC_IDX(f1[k], nf_loc)], 1); }
         if (want_bwd && o.lut >= 0) {
-            const int cst = (int)(((float)o.iy + 0.5f) * inv_CSR);
+            const int cst = ev_strip(o.iy, inv_CSR);
             bk[k] = nf_loc + o.it * L.NCS + cst;
             rb[k] = atomicAdd(&s_cnt[MPC_IDX(bk[k], nloc)], 1);
             aux[k] = ((unsigned)pol << 31) | (unsigned)((o.iy - cst * L.CSR) * p.wq + o.ix);
@@ -359,14 +353,13 @@ __global__ __launch_bounds__(256) void k_ev_bin(const mpc_shape s, const BinLayo
     int *s_loc = s_base + nloc;                              // [nloc + 1]
     unsigned short *s_bid = reinterpret_cast<unsigned short *>(s_loc + nloc + 1);     // [EV_STAGE]
     float4 *s_rec = reinterpret_cast<float4 *>(s_cnt + stage_off);                     // [EV_STAGE]
-    {
+    {   // block_prefix_excl (common.h) written out: through the helper the compiler orders two instructions of this kernel
+        // differently, and this kernel's code is held as measured
         const int per = (nloc + 255) >> 8;
         const int i0 = min(tid * per, nloc), i1 = min(i0 + per, nloc);
         int local = 0;
         for (int i = i0; i < i1; ++i) local += s_cnt[i];
-        int incl = local;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int v = __shfl_up(incl, o, 64); if ((tid & 63) >= o) incl += v; }
+        const int incl = wave_scan_incl(local);
         if ((tid & 63) == 63) s_wsum[tid >> 6] = incl;
         __syncthreads();
         int run = incl - local;
@@ -1285,17 +1278,13 @@ extern "C" int mpc_event_pos_grad(const mpc_shape *s, const float *events, const
 // ==========================================================================================
 #define EVO_ROWS 2048          // rows of one chunk (256 threads x 8)
 
-struct EvoKey { int NCS, CSR, NK; };
-
-__device__ __forceinline__ int evo_key(const EvParams &p, const EvoKey &k, const float e[6]) {
+__device__ __forceinline__ int evo_key(const EvParams &p, const EvKey &k, const float e[6]) {
     if (e[5] == 0.f && !(p.flags & MPC_F_UNIT_WEIGHT)) return k.NK;   // padding row (weight 0: it votes for nothing)
-    const int it = min(max((int)e[4], 0), p.nb - 1);
-    const int iy = min(max((int)floorf(mpc_div_sp(e[0], p.sp)), 0), p.hq - 1);      // as warp_event
-    return it * k.NCS + iy / k.CSR;
+    return ev_key(k, p.nb, (int)e[4], e[0]);
 }
 
-// grid (chunks, 2 * B): counts[b][pol][key][chunk]
-__global__ __launch_bounds__(256) void k_evo_count(const mpc_shape s, const EvoKey k, const float *__restrict__ events,
+// grid (chunks, 2 * B): counts[b][pol][key][chunk] (ev_key_device.h)
+__global__ __launch_bounds__(256) void k_evo_count(const mpc_shape s, const EvKey k, const float *__restrict__ events,
                                                    int *__restrict__ counts, int chunks) {
     extern __shared__ int s_c[];
     const EvParams p = make_params(s);
@@ -1311,71 +1300,44 @@ __global__ __launch_bounds__(256) void k_evo_count(const mpc_shape s, const EvoK
         atomicAdd(&s_c[evo_key(p, k, e)], 1);
     }
     __syncthreads();
-    int *dst = counts + (size_t)(b * 2 + pol) * (k.NK + 1) * chunks + chunk;
-    for (int i = threadIdx.x; i <= k.NK; i += 256) dst[(size_t)i * chunks] = s_c[i];
+    for (int i = threadIdx.x; i <= k.NK; i += 256) counts[evo_count_at(k, chunks, b, pol, i, chunk)] = s_c[i];
 }
 
-// counts is [b][pol][key][chunk].  Step 1, grid (ceil((NK + 1) / 4), 2 * B), 256 threads: one wavefront per key scans
-// its chunks (lanes = chunks; in place -> the chunk's first row inside the key) and leaves the key's total.
-__global__ __launch_bounds__(256) void k_evo_scan_chunks(const EvoKey k, int *__restrict__ counts, int *__restrict__ totals, int chunks) {
+// Step 1, grid (ceil((NK + 1) / 4), 2 * B), 256 threads: one wavefront per key scans its chunks (lanes = chunks; in place ->
+// the chunk's first row inside the key) and leaves the key's total.
+__global__ __launch_bounds__(256) void k_evo_scan_chunks(const EvKey k, int *__restrict__ counts, int *__restrict__ totals, int chunks) {
     const int lane = threadIdx.x & 63, key = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (key > k.NK) return;
-    int *ci = counts + ((size_t)blockIdx.y * (k.NK + 1) + key) * chunks;
+    int *ci = counts + evo_count_at(k, chunks, blockIdx.y >> 1, blockIdx.y & 1, key, 0);
     int run = 0;
     for (int c0 = 0; c0 < chunks; c0 += 64) {
         const int ch = c0 + lane;
         const int v = ch < chunks ? ci[ch] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
+        const int incl = wave_scan_incl(v);
         if (ch < chunks) ci[ch] = run + incl - v;
         run += __shfl(incl, 63);
     }
     if (lane == 0) totals[(size_t)blockIdx.y * (k.NK + 1) + key] = run;
 }
 
-// Step 2, grid 2 * B, 256 threads: exclusive scan of the NK + 1 key totals of a polarity block -> offsets (a contiguous
-// segment of keys per thread, the 256 segment sums scanned by the first wavefront)
-__global__ __launch_bounds__(256) void k_evo_scan_keys(const mpc_shape s, const EvoKey k, const int *__restrict__ totals,
+// Step 2, grid 2 * B, 256 threads: exclusive scan of the NK + 1 key totals of a polarity block -> offsets
+__global__ __launch_bounds__(256) void k_evo_scan_keys(const mpc_shape s, const EvKey k, const int *__restrict__ totals,
                                                        int *__restrict__ offsets) {
-    __shared__ int s_seg[256];
-    const EvParams p = make_params(s);
-    const int pol = blockIdx.x & 1, lane = threadIdx.x & 63;
-    const int *tot = totals + (size_t)blockIdx.x * (k.NK + 1);
-    const int per = (k.NK + 1 + 255) / 256;
-    const int k0 = min((int)threadIdx.x * per, k.NK + 1), k1 = min(k0 + per, k.NK + 1);
-    int sum = 0;
-    for (int i = k0; i < k1; ++i) sum += tot[i];
-    s_seg[threadIdx.x] = sum;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        int carry = 0;
-        for (int c0 = 0; c0 < 256; c0 += 64) {
-            const int v = s_seg[c0 + lane];
-            int incl = v;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(incl, d); if (lane >= d) incl += o; }
-            s_seg[c0 + lane] = carry + incl - v;
-            carry += __shfl(incl, 63);
-        }
-    }
-    __syncthreads();
-    int run = (pol ? p.Mp : 0) + s_seg[threadIdx.x];
-    int *o = offsets + (size_t)blockIdx.x * (k.NK + 1);
-    for (int i = k0; i < k1; ++i) { o[i] = run; run += tot[i]; }
+    __shared__ int s_wsum[4];
+    const size_t o = (size_t)blockIdx.x * (k.NK + 1);
+    block_prefix_excl(totals + o, offsets + o, k.NK + 1, s_wsum, (blockIdx.x & 1) ? s.Mp : 0);
 }
 
 // grid (chunks, 2 * B)
-__global__ __launch_bounds__(256) void k_evo_scatter(const mpc_shape s, const EvoKey k, const float *__restrict__ events,
+__global__ __launch_bounds__(256) void k_evo_scatter(const mpc_shape s, const EvKey k, const float *__restrict__ events,
                                                      const int *__restrict__ counts, const int *__restrict__ offsets,
                                                      float *__restrict__ out, int chunks) {
     extern __shared__ int s_c[];
     const EvParams p = make_params(s);
     const int b = blockIdx.y >> 1, pol = blockIdx.y & 1, chunk = blockIdx.x;
     const int r0 = pol ? p.Mp : 0, r1 = pol ? p.M : p.Mp;
-    const int *cb = counts + (size_t)(b * 2 + pol) * (k.NK + 1) * chunks + chunk;
     const int *ob = offsets + (size_t)(b * 2 + pol) * (k.NK + 1);
-    for (int i = threadIdx.x; i <= k.NK; i += 256) s_c[i] = ob[i] + cb[(size_t)i * chunks];   // first destination row of the chunk's share
+    for (int i = threadIdx.x; i <= k.NK; i += 256) s_c[i] = ob[i] + counts[evo_count_at(k, chunks, b, pol, i, chunk)];   // first destination row of the chunk's share
     __syncthreads();
     for (int j = threadIdx.x; j < EVO_ROWS; j += 256) {
         const int row = r0 + chunk * EVO_ROWS + j;
@@ -1388,11 +1350,10 @@ __global__ __launch_bounds__(256) void k_evo_scatter(const mpc_shape s, const Ev
     }
 }
 
-// the two scans of the counting sort, for a counts array [b][pol][key][chunk] someone else filled (ingest.hip)
-int mpc_evo_scans(const mpc_shape *loss, int NCS, int CSR, int *kcounts, int *totals, int32_t *offsets, int chunks, hipStream_t st) {
-    const EvoKey k{NCS, CSR, loss->nb * NCS};
-    MPC_LAUNCH(k_evo_scan_chunks, dim3(mpc_cdiv(k.NK + 1, 4), 2 * loss->B), dim3(256), 0, st, k, kcounts, totals, chunks);
-    MPC_LAUNCH(k_evo_scan_keys, dim3(2 * loss->B), dim3(256), 0, st, *loss, k, totals, (int *)offsets);
+// the two scans of the counting sort, for a counts array someone filled (mpc_event_bucket_order below, ingest.hip)
+int mpc_evo_scans(const mpc_shape *s, const EvKey &k, const EvoWs &w, int32_t *offsets, hipStream_t st) {
+    MPC_LAUNCH(k_evo_scan_chunks, dim3(mpc_cdiv(w.nk1, 4), 2 * s->B), dim3(256), 0, st, k, w.counts, w.totals, w.chunks);
+    MPC_LAUNCH(k_evo_scan_keys, dim3(2 * s->B), dim3(256), 0, st, *s, k, w.totals, (int *)offsets);
     MPC_CHECK_LAUNCH();
     return 0;
 }
@@ -1404,9 +1365,7 @@ extern "C" int32_t mpc_event_lut_strips(const mpc_shape *s) {
 
 extern "C" int64_t mpc_event_order_workspace_bytes(const mpc_shape *s) {
     if (!s || mpc_validate_shape(s)) return MPC_E_SHAPE;
-    const mpc_ws_layout L = mpc_layout(s);
-    const int64_t chunks = mpc_cdiv(s->M > 0 ? s->M : 1, EVO_ROWS);
-    return mpc_align((int64_t)(s->B > 0 ? s->B : 1) * 2 * (chunks + 1) * ((int64_t)s->nb * L.n_cstrips + 1) * 4);      // counts + key totals
+    return evo_ws(s->B, s->nb * mpc_layout(s).n_cstrips, mpc_cdiv(s->M > 0 ? s->M : 1, EVO_ROWS), nullptr).bytes;
 }
 
 extern "C" int mpc_event_bucket_order(const mpc_shape *s, const float *events_in, float *events_out, int32_t *offsets,
@@ -1417,20 +1376,17 @@ extern "C" int mpc_event_bucket_order(const mpc_shape *s, const float *events_in
     const mpc_ws_layout L = mpc_layout(s);
     MPC_CHECK_ARG(L.n_cstrips > 0, MPC_E_UNSUPPORTED, "no LDS-tiled event path for this shape (num_tref > 1 or the atomic debugging path)");
     if (s->B == 0) return 0;
+    const EvKey k{L.n_cstrips, L.cstrip_rows, s->nb * L.n_cstrips, s->sp, s->hq};
     // no rows: every bucket is empty and starts at row 0
-    if (s->M == 0) return mpc_zero_async(offsets, (size_t)s->B * 2 * ((size_t)s->nb * L.n_cstrips + 1) * sizeof(int32_t), (hipStream_t)stream);
+    if (s->M == 0) return mpc_zero_async(offsets, (size_t)s->B * 2 * (k.NK + 1) * sizeof(int32_t), (hipStream_t)stream);
     MPC_CHECK_ARG(events_in != events_out, MPC_E_SHAPE, "in-place ordering is not supported");
-    const EvoKey k{L.n_cstrips, L.cstrip_rows, s->nb * L.n_cstrips};
-    const int chunks = mpc_cdiv(s->M, EVO_ROWS);       // of the longer block at most; chunks beyond a block's rows are empty
+    const EvoWs w = evo_ws(s->B, k.NK, mpc_cdiv(s->M, EVO_ROWS), ws);       // chunks of the longer block at most; chunks beyond a block's rows are empty
     hipStream_t st = (hipStream_t)stream;
-    int *counts = (int *)ws;
-    const size_t lds = (size_t)(k.NK + 1) * 4;
-    MPC_LAUNCH(k_evo_count, dim3(chunks, 2 * s->B), dim3(256), lds, st, *s, k, events_in, counts, chunks);
-    int *totals = counts + (size_t)2 * s->B * (k.NK + 1) * chunks;
-    MPC_LAUNCH(k_evo_scan_chunks, dim3(mpc_cdiv(k.NK + 1, 4), 2 * s->B), dim3(256), 0, st, k, counts, totals, chunks);
-    MPC_LAUNCH(k_evo_scan_keys, dim3(2 * s->B), dim3(256), 0, st, *s, k, totals, (int *)offsets);
-    MPC_LAUNCH(k_evo_scatter, dim3(chunks, 2 * s->B), dim3(256), lds, st, *s, k, events_in, counts, (const int *)offsets,
-                       events_out, chunks);
+    const size_t lds = (size_t)w.nk1 * 4;
+    MPC_LAUNCH(k_evo_count, dim3(w.chunks, 2 * s->B), dim3(256), lds, st, *s, k, events_in, w.counts, w.chunks);
+    if ((rc = mpc_evo_scans(s, k, w, offsets, st))) return rc;
+    MPC_LAUNCH(k_evo_scatter, dim3(w.chunks, 2 * s->B), dim3(256), lds, st, *s, k, events_in, w.counts, (const int *)offsets,
+                       events_out, w.chunks);
     MPC_CHECK_LAUNCH();
     return 0;
 }

@@ -8,7 +8,7 @@
 // Three passes: per-chunk counts and time extrema -> per-sample scan (chunk offsets, totals, batch
 // maxima) -> stable scatter (order inside each block is the input order, as boolean masking gives).
 // The caller reads the two batch maxima to size the output (the only host round trip of ingest).
-#include "common.h"
+#include "ev_key_device.h"
 #include "bounds.h"
 #include <type_traits>
 
@@ -230,12 +230,7 @@ __device__ __forceinline__ int bin_index(double tn, int nb) {
 // thread's first positive / negative (positives from the front, the negatives behind them), np_wg / nn_wg = the totals
 __device__ __forceinline__ void ing_block_rank(int lp, int ln, int (&s_w)[2][4], int &rp, int &rn, int &np_wg, int &nn_wg) {
     const int tid = threadIdx.x;
-    int ip = lp, in_ = ln;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int a = __shfl_up(ip, o, 64), c2 = __shfl_up(in_, o, 64);
-        if ((tid & 63) >= o) { ip += a; in_ += c2; }
-    }
+    const int ip = wave_scan_incl(lp), in_ = wave_scan_incl(ln);
     if ((tid & 63) == 63) { s_w[0][tid >> 6] = ip; s_w[1][tid >> 6] = in_; }
     __syncthreads();
     int wp = 0, wn = 0;
@@ -248,6 +243,22 @@ __device__ __forceinline__ void ing_block_rank(int lp, int ln, int (&s_w)[2][4],
     rp = wp + ip - lp; rn = np_wg + wn + in_ - ln;
 }
 
+// Workgroup `chunk` of the gridDim.x of sample b zeroes its share of the sample's padding rows (loader.py:360-364: zero rows,
+// valid = 0; they stay last in their polarity block [0, Mp) / [Mp, M)) -- not a memset of the whole tensor in front of the kernel
+__device__ __forceinline__ void ing_zero_padding(const IngLayout &L, int b, int chunk, int Mp, int M, float *__restrict__ events) {
+    const int tp = L.totals[b * 2], tn_ = L.totals[b * 2 + 1];
+    const int pad_p = 3 * (Mp - tp), pad_n = 3 * (M - Mp - tn_), pad = pad_p + pad_n;
+    if (pad > 0) {
+        const int per = (pad + (int)gridDim.x - 1) / (int)gridDim.x;
+        float2 *zp = reinterpret_cast<float2 *>(events + ((size_t)b * M + tp) * 6);
+        float2 *zn = reinterpret_cast<float2 *>(events + ((size_t)b * M + Mp + tn_) * 6);
+        const int j1 = min((chunk + 1) * per, pad);
+        for (int j = chunk * per + (int)threadIdx.x; j < j1; j += 256) {
+            if (j < pad_p) zp[j] = make_float2(0.f, 0.f); else zn[j - pad_p] = make_float2(0.f, 0.f);
+        }
+    }
+}
+
 // The rows a workgroup put together in LDS -> its two runs of the output (slot `chunk` of the offset table), and its share of
 // the sample's padding rows (loader.py:360-364: zero rows, valid = 0)
 __device__ __forceinline__ void ing_flush(const float2 *s_rows, const IngLayout &L, int b, int chunk, int np_wg, int nn_wg,
@@ -258,17 +269,7 @@ __device__ __forceinline__ void ing_flush(const float2 *s_rows, const IngLayout 
     float2 *dstn = reinterpret_cast<float2 *>(events + ((size_t)b * M + max_pos + L.chunk_off[co + 1]) * 6);
     for (int j = tid; j < 3 * np_wg; j += 256) dstp[j] = s_rows[j];
     for (int j = tid; j < 3 * nn_wg; j += 256) dstn[j] = s_rows[3 * np_wg + j];
-    const int tp = L.totals[b * 2], tn_ = L.totals[b * 2 + 1];
-    const int pad_p = 3 * (max_pos - tp), pad_n = 3 * (max_neg - tn_), pad = pad_p + pad_n;
-    if (pad > 0) {
-        const int per = (pad + (int)gridDim.x - 1) / (int)gridDim.x;
-        float2 *zp = reinterpret_cast<float2 *>(events + ((size_t)b * M + tp) * 6);
-        float2 *zn = reinterpret_cast<float2 *>(events + ((size_t)b * M + max_pos + tn_) * 6);
-        const int j1 = min((chunk + 1) * per, pad);
-        for (int j = chunk * per + tid; j < j1; j += 256) {
-            if (j < pad_p) zp[j] = make_float2(0.f, 0.f); else zn[j - pad_p] = make_float2(0.f, 0.f);
-        }
-    }
+    ing_zero_padding(L, b, chunk, max_pos, M, events);
 }
 
 // grid (nchunks, B), 256 threads.  Thread t owns 4 consecutive events, so ranks follow the input order.  The rows of a
@@ -344,17 +345,13 @@ __global__ __launch_bounds__(256) void k_ingest_rect_scatter(const mpc_ingest_sh
 // built, so ordering costs no pass over the event tensor of its own (ingest + mpc_event_bucket_order read and wrote the
 // tensor once more: 175 + 50 us at 14 x 200k events).  Counting sort: per-chunk counts of (polarity, key) -> the scans of
 // the bucket-order kernels (events.hip) -> scatter.  Order inside a bucket is not defined and need not be.
-struct IngKey { int NCS, CSR, NK, sp, hq; };
-
-__device__ __forceinline__ int ing_key(const mpc_ingest_shape &s, const IngKey &k, float yv, double tn) {
-    const int it = min(max(bin_index(tn, s.nb), 0), s.nb - 1);
-    const int iy = min(max((int)floorf(mpc_div_sp(yv, k.sp)), 0), k.hq - 1);          // as warp_cell (events.hip)
-    return it * k.NCS + iy / k.CSR;
+__device__ __forceinline__ int ing_key(const mpc_ingest_shape &s, const EvKey &k, float yv, double tn) {
+    return ev_key(k, s.nb, bin_index(tn, s.nb), yv);          // (the row's bin column holds (float)bin_index: the same int)
 }
 
 // grid (nchunks, B), 256 threads, dynamic LDS 2 * (NK + 1) ints: counts[b][pol][key][chunk]
 template <typename SRC>
-__device__ __forceinline__ void ing_keycount_body(const mpc_ingest_shape s, const IngLayout L, const IngKey k,
+__device__ __forceinline__ void ing_keycount_body(const mpc_ingest_shape s, const IngLayout L, const EvKey k,
                                                   const SRC c,
                                                   const long long *__restrict__ t, const float *__restrict__ p,
                                                   const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
@@ -381,17 +378,17 @@ __device__ __forceinline__ void ing_keycount_body(const mpc_ingest_shape s, cons
     __syncthreads();
     for (int i = tid; i < 2 * (k.NK + 1); i += 256) {
         const int pol = i / (k.NK + 1), key = i - pol * (k.NK + 1);
-        kcounts[((size_t)(b * 2 + pol) * (k.NK + 1) + key) * L.nchunks + chunk] = s_k[i];
+        kcounts[evo_count_at(k, L.nchunks, b, pol, key, chunk)] = s_k[i];
     }
 }
 
 // the two kernels of this body: float coordinates (the signature it always had) / raw indices + the rectification map
-__global__ __launch_bounds__(256) void k_ingest_keycount(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const float *__restrict__ x, const float *__restrict__ y,
+__global__ __launch_bounds__(256) void k_ingest_keycount(const mpc_ingest_shape s, const IngLayout L, const EvKey k, const float *__restrict__ x, const float *__restrict__ y,
     const long long *__restrict__ t, const float *__restrict__ p,
     const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
     ing_keycount_body(s, L, k, IngXY{x, y}, t, p, counts, kcounts, vec);
 }
-__global__ __launch_bounds__(256) void k_ingest_rect_keycount(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const int *__restrict__ x, const int *__restrict__ y,
+__global__ __launch_bounds__(256) void k_ingest_rect_keycount(const mpc_ingest_shape s, const IngLayout L, const EvKey k, const int *__restrict__ x, const int *__restrict__ y,
     const float2 *__restrict__ map, int Hs, int Ws, const long long *__restrict__ t, const float *__restrict__ p,
     const int *__restrict__ counts, int *__restrict__ kcounts, int vec) {
     ing_keycount_body(s, L, k, IngRect{x, y, map, Hs, Ws}, t, p, counts, kcounts, vec);
@@ -400,7 +397,7 @@ __global__ __launch_bounds__(256) void k_ingest_rect_keycount(const mpc_ingest_s
 // grid (nchunks, B), 256 threads, dynamic LDS 2 * (NK + 1) ints.  kcounts (scanned in place) = first row of this chunk's
 // share inside every (polarity, key); offsets [B][2][NK + 1] = first row of every key
 template <typename SRC>
-__device__ __forceinline__ void ing_scatter_ordered_body(const mpc_ingest_shape s, const IngLayout L, const IngKey k,
+__device__ __forceinline__ void ing_scatter_ordered_body(const mpc_ingest_shape s, const IngLayout L, const EvKey k,
                                                          const SRC c,
                                                          const long long *__restrict__ t, const float *__restrict__ p,
                                                          const int *__restrict__ counts, int M,
@@ -414,8 +411,7 @@ __device__ __forceinline__ void ing_scatter_ordered_body(const mpc_ingest_shape 
     const double span = (double)(tmax - tmin);
     for (int i = tid; i < 2 * (k.NK + 1); i += 256) {
         const int pol = i / (k.NK + 1), key = i - pol * (k.NK + 1);
-        const size_t o = (size_t)(b * 2 + pol) * (k.NK + 1) + key;
-        s_k[i] = offsets[o] + kcounts[o * L.nchunks + chunk];
+        s_k[i] = offsets[(size_t)(b * 2 + pol) * (k.NK + 1) + key] + kcounts[evo_count_at(k, L.nchunks, b, pol, key, chunk)];
     }
     __syncthreads();
     const int i0 = chunk * ING_CHUNK + tid * 4;
@@ -439,29 +435,18 @@ __device__ __forceinline__ void ing_scatter_ordered_body(const mpc_ingest_shape 
             e[2] = make_float2((float)bin_index(tn, s.nb), 1.f);
         }
     }
-    // this workgroup's share of the sample's padding rows (they stay last in their block; no memset of the tensor)
     const int Mp = offsets[(size_t)(b * 2 + 1) * (k.NK + 1)];          // first row of the negative block = max_pos
-    const int tp = L.totals[b * 2], tn_ = L.totals[b * 2 + 1];
-    const int pad_p = 3 * (Mp - tp), pad_n = 3 * (M - Mp - tn_), pad = pad_p + pad_n;
-    if (pad > 0) {
-        const int per = (pad + (int)gridDim.x - 1) / (int)gridDim.x;
-        float2 *zp = reinterpret_cast<float2 *>(events + ((size_t)b * M + tp) * 6);
-        float2 *zn = reinterpret_cast<float2 *>(events + ((size_t)b * M + Mp + tn_) * 6);
-        const int j1 = min((chunk + 1) * per, pad);
-        for (int j = chunk * per + tid; j < j1; j += 256) {
-            if (j < pad_p) zp[j] = make_float2(0.f, 0.f); else zn[j - pad_p] = make_float2(0.f, 0.f);
-        }
-    }
+    ing_zero_padding(L, b, chunk, Mp, M, events);
 }
 
 // the two kernels of this body: float coordinates (the signature it always had) / raw indices + the rectification map
-__global__ __launch_bounds__(256) void k_ingest_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const float *__restrict__ x, const float *__restrict__ y,
+__global__ __launch_bounds__(256) void k_ingest_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const EvKey k, const float *__restrict__ x, const float *__restrict__ y,
     const long long *__restrict__ t, const float *__restrict__ p,
     const int *__restrict__ counts, int M, const int *__restrict__ kcounts, const int *__restrict__ offsets,
     float *__restrict__ events, float *__restrict__ xytp, int vec) {
     ing_scatter_ordered_body(s, L, k, IngXY{x, y}, t, p, counts, M, kcounts, offsets, events, xytp, vec);
 }
-__global__ __launch_bounds__(256) void k_ingest_rect_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const IngKey k, const int *__restrict__ x, const int *__restrict__ y,
+__global__ __launch_bounds__(256) void k_ingest_rect_scatter_ordered(const mpc_ingest_shape s, const IngLayout L, const EvKey k, const int *__restrict__ x, const int *__restrict__ y,
     const float2 *__restrict__ map, int Hs, int Ws, const long long *__restrict__ t, const float *__restrict__ p,
     const int *__restrict__ counts, int M, const int *__restrict__ kcounts, const int *__restrict__ offsets,
     float *__restrict__ events, float *__restrict__ xytp, int vec) {
@@ -581,18 +566,13 @@ extern "C" int mpc_ingest_rect_scatter(const mpc_ingest_shape *s, int32_t Hs, in
 }
 
 
-// the scans of the bucket-order kernels (events.hip)
-int mpc_evo_scans(const mpc_shape *loss, int NCS, int CSR, int *kcounts, int *totals, int32_t *offsets, int chunks, hipStream_t st);
-
 extern "C" int64_t mpc_ingest_ordered_workspace_bytes(const mpc_ingest_shape *s, const mpc_shape *loss) {
     if (!s || !loss) { mpc_set_error("mpc_ingest_ordered_workspace_bytes: null shape"); return MPC_E_NULL; }
     int rc = ing_validate(s);
     if (rc) return rc;
     const int32_t ncs = mpc_event_lut_strips(loss);
     if (ncs <= 0) { mpc_set_error("mpc_ingest_ordered_workspace_bytes: no bucketed event layout for this loss shape"); return MPC_E_UNSUPPORTED; }
-    const int64_t nk1 = (int64_t)loss->nb * ncs + 1;
-    const int64_t nch = mpc_cdiv(s->N > 0 ? s->N : 1, ING_CHUNK);
-    return mpc_align((int64_t)(s->B > 0 ? s->B : 1) * 2 * nk1 * (nch + 1) * 4);
+    return evo_ws(s->B, loss->nb * ncs, mpc_cdiv(s->N > 0 ? s->N : 1, ING_CHUNK), nullptr).bytes;
 }
 
 // Same outputs as mpc_ingest_scatter followed by mpc_event_bucket_order for the loss shape `loss` (B, nb, H, W, sp, hq, wq,
@@ -615,14 +595,14 @@ static int ing_scatter_ordered(const char *fn, const mpc_ingest_shape *s, const 
     if (s->B == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const int64_t M = (int64_t)max_pos + max_neg;
-    const IngKey k{LL.n_cstrips, LL.cstrip_rows, loss->nb * LL.n_cstrips, loss->sp, loss->hq};
+    const EvKey k{LL.n_cstrips, LL.cstrip_rows, loss->nb * LL.n_cstrips, loss->sp, loss->hq};
     if (M > 0 && s->N == 0) {
         const int e = mpc_zero_async(events, (size_t)s->B * M * 6 * sizeof(float), st);     // padding rows only (else: the scatter kernel zeroes them)
         if (e) return e;
     }
     const IngLayout L = ing_layout(s, ws).L;
-    int *kcounts = (int *)ws_order;
-    int *totals = kcounts + (size_t)2 * s->B * (k.NK + 1) * L.nchunks;
+    const EvoWs w = evo_ws(s->B, k.NK, L.nchunks, ws_order);
+    int *kcounts = w.counts;
     const size_t lds = (size_t)2 * (k.NK + 1) * sizeof(int);
     if (s->N == 0) return mpc_zero_async(offsets, (size_t)s->B * 2 * (k.NK + 1) * sizeof(int32_t), st);
     const long long *t = reinterpret_cast<const long long *>(t_us);
@@ -630,7 +610,7 @@ static int ing_scatter_ordered(const char *fn, const mpc_ingest_shape *s, const 
     if constexpr (std::is_same<SRC, IngXY>::value) MPC_LAUNCH(k_ingest_keycount, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, t, p, counts, kcounts, vec);
     else MPC_LAUNCH(k_ingest_rect_keycount, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, c.map, c.Hs, c.Ws, t, p, counts, kcounts, vec);
     MPC_CHECK_LAUNCH();
-    if ((rc = mpc_evo_scans(loss, k.NCS, k.CSR, kcounts, totals, offsets, L.nchunks, st))) return rc;
+    if ((rc = mpc_evo_scans(loss, k, w, offsets, st))) return rc;
     if constexpr (std::is_same<SRC, IngXY>::value) MPC_LAUNCH(k_ingest_scatter_ordered, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, t, p,
                                                               counts, (int)M, kcounts, (const int *)offsets, events, xytp, vec);
     else MPC_LAUNCH(k_ingest_rect_scatter_ordered, dim3(L.nchunks, s->B), dim3(256), lds, st, *s, L, k, c.x, c.y, c.map, c.Hs, c.Ws, t, p,

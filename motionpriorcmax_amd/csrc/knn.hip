@@ -410,12 +410,7 @@ __global__ __launch_bounds__(1024) void k_knn_bucket_scan(const KnnParams p, int
     const int g0 = min(tid * chunk, p.Gb), g1 = min(g0 + chunk, p.Gb);
     int local = 0;
     for (int g = g0; g < g1; ++g) local += cur[g];
-    int incl = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int v = __shfl_up(incl, o, 64);
-        if ((tid & 63) >= o) incl += v;
-    }
+    const int incl = wave_scan_incl(local);
     if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
     __syncthreads();
     int run = incl - local;

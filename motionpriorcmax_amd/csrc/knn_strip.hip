@@ -370,9 +370,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
                 padded = len == 0 ? 0 : len + ((len & 1) ? 0 : 1);
             }
         }
-        int incl = padded;
-#pragma unroll
-        for (int o2 = 1; o2 < 64; o2 <<= 1) { const int v = __shfl_up(incl, o2, 64); if ((tid & 63) >= o2) incl += v; }
+        const int incl = wave_scan_incl(padded);
         const int wmx = wave_max_i(padded);
         if ((tid & 63) == 63) { s_wsum[tid >> 6] = incl; s_wmax[tid >> 6] = wmx; }
         KS_SYNC();

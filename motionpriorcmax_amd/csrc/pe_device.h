@@ -3,7 +3,7 @@
 // to each other bit for bit hold because every line below exists once.
 #pragma once
 #include <initializer_list>
-#include "common.h"
+#include "ev_key_device.h"
 #include "bounds.h"
 
 #define PE_KMAX 8              // basis orders the basis families hold in registers (beyond: k_pe_*<0> read phi per use)
@@ -253,7 +253,7 @@ static int pe_field_basis_grad_run(const char *who, const char *beyond, const fl
 
 // the LUT cell of an event's own position (y, x) in sample b (focus.py:186-187)
 __device__ __forceinline__ int pe_own_cell(int b, float y, float x, int sp, int hq, int wq) {
-    const int iy = min(max((int)floorf(mpc_div_sp(y, sp)), 0), hq - 1), ix = min(max((int)floorf(mpc_div_sp(x, sp)), 0), wq - 1);
+    const int iy = ev_cell(y, sp, hq), ix = ev_cell(x, sp, wq);
     return (b * hq + iy) * wq + ix;
 }
 

@@ -75,14 +75,14 @@ struct mpc_ws_layout {
     int64_t off_knn_tmp_a;   // float2 [B*nb][n]
     int64_t off_knn_cursor;  // int32  [B*nb][Gb]  fill cursors of the global-memory bucket sort (only when Gb*4 B exceeds the LDS sort)
     int64_t off_knn_reach;   // float  [B*nb][tiles of the bucket grid]  backward search reach per 16x16 tile
-    int64_t off_knn_fail;    // int32  [1 + B*nb*G]  queries handed from the strip kernel to the fallback kernel
-    int64_t off_knn_retry;   // int32  [1 + B*nb*ceil(wq/2)*ceil(hq/128)]  strips the strip kernel searches again in quarters (staging overflow)
-    int64_t off_knn_farstrip; // int32 [1 + strips]  strips that hold far queries (k_knn_tail)
+    int64_t off_knn_fail;    // int32  [1 + B*nb*G]  queries for the fallback workgroups of k_knn_tail: the fail list upwards, the marked / late list downwards (knn_device.h)
+    int64_t off_knn_retry;   // int32  [1 + B*nb*ceil(wq/2)*ceil(hq/128)]  strips whose points overflowed the staging area: the retry quarters of k_knn_tail's strip workgroups
+    int64_t off_knn_farstrip; // int32 [1 + strips]  strips that hold marked queries: the far items of k_knn_tail's strip workgroups
     int64_t off_knn_ftlist;  // int32 [1 + B*nb*tiles]  (sample, bin, tile) work items of k_knn_bwd_far;  off_knn_ftbits: uint32 [B*nb][ceil(tiles/32)] the same as bits
     int64_t off_knn_ftbits;
-    int64_t off_knn_chord;   // uint8 [21][21]  chord table of the strip kernels (knn_device.h: knn_chord_cells)
-    int64_t off_knn_again;   // uint32 [2][B*nb][hq][ceil(wq/32)]  queries the strip kernel's main launch hands to its second launch; those that need more rings
-    int64_t off_knn_far;     // int32  [B*nb][1 + G]  per (sample, bin): the queries the fallback kernel served, for k_knn_bwd_far
+    int64_t off_knn_chord;   // uint8 [21][21]  chord table of the far items of k_knn_tail (knn_device.h: knn_chord_cells)
+    int64_t off_knn_again;   // uint32 [2][B*nb][hq][ceil(wq/32)]  queries the main launch (k_knn_strip) marks for the far items of k_knn_tail; those that need more rings
+    int64_t off_knn_far;     // int32  [B*nb][1 + G]  per (sample, bin): the far queries the tail launch served, for k_knn_bwd_far
     // event partition (LDS-tiled path)
     int64_t off_fcount;      // int32 [nfb + nbb + 8] bucket fill counters, marker; then [nbb] capacities and [nbb] first records of the backward buckets
     int64_t off_frec;        // float4 [nfb][fcap]
@@ -159,6 +159,12 @@ __device__ __forceinline__ int wave_scan_incl(int v) {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if ((tid & 63) >= o) v += t; }
+    return v;
+}
+// Maximum of `v` over the wavefront, in every lane (every lane active).
+__device__ __forceinline__ int wave_max_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
 }
 // Exclusive prefix of src[0 .. n) into dst[0 .. n), starting at `base`, by a workgroup of 256 threads: a contiguous segment of

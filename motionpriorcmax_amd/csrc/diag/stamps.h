@@ -18,7 +18,7 @@
 #define BK_STAMP_WRITE(ls_, tid_) do { } while (0)
 #endif
 
-// ---- -DKS_STAMP2: phases of a work item of the far pass of k_knn_tail (tools/more_stamp_probe.py) --------------------------
+// ---- -DKS_STAMP2: phases of a far item of k_knn_tail (tools/more_stamp_probe.py) --------------------------
 // (-DKS_STAMP0, round 6: the same stamps for the MAIN launch, one record per strip workgroup: tools/strip_stamp_probe.py)
 #if defined(KS_STAMP2) || defined(KS_STAMP0)
 #ifdef KS_STAMP0

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(1024) void k_knn_bucket(const KnnParams p, const fl
     BK_STAMP(0);
     const int bt = blockIdx.x / S, part = blockIdx.x - bt * S, b = bt / p.nb, t = bt - b * p.nb;
     // set-up for the strip query kernel, which follows on the stream: its per-tile maxima are accumulated with
-    // atomicMax and its fallback lists are appended to (knn_strip.hip)
+    // atomicMax and its work lists are appended to (knn_strip.hip)
     if (part == 0) for (int i = tid; i < ntiles * KNN_NCLS; i += 1024) tile_dkmax[(size_t)bt * ntiles * KNN_NCLS + i] = 0.f;
     // ... and the work lists of the forward start empty (knn_device.h: KnnLists)
     if (part == 0 && ls.far != nullptr) {
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(1024) void k_knn_bucket(const KnnParams p, const fl
     }
     if (part == 0 && ls.again != nullptr) for (int i = tid; i < ls.again_words; i += 1024) { ls.again[(size_t)bt * ls.again_words + i] = 0u; ls.grow[(size_t)bt * ls.again_words + i] = 0u; }
     if (blockIdx.x == 0 && tid == 0) { ls.fail[0] = 0; ls.retry[0] = 0; ls.farstrip[0] = 0; if (ls.ftlist) ls.ftlist[0] = 0; *knn_marked_count(ls) = 0; *knn_late_count(ls) = 0; *knn_tail_done(ls) = 0; }
-    if (blockIdx.x == 0 && tid < (KNN_RFAR + 1) * (KNN_RFAR + 1))      // (the chord table of the strip kernels' row tables)
+    if (blockIdx.x == 0 && tid < (KNN_RFAR + 1) * (KNN_RFAR + 1))      // (the chord table of the far items' row tables, knn_strip.hip)
         ls.chord[tid] = (unsigned char)max(knn_chord_cells(tid / (KNN_RFAR + 1), tid % (KNN_RFAR + 1), p.sp, p.l1 != 0), 0);
     if (blockIdx.x == 0) for (int i = tid; i < zero_words; i += 1024) zero_ptr[i] = 0;      // (mpc_focus_fwd: the event bucket counters)
     const int rows_per = (p.hb + S - 1) / S;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(1024) void k_knn_bucket(const KnnParams p, const fl
 
 // ------------------------------------------------------------------------------------------
 // Summed-area table of the cell counts of one (sample, bin): sat[y][x] = points in cells (y', x') of the bucket grid with
-// y' < y and x' < x, (hb + 1) x (wb + 1) entries.  The strip kernel and its fallback read the number of points in a query's
+// y' < y and x' < x, (hb + 1) x (wb + 1) entries.  The main and tail launch of the strip search (knn_strip.hip) read the number of points in a query's
 // search square from it (four loads) to choose the radius of the square.
 // Built from the first bucketed point of every cell (rowstart(y, x), x in [0, wb]: x = wb is one past the row), whose
 // differences along a row are the row prefixes; the sum over the rows in two levels: groups of 8 rows first (s_part), then
@@ -590,43 +590,6 @@ __global__ __launch_bounds__(NT) void k_knn_query(const KnnParams p, const float
     if (cy < p.hq && cx < p.wq) knn_tile_max_add(tile_dkmax, p, bt, cy, cx, knn_band_depth(r_init), dK);
 }
 
-__device__ __forceinline__ int wave_max_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-// Gather over the query window of one trajectory point (num_tref == 1, 'mean'): one 16-byte LDS read
-// {K-th distance, K-th index, dL/dLUT.y, dL/dLUT.x} per query cell; membership is a bitwise predicate
-// (no short-circuit branches), so the unrolled body is straight-line code.
-template <bool L1, bool NEXT>
-__device__ __forceinline__ void bwd_window(const float4 *__restrict__ lq4, const float2 *__restrict__ lgn,
-                                           int RW, int ry0, int rx0, int y0, int y1, int x0, int x1,
-                                           int sp, float off, float2 pt, int i, float &ay, float &ax,
-                                           float2 &an) {
-    ay = 0.f; ax = 0.f;
-    const float fsp = (float)sp;
-    for (int cy = y0; cy <= y1; ++cy) {
-        const float dy = ((float)(cy * sp) + off) - pt.x;
-        const float dy2 = L1 ? fabsf(dy) : dy * dy;
-        const float4 *row = lq4 + (cy - ry0) * RW - rx0;
-        const float2 *rown = lgn + (cy - ry0) * RW - rx0;
-        float qx = (float)(x0 * sp) + off;              // exact: small integers, same value as (float)(cx*sp)+off
-#pragma unroll 4
-        for (int cx = x0; cx <= x1; ++cx) {
-            const float4 e = row[cx];
-            const float dx = qx - pt.y;
-            const float d = dy2 + (L1 ? fabsf(dx) : dx * dx);
-            const int lt = d < e.x, eq = d == e.x, le = i <= __float_as_int(e.y);
-            const bool in = (lt | (eq & le)) != 0;
-            ay += in ? e.z : 0.f;
-            ax += in ? e.w : 0.f;
-            if (NEXT) { const float2 gq = rown[cx]; an.x += in ? gq.x : 0.f; an.y += in ? gq.y : 0.f; }
-            qx += fsp;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // backward, step 0: search reach of the points of every 16x16 cell tile = the largest K-th distance
 // among the tiles whose queries can reach into the tile at all (Chebyshev gap between the tile's cell
@@ -666,35 +629,29 @@ __global__ __launch_bounds__(256) void k_knn_reach(const KnnParams p, const floa
 }
 
 // ------------------------------------------------------------------------------------------
-// backward, step 1: one thread per bucketed trajectory point of a TS x TS cell tile.  The K-th
-// keys and LUT gradients of the tile and a halo of RQ cells are staged in LDS; each point scans
-// the query cells within the reach of its 16x16 tile and gathers the gradient of every cell that
-// has the point among its K nearest.  Writes per-(bin, point) partials.
-// The kernel is a chain of short dependent phases (reach -> region -> points -> window), so large
-// workgroups (TS = 32: 1024 threads, 4 points' worth of window work per phase) amortise the chain:
-// measured at C3, 16x16 tiles 210 us of which only ~70 us is the window loop.
-// grid (ceil(wq/TS), ceil(hq/TS), B*nb), TS*TS threads, dynamic LDS
+// backward, step 1 of the general gather (num_tref > 1: the loss with trefs_as_samples=False; num_tref == 1 takes
+// k_knn_bwd_tile): one thread per bucketed trajectory point of a 16x16 cell tile.  Each point scans the query cells
+// within the reach of its tile (k_knn_reach) in global memory -- nothing is staged -- and gathers, for each of the T
+// reference times, the gradient of every cell that has the point among its K nearest ('mean': weight 1 / K; 'iwd': the
+// distance weight over the query's saved normaliser), and the flow_to_next gradient (always a mean).  Writes the
+// per-(bin, point) partials tmp_g and tmp_a (zeros without flow_to_next) for k_knn_bwd_combine.
+// grid: 1-D over the gx * gy tiles of every (sample, bin), XCD-contiguous; 256 threads
 // ------------------------------------------------------------------------------------------
-#define KNN_RQ_MAX 9   // largest staged halo (cells); tiles whose reach needs more read the global arrays (7 -> 9: the 1 % of such tiles at C3 took 47 us each against 12, and were the whole duration of a B = 1 launch)
-template <int TS>
-__global__ __launch_bounds__(TS * TS) void k_knn_bwd_points(const KnnParams p, const knn_cs_t *__restrict__ cell_start,
-                                                            const float2 *__restrict__ spos,
-                                                            const knn_idx_t *__restrict__ sidx,
-                                                            const float *__restrict__ glut,
-                                                            const float *__restrict__ gnext,
-                                                            const float *__restrict__ knn_state,
-                                                            const float *__restrict__ reach,
-                                                            float2 *__restrict__ tmp_g,   // [B*nb][n][T]
-                                                            float2 *__restrict__ tmp_a,   // [B*nb][n]
-                                                            int gx, int gy) {
-    constexpr int NT = TS * TS, SUB = TS / 16;
-    extern __shared__ __align__(16) unsigned char s_dyn[];
+__global__ __launch_bounds__(256) void k_knn_bwd_points(const KnnParams p, const knn_cs_t *__restrict__ cell_start,
+                                                        const float2 *__restrict__ spos,
+                                                        const knn_idx_t *__restrict__ sidx,
+                                                        const float *__restrict__ glut,
+                                                        const float *__restrict__ gnext,
+                                                        const float *__restrict__ knn_state,
+                                                        const float *__restrict__ reach,
+                                                        float2 *__restrict__ tmp_g,   // [B*nb][n][T]
+                                                        float2 *__restrict__ tmp_a,   // [B*nb][n]
+                                                        int gx, int gy) {             // (the tiles of the bucket grid: knn_tiles_x / _y)
     __shared__ int s_rowbase[KNN_TROWS + 1];
     __shared__ int s_rowg[KNN_TROWS];
-    __shared__ float s_Rsub[SUB * SUB];
     const int tid = threadIdx.x;
-    // 1-D grid, XCD-contiguous: the gx*gy tiles of one (sample, bin) run on one XCD, so the halo cells that
-    // neighbouring tiles stage again are found in that XCD's L2
+    // 1-D grid, XCD-contiguous: the gx*gy tiles of one (sample, bin) run on one XCD, whose L2 then serves the query
+    // cells that the windows of neighbouring tiles share
     const int nblk = gx * gy * p.B * p.nb;
     const int lblk = (int)(blockIdx.x & 7) * ((nblk + 7) >> 3) + (int)(blockIdx.x >> 3);
     if (lblk >= nblk) return;
@@ -706,13 +663,9 @@ __global__ __launch_bounds__(TS * TS) void k_knn_bwd_points(const KnnParams p, c
     int tcy0, tcy1, tcx0, tcx1;           // cells of the tile's points: a border tile owns the margin beside it (knn_tile_cells)
     knn_tile_cells(by_, p.hq, p.m, tcy0, tcy1); knn_tile_cells(bx_, p.wq, p.m, tcx0, tcx1);
     const int nrow = tcy1 - tcy0;
-    // phase 1 (independent loads): reach of the 16x16 sub-tiles; per tile row the contiguous range of
-    // the bucketed arrays, turned into a running offset by a wavefront scan
-    if (tid < SUB * SUB) {
-        const int gx16 = knn_tiles_x(p.wq, p.m), gy16 = knn_tiles_y(p.hq, p.m);
-        const int ty = by_ * SUB + tid / SUB, tx = bx_ * SUB + tid % SUB;
-        s_Rsub[tid] = (ty < gy16 && tx < gx16) ? reach[((size_t)bt * gy16 + ty) * gx16 + tx] : 0.f;
-    }
+    // reach of the tile (one word at a workgroup-uniform address); per tile row the contiguous range of the bucketed
+    // arrays, turned into a running offset by a wavefront scan
+    const float R = reach[(size_t)bt * gx * gy + bxy];
     if (tid < 64) {
         int gs = 0, ge = 0;
         if (tid < nrow) { gs = cs[knn_ci(p, tcy0 + tid, tcx0)]; ge = cs[knn_ci(p, tcy0 + tid, tcx1)]; }      // cell rows of the tile, margin included
@@ -723,45 +676,14 @@ __global__ __launch_bounds__(TS * TS) void k_knn_bwd_points(const KnnParams p, c
         if (tid == 0) s_rowbase[0] = 0;
     }
     __syncthreads();
-    float R = s_Rsub[0];
-#pragma unroll
-    for (int k = 1; k < SUB * SUB; ++k) R = fmaxf(R, s_Rsub[k]);
-    const int RQ_need = (int)ceilf(R / (float)p.sp) + 1;      // halo of the staged region, in cells
-    const bool use_lds = RQ_need <= KNN_RQ_MAX;
-    const int RQ = use_lds ? RQ_need : 0;
-    const int RW = TS + 2 * RQ;
-    const int ry0 = by_ * TS - RQ, rx0 = bx_ * TS - RQ;
-    // LDS: only the fast path (num_tref == 1, 'mean') stages anything: one float4 per query cell
-    // {K-th distance, K-th index, dL/dLUT.y, dL/dLUT.x} (+ float2 of the flow_to_next gradient)
-    float4 *lq4 = reinterpret_cast<float4 *>(s_dyn);
-    float2 *lgn = reinterpret_cast<float2 *>(s_dyn + (size_t)RW * RW * 16);
-    const bool fast = use_lds && p.T == 1 && !p.iwd;
     const bool has_next = (gnext != nullptr) && (t < p.nb - 1);
     const float2 *gn2 = has_next ? reinterpret_cast<const float2 *>(gnext) + (size_t)(b * (p.nb - 1) + t) * p.G : nullptr;
     const float2 *gl2 = reinterpret_cast<const float2 *>(glut) + (size_t)bt * p.G * p.T;
-    if (fast) {
-        for (int i = tid; i < RW * RW; i += NT) {
-            const int rr = i / RW, cc = i - rr * RW;
-            const int yy = ry0 + rr, xx = rx0 + cc;
-            float dk = -1.f; int ik = -1;
-            float2 g = make_float2(0.f, 0.f), gn = make_float2(0.f, 0.f);
-            if (yy >= 0 && yy < p.hq && xx >= 0 && xx < p.wq) {
-                const size_t q = (size_t)bt * p.G + (size_t)yy * p.wq + xx;
-                dk = knn_state[q];
-                ik = reinterpret_cast<const int *>(knn_state)[BQ + q] & KNN_IDX_MASK;
-                g = gl2[(size_t)yy * p.wq + xx];
-                if (has_next) gn = gn2[(size_t)yy * p.wq + xx];
-            }
-            lq4[i] = make_float4(dk, __int_as_float(ik), g.x, g.y);
-            if (has_next) lgn[i] = gn;
-        }
-    }
-    __syncthreads();
     const int total = s_rowbase[nrow];
     const float invK = 1.f / (float)p.K, inv_sp = 1.f / (float)p.sp;
     const float2 *sp_ = spos + (size_t)bt * p.n;
     const knn_idx_t *si_ = sidx + (size_t)bt * p.n;
-    for (int pi = tid; pi < total; pi += NT) {
+    for (int pi = tid; pi < total; pi += 256) {
         int lo = 0, hi = nrow;
         while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (s_rowbase[mid] <= pi) lo = mid; else hi = mid; }
         const int g = s_rowg[lo] + (pi - s_rowbase[lo]);
@@ -775,23 +697,7 @@ __global__ __launch_bounds__(TS * TS) void k_knn_bwd_points(const KnnParams p, c
         int x0 = (int)ceilf((pt.y - R - p.off) * inv_sp);
         int x1 = (int)floorf((pt.y + R - p.off) * inv_sp);
         y0 = max(y0, 0); x0 = max(x0, 0); y1 = min(y1, p.hq - 1); x1 = min(x1, p.wq - 1);
-        if (fast) {      // the staged region always covers the window (see the note on clamped cells)
-            y0 = max(y0, ry0); x0 = max(x0, rx0); y1 = min(y1, ry0 + RW - 1); x1 = min(x1, rx0 + RW - 1);
-        }
         float2 an = make_float2(0.f, 0.f);
-        if (fast) {
-            float ay, ax;
-            if (p.l1) {
-                if (has_next) bwd_window<true, true>(lq4, lgn, RW, ry0, rx0, y0, y1, x0, x1, p.sp, p.off, pt, i, ay, ax, an);
-                else bwd_window<true, false>(lq4, lgn, RW, ry0, rx0, y0, y1, x0, x1, p.sp, p.off, pt, i, ay, ax, an);
-            } else {
-                if (has_next) bwd_window<false, true>(lq4, lgn, RW, ry0, rx0, y0, y1, x0, x1, p.sp, p.off, pt, i, ay, ax, an);
-                else bwd_window<false, false>(lq4, lgn, RW, ry0, rx0, y0, y1, x0, x1, p.sp, p.off, pt, i, ay, ax, an);
-            }
-            tmp_g[(size_t)bt * p.n + i] = make_float2(invK * ay, invK * ax);
-            if (gnext != nullptr) tmp_a[(size_t)bt * p.n + i] = make_float2(invK * an.x, invK * an.y);
-            continue;
-        }
         for (int tr = 0; tr < p.T; ++tr) {
             float ay = 0.f, ax = 0.f;
             for (int cy = y0; cy <= y1; ++cy) {
@@ -893,10 +799,11 @@ __device__ __forceinline__ void bwd_window_fast(const KnnParams &p, const float2
 //     one compare, one select and two FMAs (0/1 weight: fma(1, a, b) == a + b);
 //   * the membership test is `d <= K-th distance` unless a staged query has a point EXCLUDED at exactly its K-th
 //     distance (tie resolved by index; the forward flags such queries in bit 30 of the K-th index): those
-//     workgroups, and windows wider than KNN_BW_WMAX, take the exact (distance, index) loop of bwd_window.
+//     workgroups, and windows wider than KNN_BW_WMAX, take the exact (distance, index) loop written out in the kernel.
 // grid: 1-D, XCD-contiguous, 256 threads, dynamic LDS (RWmax^2 float4 + KNN_BW_WMAX of slack [+ float2 per cell])
 // ------------------------------------------------------------------------------------------
 #define KNN_BW_WMAX 16
+#define KNN_RQ_MAX 9   // largest staged halo (cells); tiles whose reach needs more read the global arrays (7 -> 9: the 1 % of such tiles at C3 took 47 us each against 12, and were the whole duration of a B = 1 launch)
 // Workgroups per CU the register budget is set for (7 -> 72 VGPRs, 8 -> 64).  Round 2 needed all eight (the kernel waited for its
 // LDS conflicts); without them, and with the reach phase gone, seven workgroups that spill 12 instead of 48 bytes per lane are
 // faster: 118 -> 114 us at C3.  With the flow_to_next gradient (C4: a larger register set of its own) eight remain better: 57.3
@@ -1098,7 +1005,7 @@ __global__ __launch_bounds__(256, NEXT ? KNN_BW_OCC_NEXT : (IWD ? KNN_BW_OCC_IWD
                     dk = dkv[k]; ik = ikv[k]; g = gv[k];
                     const float wn = wnv[k];
                     if (has_next) { gn = gnv[k]; if (gnext_scale != nullptr) gn = make_float2(gn.x * gns, gn.y * gns); }
-                    if (ik & KNN_FAR_FLAG) dk = -1.f;        // served by the fallback kernel: k_knn_bwd_far adds its gradient
+                    if (ik & KNN_FAR_FLAG) dk = -1.f;        // a far query, served by the tail launch: k_knn_bwd_far adds its gradient
                     else tie |= ik & KNN_TIE_FLAG;
                     // 'iwd': the query's normaliser goes into its staged gradient (a cell that is no member of anything holds 0: its
                     // weight is 0, and 0 x a non-finite quotient would not be)
@@ -1234,8 +1141,8 @@ __global__ __launch_bounds__(256, NEXT ? KNN_BW_OCC_NEXT : (IWD ? KNN_BW_OCC_IWD
 
 // ------------------------------------------------------------------------------------------
 // backward of the FAR queries (no square of up to KNN_RCAP cells around them holds K points: queries inside a band the flow
-// field emptied, whose K neighbours lie in a thin segment of a disc tens of pixels away; served by k_knn_tail or
-// the fallback kernel).  Counting them in the tile maxima would make every point of the tiles around such a band search a
+// field emptied, whose K neighbours lie in a thin segment of a disc tens of pixels away; served by a far item or a fallback
+// workgroup of k_knn_tail).  Counting them in the tile maxima would make every point of the tiles around such a band search a
 // window of hundreds of query cells for the few dozen of them that hold it; k_knn_bwd_tile therefore leaves them out, and
 // here the search runs the other way round, as in the forward: the tile's bucketed points and cell offsets are staged in LDS,
 // one thread per far query of the (sample, bin) walks the cell rows of the tile that its disc (centre, K-th distance) touches,
@@ -1461,29 +1368,16 @@ __global__ __launch_bounds__(256) void k_knn_bwd_far(const KnnParams p, const kn
     }
 }
 
-// backward, step 2: one thread per (sample, trajectory point): combine the per-bin partials.
+// backward, step 2 of the general gather (num_tref > 1; num_tref == 1: k_knn_bwd_combine_bins / _direct below): one
+// thread per (sample, trajectory point) combines the per-bin partials that k_knn_bwd_points wrote.
 //   d traj(t_ref)[tr] = sum_t g[t][tr];   d traj(t_mid)[t] = -sum_tr g[t][tr] - a[t] + a[t-1]
 __global__ __launch_bounds__(256) void k_knn_bwd_combine(const KnnParams p, const float2 *__restrict__ tmp_g,
-                                                         const float2 *__restrict__ tmp_a,   // nullptr: no flow_to_next term
+                                                         const float2 *__restrict__ tmp_a,   // (zeros without the flow_to_next term)
                                                          float *__restrict__ gtraj) {
     const size_t gi = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (gi >= (size_t)p.B * p.n) return;
     const int b = (int)(gi / p.n), i = (int)(gi - (size_t)b * p.n);
     float2 *g2 = reinterpret_cast<float2 *>(gtraj) + (size_t)b * (p.T + p.nb) * p.n;
-    if (p.T == 1) {                               // one pass over the partials
-        float sy = 0.f, sx = 0.f;
-        float2 carry = make_float2(0.f, 0.f);
-#pragma unroll 5
-        for (int t = 0; t < p.nb; ++t) {
-            const float2 g = tmp_g[(size_t)(b * p.nb + t) * p.n + i];
-            const float2 a = tmp_a ? tmp_a[(size_t)(b * p.nb + t) * p.n + i] : make_float2(0.f, 0.f);
-            sy += g.x; sx += g.y;
-            g2[(size_t)(1 + t) * p.n + i] = make_float2(-g.x + carry.x - a.x, -g.y + carry.y - a.y);
-            carry = a;
-        }
-        g2[i] = make_float2(sy, sx);
-        return;
-    }
     for (int tr = 0; tr < p.T; ++tr) {
         float sy = 0.f, sx = 0.f;
         for (int t = 0; t < p.nb; ++t) {
@@ -1575,7 +1469,7 @@ int mpc_knn_r_init(const mpc_shape *s) {
 int mpc_knn_margin(const mpc_shape *) { return KNN_MARGIN; }
 int mpc_knn_tiles(const mpc_shape *s) { return knn_tiles_x(s->wq, KNN_MARGIN) * knn_tiles_y(s->hq, KNN_MARGIN); }
 
-// true where the forward is the strip kernel + fallback (num_tref == 1: the shipped configurations)
+// true where the forward is the strip search, k_knn_strip + k_knn_tail (num_tref == 1: the shipped configurations)
 static bool knn_fwd_is_strip(const mpc_shape *s, const int32_t *idx_out) {
     return idx_out == nullptr && mpc_knn_strip_usable(s, mpc_knn_r_init(s));
 }
@@ -1583,7 +1477,7 @@ static bool knn_fwd_is_strip(const mpc_shape *s, const int32_t *idx_out) {
 static bool knn_bwd_is_tile(const mpc_shape *s) {
     return s->B > 0 && s->T == 1;          // (round 6: 'iwd' too -- the gather weights a member by its distance)
 }
-// the fallback kernel lists the queries it served for k_knn_bwd_far (and keeps them out of the tile maxima)
+// the tail launch lists the far queries it served for k_knn_bwd_far (and keeps them out of the tile maxima)
 bool mpc_knn_uses_far_list(const mpc_shape *s) { return knn_bwd_is_tile(s) && knn_fwd_is_strip(s, nullptr); }
 
 // The counting sort of the points of a (sample, bin): S workgroups per (sample, bin) with the counters in LDS -- as many as
@@ -1660,7 +1554,7 @@ int mpc_knn_lut_fwd_ex(const mpc_shape *s, const float *traj, float *flow_lut, f
     const int zero_words = (zero_event_counters && L.strip_rows > 0) ? L.nfb + 2 * L.nbb + 8 : 0;
     EvCountArgs evc = (zero_words > 0) ? mpc_event_count_args(s, events, ws) : EvCountArgs{};
     const bool strip = knn_fwd_is_strip(s, idx_out);
-    // (the fallback kernel's first B workgroups finish the count; the count rides in workgroups of the strip kernel)
+    // (the first B fallback workgroups of the tail launch finish the count; the count rides in workgroups of the main launch)
     if (s->B > 256 || !strip || !mpc_knn_strip_counts_events(s, &evc)) evc = EvCountArgs{};
     static mpc_device_once attr_once;   // raising the dynamic-LDS cap: idempotent, once per device
     if (attr_once.need()) {
@@ -1696,7 +1590,7 @@ int mpc_knn_lut_fwd_ex(const mpc_shape *s, const float *traj, float *flow_lut, f
     }
     MPC_CHECK_LAUNCH();
     const int r_init = mpc_knn_r_init(s);
-    // fast path (num_tref == 1, the shipped configurations): strip kernel + fallback (knn_strip.hip)
+    // fast path (num_tref == 1, the shipped configurations): main and tail launch of the strip search (knn_strip.hip)
     if (strip) {
         if (sat_launch) {
             const int scol = knn_sat_cols(p.hb);
@@ -1807,15 +1701,9 @@ int mpc_knn_lut_bwd_ex(const mpc_shape *s, const float *traj, const float *grad_
     float *reach = (float *)((char *)ws + L.off_knn_reach);
     static mpc_device_once attr_once;   // raising the dynamic-LDS cap: idempotent, once per device
     if (attr_once.need()) {
-        if ((rc = set_max_lds((const void *)k_knn_bwd_points<16>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<false, false, false>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<false, true, false>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<true, false, false>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<true, true, false>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<false, false, true>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<false, true, true>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<true, false, true>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bwd_tile<true, true, true>, __func__))) return rc;
+#define KB_SET_LDS(L1_, NEXT_, IWD_) if ((rc = set_max_lds((const void *)k_knn_bwd_tile<L1_, NEXT_, IWD_>, __func__))) return rc
+        KNN_VARIANT_EACH(KB_SET_LDS);
+#undef KB_SET_LDS
         attr_once.mark();
     }
     const int gxb = knn_tiles_x(s->wq, p.m), gyb = knn_tiles_y(s->hq, p.m), ntiles = gxb * gyb;
@@ -1840,32 +1728,18 @@ int mpc_knn_lut_bwd_ex(const mpc_shape *s, const float *traj, const float *grad_
             else MPC_LAUNCH(k_knn_reach_tiles<false>, dim3(s->B * s->nb), dim3(256), rl, st, p, tile_dkmax, reach, gxb, gyb, knn_band_depth(mpc_knn_r_init(s)));
             reach_pre = reach;
         }
-#define KB_LAUNCH(L1_, NEXT_)                                                                                            \
-        do { if (p.iwd) KB_LAUNCH3(L1_, NEXT_, true); else KB_LAUNCH3(L1_, NEXT_, false); } while (0)
-#define KB_LAUNCH3(L1_, NEXT_, IWD_)                                                                                     \
-        MPC_LAUNCH((k_knn_bwd_tile<L1_, NEXT_, IWD_>), gridb, dim3(256), ldsb, st, p, cell_start, spos, sidx, grad_flow_lut, \
-                           grad_flow_next, knn_state, tile_dkmax, tmp_g, tmp_a, direct, reach_pre, gxb, gyb, knn_band_depth(mpc_knn_r_init(s)), far_next, gnext_scale KB_STAMP_ARG(ws, L))
-        if (p.l1) { if (grad_flow_next) KB_LAUNCH(true, true); else KB_LAUNCH(true, false); }
-        else { if (grad_flow_next) KB_LAUNCH(false, true); else KB_LAUNCH(false, false); }
-#undef KB_LAUNCH
-#undef KB_LAUNCH3
+        KNN_VARIANT_LAUNCH(k_knn_bwd_tile, p.l1, grad_flow_next, p.iwd, gridb, dim3(256), ldsb, st, p, cell_start, spos, sidx, grad_flow_lut,
+                           grad_flow_next, knn_state, tile_dkmax, tmp_g, tmp_a, direct, reach_pre, gxb, gyb, knn_band_depth(mpc_knn_r_init(s)), far_next, gnext_scale KB_STAMP_ARG(ws, L));
         MPC_CHECK_LAUNCH();
         if (mpc_knn_uses_far_list(s)) {
-            // the queries the forward's fallback kernel served (left out of the gather above)
+            // the far queries the forward's tail launch served (left out of the gather above)
             const KnnLists ls = knn_lists(s, L, ws);
             // (no more workgroups than the list can hold items: at B = 1 a quarter of KNN_FAR_BLOCKS, and the launch usually finds
             // a few items or none)
             const long long far_items_max = (long long)s->B * s->nb * knn_tiles_x(p.wq, p.m) * knn_tiles_y(p.hq, p.m);
             const unsigned far_blocks = (unsigned)(far_items_max < KNN_FAR_BLOCKS ? (far_items_max < 1 ? 1 : far_items_max) : KNN_FAR_BLOCKS);
-#define KF_LAUNCH(L1_, NEXT_)                                                                                            \
-            do { if (p.iwd) KF_LAUNCH3(L1_, NEXT_, true); else KF_LAUNCH3(L1_, NEXT_, false); } while (0)
-#define KF_LAUNCH3(L1_, NEXT_, IWD_)                                                                                     \
-            MPC_LAUNCH((k_knn_bwd_far<L1_, NEXT_, IWD_>), dim3(far_blocks), dim3(256), 0, st, p, cell_start, spos, sidx, grad_flow_lut, grad_flow_next, \
-                               knn_state, ls, tmp_g, tmp_a, direct, gnext_scale)
-            if (p.l1) { if (grad_flow_next) KF_LAUNCH(true, true); else KF_LAUNCH(true, false); }
-            else { if (grad_flow_next) KF_LAUNCH(false, true); else KF_LAUNCH(false, false); }
-#undef KF_LAUNCH
-#undef KF_LAUNCH3
+            KNN_VARIANT_LAUNCH(k_knn_bwd_far, p.l1, grad_flow_next, p.iwd, dim3(far_blocks), dim3(256), 0, st, p, cell_start, spos, sidx, grad_flow_lut, grad_flow_next,
+                               knn_state, ls, tmp_g, tmp_a, direct, gnext_scale);
             MPC_CHECK_LAUNCH();
         }
         const int64_t totalb = (int64_t)s->B * s->n;
@@ -1874,18 +1748,16 @@ int mpc_knn_lut_bwd_ex(const mpc_shape *s, const float *traj, const float *grad_
         MPC_CHECK_LAUNCH();
         return 0;
     }
-    // num_tref > 1 or 'iwd': the general gather, one thread per bucketed point and tile (k_knn_bwd_points)
+    // num_tref > 1 ('mean' and 'iwd'): the general gather, one thread per bucketed point and tile (k_knn_bwd_points), which reads the
+    // query cells from global memory.  Both kernels rely on T > 1 here: B > 0 (above), and T == 1 took the branch above (knn_bwd_is_tile).
     MPC_LAUNCH(k_knn_reach, dim3(s->B * s->nb), dim3(256), (size_t)ntiles * sizeof(float), st, p, tile_dkmax, reach);
     MPC_CHECK_LAUNCH();
-    const int RWmax = 16 + 2 * KNN_RQ_MAX;
-    const size_t lds = (s->T == 1 && !p.iwd) ? (size_t)RWmax * RWmax * (16 + (grad_flow_next ? 8 : 0)) : 0;
     const dim3 grid(((int64_t)gxb * gyb * s->B * s->nb + 7) / 8 * 8);
-    MPC_LAUNCH(k_knn_bwd_points<16>, grid, dim3(256), lds, st, p, cell_start, spos, sidx, grad_flow_lut,
+    MPC_LAUNCH(k_knn_bwd_points, grid, dim3(256), 0, st, p, cell_start, spos, sidx, grad_flow_lut,
                        grad_flow_next, knn_state, reach, tmp_g, tmp_a, gxb, gyb);
     MPC_CHECK_LAUNCH();
     const int64_t total = (int64_t)s->B * s->n;
-    MPC_LAUNCH(k_knn_bwd_combine, dim3(mpc_cdiv(total, 256)), dim3(256), 0, st, p, tmp_g,
-                       (grad_flow_next || s->T != 1 || p.iwd) ? tmp_a : nullptr, grad_traj);
+    MPC_LAUNCH(k_knn_bwd_combine, dim3(mpc_cdiv(total, 256)), dim3(256), 0, st, p, tmp_g, tmp_a, grad_traj);
     MPC_CHECK_LAUNCH();
     return 0;
 }

@@ -9,7 +9,7 @@
 // bit 30 of the saved K-th index: some point lies at exactly the K-th distance but was excluded (tie resolved by
 // index); without it the backward's membership test is simply `d <= K-th distance`
 #define KNN_TIE_FLAG 0x40000000
-// bit 29: the query was served by the fallback kernel and is on the far list of its (sample, bin): the backward's gather
+// bit 29: the query was served by the tail launch with a far K-th distance (knn_is_far_dk) and is on the far list of its (sample, bin): the backward's gather
 // skips it (its K-th distance is not in the tile maxima either) and k_knn_bwd_far adds its gradient
 #define KNN_FAR_FLAG 0x20000000
 #define KNN_IDX_MASK 0x1fffffff
@@ -39,8 +39,8 @@ struct KnnParams {
     int l1, iwd, want_next;
     float off;   // sp/2 - 0.5 : centre of cell 0 (focus.py:117)
 };
-#define KNN_RFAR 20                // ... of its launch for the FAR queries (no square up to KNN_RCAP cells holds enough points: the
-                                   // inside of a band the flow field emptied); beyond it a query goes to the fallback kernel
+#define KNN_RFAR 20                // ... of the far items of the tail launch (FAR queries: no square up to KNN_RCAP cells holds enough points,
+                                   // the inside of a band the flow field emptied); beyond it a query goes to the fallback workgroups
 #define KNN_MARGIN (KNN_RCAP + 1)
 // smallest count of points in the (2r + 1)^2 cell square of a query for which radius r is tried (K / (pi / 4) at K = 32: the
 // disc of the ring bound holds K points if they are spread evenly over the square; calibrated on smooth flow fields)
@@ -55,30 +55,30 @@ int mpc_knn_margin(const mpc_shape *s);
 
 // Work lists of the KNN forward, all in the workspace, counters zeroed by the bucket kernels:
 //   fail     int [1 + B*nb*G]      queries for the fallback workgroups of k_knn_tail (bits 0..29 the query, bits 30..31 why)
-//   retry    int [1 + strips]      strips whose points overflowed the staging area: k_knn_strip_retry searches them in quarters
-//   farstrip int [1 + strips]      strips that hold far queries: k_knn_strip_far
+//   retry    int [1 + strips]      strips whose points overflowed the staging area: the retry quarters of k_knn_tail's strip workgroups
+//   farstrip int [1 + strips]      strips that hold marked queries (far or unfinished): the far items of k_knn_tail's strip workgroups
 //   far      int [B*nb][1 + G]     per (sample, bin): the cells (cy * wq + cx) of the far queries that were served (K-th key
 //                                  saved, flagged KNN_FAR_FLAG), for k_knn_bwd_far; null where the backward is not the tile gather
 //   ftbits   u32 [B*nb][ftwords]   tiles whose points a far query's disc can touch; ftlist int [1 + B*nb*tiles]: the same as a
 //                                  list of (sample, bin) * tiles + tile: the work items of k_knn_bwd_far
 //   again    u32 [B*nb][hq][ceil(wq/32)]  queries the main launch of the strip kernel could not finish (fewer than K candidates
-//                                  below the ring bound after all, more slots than its registers hold): k_knn_tail
-//                                  searches them with one more ring, 128 slots and chord-shaped rows
+//                                  below the ring bound after all, more slots than its registers hold): a far item of k_knn_tail
+//                                  searches them with more rings, 192 slots and chord-shaped rows
 //   grow     u32, same shape: of those, the ones that need more RINGS (too few candidates below the bound; far queries)
-//   chord    u8 [KNN_RFAR + 1][KNN_RFAR + 1]  chord[r][j] = knn_chord_cells(r, j): written by the bucket kernels, read by the strip kernels
+//   chord    u8 [KNN_RFAR + 1][KNN_RFAR + 1]  chord[r][j] = knn_chord_cells(r, j): written by the bucket kernels, read by the far items of k_knn_tail
 struct KnnLists {
     int *fail, *retry, *farstrip, *far, *ftlist;
     unsigned *ftbits, *again, *grow;
     unsigned char *chord;
     int ftwords, again_words;       // words per (sample, bin)
 };
-// number of queries the main launch marked for the second one (behind the chord table, in the same 1 KB of the workspace); next to it
+// number of queries the main launch marked for the far items of the tail launch (behind the chord table, in the same 1 KB of the workspace); next to it
 // the counters of the tail kernel (k_knn_tail): queries its strip workgroups handed to its fallback workgroups -- the LATE list,
 // which grows downwards from the end of the `fail` array (main list and late list together never exceed the number of queries) --
 // and the strip workgroups that have finished.  All zeroed by the bucket kernels.
 #ifdef __HIPCC__
 // (one 128-byte line each: knn_late_count and knn_tail_done take device-scope atomics from every XCD all through the tail launch, and a
-// plain load of knn_marked_count in the same line waited behind them -- the far pass of a UNet-like field 187 us instead of 146)
+// plain load of knn_marked_count in the same line waited behind them -- the far items of a UNet-like field 187 us instead of 146)
 __device__ __forceinline__ int *knn_marked_count(const KnnLists &ls) { return reinterpret_cast<int *>(ls.chord + 512); }
 __device__ __forceinline__ int *knn_late_count(const KnnLists &ls) { return reinterpret_cast<int *>(ls.chord + 640); }
 __device__ __forceinline__ int *knn_tail_done(const KnnLists &ls) { return reinterpret_cast<int *>(ls.chord + 768); }
@@ -86,18 +86,41 @@ __device__ __forceinline__ int *knn_bwd_far_next(const KnnLists &ls) { return re
 // the MARKED list: every query the main launch marks for the tail's strip workgroups is also listed (same place as the late list, the
 // end of the `fail` array downwards; its length is knn_marked_count), with the radius its search would start from.  With few marked
 // queries in the whole launch (KS_FORWARD_MAX) the tail's fallback workgroups take the marked list straight away, the strip
-// workgroups skip their far pass and the late list (what the retry quarters cannot finish) starts behind the marked entries;
-// otherwise the far pass runs and the late list overwrites the (then dead) marked entries.
+// workgroups skip their far items and the late list (what the retry quarters cannot finish) starts behind the marked entries;
+// otherwise the far items run and the late list overwrites the (then dead) marked entries.
 #endif
-// Blocks of queries of the second launch of the strip kernel: the main launch's strips, 2 columns x 128 rows.  The far queries of
+// Blocks of queries of the far items (strip workgroups of the tail launch): the main launch's strips, 2 columns x 128 rows.  The far queries of
 // a band along the top or bottom border are a few rows of EVERY strip, so wider, shorter blocks were tried: 4 x 64 halves the
 // workgroups of such a band and 8 x 32 quarters them, but every region row is 2 / 6 cells wider and two / three times as many
-// queries need more than the 128 slots and end up in the fallback kernel (C3, 40 px translation: 1.08 ms with 2 x 128, 1.15 with
+// queries need more than the 128 slots and end up with the fallback workgroups (C3, 40 px translation: 1.08 ms with 2 x 128, 1.15 with
 // 4 x 64, 1.21 with 8 x 32).
 #define KNN_FAR_WS 2
 #define KNN_FAR_TH 128
 __host__ __device__ static inline int knn_far_items_x(int wq) { return (wq + KNN_FAR_WS - 1) / KNN_FAR_WS; }
 __host__ __device__ static inline int knn_far_items_y(int hq) { return (hq + KNN_FAR_TH - 1) / KNN_FAR_TH; }
+
+// The (L1, NEXT, IWD) variants of a kernel template <bool L1, bool NEXT, bool IWD>: number of a variant, a statement for all eight
+// (STMT: a function-like macro of the three literals), and the launch of the one that three runtime values pick.  Macros, not a
+// generic lambda: MPC_LAUNCH records the kernel as it is spelled, with its literal template arguments, for the stage profiler.
+#define KNN_VARIANT_INDEX(l1, next, iwd) (((l1) ? 4 : 0) | ((next) ? 2 : 0) | ((iwd) ? 1 : 0))
+#define KNN_VARIANT_EACH(STMT)                                                                    \
+    do {                                                                                         \
+        STMT(false, false, false); STMT(false, false, true); STMT(false, true, false); STMT(false, true, true); \
+        STMT(true, false, false); STMT(true, false, true); STMT(true, true, false); STMT(true, true, true);     \
+    } while (0)
+#define KNN_VARIANT_LAUNCH(kern, l1, next, iwd, grid, block, lds, st, ...)                        \
+    do {                                                                                         \
+        switch (KNN_VARIANT_INDEX(l1, next, iwd)) {                                              \
+        case 0: MPC_LAUNCH((kern<false, false, false>), grid, block, lds, st, __VA_ARGS__); break; \
+        case 1: MPC_LAUNCH((kern<false, false, true>), grid, block, lds, st, __VA_ARGS__); break;  \
+        case 2: MPC_LAUNCH((kern<false, true, false>), grid, block, lds, st, __VA_ARGS__); break;  \
+        case 3: MPC_LAUNCH((kern<false, true, true>), grid, block, lds, st, __VA_ARGS__); break;   \
+        case 4: MPC_LAUNCH((kern<true, false, false>), grid, block, lds, st, __VA_ARGS__); break;  \
+        case 5: MPC_LAUNCH((kern<true, false, true>), grid, block, lds, st, __VA_ARGS__); break;   \
+        case 6: MPC_LAUNCH((kern<true, true, false>), grid, block, lds, st, __VA_ARGS__); break;   \
+        default: MPC_LAUNCH((kern<true, true, true>), grid, block, lds, st, __VA_ARGS__); break;   \
+        }                                                                                        \
+    } while (0)
 
 static KnnParams knn_params(const mpc_shape *s) {
     KnnParams p;
@@ -637,7 +660,7 @@ __device__ __forceinline__ void knn_far_mark_tiles(const KnnParams &p, const Knn
         }
 }
 // Is a query's K-th distance beyond what the backward's gather should carry in its tile maxima?  One ring more than the radius
-// of the mean density: the odd query the fallback kernel finishes with a slightly larger square stays in the gather (its
+// of the mean density: the odd query the fallback workgroups finish with a slightly larger square stays in the gather (its
 // tile searches a window two cells wider), a query of an emptied band goes on the far list (k_knn_bwd_far).
 __device__ __forceinline__ bool knn_is_far_dk(const KnnParams &p, float dK, int r_init) {
     const float lim = ((float)(r_init + KNN_FAR_RINGS) + 0.5f) * (float)p.sp;

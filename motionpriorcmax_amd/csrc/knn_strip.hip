@@ -3,7 +3,7 @@
 //
 // Same search as the tile kernel of knn.hip (square of cells around the query, ring bound, exact (distance, index)
 // order), restated so that the per-candidate work is a handful of vector instructions with no divergence:
-//   * a workgroup owns a vertical STRIP of WS query columns x TH query rows; the bucketed points of the strip's cell
+//   * a workgroup owns a vertical STRIP of KS_WS query columns x TH query rows; the bucketed points of the strip's cell
 //     columns +- r are staged row by row, so the candidates of a query -- the rows [cy - r, cy + r] of the strip --
 //     are ONE contiguous slot range (points outside the query's square are farther than the ring bound and drop out
 //     by the same `d < upper` test that makes the search exact);
@@ -28,8 +28,24 @@
 // the staging area even in quarters) is marked for the strip workgroups of the tail launch (k_knn_tail: radii up to KNN_RFAR, chord-shaped
 // regions, 192 slots) or appended to a list and searched by its fallback workgroups, one wavefront per query: the result is the exact
 // K-nearest set for any input, ties to the lowest index.
-// (Names in the comments below, from the rounds in which these were launches of their own: "second launch" / "far pass" = the strip
-// workgroups of k_knn_tail, strip_more_body; "fallback kernel" = its one-wavefront-per-query workgroups, fallback_one_query.)
+//
+// Names used in this file, knn_device.h, knn.hip, common.h, tuning.h and diag/stamps.h:
+//   main launch          k_knn_strip: one workgroup per strip, strip_body<MODE 0>.
+//   tail launch          k_knn_tail, behind it on the stream: everything the main launch left over, by two kinds of workgroup --
+//   strip workgroups     the first KS_RETRY_BLOCKS of the tail launch, strip_more_body.  Their work items are RETRY QUARTERS (a quarter
+//                        of the query rows of a strip whose points overflowed the staging area, strip_body<MODE 1>) and FAR ITEMS (the
+//                        marked queries of a block of KNN_FAR_WS x KNN_FAR_TH queries, strip_body<MODE 2>: far queries -- no square
+//                        up to KNN_RCAP cells holds enough points -- and queries the main launch could not finish);
+//   fallback workgroups  the rest of the tail launch, fallback_entry / fallback_one_query: one wavefront per listed query.
+// The lists that connect them (KnnLists, knn_device.h):
+//   retry, farstrip      main launch -> strip workgroups: the overflowed strips; the blocks that hold marked queries;
+//   again, grow          main launch -> far items: a bit per query, which queries of a block are marked and why;
+//   fail                 main launch -> fallback workgroups: single queries, upwards from the front of the array;
+//   marked               main launch -> every marked query again, downwards from the end of the same array: with at most
+//                        KS_FORWARD_MAX of them the fallback workgroups serve these and no far item runs;
+//   late                 strip workgroups -> fallback workgroups: what a retry quarter or a far item could not finish; read once every
+//                        strip workgroup has counted itself done (knn_tail_done);
+//   far, ftlist, ftbits  forward -> k_knn_bwd_far (knn.hip): the served queries whose K-th distance the gather should not carry.
 #include "knn_device.h"
 #include "ev_count_device.h"
 #include "bounds.h"
@@ -37,6 +53,7 @@
 #include <stdlib.h>
 
 #define KS_NT 256
+#define KS_WS 2                     // query columns of a strip (TH = KS_NT / KS_WS query rows); the far items' blocks are the same: KNN_FAR_WS
 #define KS_MAXCH 24                 // words of 4 slots per query on the fast path (96 slots)
 #ifndef KS_OCC_WIDE
 #define KS_OCC_WIDE 5               // workgroups per CU of the variants with the wider register set (flow_to_next, L1): 96 VGPRs
@@ -59,7 +76,7 @@
 // (256 = the CUs of an MI355X.  The figure only says among how many workgroups the strip work is dealt out: forward progress rests on
 // tail_fallback_blocks, which asks the device.  As a launch argument worked out from the queried CU count it cost k_knn_tail<2, true,
 // false, false> two more spilled registers, 16 -> 18 -- the kernel has no scalar register to spare: it stays a constant.)
-static_assert(KNN_FAR_WS * KNN_FAR_TH == KS_NT, "a block of queries of the second launch = one workgroup");
+static_assert(KNN_FAR_WS == KS_WS && KNN_FAR_WS * KNN_FAR_TH == KS_NT, "a block of queries of a far item = one workgroup");
 static_assert(KNN_RCAP <= 6, "the packed chord widths of the main launch");
 static_assert(KNN_MARGIN > KNN_RCAP, "the strip kernel must not reach the outermost ring of the bucket grid");
 
@@ -81,37 +98,32 @@ __device__ __forceinline__ float lane_f(float v, int l) { return __int_as_float(
 
 // (8-byte LDS reads go through knn_lds_f2 -- knn_device.h: single ds_read_b64; the compiler's ds_read2_b64 pairs run at half
 // the LDS rate, and the LDS is busy for 62 % of this kernel's cycles: SQ_LDS_IDX_ACTIVE)
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
-// One strip (workgroup-wide): the query rows [pr0, pr1) of strip `lblk`.  SPLIT = false: the whole strip (pr0 = 0, pr1 = TH); a
-// strip whose points do not fit the staging area (a place where the flow field packs the points) goes on the retry list and
-// is searched again by k_knn_strip_retry in quarters (SPLIT = true); what does not fit a quarter goes to the fallback list.
-// MODE 0: the main launch -- the queries whose square of up to KNN_RCAP cells holds enough points; a strip that holds others (FAR
-// queries) is noted on the farstrip list.  MODE 1: k_knn_strip_retry (SPLIT).  MODE 2: k_knn_strip_far -- the far queries of the
-// strips on that list alone, with radii up to KNN_RFAR, the region rows staged as wide as the widest CHORD that uses them (the
-// disc of the ring bound, not the square: above and below a horizontal band front the squares are a hundred cells wide);
-// served far queries go on the far list of their (sample, bin) for k_knn_bwd_far and stay out of the tile maxima.
+// One strip (workgroup-wide): the query rows [pr0, pr1) of strip `lblk`.
+// MODE 0: the main launch -- the whole strip (pr0 = 0, pr1 = TH), the queries whose square of up to KNN_RCAP cells holds enough
+// points; a strip that holds others (FAR queries) or too many unfinished ones is noted on the farstrip list, and a strip whose
+// points do not fit the staging area (a place where the flow field packs the points) goes on the retry list.
+// MODE 1: a retry quarter of the tail launch -- a quarter of the query rows of a strip on the retry list; what does not fit a quarter
+// goes on the late list.
+// MODE 2: a far item of the tail launch -- the marked queries of a strip on the farstrip list alone, with radii up to KNN_RFAR, the
+// region rows staged as wide as the widest CHORD that uses them (the disc of the ring bound, not the square: above and below a
+// horizontal band front the squares are a hundred cells wide); served queries with a far K-th distance go on the far list of their
+// (sample, bin) for k_knn_bwd_far and stay out of the tile maxima.
 #define KS_NR_MAX (KS_NT / 2 + 2 * KNN_RFAR)
-template <int WS, bool L1, bool NEXT, bool IWD, int MODE>
+template <bool L1, bool NEXT, bool IWD, int MODE>
 __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__restrict__ traj,
                                            const knn_cs_t *__restrict__ cell_start, const knn_cs_t *__restrict__ sat,
                                            const float2 *__restrict__ spos, const knn_idx_t *__restrict__ sidx,
                                            float *__restrict__ flow_lut, float *__restrict__ flow_next,
                                            float *__restrict__ knn_state, float *__restrict__ tile_dkmax,
                                            const KnnLists &ls, int r_init, int cap, int gx, int gy,
-                                           int lblk, int pr0, int pr1, unsigned char *s_dyn, int *s_wsum, int *s_wmax, unsigned char *s_rq,
-                                           int unused_ = 0) {
-    // (Round 5 measured the far pass at WAVEFRONT level -- a wavefront per block of 2 x 24 queries with its own LDS slice, no
+                                           int lblk, int pr0, int pr1, unsigned char *s_dyn, int *s_wsum, int *s_wmax, unsigned char *s_rq) {
+    // (Round 5 measured the far items at WAVEFRONT level -- a wavefront per block of 2 x 24 queries with its own LDS slice, no
     // workgroup barrier, four independent searches per workgroup instead of one wavefront searching while three wait: slower,
     // UNet-like mixture 185 us against 160, 30 % contraction 725 against 492 -- six blocks per strip each stage their own +-20-row
     // halo with 64 lanes instead of 256, and most blocks of a listed strip hold no marked query.  profiles/HISTORY_r05.md)
-    constexpr bool SPLIT = MODE == 1, FARK = MODE == 2;
+    constexpr bool FARK = MODE == 2;
     constexpr int NT = KS_NT;
-#define KS_SYNC() __syncthreads()
     KS_STP_DECL
     KS_STP();
     // (KS_PRIO, tuning.h) main launch: the load phases -- radius from the table, row table, staging: few instructions, each at the head of
@@ -119,9 +131,8 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     // level (workgroup-uniform); the early return of an overflowed strip needs none: the priority dies with the wave.
     if (MODE == 0 && KS_PRIO) MPC_PRIO(KS_PRIO == 2 ? 2 : 1);
     constexpr int MAXCH = FARK ? KS_MAXCH_FAR : (L1 ? KS_MAXCH_L1 : KS_MAXCH);      // words of four slots per query
-    (void)SPLIT;
     constexpr int RC = FARK ? KNN_RFAR : KNN_RCAP;
-    constexpr int TH = KS_NT / WS;
+    constexpr int TH = KS_NT / KS_WS;
     constexpr int NR = TH + 2 * RC;                     // region rows: the strip's query rows and the largest radius above and below
     static_assert(NR <= NT && NR <= KS_NR_MAX, "one thread per region row");
     // queries for the one-wavefront-per-query search: the main launch appends to the `fail` list (counter fail[0], entries upwards from
@@ -130,7 +141,6 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     // strip workgroups are done.  (Everything about the lists is worked out where a push happens -- a rare path --, not kept live
     // across the search: the kernel has no scalar register to spare, and a spilled one costs a vector register.)
     int *const fail = ls.fail;
-    (void)unused_;
     // main launch: the queries a workgroup marks for the tail's strip workgroups also go on the MARKED list (knn_device.h) with the
     // radius that search would start from.  Workgroup-level: the ONE atomic with which the workgroup adds its marked queries to the
     // launch's count (it did that before) also reserves their places -- a list append per wavefront (a second global counter) cost
@@ -150,17 +160,17 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     };
     const int tid = threadIdx.x;
     if (MODE != 1) {
-        // (main and second launch) the width of every region row, collected below with LDS atomics: starts at 0.  The table lives where
+        // (main launch and far items) the width of every region row, collected below with LDS atomics: starts at 0.  The table lives where
         // the first bucketed slots of the rows go later (s_row); this early barrier costs nothing: every wavefront is here at once
         if (tid < NR) reinterpret_cast<int2 *>(s_dyn)[MPC_IDX(tid, NR)].x = 0;
         if (tid == 0) s_rq[0] = 0;                    // (main launch: "this strip holds far queries", set below; it has no other use for s_rq)
-        KS_SYNC();
+        __syncthreads();
     }
     const int bt = lblk / (gx * gy), bxy = lblk - bt * gx * gy;
     const int sy = bxy / gx, sx = bxy - sy * gx;
     const int b = bt / p.nb, t = bt - b * p.nb;
-    const int qx0 = sx * WS, qy0 = sy * TH;
-    const int qx1 = min(qx0 + WS, p.wq) - 1, qy1 = min(qy0 + TH, p.hq) - 1;
+    const int qx0 = sx * KS_WS, qy0 = sy * TH;
+    const int qx1 = min(qx0 + KS_WS, p.wq) - 1, qy1 = min(qy0 + TH, p.hq) - 1;
     const int ry_base = qy0 - RC;                // grid row of region row 0 (may lie outside the bucket grid: an empty row)
     // ---- LDS carve-up ----------------------------------------------------------------------------
     int2 *s_row = reinterpret_cast<int2 *>(s_dyn);             // [NR] {first bucketed slot, points (-1: no such row)}
@@ -182,18 +192,18 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     // border of the image are the expensive ones (half of their neighbourhood lies outside the image: larger squares, up to
     // 96 slots against 63) and a wavefront pays for its most expensive lane, so the group holding the bottom border trades
     // places with group 1: ONE wavefront of a full-height strip carries both borders, not two.
-    int grp = tid / (16 * WS);
+    int grp = tid / (16 * KS_WS);
     if (qy0 == 0 && p.hq <= TH) {
         const int gb = (p.hq - 1) >> 4;
         if (gb >= 2) grp = (grp == 1) ? gb : ((grp == gb) ? 1 : grp);
     }
-    int cy = qy0 + grp * 16 + (tid % (16 * WS)) / WS, cx = qx0 + tid % WS;
+    int cy = qy0 + grp * 16 + (tid % (16 * KS_WS)) / KS_WS, cx = qx0 + tid % KS_WS;
     const bool valid = cy <= qy1 && cx <= qx1;
     // Radius from the summed-area table (four loads per radius tried): the smallest r whose square holds `need` points.
     // Starts at the radius of the mean density; only a clearly denser place tries smaller ones.
     const int aw = (p.wq + 31) >> 5;
     const int aoff = bt * ls.again_words + min(cy, p.hq - 1) * aw + (min(cx, p.wq - 1) >> 5);      // this query's word of the `again` / `grow` maps
-    // (the second launch: only the queries the main launch marked look at the table at all -- `grow` alone: a far query, no
+    // (a far item: only the queries the main launch marked look at the table at all -- `grow` alone: a far query, no
     // square up to KNN_RCAP holds enough points; `again`: one it could not finish, with `grow` if for too few candidates)
     // (the radius hint of a marked query -- below -- is requested with the two words, for every query: one round trip, not two)
     int r_hint = 0;
@@ -204,7 +214,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     int r = 0, nr = 0;                                  // radius and the points in its square
     bool served = false;
     const int need_q = knn_square_need(p.K, p.l1);
-    // (second launch: the radius the main launch worked out for a far query / tried for one it could not finish, left in the
+    // (a far item: the radius the main launch worked out for a far query / tried for one it could not finish, left in the
     // query's K-th distance slot of knn_state -- whichever kernel serves the query overwrites it.  Reading the table again here
     // was a chain of four to five dependent round trips in front of everything else a work item does: 12 of its 29 us.)
     if (FARK && marked) r = r_hint;
@@ -225,7 +235,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
         }
         served = r <= KNN_RCAP;
     }
-    bool isfar = FARK ? farq : (valid && !served);      // no square up to KNN_RCAP holds enough points: the second launch's query
+    bool isfar = FARK ? farq : (valid && !served);      // no square up to KNN_RCAP holds enough points: a far item's query
     if (!FARK) {
         // The count says how many points the SQUARE holds; the disc of the ring bound holds pi / 4 of them, give or take the
         // scatter of the positions.  With fewer than need + need / 7 points in the square (47 for K = 32: the lattice has 49
@@ -238,16 +248,16 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
         const bool marginal = served && r < KNN_RCAP && nr < need + need / 7;
         const int nm = __popcll(__ballot(marginal)), nv = __popcll(__ballot(served));
         if (marginal && (4 * nm >= nv || nr < need + 2)) ++r;
-        // (for the launch that follows: `grow` without `again` = far; the strip goes onto its work list when this workgroup ends)
-        // (MODE 0 only: the quarters of an overflowed strip run beside the second launch's far pass -- which may have served the
+        // (for the tail launch: `grow` without `again` = far; the strip goes onto its work list when this workgroup ends)
+        // (MODE 0 only: the retry quarters of an overflowed strip run beside the far items -- which may have served the
         // query and written its K-th distance by now -- and the main launch marked the strip's far queries before it gave up)
         if (MODE == 0 && isfar) {
-            // smallest radius in (KNN_RCAP, KNN_RFAR] whose square holds the far queries' count, for the second launch: bisection
+            // smallest radius in (KNN_RCAP, KNN_RFAR] whose square holds the far queries' count, for the far item: bisection
             // (the count grows with the radius), four probes instead of up to fourteen -- here, where five other workgroups of
-            // the CU cover the round trips (KNN_RFAR + 1: nothing within KNN_RFAR, the fallback kernel)
+            // the CU cover the round trips (KNN_RFAR + 1: nothing within KNN_RFAR, the fallback workgroups)
             // (a LOWER BOUND of the candidates below the ring bound -- the points of the cells inside a cross of rectangles
             // inscribed in the disc, five rectangle counts -- instead of this estimate was measured: no fewer queries on the
-            // fallback list, larger radii, queries in dense places beyond the 256 slots: not kept)
+            // fail list, larger radii, queries in dense places beyond the 256 slots: not kept)
             const int need_far = knn_square_need_far(p.K, p.l1);
             int lo = KNN_RCAP, hi = KNN_RFAR + 1;       // (lo: too few; hi: enough)
             while (hi - lo > 1) {
@@ -256,30 +266,30 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             }
             reinterpret_cast<int *>(knn_state)[MPC_IDX((size_t)bt * p.G + (size_t)cy * p.wq + cx, (long long)p.B * p.nb * p.G)] = hi;
             atomicOr(ls.grow + MPC_IDX(aoff, (long long)p.B * p.nb * ls.again_words), 1u << (cx & 31)); s_rq[0] = 1;
-            r = hi;                                      // (the far pass starts there; so does the marked-list entry below)
+            r = hi;                                      // (the far item starts there; so does the marked-list entry below)
         }
 
     }
     if (FARK) {
         served = false;
-        if (isfar) served = r <= KNN_RFAR;              // (else: the fallback kernel)
+        if (isfar) served = r <= KNN_RFAR;              // (else: the fallback workgroups)
         else if (bit_again) {
             // the main launch could not finish it: too few candidates below the ring bound -- two more rings -- or more slots
-            // than its registers hold -- the same radius with this launch's 192 slots
+            // than its registers hold -- the same radius with a far item's 192 slots
             if (bit_grow) r = min(r + 2, KNN_RFAR);
             served = true;
         }
     }
     bool mine = FARK ? marked : (valid && !isfar);
-    {   // radius of the widest square of every query row (the WS lanes of a row are neighbours)
+    {   // radius of the widest square of every query row (the KS_WS lanes of a row are neighbours)
         int rr = (mine && served) ? r : 0;
 #pragma unroll
-        for (int o2 = 1; o2 < WS; o2 <<= 1) rr = max(rr, __shfl_xor(rr, o2, 64));
-        if (MODE == 1) { if ((tid % WS) == 0 && cy - qy0 < TH) s_rq[MPC_IDX(cy - qy0, KS_NT / WS)] = (unsigned char)rr; }
+        for (int o2 = 1; o2 < KS_WS; o2 <<= 1) rr = max(rr, __shfl_xor(rr, o2, 64));
+        if (MODE == 1) { if ((tid % KS_WS) == 0 && cy - qy0 < TH) s_rq[MPC_IDX(cy - qy0, KS_NT / KS_WS)] = (unsigned char)rr; }
         else if (MODE == 2) { }                          // (pushed per query after the compaction below)
-        else if ((tid % WS) == 0 && rr > 0) {
+        else if ((tid % KS_WS) == 0 && rr > 0) {
             // main launch: every query row pushes the width of its disc's chord onto the region rows it uses -- 2 r + 1 LDS
-            // atomics per row of queries instead of every region row looking at 13 query rows (the loop of the other launches)
+            // atomics per row of queries instead of every region row looking at 13 query rows (the loop of the retry quarters)
             int2 *s_w = reinterpret_cast<int2 *>(s_dyn);
             const int rc = cy - qy0 + RC;                   // region row of this query row
             for (int j = -rr; j <= rr; ++j) {
@@ -298,12 +308,12 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     }
     // chord of the disc of radius r at row offset j, for the row tables below (knn_device.h)
     __shared__ unsigned char s_chord[(RC + 1) * (RC + 1)];
-    __shared__ unsigned s_ft[FARK ? KNN_FT_LDS_WORDS : 1];          // far pass: tiles the served far queries' discs touch (knn_far_mark_tiles_lds)
+    __shared__ unsigned s_ft[FARK ? KNN_FT_LDS_WORDS : 1];          // far items: tiles the served far queries' discs touch (knn_far_mark_tiles_lds)
     if (FARK && tid < KNN_FT_LDS_WORDS) s_ft[tid] = 0u;
     if (FARK) for (int i = tid; i < (RC + 1) * (RC + 1); i += NT) s_chord[i] = ls.chord[(i / (RC + 1)) * (KNN_RFAR + 1) + i % (RC + 1)];
-    // (the barrier the row tables need anyway) MODE 0: any far query in this strip?  Then it goes on the list of
-    // k_knn_tail when this workgroup ends
-    KS_SYNC();
+    // (the barrier the row tables need anyway) MODE 0: any far query in this strip?  Then it goes on the farstrip
+    // list when this workgroup ends
+    __syncthreads();
     KS_STP();        // 1: marks read, radius from the table
     const bool anyfar = MODE == 0 && s_rq[0] != 0;
     if (FARK) {
@@ -336,7 +346,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             const int rc = cy - qy0 + RC;
             for (int j = -r; j <= r; ++j) atomicMax(&s_w[MPC_IDX(rc + j, NR)].x, (int)s_chord[MPC_IDX(r * (RC + 1) + abs(j), (RC + 1) * (RC + 1))]);
         }
-        KS_SYNC();                                               // (before the row tables are read and the staging area is written)
+        __syncthreads();                                               // (before the row tables are read and the staging area is written)
         KS_STP();    // 2: compaction, chords pushed
     }
     const size_t q = (size_t)bt * p.G + (size_t)cy * p.wq + cx;       // global query id
@@ -371,16 +381,16 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             }
         }
         const int incl = wave_scan_incl(padded);
-        const int wmx = wave_max_i(padded);
+        const int wmx = wave_max_int(padded);
         if ((tid & 63) == 63) { s_wsum[tid >> 6] = incl; s_wmax[tid >> 6] = wmx; }
-        KS_SYNC();
+        __syncthreads();
         int run = incl - padded;
         for (int w = 0; w < (tid >> 6); ++w) run += s_wsum[w];
         if (tid < NR) { s_rowstart[MPC_IDX(tid, NR + 1)] = run; s_row[MPC_IDX(tid, NR)] = make_int2(gs, len); }
         if (tid == NR - 1) s_rowstart[NR] = run + padded;
         // row pitch of the staging loop = the longest row of the region
         pitch = max(max(max(s_wmax[0], s_wmax[1]), max(s_wmax[2], s_wmax[3])), 1);
-        KS_SYNC();
+        __syncthreads();
         return s_rowstart[NR];
     };
     const bool inpass = mine && (cy - qy0) >= pr0 && (cy - qy0) < pr1;
@@ -388,7 +398,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
     KS_STP();        // 3: row table
     bool overflow = false;
     if (total > cap) {
-        if (MODE == 0) {              // (workgroup-uniform) again in quarters: k_knn_tail
+        if (MODE == 0) {              // (workgroup-uniform) again as retry quarters of the tail launch
             const int nfq = anyfar ? __syncthreads_count(isfar ? 1 : 0) : 0;
             if (tid == 0) {
                 ls.retry[MPC_IDX(1 + atomicAdd(&ls.retry[0], 1), 1 + (long long)gx * gy * p.B * p.nb)] = lblk;
@@ -397,7 +407,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             if (anyfar) mark_list(isfar, (size_t)bt * p.G + (size_t)cy * p.wq + cx, r, nfq);      // (workgroup-uniform)
             return;
         }
-        overflow = true;              // even a quarter of the strip (or the far queries' region) does not fit: to the fallback list
+        overflow = true;              // even a quarter of the strip (or the far item's region) does not fit: to the late list
     }
     {
         const bool act = inpass && served && !overflow;
@@ -409,7 +419,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             const bool has_next = NEXT && (t < p.nb - 1);
             // item -> (row, slot of the row) with a reciprocal multiply: (it + 0.5) / pitch is at least 0.5 / pitch away from
             // an integer, far more than the rounding of the product (it < 2^14)
-            // (second launch: item = staged slot, its row by a search over the first slots of the rows -- the rows of a far
+            // (far items: item = staged slot, its row by a search over the first slots of the rows -- the rows of a far
             // query's region are up to 42 cells wide and nearly all of them empty: on the (row, slot of the row) grid of the
             // main launch a workgroup walked 7 000 items for 300 points, nine rounds of dependent loads)
             const int items = FARK ? total : NR * pitch;
@@ -464,7 +474,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
                 if (NEXT) lnext[MPC_IDX(i, cap + KS_TAIL(MAXCH))] = make_float2(0.f, 0.f);
             }
         }
-        KS_SYNC();
+        __syncthreads();
         KS_STP();    // 4: staged
         if (MODE == 0 && KS_PRIO) MPC_PRIO(0);
 
@@ -494,7 +504,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
         const float lo_d = 0.4f * upper;
         // (hardware reciprocal, 1 ulp: any constant near this one gives a monotone map; the largest byte stays below 127.5)
         const float nscale = -(float)(KS_NLEV - 1) * __builtin_amdgcn_rcpf(upper - lo_d), loff = -upper * nscale;
-        const int nmax = __builtin_amdgcn_readfirstlane(wave_max_i(nsl));      // wave-uniform trip count (slots)
+        const int nmax = __builtin_amdgcn_readfirstlane(wave_max_int(nsl));      // wave-uniform trip count (slots)
         const float2 *pp = lpos + s;
         // (every lane reads its range rounded up to the wavefront's trip count: the dummy slots behind the staged ones are there for that)
         MPC_EXPECT(s + ((nmax + 7) & ~7) <= cap + KS_TAIL(MAXCH));
@@ -543,7 +553,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
                     constexpr int T2 = MAXCH < 32 ? MAXCH : 32;
 #pragma unroll
                     for (int c = KS_BASECH + 4; c < T2; ++c) acc += __popc((w[c] + C) & 0x80808080u);
-                    // (the second launch: up to 192 or 256 slots, in two more steps)
+                    // (far items: up to 192 or 256 slots, in two more steps)
                     if (MAXCH > 32 && nmax > 128) {
                         asm volatile("" ::: "memory");
                         constexpr int T3 = MAXCH < 48 ? MAXCH : 48;
@@ -644,11 +654,11 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
         {
             float dd[KS_LMAX]; int ii[KS_LMAX], jj[KS_LMAX], kraw[KS_LMAX];
             const bool light = live && !heavy;
-            const int mmax = __builtin_amdgcn_readfirstlane(wave_max_i(light ? inbin : 0));
+            const int mmax = __builtin_amdgcn_readfirstlane(wave_max_int(light ? inbin : 0));
             // the masks of the K-th level, 64 slots each (NM of them: two on the main launch)
             unsigned long long em = ((unsigned long long)E[1] << 32) | E[0];
             unsigned long long e2 = ((unsigned long long)(NE > 3 ? E[3] : 0u) << 32) | E[2];      // slots 64 ..
-            unsigned long long e3 = 0ull, e4 = 0ull;                                               // slots 128 .., 192 .. (second launch)
+            unsigned long long e3 = 0ull, e4 = 0ull;                                               // slots 128 .., 192 .. (far items)
             if (NE > 4) e3 = ((unsigned long long)(NE > 5 ? E[NE > 5 ? 5 : 0] : 0u) << 32) | E[NE > 4 ? 4 : 0];
             if (NE > 6) e4 = ((unsigned long long)(NE > 7 ? E[NE > 7 ? 7 : 0] : 0u) << 32) | E[NE > 6 ? 6 : 0];
 #pragma unroll
@@ -694,7 +704,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
                 const int h = __ffsll((long long)hm) - 1;
                 hm &= hm - 1ull;
                 const int hs = lane_i(s, h), hneed = lane_i(need, h);
-                constexpr int NM = (NE + 1) / 2;                  // chunks of 64 slots (two on the main launch, four on the second)
+                constexpr int NM = (NE + 1) / 2;                  // chunks of 64 slots (two on the main launch, four in a far item)
                 unsigned hw[2 * NM];
 #pragma unroll
                 for (int e = 0; e < 2 * NM; ++e) hw[e] = e < NE ? lane_u(E[e < NE ? e : 0], h) : 0u;
@@ -775,25 +785,25 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             reinterpret_cast<int *>(knn_state)[BQ + MPC_IDX(q, BQ)] = iK | (tie ? KNN_TIE_FLAG : 0) | ((FARK && ls.far != nullptr && knn_is_far_dk(p, dK, r_init)) ? KNN_FAR_FLAG : 0);
             KS_INBIN_STAT(knn_state, BQ, q, inbin, nsl, IWD, norm);         // (the 'mean' backward never reads the normaliser)
         }
-        {   // queries for the fallback kernel: one atomic per wavefront reserves their places in the list
+        {   // queries for the fallback workgroups: one atomic per wavefront reserves their places in the list
             // (main launch: a query with too few candidates below the ring bound or too many slots gets a second chance in
-            // k_knn_tail -- more rings, 128 slots, only such queries staged: its bit in the `again` map -- if the
-            // strip has more than KS_MORE_MIN of them or far queries; the odd one: the fallback list)
+            // a far item -- more rings, 192 slots, only such queries staged: its bit in the `again` map -- if the
+            // strip has more than KS_MORE_MIN of them or far queries; the odd one: the fail list)
             const bool late = MODE == 0 && inpass && !live && why < 2u;
             int nlate = 0;
             if (MODE == 0) nlate = __syncthreads_count(late ? 1 : 0);
             // ... or the strip goes there anyway for its far queries
             const bool to_more = MODE == 0 && (nlate > KS_MORE_MIN || anyfar);
             if (late && to_more) {
-                reinterpret_cast<int *>(knn_state)[MPC_IDX(q, (long long)p.B * p.nb * p.G)] = r;          // (the radius that was tried, for the second launch)
+                reinterpret_cast<int *>(knn_state)[MPC_IDX(q, (long long)p.B * p.nb * p.G)] = r;          // (the radius that was tried, for the far item)
                 atomicOr(ls.again + MPC_IDX(aoff, (long long)p.B * p.nb * ls.again_words), 1u << (cx & 31));
                 if (why == 0u) atomicOr(ls.grow + MPC_IDX(aoff, (long long)p.B * p.nb * ls.again_words), 1u << (cx & 31));
             }
 
-            // (and the number of queries marked for it: with only a handful in the whole launch it hands them on to the fallback kernel)
+            // (and the number of queries marked for it: with only a handful in the whole launch the fallback workgroups take them)
             const int nfq = (MODE == 0 && anyfar) ? __syncthreads_count(isfar ? 1 : 0) : 0;
             if (to_more && tid == 0) ls.farstrip[MPC_IDX(1 + atomicAdd(&ls.farstrip[0], 1), 1 + (long long)gx * gy * p.B * p.nb)] = lblk;
-            // (the far pass gives a query that held too few candidates two more rings, one with too many slots the same radius, a far
+            // (a far item gives a query that held too few candidates two more rings, one with too many slots the same radius, a far
             // query the radius the bisection above found)
             if (to_more) mark_list((late && to_more) || (MODE == 0 && isfar), q, isfar ? r : (why == 0u ? min(r + 2, KNN_RFAR) : r), nlate + nfq);      // (workgroup-uniform)
             const bool push = inpass && !live && !(late && to_more);
@@ -807,7 +817,7 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
                 if (lane == first) base = atomicAdd(MODE == 0 ? &fail[0] : knn_late_count(ls), __popcll(pm));
                 base = __shfl(base, first, 64);
                 // (entry: the query, why in bits 30..31 and -- where the query ids leave room: fewer than 2^24 queries -- the radius
-                // that was tried in bits 24..29, so that the fallback kernel need not read it off the summed-area table again)
+                // that was tried in bits 24..29, so that the fallback workgroup need not read it off the summed-area table again)
                 const unsigned hint = ((size_t)p.B * p.nb * p.G < (1u << 24) && served) ? (unsigned)min(r, 63) << 24 : 0u;
                 const int k = base + __popcll(pm & ((1ull << lane) - 1ull));
                 if (push) fail[MPC_IDX(MODE == 0 ? 1 + (long long)k : fcap - (long long)(late_base + k), 1 + fcap)] = (int)((unsigned)q | hint | (why << 30));
@@ -815,26 +825,26 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
             }
         }
         // largest K-th distance per 16x16 tile of the bucket grid and class of query (bounds the search windows of the gather
-        // backward): a wavefront covers 64 / WS consecutive rows of one tile column, i.e. 64 / (16 WS) tiles of 16 WS lanes each
+        // backward): a wavefront covers 64 / KS_WS consecutive rows of one tile column, i.e. 64 / (16 KS_WS) tiles of 16 KS_WS lanes each
         // (the tiles of the query grid).  Only wavefronts next to the image border hold anything but class 0 (knn_device.h).
         if (!FARK) {
-            static_assert(FARK || WS == 2, "32 lanes = one tile");
+            static_assert(KS_WS == 2, "32 lanes = one tile");
             const int bd = knn_band_depth(r_init);
             const unsigned cls = live ? knn_query_classes(p, cy, cx, bd) : 0u;
             const bool plain = __ballot(cls > 1u) == 0ull;
             const int gx16 = knn_tiles_x(p.wq, p.m), gy16 = knn_tiles_y(p.hq, p.m);
             int *dst = reinterpret_cast<int *>(tile_dkmax) + (((size_t)bt * gy16 + (min(cy, p.hq - 1) >> 4)) * gx16 + (qx0 >> 4)) * KNN_NCLS;
-            const bool writer = (tid & (16 * WS - 1)) == 0 && cy <= qy1;
+            const bool writer = (tid & (16 * KS_WS - 1)) == 0 && cy <= qy1;
 #pragma unroll
             for (int c = 0; c < KNN_NCLS; ++c) {
                 if (c > 0 && plain) break;
                 float m = ((cls >> c) & 1u) ? dK : 0.f;
 #pragma unroll
-                for (int o2 = 8 * WS; o2 > 0; o2 >>= 1) m = fmaxf(m, __shfl_xor(m, o2, 64));
+                for (int o2 = 8 * KS_WS; o2 > 0; o2 >>= 1) m = fmaxf(m, __shfl_xor(m, o2, 64));
                 if (writer && m > 0.f) atomicMax(dst + c, __float_as_int(m));
             }
         } else if (ls.far != nullptr) {
-            // a served query of the second launch with a K-th distance the gather should not carry: onto the far list of its
+            // a served query of a far item with a K-th distance the gather should not carry: onto the far list of its
             // (sample, bin) (one atomic per wavefront) and its tiles onto the work list of k_knn_bwd_far; the others into the
             // tile maxima like any query
             const bool isf = live && knn_is_far_dk(p, dK, r_init);
@@ -855,18 +865,17 @@ __device__ __forceinline__ void strip_body(const KnnParams &p, const float *__re
                 }
             }
             if (ls.ftwords <= KNN_FT_LDS_WORDS) {           // (workgroup-uniform)
-                KS_SYNC();
+                __syncthreads();
                 if (tid < ls.ftwords) { knn_far_flush_tiles(p, ls, bt, s_ft, tid); s_ft[tid] = 0u; }
             }
         } else if (live) knn_tile_max_add(tile_dkmax, p, bt, cy, cx, knn_band_depth(r_init), dK);      // (far query, general gather backward)
         KS_STP_WRITE(ls, tid, mine, total);      // 5: searched, lists written
     }
-#undef KS_SYNC
 }
 
 // 1-D grid of gx * gy * B * nb workgroups (gx strips, gy row blocks) in XCD-contiguous order, 256 threads,
 // dynamic LDS sized by the launcher
-template <int WS, bool L1, bool NEXT, bool IWD>
+template <bool L1, bool NEXT, bool IWD>
 __global__ __launch_bounds__(KS_NT, (NEXT || L1) ? KS_OCC_WIDE : 6) void k_knn_strip(const KnnParams p, const float *__restrict__ traj,
                                                      const knn_cs_t *__restrict__ cell_start, const knn_cs_t *__restrict__ sat,
                                                      const float2 *__restrict__ spos, const knn_idx_t *__restrict__ sidx,
@@ -876,7 +885,7 @@ __global__ __launch_bounds__(KS_NT, (NEXT || L1) ? KS_OCC_WIDE : 6) void k_knn_s
                                                      const EvCountArgs evc, int n_evc, int evc_stride) {
     extern __shared__ __align__(16) unsigned char s_dyn[];
     __shared__ int s_wsum[KS_NT / 64 + 1], s_wmax[KS_NT / 64];      // (s_wsum[KS_NT / 64]: "pushed onto the late list", tail kernel only)
-    __shared__ unsigned char s_rq[KS_NT / WS];          // radius of the widest square of every query row of the strip (0: none)
+    __shared__ unsigned char s_rq[KS_NT / KS_WS];          // radius of the widest square of every query row of the strip (0: none)
     // mpc_focus_fwd: some workgroups do not search -- they count the event rows per backward bucket for the event kernels
     // that follow (ev_count_device.h).  This kernel is bound by vector-instruction issue and leaves HBM idle, so the 67 MB of
     // C3's events are read beside it.  The counting workgroups come in groups of 8 (one per XCD: the search workgroups keep
@@ -895,13 +904,13 @@ __global__ __launch_bounds__(KS_NT, (NEXT || L1) ? KS_OCC_WIDE : 6) void k_knn_s
     const int nblk = gx * gy * p.B * p.nb;
     const int lblk = (pblk & 7) * ((nblk + 7) >> 3) + (pblk >> 3);
     if (lblk >= nblk) return;
-    strip_body<WS, L1, NEXT, IWD, 0>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls,
-                                     r_init, cap, gx, gy, lblk, 0, KS_NT / WS, s_dyn, s_wsum, s_wmax, s_rq);
+    strip_body<L1, NEXT, IWD, 0>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls,
+                                     r_init, cap, gx, gy, lblk, 0, KS_NT / KS_WS, s_dyn, s_wsum, s_wmax, s_rq);
 }
 
 // strip workgroups of the tail kernel that have anything to do (the others neither work nor count themselves done): workgroup wg
 // takes the retry items wg, wg + nwg, ... and the far items likewise
-// few marked queries in the whole launch: no far pass, the fallback workgroups take the marked list
+// few marked queries in the whole launch: no far items, the fallback workgroups take the marked list
 __device__ __forceinline__ bool strip_forward(const KnnLists &ls) { return *knn_marked_count(ls) <= KS_FORWARD_MAX; }
 __device__ __forceinline__ int strip_more_busy(const KnnParams &p, const KnnLists &ls, int gx, int gy, int nwg) {
     const int nstrips = gx * gy * p.B * p.nb;
@@ -914,7 +923,7 @@ __device__ __forceinline__ int strip_more_busy(const KnnParams &p, const KnnList
 // round), then the strips on the farstrip list (their far queries and the queries the main launch could not finish).  `nwg` of them,
 // this one is number `wg` (the list lengths are only known on the device; nothing to do for the lattice-like point sets of the
 // benchmark: both lists empty or nearly)
-template <int WS, bool L1, bool NEXT, bool IWD>
+template <bool L1, bool NEXT, bool IWD>
 __device__ __forceinline__ void strip_more_body(const KnnParams &p, const float *__restrict__ traj,
                                                 const knn_cs_t *__restrict__ cell_start, const knn_cs_t *__restrict__ sat,
                                                 const float2 *__restrict__ spos, const knn_idx_t *__restrict__ sidx,
@@ -922,37 +931,37 @@ __device__ __forceinline__ void strip_more_body(const KnnParams &p, const float 
                                                 float *__restrict__ knn_state, float *__restrict__ tile_dkmax,
                                                 const KnnLists &ls, int r_init, int cap, int gx, int gy, int wg, int nwg,
                                                 unsigned char *s_dyn, int *s_wsum, int *s_wmax, unsigned char *s_rq) {
-    constexpr int TH = KS_NT / WS;
+    constexpr int TH = KS_NT / KS_WS;
     const int nstrips = gx * gy * p.B * p.nb;
     const int gxf = knn_far_items_x(p.wq), gyf = knn_far_items_y(p.hq);
     // (only a few marked queries in the whole launch -- a B = 1 step with a dozen of them in three strips paid a full work item's
-    // 25 us for them: the fallback workgroups take them from the MARKED list beside what they have anyway, no far pass.  As a zero
-    // trip count read before both loops: an early return between the loops cost the far pass 25 % -- 14 spilled registers instead
+    // 25 us for them: the fallback workgroups take them from the MARKED list beside what they have anyway, no far items.  As a zero
+    // trip count read before both loops: an early return between the loops cost the far items 25 % -- 14 spilled registers instead
     // of 8, reloaded inside its search)
     const int nretry = 4 * min(ls.retry[0], nstrips), nfar = strip_forward(ls) ? 0 : min(ls.farstrip[0], gxf * gyf * p.B * p.nb);
     for (int w = wg; w < nretry; w += nwg) {
         const int quarter = w & 3;
-        strip_body<WS, L1, NEXT, IWD, 1>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls,
+        strip_body<L1, NEXT, IWD, 1>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls,
                                          r_init, cap, gx, gy, ls.retry[1 + (w >> 2)], quarter * (TH / 4), (quarter + 1) * (TH / 4), s_dyn, s_wsum, s_wmax, s_rq);
         __syncthreads();
     }
     for (int w = wg; w < nfar; w += nwg) {
-        strip_body<KNN_FAR_WS, L1, NEXT, IWD, 2>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls,
+        strip_body<L1, NEXT, IWD, 2>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls,
                                                  r_init, cap, gxf, gyf, ls.farstrip[1 + w], 0, KNN_FAR_TH, s_dyn, s_wsum, s_wmax, s_rq);
         __syncthreads();
     }
 }
 
 // ------------------------------------------------------------------------------------------
-// The queries the strip kernel could not serve: ONE WAVEFRONT per query -- a thread per query spends ~100 us in dependent global
+// The fallback workgroups of the tail launch -- the queries the strip search could not serve: ONE WAVEFRONT per query -- a thread per query spends ~100 us in dependent global
 // loads (measured in round 4: 5-7 ns per query against ~3.5).  The lanes take the rows of the query's search region, then its
 // candidates (up to 64 * KS_FB_SLOTS of them; more: rows and candidates in rounds of 64, those below the ring bound compacted in
 // LDS), and the K-th key is found by a bitwise search with ballots.  The search starts from the radius the strip kernel tried (hint in
 // the list entry) or from one read off the summed-area table, and looks only at the cells of each row that can hold a point below
 // the ring bound (a band query's neighbours lie in a thin segment of a large disc).
-// With `far` (the backward is the tile gather) every query served here goes on the far list of its (sample, bin), is flagged
-// KNN_FAR_FLAG and stays out of the tile maxima: k_knn_bwd_far computes its gradient (knn.hip).
-// grid: KS_FB_BLOCKS workgroups (the list length is only known on the device), 256 threads
+// With `far` (the backward is the tile gather) a query served here with a far K-th distance (knn_is_far_dk) goes on the far list of
+// its (sample, bin), is flagged KNN_FAR_FLAG and stays out of the tile maxima: k_knn_bwd_far computes its gradient (knn.hip).
+// Up to KS_FB_BLOCKS workgroups of k_knn_tail (the list lengths are only known on the device), four queries at a time each
 // ------------------------------------------------------------------------------------------
 // first radius of a fallback search from the summed-area table: up to KNN_RCAP the smallest square with 1.25 x the strip
 // kernel's count (which it has tried); beyond it the far queries' rule, found by doubling and bisection (a band 20 rings deep
@@ -1236,12 +1245,12 @@ __device__ __forceinline__ void fallback_entry(const KnnParams &p, const float *
 }
 
 // ------------------------------------------------------------------------------------------
-// The TAIL of the KNN forward, one launch (round 5; rounds 2-4: k_knn_strip_more, then k_knn_fallback): everything the main launch
+// The TAIL of the KNN forward, one launch (round 5; rounds 2-4: two launches): everything the main launch
 // of the strip kernel left over.
 //   workgroups [0, KS_RETRY_BLOCKS): the strip work (strip_more_body) -- overflowed strips in quarters, the far queries; what they
 //     cannot finish goes on the LATE list; when a workgroup is through, it counts itself done;
 //   workgroups [KS_RETRY_BLOCKS, + KS_FB_BLOCKS): one wavefront per query of the main launch's `fail` list -- at once, BESIDE the strip
-//     workgroups: both halves are chains of dependent round trips at low occupancy (a work item of the far pass ~25 us on one
+//     workgroups: both halves are chains of dependent round trips at low occupancy (a far item ~25 us on one
 //     wavefront of four, a fallback query ~14 us), side by side they cost what the longer one costs -- then, once every strip
 //     workgroup is done, the late list.
 //     FORWARD PROGRESS of that wait (round 6): the strip workgroups wait for nobody, so they finish as soon as they are resident; a
@@ -1251,10 +1260,10 @@ __device__ __forceinline__ void fallback_entry(const KnnParams &p, const float *
 //     dispatches in.  Round 5 relied on dispatch in blockIdx order, which HIP does not promise; the late list in a launch
 //     of its own was measured too: +9 us on the white-noise step (profiles/HISTORY_r06.md section 2).
 // One launch instead of two for the lattice-like point sets of the benchmark, whose lists are (nearly) empty.
-// grid: KS_RETRY_BLOCKS + KS_FB_BLOCKS workgroups (the list lengths are only known on the device), 256 threads, dynamic LDS of the
-// far pass (the fallback workgroups use its first 16 KB)
+// grid: KS_RETRY_BLOCKS + KS_FB_BLOCKS workgroups (the list lengths are only known on the device), 256 threads, dynamic LDS of a
+// far item (the fallback workgroups use its first 16 KB)
 // ------------------------------------------------------------------------------------------
-template <int WS, bool L1, bool NEXT, bool IWD>
+template <bool L1, bool NEXT, bool IWD>
 __global__ __launch_bounds__(KS_NT, KS_MORE_OCC) void k_knn_tail(const KnnParams p, const float *__restrict__ traj,
                                                      const knn_cs_t *__restrict__ cell_start, const knn_cs_t *__restrict__ sat,
                                                      const float2 *__restrict__ spos, const knn_idx_t *__restrict__ sidx,
@@ -1263,13 +1272,13 @@ __global__ __launch_bounds__(KS_NT, KS_MORE_OCC) void k_knn_tail(const KnnParams
                                                      const KnnLists ls, int r_init, int cap, int gx, int gy, const EvCountArgs evc) {
     extern __shared__ __align__(16) unsigned char s_dyn[];
     __shared__ int s_wsum[KS_NT / 64 + 1], s_wmax[KS_NT / 64];      // (s_wsum[KS_NT / 64]: this strip workgroup put queries on the late list)
-    __shared__ unsigned char s_rq[KS_NT / WS];
+    __shared__ unsigned char s_rq[KS_NT / KS_WS];
     KT_DECL
     KT_T(0);
     if ((int)blockIdx.x < KS_RETRY_BLOCKS) {
         if (threadIdx.x == 0) s_wsum[KS_NT / 64] = 0;
         __syncthreads();
-        strip_more_body<WS, L1, NEXT, IWD>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy,
+        strip_more_body<L1, NEXT, IWD>(p, traj, cell_start, sat, spos, sidx, flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy,
                                            (int)blockIdx.x, KS_RETRY_BLOCKS, s_dyn, s_wsum, s_wmax, s_rq);
         // (its late-list entries go out with one device-wide fence -- an L2 write-back on this chip: only a workgroup that pushed any
         // pays for it; 1 024 unconditional fences were 40 us of a 60 us launch, one per push 67 us of a 30 % contraction's 490 --
@@ -1321,13 +1330,13 @@ __global__ __launch_bounds__(KS_NT, KS_MORE_OCC) void k_knn_tail(const KnnParams
 // launcher (called by mpc_knn_lut_fwd once the points are bucketed; `fail[0]`, the far-list counters and tile_dkmax zeroed by
 // the bucket kernel)
 // ------------------------------------------------------------------------------------------
-// staging capacity (slots) of a strip and the dynamic LDS of the main launch / of the launch for the far queries (more region
+// staging capacity (slots) of a strip and the dynamic LDS of the main launch / of a far item of the tail launch (more region
 // rows, more dummy slots behind the staged ones)
-static bool strip_geometry(const mpc_shape *s, int r_init, int WS, int *cap_out, size_t *lds_out, size_t *lds_far_out = nullptr) {
-    const int TH = KS_NT / WS;
+static bool strip_geometry(const mpc_shape *s, int r_init, int *cap_out, size_t *lds_out, size_t *lds_far_out = nullptr) {
+    const int TH = KS_NT / KS_WS;
     if (TH + 2 * KNN_RFAR > KS_NT || r_init > KNN_RCAP) return false;
     const double dens = (double)s->n / ((double)s->hq * s->wq);
-    const double row_pts = dens * (WS + 2 * r_init);                       // points per region row of an inner strip
+    const double row_pts = dens * (KS_WS + 2 * r_init);                       // points per region row of an inner strip
     // slots of an inner query: its rows, one dummy slot per even row; must leave room for denser places
     const int maxch = (s->flags & MPC_F_DIST_L1) ? KS_MAXCH_L1 : KS_MAXCH;
     if ((2 * r_init + 1) * (row_pts + 0.5) * 1.3 > 4 * maxch) return false;
@@ -1349,13 +1358,13 @@ bool mpc_knn_strip_usable(const mpc_shape *s, int r_init) {
     int cap; size_t lds;
     if (s->T != 1 || s->n >= 65536 || s->K < 1 || s->K > 4 * ((s->flags & MPC_F_DIST_L1) ? KS_MAXCH_L1 : KS_MAXCH)) return false;
     if (s->hq < 2 * r_init + 2 || s->wq < 2 * r_init + 2) return false;       // tiny grids: the square is the whole grid
-    return strip_geometry(s, r_init, 2, &cap, &lds);
+    return strip_geometry(s, r_init, &cap, &lds);
 }
 
 // can the strip kernel's spare workgroups count the event rows of `evc` (their LDS holds one counter per backward bucket of a sample)?
 bool mpc_knn_strip_counts_events(const mpc_shape *s, const EvCountArgs *evc) {
     int cap; size_t lds;
-    if (!evc || !evc->events || !strip_geometry(s, mpc_knn_r_init(s), 2, &cap, &lds)) return false;
+    if (!evc || !evc->events || !strip_geometry(s, mpc_knn_r_init(s), &cap, &lds)) return false;
     return (size_t)evc->nb * evc->NCS * sizeof(int) <= lds && evc->B <= 256;
 }
 
@@ -1401,9 +1410,9 @@ int mpc_knn_strip_launch(const mpc_shape *s, const float *traj, const knn_cs_t *
     const KnnParams p = knn_params(s);
     const KnnLists ls = *lists;
     int cap = 0; size_t lds = 0, lds_far = 0;
-    if (!strip_geometry(s, r_init, 2, &cap, &lds, &lds_far)) { mpc_set_error("mpc_knn_strip_launch: shape not served by the strip kernel"); return MPC_E_UNSUPPORTED; }
-    constexpr int WS = 2, TH = KS_NT / WS;
-    const int gx = mpc_cdiv(s->wq, WS), gy = mpc_cdiv(s->hq, TH);
+    if (!strip_geometry(s, r_init, &cap, &lds, &lds_far)) { mpc_set_error("mpc_knn_strip_launch: shape not served by the strip kernel"); return MPC_E_UNSUPPORTED; }
+    constexpr int TH = KS_NT / KS_WS;
+    const int gx = mpc_cdiv(s->wq, KS_WS), gy = mpc_cdiv(s->hq, TH);
     EvCountArgs ec{};
     if (evc) ec = *evc;                 // (the caller checked mpc_knn_strip_counts_events)
     const int n_evc = (ev_count_blocks(ec) + 7) / 8 * 8;
@@ -1413,29 +1422,19 @@ int mpc_knn_strip_launch(const mpc_shape *s, const float *traj, const knn_cs_t *
     const dim3 grid((unsigned)total);
     // (the tail launch: nothing to do unless a strip overflowed its staging area / holds far queries / the main launch listed
     // queries for the one-wavefront-per-query search -- workgroups that read two words)
-    size_t lds_tail = lds_far > lds ? lds_far : lds;       // (far pass; the quarters of an overflowed strip use the main launch's carve-up)
+    size_t lds_tail = lds_far > lds ? lds_far : lds;       // (a far item; the retry quarters of an overflowed strip use the main launch's carve-up)
     if (lds_tail < 4 * 256 * sizeof(float4)) lds_tail = 4 * 256 * sizeof(float4);
-#define KS_LAUNCH(L1_, NEXT_, IWD_)                                                                                       \
-    do {                                                                                                                  \
-        MPC_LAUNCH((k_knn_strip<WS, L1_, NEXT_, IWD_>), grid, dim3(KS_NT), lds, st, p, traj, cell_start, sat, spos, sidx, \
-                           flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy, ec, n_evc, evc_stride);   \
-        const int fb_ = tail_fallback_blocks((const void *)k_knn_tail<WS, L1_, NEXT_, IWD_>, (L1_ ? 4 : 0) | (NEXT_ ? 2 : 0) | (IWD_ ? 1 : 0), \
-                                             lds_tail, ec.events ? ec.B : 0);                                             \
-        if (fb_ < 0) return fb_;                                                                                          \
-        MPC_LAUNCH((k_knn_tail<WS, L1_, NEXT_, IWD_>), dim3(KS_RETRY_BLOCKS + fb_), dim3(KS_NT), lds_tail, st, p, traj, cell_start, sat, spos, sidx, \
-                           flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy, ec);                      \
-    } while (0)
-    switch ((p.l1 ? 4 : 0) | (p.want_next ? 2 : 0) | (p.iwd ? 1 : 0)) {
-    case 0: KS_LAUNCH(false, false, false); break;
-    case 1: KS_LAUNCH(false, false, true); break;
-    case 2: KS_LAUNCH(false, true, false); break;
-    case 3: KS_LAUNCH(false, true, true); break;
-    case 4: KS_LAUNCH(true, false, false); break;
-    case 5: KS_LAUNCH(true, false, true); break;
-    case 6: KS_LAUNCH(true, true, false); break;
-    default: KS_LAUNCH(true, true, true); break;
-    }
-#undef KS_LAUNCH
+    const int inst = KNN_VARIANT_INDEX(p.l1, p.want_next, p.iwd);
+    const void *tail_fn[8];
+#define KS_TAIL_FN(L1_, NEXT_, IWD_) tail_fn[KNN_VARIANT_INDEX(L1_, NEXT_, IWD_)] = (const void *)k_knn_tail<L1_, NEXT_, IWD_>
+    KNN_VARIANT_EACH(KS_TAIL_FN);
+#undef KS_TAIL_FN
+    KNN_VARIANT_LAUNCH(k_knn_strip, p.l1, p.want_next, p.iwd, grid, dim3(KS_NT), lds, st, p, traj, cell_start, sat, spos, sidx,
+                       flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy, ec, n_evc, evc_stride);
+    const int fb = tail_fallback_blocks(tail_fn[inst], inst, lds_tail, ec.events ? ec.B : 0);
+    if (fb < 0) return fb;
+    KNN_VARIANT_LAUNCH(k_knn_tail, p.l1, p.want_next, p.iwd, dim3(KS_RETRY_BLOCKS + fb), dim3(KS_NT), lds_tail, st, p, traj, cell_start, sat, spos, sidx,
+                       flow_lut, flow_next, knn_state, tile_dkmax, ls, r_init, cap, gx, gy, ec);
     MPC_CHECK_LAUNCH();
     return 0;
 }

@@ -104,23 +104,23 @@
                                     // most of what the load phases gain the search gives back, the rest is the 10 us.  2 buys nothing over 1.
 #endif
 #ifndef KS_MORE_MIN
-#define KS_MORE_MIN 16               // a strip goes to the second launch for its unfinished queries if it has more than this many (or far queries)
+#define KS_MORE_MIN 16               // a strip becomes a far item of the tail launch for its unfinished queries if it has more than this many (or far queries)
 #endif
 #ifndef KS_MAIN_CHORD
 #define KS_MAIN_CHORD 1            // main launch: region rows as wide as the widest chord (1) or square (0) that uses them
 #endif
 #ifndef KS_MAXCH_FAR
-#define KS_MAXCH_FAR 48             // ... of the launch for the far queries (192 slots: a band along the left or right border -- every region row
+#define KS_MAXCH_FAR 48             // ... of a far item of the tail launch (192 slots: a band along the left or right border -- every region row
                                    // as wide as the widest chord -- needs ~160; 256 slots at three workgroups per CU measured slower, see KS_MORE_OCC)
 #endif
 #ifndef KS_SB
 #define KS_SB 3                     // staging: items per thread whose global loads are in flight together
 #endif
 #ifndef KS_FORWARD_MAX
-#define KS_FORWARD_MAX 1024         // the main launch marked at most this many queries: the tail's one-wavefront search takes them from the marked list, no far pass
+#define KS_FORWARD_MAX 1024         // the main launch marked at most this many queries: the tail's fallback workgroups take them from the marked list, no far items
 #endif
 #ifndef KS_MORE_OCC
-#define KS_MORE_OCC 4               // workgroups per CU of the second launch = its register budget (128; 13 registers spill).  The launch is bound
+#define KS_MORE_OCC 4               // workgroups per CU of the tail launch (k_knn_tail) = its register budget (128; 13 registers spill).  The launch is bound
                                    // by the latency of its work items: C3, 40 px translation / 48 px contraction band: 4 per CU with 192 slots
                                    // 161 / 308 us, 3 per CU with 192 slots 179 / 351, with 256 slots 190 / 368, 2 per CU 258 / -
 #endif

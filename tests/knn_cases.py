@@ -10,7 +10,7 @@ the flow of a point has nothing to do with where it lies, and exchanging one nei
 |e - e'| / K.  separation() measures that for every query: the K-th neighbour replaced by the (K + 1)-th.
 
 Selection.  Ranked in float32 with the operand order of focus.py:132-135 (knn_wide_cases.distances), ordered by (distance,
-index) (knn_wide_cases.ordered_knn): the kernels' own arithmetic (knn_device.h:146-150 pair_dist, -ffp-contract=off), so the
+index) (knn_wide_cases.ordered_knn): the kernels' own arithmetic (pair_dist, knn_device.h:169-173, -ffp-contract=off), so the
 neighbour sets are the same on both sides bit for bit, ties included, and no query is excused.
 
 Values.  float64 over those sets: 'mean', 'iwd' (1 / (d + 1e-9), d in float64 from the positions; K == 1 is a plain gather,
@@ -20,35 +20,38 @@ Allowances.  gamma(k) = k u / (1 - k u), u = 2^-24, times the same chain on abso
 lane order or a shuffle tree, so every sum of m terms takes the order-free bound of m - 1 additions (an addition of an exact
 zero -- a slot that is no neighbour, an empty lane -- rounds nothing).  k per kernel, longest path, with the source lines:
 
-  flow of a point          1   traj(t_ref) - traj(t_mid), one subtraction: knn_strip.hip:440-441, 1183, 1186; knn_device.h:197, 202
+  flow of a point          1   traj(t_ref) - traj(t_mid), one subtraction: knn_strip.hip:455-456, 1199, 1202; knn_device.h:220, 225
   D  distance              4   'l2': q - p (1), its square (2 more: the error of q - p twice, the product once), the sum (1);
-                           2   'l1': q - p (1), the sum (1).  The cell centre cy * sp + off is exact.     knn_device.h:146-150
+                           2   'l1': q - p (1), the sum (1).  The cell centre cy * sp + off is exact.   pair_dist, knn_device.h:169-173
   W  'iwd' weight      D + 4   d + 1e-9f (1, and 1 for the constant 1e-9f against 1e-9), the reciprocal: v_rcp_f32 at 1 ulp =
-                               2 u on the strip path and in the tile gather (knn_strip.hip:73; knn.hip:882, 1194, 1213), one
-                               IEEE division (1) elsewhere (knn_device.h:367, 401, 425, 465, 522; knn_strip.hip:1184)
-  strip pass 2, 'mean'     K + 1   flow 1, K - 1 additions (fmaf with a flag of 128.0 or 0.0: knn_strip.hip:625; the factor 128
-                               is a power of two), the K-th level light (:675) or heavy (:724 lane sums, :731 shuffle tree, :741
-                               fmaf(128, c, s)) -- still K - 1 additions in all --, then sum * 2^-(7 + log2 K), exact (:758), or
-                               (sum * 2^-7) / K: 1 (:759).  flow_next the same (:626, 676, 725, 743, 763-764)
-  strip pass 2, 'iwd'      numerator W + 1 (flow) + 1 (the product: fused at :624 and :674, separate at :724) + K - 1;
-                           normaliser N = W + K - 1 (:624, 674, 724, 732, 741); the quotient 1 (:752): 2 W + 2 K + 1.
-                           The saved normaliser is sw * 2^-7, exact (:752): N
-  one-wavefront fallback   'mean' K + 1: flow 1 (:1183), lane sums and shuffle tree K - 1 (:1185, 1190-1193), / K 1 (:1202);
-                           'iwd' as the strip's with the separate product (:1184) and IEEE divisions (:1201): <= 2 W + 2 K + 1
-  k_knn_query              knn_one_query, knn_device.h: 'mean' K + 1 (:197, 368, 402, 426, 466, 525, 502, 535); 'iwd'
-                           <= 2 W + 2 K + 1 (:367, 401, 425, 465, 522-523, 501, 534); T flows: the same per reference time
+                               2 u on the strip path and in the tile gather (ks_iwd_weight, knn_strip.hip:93; knn.hip:783, 1102,
+                               1121), one IEEE division (1) elsewhere (knn_device.h:390, 424, 448, 488, 545; knn_strip.hip:1200;
+                               knn.hip:716)
+  strip pass 2, 'mean'     K + 1   flow 1, K - 1 additions (fmaf with a flag of 128.0 or 0.0: knn_strip.hip:641; the factor 128
+                               is a power of two), the K-th level light (:691) or heavy (:740 lane sums, :747 shuffle tree, :758
+                               fmaf(128, c, s)) -- still K - 1 additions in all --, then sum * 2^-(7 + log2 K), exact (:775), or
+                               (sum * 2^-7) / K: 1 (:776).  flow_next the same (:642, 692, 741, 749, 759, 780-781)
+  strip pass 2, 'iwd'      numerator W + 1 (flow) + 1 (the product: fused at :640 and :690, separate at :740) + K - 1;
+                           normaliser N = W + K - 1 (:640, 690, 740, 748, 757); the quotient 1 (:769): 2 W + 2 K + 1.
+                           The saved normaliser is sw * 2^-7, exact (:769): N
+  one-wavefront fallback   fallback_one_query: 'mean' K + 1: flow 1 (:1199), lane sums and shuffle tree K - 1 (:1201, 1206-1209),
+                           / K 1 (:1218); 'iwd' as the strip's with the separate product (:1200) and IEEE divisions (:1217):
+                           <= 2 W + 2 K + 1
+  k_knn_query              knn_one_query, knn_device.h: 'mean' K + 1 (:220, 391, 425, 449, 489, 548, 525, 558); 'iwd'
+                           <= 2 W + 2 K + 1 (:390, 424, 448, 488, 545-546, 524, 557); T flows: the same per reference time
   tile gather              k_knn_bwd_tile, per point and bin: 'mean' the member gradients K-free: M - 1 additions over its M
-                           members (knn.hip:884, 1195, 1214), 1 / K rounded (1, :1133) and the product (1, :1223, 1225): C = 2;
-                           'iwd': the staged gradient is dL/dLUT / normaliser (1, and the normaliser's own N), the weight W,
-                           the product fused (:882-883, 1194) -- or rcp((d + 1e-9) * normaliser), one product more (:1213):
-                           C = W + N + 2.  The flow_next sums are means in both schemes (:885, 1196, 1215, 1226)
+                           members (knn.hip:785, 1103, 1122), 1 / K rounded (1, :1040-1041) and the product (1, :1132, 1134): C = 2;
+                           'iwd': the staged gradient is dL/dLUT / normaliser (1, :1012, and the normaliser's own N), the weight W,
+                           the product fused (:783-784, 1102) -- or rcp((d + 1e-9) * normaliser), one product more (:1121):
+                           C = W + N + 2.  The flow_next sums are means in both schemes (:786, 1104, 1123, 1135)
   far backward             k_knn_bwd_far: integer sums of round(g * 2^(40 - ex)), 2^ex the power of two above the largest
-                           |gradient| of the list (knn.hip:1336-1337): at most |g|max * 2^-40 per add (:1417-1421), then the
-                           conversion (1, :1438), 1 / K and its product (2) and the addition to the gather's value (:1442,
-                           1446: one of the M - 1): C = 3; 'iwd' (1 / (d + 1e-9)) / normaliser (W + N + 1), times g (1, :1416-1417)
+                           |gradient| of the list (knn.hip:1244-1246): at most |g|max * 2^-40 per add (:1326-1330), then the
+                           conversion (1, :1347), 1 / K and its product (2) and the addition to the gather's value (:1351,
+                           1355: one of the M - 1): C = 3; 'iwd' (1 / (d + 1e-9)) / normaliser (W + N + 1), times g (1, :1325-1327)
                            and the conversion (1): C = W + N + 3
-  k_knn_bwd_points         num_tref > 1: w = 1 / K (1), ay += w * g (product 1, :815-816), flow_next the same (:817): C = 2
-  combines                 k_knn_bwd_combine (:1478-1479, 1489, 1498-1501), _bins (:1526-1527, 1534), _direct (:1552): additions of the
+  k_knn_bwd_points         num_tref > 1: w = 1 / K (1, knn.hip:683), ay += w * g (product 1, :716-717), flow_next the same (:718): C = 2;
+                           'iwd': w = (1 / (d + 1e-9)) / normaliser (W + N + 1, :716) and the product (1): C = W + N + 2
+  combines                 k_knn_bwd_combine (knn.hip:1385, 1394, 1397), _bins (:1422-1423, 1430), _direct (:1448): additions of the
                            per-bin values only; with all members of an element counted in M they are among its M - 1 additions
 
 So per element: flow_lut 'mean' and flow_next gamma(K + 1) mean|flow|; flow_lut 'iwd' gamma(2 W + 2 K + 1) sum(w |flow|) / sum(w);
@@ -66,9 +69,9 @@ from knn_wide_cases import distances, ordered_knn
 
 U = 2.0 ** -24
 KNN_TIE_FLAG, KNN_FAR_FLAG, KNN_IDX_MASK = 0x40000000, 0x20000000, 0x1fffffff      # knn_device.h:11-15
-KNN_NCLS, KNN_RCAP, KNN_RFAR, KNN_FAR_RINGS = 5, 6, 20, 2                          # knn_device.h:22, 42; tuning.h:137, 140
+KNN_NCLS, KNN_RCAP, KNN_RFAR, KNN_FAR_RINGS = 5, 6, 20, 2                          # knn_device.h:22, 42; tuning.h:154, 157
 KNN_MARGIN = KNN_RCAP + 1                                                          # knn_device.h:44
-KS_MAXCH, KS_MAXCH_L1, KS_MAXCH_FAR, KS_LMAX, KS_FORWARD_MAX = 24, 32, 48, 4, 1024  # knn_strip.hip:40, 45, 51; tuning.h:96, 103
+KS_MAXCH, KS_MAXCH_L1, KS_MAXCH_FAR, KS_LMAX, KS_FORWARD_MAX = 24, 32, 48, 4, 1024  # knn_strip.hip:57, 62, 68; tuning.h:113, 120
 MPC_KNN_LDS_SORT_CELLS = 150 * 1024 // 4                                           # common.h:11
 SEPARATION = 20.0
 FAR_QUANTUM = 2.0 ** -40
@@ -163,14 +166,14 @@ class Case:
 
 # ---- the library's plans, restated ---------------------------------------------------------------------------------------------
 def r_init(c):
-    """knn.hip:1564-1570."""
+    """mpc_knn_r_init, knn.hip:1460-1466."""
     dens = c.n / (c.hq * c.wq)
     ball = 2.0 if c.norm == 'l1' else 3.14159265
     return max(int(math.ceil(math.sqrt(c.K / ball / (dens if dens > 0 else 1.0)) - 0.5)), 1)
 
 
 def strip_usable(c):
-    """knn_strip.hip:1319-1346: does the forward of this case run the strip kernel (and the backward the far list)?"""
+    """mpc_knn_strip_usable and strip_geometry, knn_strip.hip:1335-1362: does the forward of this case run the strip kernel (and the backward the far list)?"""
     r = r_init(c)
     maxch = KS_MAXCH_L1 if c.norm == 'l1' else KS_MAXCH
     if c.T != 1 or c.n >= 65536 or c.K < 1 or c.K > 4 * maxch or c.hq < 2 * r + 2 or c.wq < 2 * r + 2 or r > KNN_RCAP:
@@ -186,7 +189,7 @@ def strip_usable(c):
 
 
 def sort_plan(c):
-    """knn.hip:1590-1602 -> (S workgroups per (sample, bin), global-memory sort?)."""
+    """knn_sort_plan, knn.hip:1486-1498 -> (S workgroups per (sample, bin), global-memory sort?)."""
     hb, wb = c.hq + 2 * KNN_MARGIN, c.wq + 2 * KNN_MARGIN
     S = max(min(256 // (c.B * c.nb), 8, hb), 1)
     tail = (c.n + 1) // 2 * 2 * 2 + (c.n + 31) // 32 * 4
@@ -197,13 +200,13 @@ def sort_plan(c):
 
 
 def far_limit(c):
-    """knn_device.h:642-645: a K-th distance beyond it is the far backward's (where the forward is the strip kernel)."""
+    """knn_is_far_dk, knn_device.h:665-668: a K-th distance beyond it is the far backward's (where the forward is the strip kernel)."""
     lim = torch.tensor((r_init(c) + KNN_FAR_RINGS) + 0.5, dtype=torch.float32) * torch.tensor(float(c.sp), dtype=torch.float32)
     return lim if c.norm == 'l1' else lim * lim
 
 
 def query_classes(c):
-    """knn_device.h:578-581 with bd = r_init + 1 (:572) -> [hq * wq, 5] bool, and the 16 x 16 tile of every query (:129-130, 587)."""
+    """knn_query_classes, knn_device.h:601-604 with bd = r_init + 1 (knn_band_depth, :595) -> [hq * wq, 5] bool, and the 16 x 16 tile of every query (:152-153, 610)."""
     bd = r_init(c) + 1
     cy, cx = torch.meshgrid(torch.arange(c.hq), torch.arange(c.wq), indexing='ij')
     cy, cx = cy.reshape(-1), cx.reshape(-1)
@@ -571,7 +574,7 @@ def g_family(H, W, patch, family, B=1, nb=3, seed=0):
 
 
 def cell_of(v, sp):
-    """knn_device.h:114-118 without the clamp: cell c covers [c sp - 0.5, (c + 1) sp - 0.5)."""
+    """cell_of, knn_device.h:137-141 without the clamp: cell c covers [c sp - 0.5, (c + 1) sp - 0.5)."""
     return torch.floor((v + 0.5) / sp)
 
 
@@ -678,7 +681,7 @@ def _c_lattice(name, sp=4, patch=4, norm='l2', scheme='mean', want_next=False, e
     H, W = 160, 192
     c = make(name, g_lattice(H, W, patch), H, W, sp=sp, norm=norm, scheme=scheme, want_next=want_next, seed=_eseed(norm, scheme))
     c.expect = expect if expect is not None else (STRIP if strip_usable(c) else QUERY) + (('ref_ties', '>', 1000),)
-    if (sp, patch) == (2, 4):              # a quarter of the density: every strip has far queries, and the far pass leaves a late list
+    if (sp, patch) == (2, 4):              # a quarter of the density: every strip has far queries, and the far items leave a late list
         c.expect += FAR + FAR_PASS + (('late', '>', 0),)
     return c
 
@@ -757,9 +760,9 @@ def _c_family(name, family, B=1, nb=3, expect=None, norm='l2', scheme='mean', wa
 
 def _c_crowded_stripe(name):
     """Staging overflow: the lattice with two more points in every tile of six columns -- three times the density in a strip and
-    its halo (a wider stripe lifts the mean density beyond what the strip kernel takes, knn_strip.hip:1326).  There a query's own
+    its halo (a wider stripe lifts the mean density beyond what the strip kernel takes, strip_geometry, knn_strip.hip:1342).  There a query's own
     radius is 2 cells (75 points in its square, within the 96 slots), so the strip stages 6 columns x 40 rows x 3 = 720 points
-    where the area holds 1.15 x the mean density of 1.25 plus 32: 592 (knn_strip.hip:1327-1329)."""
+    where the area holds 1.15 x the mean density of 1.25 plus 32: 592 (knn_strip.hip:1343-1345)."""
     H, W = 160, 192
     p = tile_centres(H, W, 4)
     inside = (p[:, 1] >= 80) & (p[:, 1] < 104)
@@ -807,15 +810,16 @@ def _c_global_sort(name):
     return c
 
 
-def _c_T2(name, hq, wq):
+def _c_T2(name, hq, wq, norm='l2', scheme='mean', want_next=True, T=2):
+    """num_tref > 1: the general tile kernel forward and the general gather (k_knn_bwd_points, k_knn_bwd_combine), three bins."""
     H, W = _grid(hq, wq)
-    return make(name, g_jitter(H, W, 4, nb=3, seed=hq), H, W, T=2, want_next=True,
+    return make(name, g_jitter(H, W, 4, nb=3, seed=hq), H, W, norm=norm, scheme=scheme, want_next=want_next, T=T,
                 expect=QUERY + (('k_knn_bwd_points', '>', 0), ('k_knn_bwd_combine', '>', 0)))
 
 
 FAR = (('far_flags', '>', 0),)
-# the tail launch's two ways: few marked queries -- its one-wavefront search takes them from the marked list, no far pass, no strip
-# workgroup counts itself done --, or more than KS_FORWARD_MAX: the far pass
+# the tail launch's two ways: few marked queries -- its fallback workgroups take them from the marked list, no far items, no strip
+# workgroup counts itself done --, or more than KS_FORWARD_MAX: the far items
 SMALL_TAIL = (('marked', '>', 0), ('marked', '<=', KS_FORWARD_MAX), ('done', '==', 0))
 FAR_PASS = (('marked', '>', KS_FORWARD_MAX), ('done', '>', 0))
 CASES = {}
@@ -848,7 +852,7 @@ for _p in (6, 7, 16, 17, 128, 129):
 CASES['margin_points'] = (_c_margin, ())
 CASES['bin_outside'] = (_c_bin_outside, ())
 CASES['band_translate40'] = (_c_family, ('translate40', 3, 3, STRIP + FAR + FAR_PASS))
-# (translate10 empties 2.5 cell rows of this grid: its few stray queries go on the fallback list and nothing is marked; the marked list
+# (translate10 empties 2.5 cell rows of this grid: its few stray queries go on the fail list and nothing is marked; the marked list
 # with at most 1 024 entries is the route of translate40_* at B = 1, margin_points, bin_outside and pile_128 / 129)
 CASES['band_translate10'] = (_c_family, ('translate10', 1, 1, STRIP + (('fails', '>', 0), ('marked', '<=', KS_FORWARD_MAX), ('done', '==', 0))))
 # (a 40 x 48 grid under diverge-45 does not overflow the staging area -- the emptied border rows make room for the packed middle;
@@ -865,6 +869,10 @@ for _n in (8192, 8193, 16384, 16385, 20480, 20481, 24576, 24577):
 CASES['global_sort'] = (_c_global_sort, ())
 CASES['T2_17x33'] = (_c_T2, (17, 33))
 CASES['T2_40x48'] = (_c_T2, (40, 48))
+# (the 'iwd' weight of the general gather, and its flow_next partials read as zeros; three reference times through both loops of the
+# combine on a grid under one tile in height and just over one in width)
+CASES['T2_17x33_iwd_l1'] = (_c_T2, (17, 33, 'l1', 'iwd', False))
+CASES['T3_15x17'] = (_c_T2, (15, 17, 'l2', 'mean', False, 3))
 
 # one case per route also goes through ops.KnnLutFn
 FN_CASES = ('strip_h129_w9', 'bwd_17x33', 'tiny_7x9', 'band_translate40', 'band_translate10', 'global_sort', 'T2_17x33', 'lattice_l1_iwd_next')

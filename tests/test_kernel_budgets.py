@@ -36,8 +36,8 @@ def _llvm_bin():
 def _waves(name):
     m = re.match(r'(\w+)(?:<(.*)>)?$', name)
     kern, args = m.group(1), [a.strip() for a in (m.group(2) or '').split(',')]
-    if kern == 'k_knn_strip':           # <WS, L1, NEXT, IWD>: (NEXT || L1) ? KS_OCC_WIDE = 5 : 6
-        return 5 if 'true' in args[1:3] else 6
+    if kern == 'k_knn_strip':           # <L1, NEXT, IWD>: (NEXT || L1) ? KS_OCC_WIDE = 5 : 6
+        return 5 if 'true' in args[0:2] else 6
     if kern == 'k_knn_tail':            # KS_MORE_OCC = 4
         return 4
     if kern == 'k_knn_bwd_tile':        # <L1, NEXT, IWD>: NEXT ? KNN_BW_OCC_NEXT = 6 : (IWD ? KNN_BW_OCC_IWD = 7 : KNN_BW_OCC = 7)
@@ -51,22 +51,22 @@ def _waves(name):
 
 # name: (vgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size) of the parent commit
 RECORDED = {
-    'k_knn_strip<2, false, false, false>': (0, 0, 432),
-    'k_knn_strip<2, false, false, true>': (1, 8, 432),
-    'k_knn_strip<2, false, true, false>': (1, 8, 432),
-    'k_knn_strip<2, false, true, true>': (11, 48, 432),
-    'k_knn_strip<2, true, false, false>': (0, 0, 432),
-    'k_knn_strip<2, true, false, true>': (0, 0, 432),
-    'k_knn_strip<2, true, true, false>': (9, 40, 432),
-    'k_knn_strip<2, true, true, true>': (23, 96, 432),
-    'k_knn_tail<2, false, false, false>': (14, 60, 880),
-    'k_knn_tail<2, false, false, true>': (20, 84, 880),
-    'k_knn_tail<2, false, true, false>': (32, 128, 880),
-    'k_knn_tail<2, false, true, true>': (48, 168, 880),
-    'k_knn_tail<2, true, false, false>': (16, 60, 880),
-    'k_knn_tail<2, true, false, true>': (21, 84, 880),
-    'k_knn_tail<2, true, true, false>': (36, 124, 880),
-    'k_knn_tail<2, true, true, true>': (56, 168, 880),
+    'k_knn_strip<false, false, false>': (0, 0, 432),
+    'k_knn_strip<false, false, true>': (1, 8, 432),
+    'k_knn_strip<false, true, false>': (1, 8, 432),
+    'k_knn_strip<false, true, true>': (11, 48, 432),
+    'k_knn_strip<true, false, false>': (0, 0, 432),
+    'k_knn_strip<true, false, true>': (0, 0, 432),
+    'k_knn_strip<true, true, false>': (9, 40, 432),
+    'k_knn_strip<true, true, true>': (23, 96, 432),
+    'k_knn_tail<false, false, false>': (14, 60, 880),
+    'k_knn_tail<false, false, true>': (20, 84, 880),
+    'k_knn_tail<false, true, false>': (32, 128, 880),
+    'k_knn_tail<false, true, true>': (48, 168, 880),
+    'k_knn_tail<true, false, false>': (16, 60, 880),
+    'k_knn_tail<true, false, true>': (21, 84, 880),
+    'k_knn_tail<true, true, false>': (36, 124, 880),
+    'k_knn_tail<true, true, true>': (56, 168, 880),
     'k_knn_bwd_tile<false, false, false>': (2, 12, 272),
     'k_knn_bwd_tile<false, false, true>': (2, 12, 272),
     'k_knn_bwd_tile<false, true, false>': (10, 44, 272),

@@ -106,7 +106,7 @@ def test_cases_are_what_their_names_say():
     for name in ('strip_h127_w9', 'strip_h128_w9', 'strip_h129_w9', 'strip_h8_w8'):
         c = KC.case(name)
         assert KC.strip_usable(c) and c.wq >= 2 * KC.r_init(c) + 2 and (c.hq, c.wq) == tuple(int(v[1:]) for v in name.split('_')[1:])
-    for name in ('tiny_1x1_n_eq_K', 'tiny_7x9', 'tiny_3x40', 'K_97', 'K_129_l1', 'T2_17x33'):
+    for name in ('tiny_1x1_n_eq_K', 'tiny_7x9', 'tiny_3x40', 'K_97', 'K_129_l1', 'T2_17x33', 'T2_17x33_iwd_l1', 'T3_15x17'):
         assert not KC.strip_usable(KC.case(name)), name
     assert KC.case('tiny_1x1_n_eq_K').n == KC.case('tiny_1x1_n_eq_K').K and KC.case('K_eq_n_12x12').n == 32
     assert [KC.sort_plan(KC.case(f'plan_{v}'))[0] for v in (1, 64, 100, 135)] == [8, 4, 2, 1]

@@ -5,7 +5,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libmpcmax.so')
-SOURCES = ['api.hip', 'contrast.hip', 'events.hip', 'knn.hip', 'knn_strip.hip', 'knn_wide.hip', 'voxel.hip', 'ingest.hip', 'flow.hip', 'curves.hip', 'cvx_curves.hip', 'corr_lookup.hip', 'corr_pyramid.hip', 'val_metrics.hip', 'tiles.hip', 'grid_traj.hip', 'repr.hip', 'flow_targets.hip', 'dsec_io.hip', 'pe_curves.hip']
+SOURCES = ['api.hip', 'contrast.hip', 'events.hip', 'knn.hip', 'knn_strip.hip', 'knn_wide.hip', 'voxel.hip', 'ingest.hip', 'flow.hip', 'curves.hip', 'cvx_curves.hip', 'corr_lookup.hip', 'corr_pyramid.hip', 'val_metrics.hip', 'tiles.hip', 'grid_traj.hip', 'repr.hip', 'flow_targets.hip', 'dsec_io.hip', 'pe_curves.hip', 'pe_basis.hip', 'ev_order.hip']
 FLAGS = ['-shared', '-fPIC', '-O3', '--offload-arch=gfx950', '-ffp-contract=off', '-std=c++17',
          '-Wall', '-Wno-unused-function']
 
@@ -55,7 +55,10 @@ def build_library(force=False, verbose=False, out=None):
                 print(' '.join(cmd))
             subprocess.run(cmd, check=True, cwd=CSRC)
             return obj
-        with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as ex:
+        jobs = min(len(SOURCES), os.cpu_count() or 1)
+        if os.environ.get('MAX_JOBS', '').isdigit():          # (the build host's cap on parallel compilers)
+            jobs = max(1, min(jobs, int(os.environ['MAX_JOBS'])))
+        with ThreadPoolExecutor(max_workers=jobs) as ex:
             objs = list(ex.map(compile_one, SOURCES))
         cmd = [hipcc, '-shared', '-fPIC', '--offload-arch=gfx950', '-o', out] + objs
         if verbose:

@@ -143,6 +143,19 @@ int mpc_validate_shape(const mpc_shape *s) {
     return 0;
 }
 
+// (per device: a process may drive GPUs with different CU counts; 0 = not asked yet.  Two threads may both ask: they store the same)
+int mpc_cu_count() {
+    static std::atomic<int> ncu_of[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    int ncu = ncu_of[dev & 63].load();
+    if (ncu <= 0) {
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) { (void)hipGetLastError(); ncu = 256; }
+        ncu_of[dev & 63].store(ncu);
+    }
+    return ncu;
+}
+
 mpc_ws_layout mpc_layout(const mpc_shape *s) {
     mpc_ws_layout L;
     memset(&L, 0, sizeof(L));
@@ -169,8 +182,8 @@ mpc_ws_layout mpc_layout(const mpc_shape *s) {
     L.off_knn_cursor = off; off += mpc_knn_big_sort(s) ? mpc_align(bt * Gb * sizeof(int32_t)) : 0;
     L.off_knn_reach = off;  off += mpc_align(bt * ktiles * sizeof(float));
     L.off_knn_fail = off;   off += mpc_align((1 + bt * (int64_t)L.G) * sizeof(int32_t));
-    L.off_knn_retry = off;  off += mpc_align((1 + bt * (int64_t)mpc_cdiv(s->wq, 2) * mpc_cdiv(s->hq, 128)) * sizeof(int32_t));
     const int64_t fitems = (int64_t)mpc_cdiv(s->wq, 2) * mpc_cdiv(s->hq, 128);       // (knn_device.h: KNN_FAR_WS x KNN_FAR_TH blocks of queries)
+    L.off_knn_retry = off;  off += mpc_align((1 + bt * fitems) * sizeof(int32_t));
     L.off_knn_farstrip = off; off += mpc_align((1 + bt * fitems) * sizeof(int32_t));
     L.off_knn_ftlist = off; off += mpc_knn_uses_far_list(s) ? mpc_align((1 + bt * ktiles) * sizeof(int32_t)) : 0;
     L.off_knn_ftbits = off; off += mpc_knn_uses_far_list(s) ? mpc_align(bt * ((ktiles + 31) / 32) * sizeof(int32_t)) : 0;
@@ -187,6 +200,7 @@ mpc_ws_layout mpc_layout(const mpc_shape *s) {
     if (L.cstrip_rows > s->hq) L.cstrip_rows = s->hq;
     if (L.strip_rows > 0 && L.cstrip_rows > 0 && s->T == 1 && s->B > 0 && !(s->flags & MPC_F_ATOMIC_PATH)) {
         L.n_strips = mpc_cdiv(s->H, L.strip_rows);
+        const int64_t mpol = (L.P == 2) ? (s->Mp > s->M - s->Mp ? s->Mp : s->M - s->Mp) : s->M;      // rows of the larger polarity block
         {
             // k_iwe_accum keeps a strip of 64-bit accumulators in LDS: one 1024-thread workgroup per CU with the largest strip
             // that fits, two with strips of half that height.  Its time is (rounds of workgroups) x (rows of a strip + a fixed
@@ -195,20 +209,7 @@ mpc_ws_layout mpc_layout(const mpc_shape *s) {
             // at C3 (14 x 2 images): 16 strips of 30 rows (448 workgroups = 1.75 rounds) 23.6 us, 18 of 27 (1.97 rounds) 22.3,
             // 36 of 14 (two per CU, 1.97 rounds) 19.9, 54 of 9: 20.8 with k_ev_bin + 1.7; at B = 1 thin strips are the parallelism
             // there is (C4: 16 strips 15.3 us, 32: 10.6).  MPC_EV_STRIPS=<n> forces a count (tuning).
-            // (per device: a process may drive GPUs with different CU counts; -1 = not asked yet)
-            static std::atomic<int> ncu_of[64];
-            static std::atomic<bool> ncu_init{false};
-            if (!ncu_init.exchange(true)) for (auto &v : ncu_of) v.store(0);
-            int dev = 0;
-            if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-            int ncu = ncu_of[dev & 63].load();
-            if (ncu <= 0) {
-                if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) {
-                    (void)hipGetLastError();
-                    ncu = 256;
-                }
-                ncu_of[dev & 63].store(ncu);
-            }
+            const int ncu = mpc_cu_count();
             static const int forced = getenv("MPC_EV_STRIPS") ? atoi(getenv("MPC_EV_STRIPS")) : 0;
             const int n0 = L.n_strips;
             auto cost_of = [&](int n) {
@@ -222,9 +223,8 @@ mpc_ws_layout mpc_layout(const mpc_shape *s) {
             double best_cost = cost_of(n0);
             // (every forward bucket is sized for the worst case -- all events of its polarity block: more strips, more committed
             // memory.  Beyond 1.5 GB of forward records the smallest count stays: C3 1.2 GB at 35 strips, 0.5 at 16)
-            const int64_t mpol_ = (L.P == 2) ? (s->Mp > s->M - s->Mp ? s->Mp : s->M - s->Mp) : s->M;
             for (int n = n0 + 1; n <= 3 * n0 && mpc_cdiv(s->H, n) >= 8; ++n) {
-                if ((int64_t)s->B * L.P * n * (mpol_ > 0 ? mpol_ : 1) * 12 > (int64_t)1536 << 20) break;
+                if ((int64_t)s->B * L.P * n * (mpol > 0 ? mpol : 1) * 12 > (int64_t)1536 << 20) break;
                 const double cost = cost_of(n);
                 if (cost < best_cost * 0.999) { best_cost = cost; best = n; }
             }
@@ -244,7 +244,6 @@ mpc_ws_layout mpc_layout(const mpc_shape *s) {
         // all M rows of its sample (nbb * M * 16 bytes: 4.7 GB at C3), or -- where that exceeds MPC_EV_EXACT_ABOVE_MB
         // (default 6144: 2 % of the 288 GB) -- the buckets are sized EXACTLY by a counting pass over the events
         // (ev_count_device.h), M records per sample in all, at the price of that pass (+11 us per C3 step when forced).
-        const int64_t mpol = (L.P == 2) ? (s->Mp > s->M - s->Mp ? s->Mp : s->M - s->Mp) : s->M;
         L.fcap = (int)(mpol > 0 ? mpol : 1);
         L.bcap = (int)(s->M > 0 ? s->M : 1);                 // records of one bucket, or (b_exact) of one SAMPLE
         static const int64_t exact_above = (getenv("MPC_EV_EXACT_ABOVE_MB") ? atoll(getenv("MPC_EV_EXACT_ABOVE_MB")) : 6144) << 20;

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <atomic>
+#include <initializer_list>
 #include "../../include/mpcmax.h"
 #include "tuning.h"
 
@@ -55,6 +56,19 @@ struct mpc_device_once {
     bool need() const { return !((done.load(std::memory_order_acquire) >> dev()) & 1ull); }
     void mark() { done.fetch_or(1ull << dev(), std::memory_order_release); }
 };
+// Raise the dynamic-LDS cap of `kernels` to `bytes`, once per device (`once`: the caller's static).  0, or the HIP code with the
+// message "<who>: <HIP's text>" -- `once` then stays unmarked and the next call tries again.
+static inline int mpc_raise_lds_cap(mpc_device_once &once, const char *who, int bytes, std::initializer_list<const void *> kernels) {
+    if (!once.need()) return 0;
+    for (const void *fn : kernels) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) { mpc_set_error("%s: %s", who, hipGetErrorString(e)); return (int)e; }
+    }
+    once.mark();
+    return 0;
+}
+// CUs of the current device, cached per device; 256 (an MI355X) where the query fails (api.hip)
+int mpc_cu_count();
 
 static inline int64_t mpc_align(int64_t x, int64_t a = 256) { return (x + a - 1) / a * a; }
 static inline int mpc_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

@@ -26,7 +26,7 @@ static inline EvoWs evo_ws(int B, int NK, int chunks, void *ws) {
 __host__ __device__ static inline size_t evo_count_at(const EvKey &k, int chunks, int b, int pol, int key, int chunk) {
     return ((size_t)(b * 2 + pol) * (k.NK + 1) + key) * chunks + chunk;
 }
-// the two scans of the counting sort over a filled counts array -> offsets [B][2][NK + 1] (events.hip)
+// the two scans of the counting sort over a filled counts array -> offsets [B][2][NK + 1] (ev_order.hip)
 int mpc_evo_scans(const mpc_shape *s, const EvKey &k, const EvoWs &w, int32_t *offsets, hipStream_t st);
 
 #ifdef __HIPCC__

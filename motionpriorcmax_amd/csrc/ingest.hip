@@ -341,10 +341,10 @@ __global__ __launch_bounds__(256) void k_ingest_rect_scatter(const mpc_ingest_sh
 
 // ---- ingest straight into the bucket-ordered layout (both halves in one) -----------------------------
 // The rows of each polarity block ordered by (time bin, LUT strip) -- the key of the loss's backward buckets
-// (events.hip: mpc_event_bucket_order) -- as ingest WRITES them: the key of an event is known the moment its row is
+// (ev_order.hip: mpc_event_bucket_order) -- as ingest WRITES them: the key of an event is known the moment its row is
 // built, so ordering costs no pass over the event tensor of its own (ingest + mpc_event_bucket_order read and wrote the
 // tensor once more: 175 + 50 us at 14 x 200k events).  Counting sort: per-chunk counts of (polarity, key) -> the scans of
-// the bucket-order kernels (events.hip) -> scatter.  Order inside a bucket is not defined and need not be.
+// the bucket-order kernels (ev_order.hip) -> scatter.  Order inside a bucket is not defined and need not be.
 __device__ __forceinline__ int ing_key(const mpc_ingest_shape &s, const EvKey &k, float yv, double tn) {
     return ev_key(k, s.nb, bin_index(tn, s.nb), yv);          // (the row's bin column holds (float)bin_index: the same int)
 }

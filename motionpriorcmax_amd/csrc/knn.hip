@@ -1516,12 +1516,6 @@ static KnnLists knn_lists(const mpc_shape *s, const mpc_ws_layout &L, void *ws) 
     return ls;
 }
 
-static int set_max_lds(const void *fn, const char *who) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    if (e != hipSuccess) { mpc_set_error("%s: %s", who, hipGetErrorString(e)); return (int)e; }
-    return 0;
-}
-
 extern "C" int mpc_knn_lut_fwd(const mpc_shape *s, const float *traj, float *flow_lut, float *flow_next,
                                float *knn_state, int32_t *idx_out, void *ws, void *stream) {
     return mpc_knn_lut_fwd_ex(s, traj, flow_lut, flow_next, knn_state, idx_out, ws, stream, 0, nullptr, nullptr);
@@ -1557,16 +1551,11 @@ int mpc_knn_lut_fwd_ex(const mpc_shape *s, const float *traj, float *flow_lut, f
     // (the first B fallback workgroups of the tail launch finish the count; the count rides in workgroups of the main launch)
     if (s->B > 256 || !strip || !mpc_knn_strip_counts_events(s, &evc)) evc = EvCountArgs{};
     static mpc_device_once attr_once;   // raising the dynamic-LDS cap: idempotent, once per device
-    if (attr_once.need()) {
-        if ((rc = set_max_lds((const void *)k_knn_bucket<true, 8>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bucket<true, 16>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bucket<true, 20>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bucket<true, 24>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_bucket<false, 1>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_query<256>, __func__))) return rc;
-        if ((rc = set_max_lds((const void *)k_knn_query<512>, __func__))) return rc;
-        attr_once.mark();
-    }
+    if ((rc = mpc_raise_lds_cap(attr_once, __func__, 150 * 1024,
+                                {(const void *)k_knn_bucket<true, 8>, (const void *)k_knn_bucket<true, 16>, (const void *)k_knn_bucket<true, 20>,
+                                 (const void *)k_knn_bucket<true, 24>, (const void *)k_knn_bucket<false, 1>, (const void *)k_knn_query<256>,
+                                 (const void *)k_knn_query<512>})))
+        return rc;
     int S; size_t sort_lds;
     bool sat_launch = true;          // (the LDS sort of a whole (sample, bin) builds the summed-area table itself)
     if (knn_sort_plan(s, &S, &sort_lds)) {
@@ -1700,12 +1689,11 @@ int mpc_knn_lut_bwd_ex(const mpc_shape *s, const float *traj, const float *grad_
     const float *tile_dkmax = knn_state + 3 * (size_t)s->B * s->nb * p.G;
     float *reach = (float *)((char *)ws + L.off_knn_reach);
     static mpc_device_once attr_once;   // raising the dynamic-LDS cap: idempotent, once per device
-    if (attr_once.need()) {
-#define KB_SET_LDS(L1_, NEXT_, IWD_) if ((rc = set_max_lds((const void *)k_knn_bwd_tile<L1_, NEXT_, IWD_>, __func__))) return rc
-        KNN_VARIANT_EACH(KB_SET_LDS);
-#undef KB_SET_LDS
-        attr_once.mark();
-    }
+    const void *bt[8];
+#define KB_TILE_FN(L1_, NEXT_, IWD_) bt[KNN_VARIANT_INDEX(L1_, NEXT_, IWD_)] = (const void *)k_knn_bwd_tile<L1_, NEXT_, IWD_>
+    KNN_VARIANT_EACH(KB_TILE_FN);
+#undef KB_TILE_FN
+    if ((rc = mpc_raise_lds_cap(attr_once, __func__, 150 * 1024, {bt[0], bt[1], bt[2], bt[3], bt[4], bt[5], bt[6], bt[7]}))) return rc;
     const int gxb = knn_tiles_x(s->wq, p.m), gyb = knn_tiles_y(s->hq, p.m), ntiles = gxb * gyb;
     if (knn_bwd_is_tile(s)) {
         const int RWm = 16 + 2 * KNN_RQ_MAX;

@@ -27,7 +27,7 @@
 // torch and agrees bit for bit):
 //   BEZIER      u = 1 - t;  tp_1 = t, tp_i = tp_{i-1} * t;  up_0 = 1, up_1 = u, up_i = up_{i-1} * u;  E_i = (C(d, i) * tp_i) * up_{d-i}
 //               (t = 0: every E_i is exactly 0; t = 1: E_d is exactly 1, the others exactly 0 -- the shortcut rows of curves/base.py:102-106)
-//   POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t                                (the lines of pe_phi, events.hip)
+//   POLYNOMIAL  E_1 = t, E_i = E_{i-1} * t                                (the lines of pe_phi, pe_basis.hip)
 //   TABLE       pe_tab_locate / pe_tab_lerp (pe_device.h, with the definition)
 //   BSPLINE     the clamped (open-uniform) cubic B-spline of d + 1 control points (P0 = 0), L = d - 2 spans, d >= 3 (pec_bspline):
 //                 tc = min(max(t, 0), 1);  x = tc * (float)L;  s = min((int)floorf(x), L - 1)
@@ -44,6 +44,7 @@
 //               so phi_j is exactly +0 outside the windows of t_ref and t: k_pec_warp reads the coefficient pairs of the others only
 //               (c * 0 added to a sum that starts at +0 never changes it for finite c: the same bits as the dense sum), the two
 //               gradient kernels add nothing for them (a zero in the integer sums; +-0 in the float atomics).
+#include "ev_device.h"         // load_event
 #include "pe_device.h"
 #include "cvx_device.h"
 
@@ -120,12 +121,6 @@ __device__ __forceinline__ void pec_basis(const PecBasis &pb, float t, float E[P
             if (j < d) E[j] = pe_tab_lerp(r0[j], r1[j], f);
         }
     }
-}
-
-__device__ __forceinline__ void pec_load_row(const float *__restrict__ rows, size_t row, float e[6]) {
-    const float2 *p = reinterpret_cast<const float2 *>(rows + row * 6);
-    const float2 a = p[0], b = p[1], c = p[2];
-    e[0] = a.x; e[1] = a.y; e[2] = b.x; e[3] = b.y; e[4] = c.x; e[5] = c.y;
 }
 
 // ---- head rows ------------------------------------------------------------------------------------------------------------------
@@ -206,7 +201,7 @@ __device__ __forceinline__ void pec_warp_body(const mpc_shape &s, const float *_
     for (size_t row = (size_t)blockIdx.x * 256 + threadIdx.x; row < total; row += (size_t)gridDim.x * 256) {
         const int b = (int)(row / s.M);
         float e[6];
-        pec_load_row(events, row, e);
+        load_event(events, row, e);
         const int cell = pe_own_cell(b, e[0], e[1], s.sp, s.hq, s.wq);
         const float *c = coef + (size_t)cell * 2 * d;
         float E[PEC_DMAX];
@@ -404,7 +399,7 @@ __global__ __launch_bounds__(256) void k_pec_field_adj(const float *__restrict__
 }
 
 // ---- the gradient w.r.t. a tabulated basis (a table that trains: FocusLoss.calc_per_event_curves with basis_table.requires_grad) ----
-// Through the events: pe_table_grad_body / pe_table_finish_one (pe_device.h -- the ONE implementation, events.hip's k_pe_table_grad is
+// Through the events: pe_table_grad_body / pe_table_finish_one (pe_device.h -- the ONE implementation, pe_basis.hip's k_pe_table_grad is
 // its <KB, 8> instantiation; the comment on the fixed-point bounds and on time-sorted batches is there) with 16 orders: `coef` are the
 // tile rows of k_pec_head_rows, the records those of k_pec_warp.  <10>: the shipped curve degree, its loops unrolled; <0>: any other d.
 template <int KB>
@@ -466,19 +461,8 @@ static int pec_orders_per_pass(const mpc_shape *s, const mpc_ws_layout &L, int d
 // spread a strip's adds over more CUs at the price of streaming its rows once more per pass: the smallest count whose workgroups
 // still fit the device in one round (all choices write the same bits: integer sums per element).  Measured at the C4 shape
 // (1 x 500 k events, 7 strips, d = 10): 3 orders per pass (28 workgroups) 179 us, 1 order per pass (70 workgroups) 160 us.
-static int pec_cu_count() {
-    static std::atomic<int> ncu_of[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-    int ncu = ncu_of[dev & 63].load();
-    if (ncu <= 0) {
-        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) { (void)hipGetLastError(); ncu = 256; }
-        ncu_of[dev & 63].store(ncu);
-    }
-    return ncu;
-}
 static int pec_choose_orders(const mpc_shape *s, const mpc_ws_layout &L, int d, int kmax) {
-    const int64_t groups = (int64_t)s->B * L.n_cstrips, ncu = pec_cu_count();
+    const int64_t groups = (int64_t)s->B * L.n_cstrips, ncu = mpc_cu_count();
     for (int kc = 1; kc < kmax; ++kc)
         if (groups * ((d + kc - 1) / kc) <= ncu) return kc;
     return kmax;
@@ -600,13 +584,8 @@ extern "C" int mpc_pec_rows_grad(const mpc_shape *s, const float *rows_warped, c
     const int npass = (d + kc - 1) / kc;
     const size_t lds = (size_t)L.cstrip_rows * s->wq * 2 * kc * 8;
     static mpc_device_once attr_once;
-    if (attr_once.need()) {
-        // (the kernel has 1 KB of static LDS of its own)
-        hipError_t e = hipFuncSetAttribute((const void *)k_pec_accum, hipFuncAttributeMaxDynamicSharedMemorySize, PE_LDS_MAX + 2048);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_pec_accum_bsp, hipFuncAttributeMaxDynamicSharedMemorySize, PE_LDS_MAX + 2048);
-        if (e != hipSuccess) { mpc_set_error("%s: %s", __func__, hipGetErrorString(e)); return (int)e; }
-        attr_once.mark();
-    }
+    // (the kernel has 1 KB of static LDS of its own)
+    if ((rc = mpc_raise_lds_cap(attr_once, __func__, PE_LDS_MAX + 2048, {(const void *)k_pec_accum, (const void *)k_pec_accum_bsp}))) return rc;
     if (basis == MPC_PEC_BSPLINE)
         MPC_LAUNCH(k_pec_accum_bsp, dim3(s->B * L.n_cstrips * npass), dim3(PEC_NT), lds, st, *s, L.cstrip_rows, L.n_cstrips, kc, npass, offsets,
                    rows_warped, reinterpret_cast<const float2 *>(grad_pos), pb, t_ref, scal, grad_out, grad_rows);

@@ -1,9 +1,8 @@
-// The per-event continuous-time warp, the code its three families share (events.hip: the basis tensor / built-in polynomial and the
+// The per-event continuous-time warp, the code its three families share (pe_basis.hip: the basis tensor / built-in polynomial and the
 // tabulated basis; pe_curves.hip: RAFT-spline curves; tiles.hip: the smoothness field of both).  The tests that hold the families
-// to each other bit for bit hold because every line below exists once.
+// to each other bit for bit hold because every line below exists once; the event row they all read is ev_device.h.
 #pragma once
-#include <initializer_list>
-#include "ev_key_device.h"
+#include "ev_device.h"
 #include "bounds.h"
 
 #define PE_KMAX 8              // basis orders the basis families hold in registers (beyond: k_pe_*<0> read phi per use)
@@ -75,7 +74,7 @@ __device__ __forceinline__ float pe_tab_lerp(float a, float a1, float f) {
     return a + f * d;
 }
 
-// ---- the gradient w.r.t. a tabulated basis through the events (events.hip: mpc_pe_table_basis_grad, k <= 8; pe_curves.hip:
+// ---- the gradient w.r.t. a tabulated basis through the events (pe_basis.hip: mpc_pe_table_basis_grad, k <= 8; pe_curves.hip:
 // mpc_pec_table_basis_grad, d <= 16 -- ONE body, instantiated on the largest order count KMAX) ----
 //   pe_table_grad_body : ONE streaming pass over the rows' (t, cell), the stored unscaled (gy, gx) and the tile rows (cache-resident,
 //               cell-coherent in the ordered layout).  G_j = gy c[cell][0][j] + gx c[cell][1][j];  acc[i][j] += (1 - f) G_j,
@@ -171,13 +170,8 @@ static int pe_table_basis_grad_run(const char *who, const mpc_shape *s, int S, i
     if (e0) return e0;
     const int64_t total = (int64_t)s->B * s->M;
     if (total > 0) {
-        if (once.need()) {
-            for (const void *fn : fns) {
-                hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (PE_TABLE_MAX_ENTRIES + KMAX) * 8);
-                if (e != hipSuccess) { mpc_set_error("%s: %s", who, hipGetErrorString(e)); return (int)e; }
-            }
-            once.mark();
-        }
+        const int rc = mpc_raise_lds_cap(once, who, (PE_TABLE_MAX_ENTRIES + KMAX) * 8, fns);          // (the knots and the KMAX sums)
+        if (rc) return rc;
         // (one workgroup per CU and 1024 rows per trip; a batch of more than 256 Ki rows makes further trips)
         const int grid = (int)((total + PE_TAB_NT - 1) / PE_TAB_NT < 256 ? (total + PE_TAB_NT - 1) / PE_TAB_NT : 256);
         launch_grad(grid, (size_t)nall * 8, reinterpret_cast<unsigned long long *>(acc));

@@ -423,7 +423,7 @@ extern "C" int mpc_repr_grid(const mpc_repr_shape *s, const float *x, const floa
     const ReprLayout &L = h.L;
     hipStream_t st = (hipStream_t)stream;
     static mpc_device_once attr_once;
-    rc = sb_raise_lds_cap(attr_once, __func__, k_repr_accum<0>, k_repr_accum<1>, k_repr_accum<2>);
+    rc = mpc_raise_lds_cap(attr_once, __func__, SB_LDS_CAP, {(const void *)k_repr_accum<0>, (const void *)k_repr_accum<1>, (const void *)k_repr_accum<2>});
     if (!rc) rc = sb_zero_counters(L, s->B, st);
     if (rc) return rc;
     if (s->N > 0) {

@@ -128,15 +128,5 @@ static inline int sb_zero_counters(const StripBuckets &L, int B, hipStream_t st)
     return mpc_zero_async(L.gcount, (size_t)(L.NBk + 2 * B + 8) * 4, st);
 }
 
-// the three instantiations of an accumulate kernel may take all of a CU's LDS as dynamic LDS: idempotent, once per device
-template <typename K>
-static inline int sb_raise_lds_cap(mpc_device_once &once, const char *who, K k0, K k1, K k2) {
-    if (!once.need()) return 0;
-    const K ks[3] = {k0, k1, k2};
-    for (K k : ks) {
-        const hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        if (e != hipSuccess) { mpc_set_error("%s: %s", who, hipGetErrorString(e)); return (int)e; }
-    }
-    once.mark();
-    return 0;
-}
+// the three instantiations of an accumulate kernel may take all of a CU's LDS as dynamic LDS (mpc_raise_lds_cap)
+#define SB_LDS_CAP (160 * 1024 - 1024)

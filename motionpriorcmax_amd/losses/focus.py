@@ -131,13 +131,69 @@ class FocusLoss(base.TrajectoryLossBase):
         t_mid = (t_bins[:-1] + t_bins[1:]) / 2
         return torch.concat((t_ref, t_mid), dim=0)
 
+    def _num_pos_events(self, batch, check=True):
+        """batch['num_pos_events'], -1 where the batch has none (polarity_aware_batching needs it)."""
+        num_pos_events = batch['num_pos_events'] if 'num_pos_events' in batch else -1
+        assert not check or not self.polarity_aware_batching or num_pos_events > -1
+        return num_pos_events
+
+    @staticmethod
+    def _t_ref_on(t_ref, dev):
+        """t_ref (scalar tensor / float) as a float32 tensor [1] on `dev`.  No host -> device copy inside the step: a copy from
+        pageable memory waits for the stream, and the host then no longer runs ahead of the device -- round 6: 0.86 ms per step of
+        which 0.36 were kernels.  A float t_ref becomes a fill kernel."""
+        if torch.is_tensor(t_ref):
+            return t_ref.to(device=dev, dtype=torch.float32).reshape(1)
+        return torch.full((1,), float(t_ref), dtype=torch.float32, device=dev)
+
+    def _bin_mid_times_on(self, dev):
+        """The num_bins bin mid-times, kept on every device that asked (no copy inside the step)."""
+        tm = self._tmid_dev.get(dev)
+        if tm is None:
+            from ..utils.synth import bin_mid_times
+            tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
+        return tm
+
+    def _own_cell_focus(self, c_rows, phi, events, t_ref, num_pos_events):
+        """The per-event warp in plain torch around the vote / objective kernels (cross-check of the fused kernels, and the route
+        of a phi that is in the graph): every event moves by the rows [B*G, 2k] of its own LUT cell times phi [B, M, k]
+        -> (focus, iwes)."""
+        sp, (hq, wq) = self.lut_superpixel_size, self._cfg.lut_grid
+        B, M = events.shape[0], events.shape[1]
+        with torch.no_grad():
+            iy = torch.div(events[..., 0], sp, rounding_mode='floor').long().clamp_(0, hq - 1)      # focus.py:186-187
+            ix = torch.div(events[..., 1], sp, rounding_mode='floor').long().clamp_(0, wq - 1)
+            idx = (torch.arange(B, device=events.device).view(-1, 1) * (hq * wq) + iy * wq + ix).reshape(-1)
+        ce = ops.GatherRowsFn.apply(c_rows, idx).view(B, M, 2, phi.shape[-1])
+        warped = events[..., :2] + (ce * phi[:, :, None, :]).sum(-1)                              # [B, M, 2]  (y, x)
+        return ops.PrewarpedFocusFn.apply(warped, events, t_ref, self._cfg, int(num_pos_events))
+
+    def _rows_smoothness(self, c_rows, phim, B, in_graph):
+        """The smoothness term of the field rows x phim (phim [nbm, k]; None: no term).  in_graph: phim carries a gradient (a table
+        that trains) -- BasisFieldFn treats phim as a constant, so the same product in plain torch."""
+        if phim is None:
+            return torch.zeros((), device=c_rows.device)
+        hq, wq = self._cfg.lut_grid
+        if in_graph:
+            nbm, k = phim.shape
+            field = (c_rows.reshape(B * hq * wq * 2, k) @ phim.t()).view(B, hq * wq, 2, nbm).permute(0, 3, 1, 2).reshape(B * nbm, hq, wq, 2)
+        else:
+            field = ops.BasisFieldFn.apply(c_rows, phim, B, hq, wq)                                # [B*nbm, hq, wq, 2]
+        return ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
+
+    def _triple(self, loss, focus, smooth, iwes, B):
+        """What `calc` returns: (loss with grad, {'focus_loss', 'smoothness_loss'} detached, {'iwes': [B, T, 2, H, W] or
+        [B, T, H, W]} detached)."""
+        h, w = self._cfg.image_shape
+        iwes = iwes.reshape(B, self.num_tref, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, self.num_tref, h, w)
+        return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
+
     def order_events(self, batch):
         """Not in the reference (layout half): `batch` with its event rows ordered by (time bin, LUT
         strip) inside each polarity block and the table `event_offsets` added.  `calc` returns the same loss and
         gradient for the ordered batch bit for bit, and with the table skips one record per event in each direction.
         Meant for the data pipeline: once per batch, next to `utils.ingest_events`."""
-        num_pos = batch['num_pos_events'] if 'num_pos_events' in batch else -1
-        ev, offs = ops.event_bucket_order(self._cfg, batch['events'], int(num_pos))
+        ev, offs = ops.event_bucket_order(self._cfg, batch['events'], int(self._num_pos_events(batch, check=False)))
         out = dict(batch)
         out['events'], out['event_offsets'] = ev, offs
         return out
@@ -186,28 +242,19 @@ class FocusLoss(base.TrajectoryLossBase):
                 raise ValueError("basis_table must be a 2-D float32 tensor [samples + 1, num_basis] on the events' device")
             if basis_table.shape[1] != num_basis:
                 raise ValueError(f'basis_table has {basis_table.shape[1]} columns, num_basis is {num_basis}')
-        num_pos_events = batch['num_pos_events'] if 'num_pos_events' in batch else -1
-        assert not self.polarity_aware_batching or num_pos_events > -1
+        num_pos_events = self._num_pos_events(batch)
         dev = events.device
-        h, w = self._cfg.image_shape
         sp = self.lut_superpixel_size
         tile = sp if tile_size is None else int(tile_size)
         if tile != sp:
             raise ValueError('the coefficient tiles must be the look-up-table cells (tile_size == lut_superpixel_size)')
         hq, wq = self._cfg.lut_grid
-        B, M = events.shape[0], events.shape[1]
-        G = hq * wq
+        B = events.shape[0]
         # the coefficients at the tile centres (get_optical_flow_tile_mask + coeffs_grid_to_list, trajectories.py:3-52: offset
         # tile // 2, row-major -- as a strided view, whose backward is a strided copy), scales summed as compute_basis does
         if coeff_grid.dim() != 5 or coeff_grid.shape[2] != 2 * num_basis or -(-coeff_grid.shape[3] // tile) != hq or -(-coeff_grid.shape[4] // tile) != wq:
             raise ValueError(f'coeff_grid {tuple(coeff_grid.shape)} is not [B, scales, {2 * num_basis}, H, W] of this image shape')
-        # (no host -> device copy inside the step: a copy from pageable memory waits for the stream, and the host then no longer runs
-        # ahead of the device -- round 6: 0.86 ms per step of which 0.36 were kernels.  A float t_ref becomes a fill kernel, the bin
-        # mid-times are kept on the device.)
-        if torch.is_tensor(t_ref):
-            t_ref = t_ref.to(device=dev, dtype=torch.float32).reshape(1)
-        else:
-            t_ref = torch.full((1,), float(t_ref), dtype=torch.float32, device=dev)
+        t_ref = self._t_ref_on(t_ref, dev)
         offsets = batch['event_offsets'] if 'event_offsets' in batch else None     # from order_events / ingest (optional)
         # a table: the fused node where the library serves (k, num_bins, table size) -- the kernels read the table --, else the
         # plain-torch chain below with phi from the table INSIDE the graph (autograd carries its gradient to the table)
@@ -224,10 +271,7 @@ class FocusLoss(base.TrajectoryLossBase):
                 phi = basis_values(t_ref, num_basis, basis_type, basis_network) - basis_values(events[..., 2], num_basis, basis_type, basis_network)
         phim = None
         if self.smooth_weight > 0:
-            from ..utils.synth import bin_mid_times
-            tm = self._tmid_dev.get(dev)
-            if tm is None:
-                tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
+            tm = self._bin_mid_times_on(dev)
             if basis_table is not None:
                 bv = table_basis_values(basis_table, torch.cat((t_ref, tm)))       # (one evaluation for t_ref and the mid-times: half the operators)
                 phim = bv[:1] - bv[1:]                                               # [nb, k], in the graph
@@ -237,37 +281,19 @@ class FocusLoss(base.TrajectoryLossBase):
         if tab_fused:
             loss, focus, smooth, iwes = ops.PerEventBasisCalcFn.apply(coeff_grid, events, None, phim, t_ref, self._cfg, int(num_pos_events), offsets,
                                                                       int(num_basis), tile, basis_table)
-            iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
-            return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
+            return self._triple(loss, focus, smooth, iwes, B)
         if fused and num_basis <= 8 and self.num_bins <= 64:
             # one autograd node of library calls (ops.PerEventBasisCalcFn): the step is no longer bound by the host
             loss, focus, smooth, iwes = ops.PerEventBasisCalcFn.apply(coeff_grid, events, phi, phim, t_ref, self._cfg, int(num_pos_events), offsets,
                                                                       int(num_basis), tile)
-            iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
-            return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
+            return self._triple(loss, focus, smooth, iwes, B)
         c_rows = ops.TileCoeffRowsFn.apply(coeff_grid, tile)                                       # [B*G, 2k]: per tile (y: k, x: k)
         if fused:
             focus, iwes = ops.PerEventBasisFocusFn.apply(c_rows, events, phi, t_ref, self._cfg, int(num_pos_events), offsets)
         else:
-            # the same in plain torch around the vote / objective kernels (cross-check of the fused kernels)
-            with torch.no_grad():
-                iy = torch.div(events[..., 0], sp, rounding_mode='floor').long().clamp_(0, hq - 1)      # focus.py:186-187
-                ix = torch.div(events[..., 1], sp, rounding_mode='floor').long().clamp_(0, wq - 1)
-                idx = (torch.arange(B, device=dev).view(-1, 1) * G + iy * wq + ix).reshape(-1)
-            ce = ops.GatherRowsFn.apply(c_rows, idx).view(B, M, 2, num_basis)
-            warped = events[..., :2] + (ce * phi[:, :, None, :]).sum(-1)                              # [B, M, 2]  (y, x)
-            focus, iwes = ops.PrewarpedFocusFn.apply(warped, events, t_ref, self._cfg, int(num_pos_events))
-        smooth = torch.zeros((), device=dev)
-        if phim is not None and basis_table is not None:
-            # (BasisFieldFn treats phim as a constant; a table's phim is in the graph: the same product in plain torch)
-            field = (c_rows.reshape(B * G * 2, num_basis) @ phim.t()).view(B, G, 2, self.num_bins).permute(0, 3, 1, 2).reshape(B * self.num_bins, hq, wq, 2)
-            smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
-        elif phim is not None:
-            field = ops.BasisFieldFn.apply(c_rows, phim, B, hq, wq)                                # [B*nb, hq, wq, 2]
-            smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
-        loss = focus + smooth
-        iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
-        return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
+            focus, iwes = self._own_cell_focus(c_rows, phi, events, t_ref, num_pos_events)
+        smooth = self._rows_smoothness(c_rows, phim, B, in_graph=basis_table is not None)
+        return self._triple(focus + smooth, focus, smooth, iwes, B)
 
     PEC_TILES = (2, 4, 8, 16)
 
@@ -362,16 +388,10 @@ class FocusLoss(base.TrajectoryLossBase):
         events = batch['events']
         if events.shape[0] != params.shape[0]:
             raise ValueError(f'params hold {params.shape[0]} samples, the events {events.shape[0]}')
-        num_pos_events = batch['num_pos_events'] if 'num_pos_events' in batch else -1
-        assert not self.polarity_aware_batching or num_pos_events > -1
+        num_pos_events = self._num_pos_events(batch)
         dev = events.device
-        h, w = self._cfg.image_shape
-        hq, wq = self._cfg.lut_grid
         B = events.shape[0]
-        if torch.is_tensor(t_ref):
-            t_ref = t_ref.to(device=dev, dtype=torch.float32).reshape(1)
-        else:
-            t_ref = torch.full((1,), float(t_ref), dtype=torch.float32, device=dev)
+        t_ref = self._t_ref_on(t_ref, dev)
         offsets = batch['event_offsets'] if 'event_offsets' in batch else None
         if fused and basis_table is not None and basis_table.device != dev:
             fused = False
@@ -384,10 +404,7 @@ class FocusLoss(base.TrajectoryLossBase):
             basis_table = basis_table.to(dev) if trains else basis_table.detach().to(dev)
         phim = None
         if self.smooth_weight > 0:
-            from ..utils.synth import bin_mid_times
-            tm = self._tmid_dev.get(dev)
-            if tm is None:
-                tm = self._tmid_dev[dev] = bin_mid_times(self.num_bins).to(dev)
+            tm = self._bin_mid_times_on(dev)
             if trains:
                 # (in the graph: the lines of curve_event_basis('TABLE'), the same bits)
                 if self.smooth_type == 'on_flow_to_next':
@@ -417,34 +434,19 @@ class FocusLoss(base.TrajectoryLossBase):
         elif trains:
             # plain torch around the vote / objective kernels with phi INSIDE the graph (autograd carries its gradient to the table):
             # the chain of calc_per_event_basis for a table the library does not serve, and the cross-check of the fused node
-            sp, G, M = self.lut_superpixel_size, hq * wq, events.shape[1]
             phi = table_basis_values(basis_table, t_ref) - table_basis_values(basis_table, events[..., 2])
             c_rows = curve_head_rows(params, up_mask, scale, tile)
-            with torch.no_grad():
-                iy = torch.div(events[..., 0], sp, rounding_mode='floor').long().clamp_(0, hq - 1)      # focus.py:186-187
-                ix = torch.div(events[..., 1], sp, rounding_mode='floor').long().clamp_(0, wq - 1)
-                idx = (torch.arange(B, device=dev).view(-1, 1) * G + iy * wq + ix).reshape(-1)
-            ce = ops.GatherRowsFn.apply(c_rows, idx).view(B, M, 2, d)
-            warped = events[..., :2] + (ce * phi[:, :, None, :]).sum(-1)                              # [B, M, 2]  (y, x)
-            focus, iwes = ops.PrewarpedFocusFn.apply(warped, events, t_ref, self._cfg, int(num_pos_events))
-            smooth = torch.zeros((), device=dev)
-            if phim is not None:
-                nbm = phim.shape[0]
-                field = (c_rows.reshape(B * G * 2, d) @ phim.t()).view(B, G, 2, nbm).permute(0, 3, 1, 2).reshape(B * nbm, hq, wq, 2)
-                smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
+            focus, iwes = self._own_cell_focus(c_rows, phi, events, t_ref, num_pos_events)
+            smooth = self._rows_smoothness(c_rows, phim, B, in_graph=True)
             loss = focus + smooth
         else:
             with torch.no_grad():
                 phi = curve_event_basis(t_ref, d, curve_type, basis_table) - curve_event_basis(events[..., 2], d, curve_type, basis_table)
             c_rows = curve_head_rows(params, up_mask, scale, tile)
             focus, iwes = ops.PerEventBasisFocusFn.apply(c_rows, events, phi, t_ref, self._cfg, int(num_pos_events), offsets)
-            smooth = torch.zeros((), device=dev)
-            if phim is not None:
-                field = ops.BasisFieldFn.apply(c_rows, phim, B, hq, wq)
-                smooth = ops.LutSmoothFn.apply(field, self._cfg, float(self.smooth_weight))
+            smooth = self._rows_smoothness(c_rows, phim, B, in_graph=False)
             loss = focus + smooth
-        iwes = iwes.reshape(B, 1, 2, h, w) if self.polarity_aware_batching else iwes.reshape(B, 1, h, w)
-        return loss, {'focus_loss': focus.detach(), 'smoothness_loss': smooth.detach()}, {'iwes': iwes.detach()}
+        return self._triple(loss, focus, smooth, iwes, B)
 
     AUTO_STATIC_MAX_EVENTS = 150_000     # B * M up to which the captured plan wins (C2: 0.16 against 0.20 ms; C4, 500k events: it loses)
     AUTO_STATIC_AFTER = 3                 # consecutive calcs of one shape before it is captured
@@ -479,8 +481,7 @@ class FocusLoss(base.TrajectoryLossBase):
         Returns (loss with grad, {'focus_loss', 'smoothness_loss'} detached,
                  {'iwes': [B, T, 2, H, W] or [B, T, H, W]} detached)."""
         events = batch['events']
-        num_pos_events = batch['num_pos_events'] if 'num_pos_events' in batch else -1
-        assert not self.polarity_aware_batching or num_pos_events > -1
+        num_pos_events = self._num_pos_events(batch)
 
         t_ref = times[:self.num_tref]
         offsets = batch['event_offsets'] if 'event_offsets' in batch else None     # from order_events (optional)
@@ -504,20 +505,4 @@ class FocusLoss(base.TrajectoryLossBase):
                 out = ops.FocusCalcFn.apply(trajectories, events, t_ref, self._cfg, int(num_pos_events), offsets)
         else:
             out = ops.FocusCalcFn.apply(trajectories, events, t_ref, self._cfg, int(num_pos_events), offsets)
-        loss, focus_loss, smooth_loss, iwes = out
-
-        h, w = self._cfg.image_shape
-        b = events.shape[0]
-        if self.polarity_aware_batching:
-            iwes = iwes.reshape(b, self.num_tref, 2, h, w)
-        else:
-            iwes = iwes.reshape(b, self.num_tref, h, w)
-
-        log_metadata = {
-            'focus_loss': focus_loss.detach(),
-            'smoothness_loss': smooth_loss.detach(),
-        }
-        misc_metadata = {
-            'iwes': iwes.detach()
-        }
-        return loss, log_metadata, misc_metadata
+        return self._triple(*out, events.shape[0])

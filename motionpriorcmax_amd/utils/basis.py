@@ -45,7 +45,7 @@ def basis_values(times, num_basis, basis_type, basis_network=None):
 def table_basis_values(table, times):
     """A TABULATED basis at arbitrary times: table [S + 1, k] holds samples of the k basis functions at the knots i / S, times [...]
     -> [..., k], interpolated linearly.  This is the definition of FocusLoss.calc_per_event_basis(basis_type='table') and the lines
-    are those of the kernels (csrc/events.hip: pe_tab_locate / pe_tab_basis), one operation each, so that the fp32 result agrees
+    are those of the kernels (csrc/pe_device.h: pe_tab_locate; csrc/pe_basis.hip: pe_tab_basis), one operation each, so that the fp32 result agrees
     with them bit for bit: times outside [0, 1] are clamped, t == 1 lies in the last interval with f == 1.  Plain torch, any floating
     dtype (the promotion of the two arguments'), differentiable w.r.t. `table`."""
     if table.dim() != 2 or table.shape[0] < 2:
@@ -95,7 +95,7 @@ def curve_event_basis(times, d, curve_type, basis_table=None):
                     E_i = (C(d, i) * tp_i) * up_{d-i}, i = 1..d (P0 = 0: reference curves/bezier.py:92-113).  At t = 0 every E_i is
                     exactly 0; at t = 1, E_d is exactly 1 and the others exactly 0 (the shortcut rows of curves/base.py:102-106).
                     The binomials are exact fp32 constants up to d = 26 (the kernels serve d <= 16).
-      'POLYNOMIAL'  E_1 = t, E_i = E_{i-1} * t (the lines of pe_phi, csrc/events.hip; curves/polynomial.py:55-58 up to the rounding
+      'POLYNOMIAL'  E_1 = t, E_i = E_{i-1} * t (the lines of pe_phi, csrc/pe_basis.hip; curves/polynomial.py:55-58 up to the rounding
                     of pow)
       'TABLE'       `table_basis_values(basis_table, t)`: basis_table [S + 1, d] sampled at the knots i / S, interpolated linearly
                     (a frozen learned basis, say; the cubic B-spline has a kind of its own)

@@ -1,5 +1,5 @@
-"""Named cases of the event kernels (csrc/events.hip: k_ev_bin -> k_iwe_accum forward, k_lut_accum backward in its record and
-ordered variants, the global-atomic kernels k_splat_fwd_atomic / k_splat_bwd_atomic), their float64 reference, and the rule by which
+"""Named cases of the event kernels (csrc/events.hip over csrc/ev_device.h: k_ev_bin -> k_iwe_accum forward, k_lut_accum backward in its
+record and ordered variants, the global-atomic kernels k_splat_fwd_atomic / k_splat_bwd_atomic), their float64 reference, and the rule by which
 every output element is compared with it.  A helper module (no fixtures): tests/test_event_cases_host.py checks the cases, the
 reference and the comparator on the CPU (a float32 stand-in passes, nine mutants of it fail), tests/test_gpu_event_cases.py runs
 the cases on the device.
@@ -7,25 +7,26 @@ the cases on the device.
 The reference restates oracle.focus_oracle.warp_events / event_weights / bilinear_vote (reference focus.py:182-230,
 event_image_converter.py:333-391) and their adjoint with respect to the LUT; it never calls the library.  DISCRETE DECISIONS are taken
 in float32 exactly as the kernel takes them (`decisions`): the LUT cell it = int(bin), iy = floor(y / sp), ix = floor(x / sp) clamped
-to the table (the documented deviation, events.hip:42-45; the division is mpc_div_sp, common.h:136-138: a multiplication by the exact
-reciprocal for a power of two, an IEEE division otherwise), pos = fl32(lut + event) [56-57], dt = clamp(|t - t_ref|, 0, 1) and the
-weight (1 - dt) * valid [61-62], the four strict border comparisons [66], floor(fl32(pos + 1e-6f)) [70], weight == 0 votes for nothing
-[76], polarity block by row index < num_pos [110, 332].  VALUES are float64 of those float32 inputs: fy = y - y0, the four tap products,
-the weight, the position gradients gy = w ((1 - fx)(g10 - g00) + fx (g11 - g01)) and gx likewise, their sum per LUT cell, and
+to the table (the documented deviation, ev_device.h:31-34; the division is mpc_div_sp, common.h:150-152: a multiplication by the exact
+reciprocal for a power of two, an IEEE division otherwise), pos = fl32(lut + event) [43-44], dt = clamp(|t - t_ref|, 0, 1) and the
+weight (1 - dt) * valid [48-49], the four strict border comparisons [53], floor(fl32(pos + 1e-6f)) [57], weight == 0 votes for nothing
+[63], polarity block by row index < num_pos [events.hip:29, 253].  VALUES are float64 of those float32 inputs: fy = y - y0, the four tap
+products, the weight, the position gradients gy = w ((1 - fx)(g10 - g00) + fx (g11 - g01)) and gx likewise, their sum per LUT cell, and
 grad_out * (GCOEF * sum + add_term).
 
 Every bound is a running error bound: gamma(k) = k u / (1 - k u), u = 2^-24, k = the fp32 roundings on the longest path of the kernel
 to that value, applied to the absolute values.  The library is built with -ffp-contract=off (a contracted multiply-add rounds once
-instead of twice, so contraction could only lower the counts).  The counts (lines of csrc/events.hip):
+instead of twice, so contraction could only lower the counts).  The counts (lines of csrc/ev_device.h, or of
+csrc/events.hip where it is named):
 
-  N_TAP  9  a tap (1 - fy) (1 - fx) w: e[2] - t_ref (1) [61], 1 - dt (1), * valid (1) [62], fy = y - y0f (1) [71], 1 - fy (1), fx (1)
-            [72], 1 - fx (1), the two products (2) [417-420; 116-119].  (A first count of 8 had left out fx.)
+  N_TAP  9  a tap (1 - fy) (1 - fx) w: e[2] - t_ref (1) [48], 1 - dt (1), * valid (1) [49], fy = y - y0f (1) [58], 1 - fy (1), fx (1)
+            [59], 1 - fx (1), the two products (2) [events.hip:337-340; 35-38].  (A first count of 8 had left out fx.)
   N_G    9  gy = w ((1 - fx)(g10 - g00) + fx (g11 - g01)): the weight's 3, fx (1), 1 - fx (1), g10 - g00 (1), the product (1), the
-            addition (1), * w (1) [499-500; 140-141]; gx the same through fy
-  N_OUT  3  a cell of d/dLUT beyond its sum: the cast of the sum in mpc_from_fixed (1) [common.h:201-203], coef = GCOEF * grad_out (1)
-            [647], coef * sum (1) [650]; with add_term two more, grad_out * add (1) and the addition (1) [651]
-  N_AT   2  a contribution of k_splat_bwd_atomic beyond gy: coef (1) [153], coef * gy (1) [167]; the initial value grad_out * add_term
-            (mpc_scale, one rounding) counts as one more contribution
+            addition (1), * w (1) [events.hip:419-420; 93-94]; gx the same through fy
+  N_OUT  3  a cell of d/dLUT beyond its sum: the cast of the sum in mpc_from_fixed (1) [common.h:253-255], coef = GCOEF * grad_out (1)
+            [events.hip:567], coef * sum (1) [570]; with add_term two more, grad_out * add (1) and the addition (1) [571]
+  N_AT   2  a contribution of k_splat_bwd_atomic beyond gy: coef (1) [events.hip:58], coef * gy (1) [72]; the initial value grad_out *
+            add_term (mpc_scale, one rounding) counts as one more contribution
 
   One rounding is NOT relative to the value it ends in: dt = |t - t_ref| is rounded relative to dt, and 1 - dt cancels, so the weight
   carries the ABSOLUTE error u dt |valid| whatever is left of it (a weight of 1e-6 from dt = 1 - 1e-6 may be off by 6 %).  Every tap
@@ -34,7 +35,7 @@ instead of twice, so contraction could only lower the counts).  The counts (line
   the image but y in (-0.5, 0), where fy >= 0.5 and the factor 1 - fy only meets taps outside the image).
 
   forward pixel     sum over taps (gamma(N_TAP) |tap64| + E_DT + 2^-30 [tap != 0]) + u |sum|: 2^-30 is the truncation of one
-                    conversion (ev_to_fixed_small [238-240], mpc_to_fixed [common.h:197-200]: both are the exact truncation of
+                    conversion (ev_to_fixed_small [events.hip:159-161], mpc_to_fixed [common.h:249-252]: both are the exact truncation of
                     tap * 2^30), u |sum| the cast in mpc_from_fixed.  mpc_event_splat_fwd_fixed: the same without the cast.
   backward cell     |coef| sum over events (gamma(N_G) |w| A + E_DT + 2^-30 [A > 0]), A = |1 - fx| (|g10| + |g00|) + |fx| (|g11| +
                     |g01|), then gamma(N_OUT) of the product and u each for grad_out * add_term and the addition.  mpc_to_fixed's
@@ -95,7 +96,7 @@ class Case:
         return c
 
 
-# ---- discrete decisions, float32 (events.hip: warp_cell, warp_event_with) ----------------------------------------------------------
+# ---- discrete decisions, float32 (ev_device.h: warp_cell, warp_event_with) ----------------------------------------------------------
 def div_sp(v, sp):
     return v * f32(1.0 / sp) if (sp & (sp - 1)) == 0 else v / f32(sp)
 
@@ -147,7 +148,7 @@ def decisions(c, no_warp=False, unit_weight=False, mutant=None):
         i = np.arange(M)[None, :, None]
         pol = ((i > c.num_pos) if mutant == 'pol_gt' else (i >= c.num_pos)) if c.split else np.zeros_like(i, dtype=bool)
         pol = np.broadcast_to(pol, sh).astype(np.int64)
-        # a position whose taps can reach the image (the kernel clamps the floor to [-4, H + 4] before the int conversion [74-75])
+        # a position whose taps can reach the image (the kernel clamps the floor to [-4, H + 4] before the int conversion [ev_device.h:61-62])
         near = (y0f >= -1) & (y0f <= H - 1) & (x0f >= -1) & (x0f <= W - 1)
     img = (np.arange(B)[:, None, None] * T + np.arange(T)[None, None, :]) * c.P + pol
     return dict(y=y, x=x, w=w, y0f=y0f, x0f=x0f, live=(w != 0), near=near, pol=pol, img=img, w64=w64, e_dt=e_dt,

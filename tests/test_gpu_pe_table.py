@@ -1,5 +1,5 @@
 """FocusLoss.calc_per_event_basis(basis_type='table') on the GPU: the kernels that read a tabulated motion basis and reduce the
-batch's gradient onto its entries (csrc/events.hip: the TAB instantiations of k_pe_warp / k_pe_grad / k_pe_accum, k_pe_table_grad;
+batch's gradient onto its entries (csrc/pe_basis.hip: the TAB instantiations of k_pe_warp / k_pe_grad / k_pe_accum, k_pe_table_grad;
 csrc/tiles.hip: k_field_basis_grad_*) against the DEFINITION in tests/pe_table_cases.py (the oracle's per-event path with the
 table formula), fp32 and float64.  The rules are those of `_against_oracle` in tests/test_gpu_per_event.py, restated here."""
 import itertools

@@ -43,7 +43,7 @@ def test_bezier_mirror_against_float64_bernstein(d):
 
 
 def test_polynomial_and_table_mirrors():
-    """The POLYNOMIAL mirror is the lines of pe_phi (csrc/events.hip), bit for bit: that is what makes the curve kernels equal
+    """The POLYNOMIAL mirror is the lines of pe_phi (csrc/pe_basis.hip), bit for bit: that is what makes the curve kernels equal
     calc_per_event_basis(basis_type='polynomial') and the fused=False route bitwise.  Against `basis_values(..., 'polynomial')`,
     which raises t to the power j in one call, it is bit-equal for j = 1 only: an iterated product rounds j - 1 times and pow is
     not correctly rounded either (the figures are printed: a few units of 2^-24 on a minority of the times) -- so the higher

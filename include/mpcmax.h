@@ -250,6 +250,14 @@ int32_t mpc_pe_grad_ordered_supported(const mpc_shape *s, int32_t k);
  *                         mpc_pe_grad) + grad_out[0] * (adjoint of mpc_pe_basis_field applied to grad_field, or nothing if NULL)  */
 int mpc_pe_tile_rows(const float *grid, float *coef_rows, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream);
 int mpc_pe_tile_rows_bwd(const float *grad_rows, float *grad_grid, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream);
+/* The same two calls on a coefficient grid in the network's own precision (see "element types of the network tensors" below):
+ * grid / grad_grid [B][S][c2][H][W] of element type `dtype`; coef_rows and grad_rows stay fp32.  mpc_pe_tile_rows IS
+ * mpc_pe_tile_rows_dt(MPC_DT_F32).  The 16-bit gradient is written with 16-byte stores of 8 elements where W is a multiple of 8 and
+ * the row start is 16-byte aligned, element by element otherwise. */
+int mpc_pe_tile_rows_dt(const void *grid, int32_t dtype, float *coef_rows, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile,
+                        void *stream);
+int mpc_pe_tile_rows_bwd_dt(const float *grad_rows, void *grad_grid, int32_t dtype, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W,
+                            int32_t tile, void *stream);
 int mpc_pe_basis_field(const float *coef_rows, const float *phim, float *field, int32_t B, int32_t G, int32_t k, int32_t nb, void *stream);
 int mpc_pe_rows_grad_finish(const float *grad_parts, int32_t split, const float *grad_field, const float *phim, const float *grad_out,
                             float *grad_coef_rows, int32_t B, int32_t G, int32_t k, int32_t nb, void *stream);
@@ -355,6 +363,13 @@ int32_t mpc_pec_supported(const mpc_shape *s, int32_t d, int32_t basis, int32_t 
 int mpc_pec_head_rows(const float *params, const float *mask, float scale, int32_t tile, float *rows,
                       int32_t B, int32_t d, int32_t h, int32_t w, void *stream);
 int64_t mpc_pec_head_rows_bwd_workspace_bytes(int32_t B, int32_t d, int32_t h, int32_t w, int32_t tile);
+/* The two head calls on a mask in the network's own precision: mask / grad_mask [B][576][h][w] of element type `dtype` (ignored where
+ * mask is NULL, but still checked); params, rows and their gradients stay fp32, the workspace is the same.  mpc_pec_head_rows(_bwd) ARE
+ * these with MPC_DT_F32; the backward forwards to mpc_cvx_traj_bwd_dt. */
+int mpc_pec_head_rows_dt(const float *params, const void *mask, int32_t dtype, float scale, int32_t tile, float *rows,
+                         int32_t B, int32_t d, int32_t h, int32_t w, void *stream);
+int mpc_pec_head_rows_bwd_dt(const float *grad_rows, const float *params, const void *mask, int32_t dtype, float scale, int32_t tile,
+                             float *grad_params, void *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream);
 int mpc_pec_head_rows_bwd(const float *grad_rows, const float *params, const float *mask, float scale, int32_t tile,
                           float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream);
 int mpc_pec_warp(const mpc_shape *s, const float *events, const float *rows, int32_t basis, int32_t d, const float *table, int32_t S,
@@ -629,6 +644,31 @@ int mpc_cvx_traj_bwd(const float *grad_traj, const float *params, const float *m
 int mpc_cvx_flow_fwd(const float *params, const float *mask, const float *basis, float scale, float *flows,
                      int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream);
 
+/* ---- element types of the network tensors (additive: the version number is unchanged, the binding checks the symbols by name).
+ * The networks in front of these nodes run under autocast or as .half() / .bfloat16() models, so their two large outputs -- the
+ * coefficient grid and the convex-upsampling mask -- arrive in 16 bits.  Every `_dt` entry point is the call of the same name with
+ * `void *` for that tensor and for its gradient plus the element type; EVERYTHING else in the signature stays fp32 (traj, rows, basis,
+ * dphi, params / grad_params, grad_traj, grad_dphi, workspaces), and the workspace-size queries are those of the fp32 calls.
+ *   load    fp16 by the hardware convert, bf16 as bits << 16: exact, and the arithmetic behind the load is that of the fp32 kernels --
+ *           every forward output equals, bit for bit, what the fp32 call returns for the upcast tensor
+ *   store   each gradient element is computed in fp32 exactly as in the fp32 call and rounded ONCE to `dtype`, round to nearest even:
+ *           bf16 by  NaN -> 0x7FC0, else u += 0x7FFF + ((u >> 16) & 1), u >>= 16  (the bits of torch.Tensor.to(torch.bfloat16)); fp16 by
+ *           the hardware convert (overflow to +-inf, subnormals kept).  Elements off the tile centres are +0.
+ * The fp32 entry points ARE the `_dt` ones with MPC_DT_F32: one copy of the host code, the same kernels and bits as before.  Any other
+ * dtype code: MPC_E_UNSUPPORTED with an error string, no launch. */
+#define MPC_DT_F32 0
+#define MPC_DT_F16 1
+#define MPC_DT_BF16 2
+int mpc_cvx_traj_fwd_dt(const float *params, const void *mask, int32_t dtype, const float *basis, float scale, float *traj,
+                        int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile, void *stream);
+int mpc_cvx_flow_fwd_dt(const float *params, const void *mask, int32_t dtype, const float *basis, float scale, float *flows,
+                        int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream);
+/* grad_mask in `dtype`: the zero fill keeps its plane / chunk walk (1024 elements a chunk), 16-byte stores of 8 elements where the
+ * ADDRESS of the 8 is 16-byte aligned (a plane of odd h * w starts at any even address), element by element otherwise. */
+int mpc_cvx_traj_bwd_dt(const float *grad_traj, const float *params, const void *mask, int32_t dtype, const float *basis, float scale,
+                        float *grad_params, void *grad_mask, int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile,
+                        void *ws, void *stream);
+
 /* ---- row A3 of SURVEY.md 8(a): the network's coefficient grid -> `trajectories` for the loss, and back.
  * Reference: src/modules/trajectory_net.py:57-119 (compute_basis, calculate_coords, calculate_trajectories_at_t: the reference's
  * TrajectoryNet.step, :142-161), src/utils/trajectories.py:3-52 (tile mask, coeffs_grid_to_list), src/utils/basis.py:4-46.
@@ -656,6 +696,15 @@ int mpc_grid_traj_fwd(const float *grid, const float *times, const float *dphi, 
 int mpc_grid_traj_bwd(const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time, const float *rows,
                       float *grad_grid, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W,
                       int32_t tile, int32_t n_t, void *stream);
+/* The same two calls on a grid of element type `dtype` (MPC_DT_*, above): grid / grad_grid [B][S][2k][H][W]; traj, rows, dphi and
+ * grad_dphi stay fp32.  The 16-bit gradient is written with 16-byte stores of 8 elements where W is a multiple of 8 and grad_grid is
+ * 16-byte aligned, element by element otherwise. */
+int mpc_grid_traj_fwd_dt(const void *grid, int32_t dtype, const float *times, const float *dphi, int32_t basis, float anchor_time,
+                         int32_t add_offsets, float *traj, float *rows, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W, int32_t tile,
+                         int32_t n_t, void *stream);
+int mpc_grid_traj_bwd_dt(const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time, const float *rows,
+                         void *grad_grid, int32_t dtype, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k, int32_t H,
+                         int32_t W, int32_t tile, int32_t n_t, void *stream);
 
 /* ---- the RAFT-spline validation step's flow metrics (what scripts/trajectory_inference.py logs) as one fused reduction.
  * Reference: src/modules/raft_spline.py:88-215 (validation_step: which metric sees which prediction and mask), src/modules/utils.py

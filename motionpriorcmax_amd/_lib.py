@@ -25,6 +25,7 @@ F_NO_BWD_RECORDS = 1 << 11
 
 E_NULL, E_SHAPE, E_UNSUPPORTED = -1, -2, -4        # include/mpcmax.h
 BASIS_POLY, BASIS_DCT, BASIS_MATRIX = 0, 1, 2
+DT_F32, DT_F16, DT_BF16 = 0, 1, 2                   # include/mpcmax.h: MPC_DT_*, the element type of a `_dt` entry point's network tensor
 SCAL_LOSS, SCAL_FOCUS, SCAL_SMOOTH, SCAL_VAL, SCAL_GCOEF, SCAL_COUNT = 0, 1, 2, 3, 4, 8
 
 class Shape(ctypes.Structure):
@@ -143,6 +144,8 @@ SIGNATURES = {
     'mpc_pe_grad_ordered_supported': (i32, [sp, i32]),
     'mpc_pe_tile_rows': (cint, [vp, vp] + [i32] * 6 + [vp]),
     'mpc_pe_tile_rows_bwd': (cint, [vp, vp] + [i32] * 6 + [vp]),
+    'mpc_pe_tile_rows_dt': (cint, [vp, i32, vp] + [i32] * 6 + [vp]),
+    'mpc_pe_tile_rows_bwd_dt': (cint, [vp, vp, i32] + [i32] * 6 + [vp]),
     'mpc_pe_basis_field': (cint, [vp, vp, vp] + [i32] * 4 + [vp]),
     'mpc_pe_rows_grad_finish': (cint, [vp, i32, vp, vp, vp, vp] + [i32] * 4 + [vp]),
     'mpc_pe_table_supported': (i32, [sp, i32, i32]),
@@ -156,6 +159,8 @@ SIGNATURES = {
     'mpc_pec_head_rows': (cint, [vp, vp, f32, i32, vp] + [i32] * 4 + [vp]),
     'mpc_pec_head_rows_bwd_workspace_bytes': (i64, [i32] * 5),
     'mpc_pec_head_rows_bwd': (cint, [vp, vp, vp, f32, i32, vp, vp] + [i32] * 4 + [vp, vp]),
+    'mpc_pec_head_rows_dt': (cint, [vp, vp, i32, f32, i32, vp] + [i32] * 4 + [vp]),
+    'mpc_pec_head_rows_bwd_dt': (cint, [vp, vp, vp, i32, f32, i32, vp, vp] + [i32] * 4 + [vp, vp]),
     'mpc_pec_warp': (cint, [sp, vp, vp, i32, i32, vp, i32, vp, vp, vp]),
     'mpc_pec_rows_grad': (cint, [sp, vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i32, vp, vp]),
     'mpc_pec_rows_grad_passes': (i32, [sp, i32, i32]),
@@ -199,9 +204,14 @@ SIGNATURES = {
     'mpc_cvx_traj_bwd_workspace_bytes': (i64, [i32] * 6),
     'mpc_cvx_traj_bwd': (cint, [vp, vp, vp, vp, f32, vp, vp] + [i32] * 6 + [vp, vp]),
     'mpc_cvx_flow_fwd': (cint, [vp, vp, vp, f32, vp] + [i32] * 5 + [vp]),
+    'mpc_cvx_traj_fwd_dt': (cint, [vp, vp, i32, vp, f32, vp] + [i32] * 6 + [vp]),
+    'mpc_cvx_flow_fwd_dt': (cint, [vp, vp, i32, vp, f32, vp] + [i32] * 5 + [vp]),
+    'mpc_cvx_traj_bwd_dt': (cint, [vp, vp, vp, i32, vp, f32, vp, vp] + [i32] * 6 + [vp, vp]),
     'mpc_grid_traj_scratch_floats': (i64, [i32] * 6),
     'mpc_grid_traj_fwd': (cint, [vp, vp, vp, i32, f32, i32, vp, vp] + [i32] * 7 + [vp]),
     'mpc_grid_traj_bwd': (cint, [vp, vp, vp, i32, f32, vp, vp, vp, vp] + [i32] * 7 + [vp]),
+    'mpc_grid_traj_fwd_dt': (cint, [vp, i32, vp, vp, i32, f32, i32, vp, vp] + [i32] * 7 + [vp]),
+    'mpc_grid_traj_bwd_dt': (cint, [vp, vp, vp, i32, f32, vp, vp, i32, vp, vp] + [i32] * 7 + [vp]),
     'mpc_val_metrics_workspace_bytes': (i64, [vlp]),
     'mpc_val_metrics': (cint, [vlp, vp, vp, vp, vp, f32] + [vp] * 9),
     'mpc_corr_lookup_supported': (cint, [cdp]),

@@ -33,6 +33,23 @@ int mpc_zero_async(void *ptr, size_t bytes, hipStream_t stream);
         }                                                                \
     } while (0)
 
+// The same two for host code shared by several entry points (a template over the element type): `who` is the entry point's name
+#define MPC_CHECK_ARG_WHO(who, cond, code, msg)                          \
+    do {                                                                 \
+        if (!(cond)) {                                                   \
+            mpc_set_error("%s: %s", who, msg);                           \
+            return (code);                                               \
+        }                                                                \
+    } while (0)
+#define MPC_CHECK_LAUNCH_WHO(who)                                        \
+    do {                                                                 \
+        hipError_t e__ = hipGetLastError();                              \
+        if (e__ != hipSuccess) {                                         \
+            mpc_set_error("%s: %s", who, hipGetErrorString(e__));        \
+            return (int)e__;                                             \
+        }                                                                \
+    } while (0)
+
 // Every kernel launch of the library goes through MPC_LAUNCH: the launch itself, and -- only while the diagnostics timer of
 // mpc_profile_start() / mpc_profile_stop() is on (bench.py's instrumented pass; never inside a graph capture) -- a HIP event
 // before and after it ON THE LAUNCH STREAM, so that the duration of every kernel is measured live, per launch.

@@ -25,8 +25,8 @@
 
 #define CVX_FILL_ELEMS 1024    // elements of one mask plane a zero-fill workgroup covers (256 threads x 4)
 
-template <int D>
-__global__ __launch_bounds__(256) void k_cvx_traj_fwd(const float *__restrict__ params, const float *__restrict__ mask,
+template <int D, typename M>
+__global__ __launch_bounds__(256) void k_cvx_traj_fwd(const float *__restrict__ params, const M *__restrict__ mask,
                                                       const float *__restrict__ basis, float scale, float *__restrict__ traj,
                                                       int B, int d, int T, int h, int w, int tile, int ntx, int n) {
     extern __shared__ float s_basis[];          // [T][d]
@@ -53,8 +53,8 @@ __global__ __launch_bounds__(256) void k_cvx_traj_fwd(const float *__restrict__ 
 }
 
 // flows [T][B][2][8h][8w], (x, y) order: one thread per pixel, every store coalesced over x
-template <int D>
-__global__ __launch_bounds__(256) void k_cvx_flow_fwd(const float *__restrict__ params, const float *__restrict__ mask,
+template <int D, typename M>
+__global__ __launch_bounds__(256) void k_cvx_flow_fwd(const float *__restrict__ params, const M *__restrict__ mask,
                                                       const float *__restrict__ basis, float scale, float *__restrict__ flows,
                                                       int B, int d, int T, int h, int w) {
     extern __shared__ float s_basis[];
@@ -87,10 +87,10 @@ __device__ __forceinline__ bool cvx_is_centre(int v, int tile) {
     return v >= s && (v - s) % tile == 0;
 }
 
-template <int D>
+template <int D, typename M>
 __global__ __launch_bounds__(256) void k_cvx_bwd_centres(const float *__restrict__ grad_traj, const float *__restrict__ params,
-                                                         const float *__restrict__ mask, const float *__restrict__ basis, float scale,
-                                                         float *__restrict__ grad_mask, float *__restrict__ ws_dflow,
+                                                         const M *__restrict__ mask, const float *__restrict__ basis, float scale,
+                                                         M *__restrict__ grad_mask, float *__restrict__ ws_dflow,
                                                          float *__restrict__ ws_w, int B, int d, int T, int h, int w, int tile,
                                                          int ntx, int n, int nA, int fill_chunks) {
     extern __shared__ float s_basis[];
@@ -103,11 +103,14 @@ __global__ __launch_bounds__(256) void k_cvx_bwd_centres(const float *__restrict
         const bool uni = (8 % tile) == 0;         // then every cell of a plane holds a centre at (sy, sx), or none does
         const bool plane_centre = cvx_is_centre(sy, tile) && cvx_is_centre(sx, tile);
         if (uni && plane_centre) return;
-        float *gp = grad_mask + (size_t)pl * plane;
-        const size_t e0 = (size_t)chunk * CVX_FILL_ELEMS + threadIdx.x * 4;
-        bool z[4], all = e0 + 3 < plane;
+        M *gp = grad_mask + (size_t)pl * plane;
+        // a thread covers V elements = one 16-byte store: 4 fp32 (256 threads a chunk) or 8 fp16 / bf16 (the first 128 threads)
+        constexpr int V = MPC_VEC(M);
+        if ((int)threadIdx.x * V >= CVX_FILL_ELEMS) return;
+        const size_t e0 = (size_t)chunk * CVX_FILL_ELEMS + threadIdx.x * V;
+        bool z[V], all = e0 + (V - 1) < plane;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < V; ++q) {
             const size_t e = e0 + q;
             z[q] = false;
             if (e < plane) {
@@ -117,11 +120,15 @@ __global__ __launch_bounds__(256) void k_cvx_bwd_centres(const float *__restrict
             }
             all = all && z[q];
         }
+        // (the test is on the ADDRESS: the planes of an odd h * w start at every multiple of 4 bytes, or of 2 with a 16-bit mask)
         if (all && (((uintptr_t)(gp + e0)) & 15) == 0) {
-            *reinterpret_cast<float4 *>(gp + e0) = make_float4(0.f, 0.f, 0.f, 0.f);
+            float zero[V];
+#pragma unroll
+            for (int q = 0; q < V; ++q) zero[q] = 0.f;
+            mpc_store_vec(gp + e0, zero);
         } else {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) if (z[q]) gp[e0 + q] = 0.f;
+            for (int q = 0; q < V; ++q) if (z[q]) mpc_st(gp + e0 + q, 0.f);
         }
         return;
     }
@@ -176,9 +183,9 @@ __global__ __launch_bounds__(256) void k_cvx_bwd_centres(const float *__restrict
         g9[k] = a;
         dot = dot + wk[k] * a;
     }
-    float *gm = grad_mask + ((size_t)b * 576 + sy * 8 + sx) * plane + (size_t)cy * w + cx;
+    M *gm = grad_mask + ((size_t)b * 576 + sy * 8 + sx) * plane + (size_t)cy * w + cx;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) gm[(size_t)k * 64 * plane] = wk[k] * (g9[k] - dot);
+    for (int k = 0; k < 9; ++k) mpc_st(gm + (size_t)k * 64 * plane, wk[k] * (g9[k] - dot));      // (one rounding to the mask's type)
 }
 
 // grad_params: one thread per (cell, channel, sample) = (x chunk of 256 cells, blockIdx.y, blockIdx.z)
@@ -219,41 +226,44 @@ static int cvx_check(const char *who, int B, int d, int T, int h, int w, int til
     return 0;
 }
 
-#define CVX_DISPATCH(kern, grid, lds, st, ...)                                                              \
+#define CVX_DISPATCH(kern, M, grid, lds, st, ...)                                                           \
     do {                                                                                                    \
-        if (d <= 4) MPC_LAUNCH(kern<4>, grid, dim3(256), lds, st, __VA_ARGS__);                             \
-        else if (d <= 10) MPC_LAUNCH(kern<10>, grid, dim3(256), lds, st, __VA_ARGS__);                      \
-        else MPC_LAUNCH(kern<CVX_DMAX>, grid, dim3(256), lds, st, __VA_ARGS__);                             \
+        if (d <= 4) MPC_LAUNCH((kern<4, M>), grid, dim3(256), lds, st, __VA_ARGS__);                        \
+        else if (d <= 10) MPC_LAUNCH((kern<10, M>), grid, dim3(256), lds, st, __VA_ARGS__);                 \
+        else MPC_LAUNCH((kern<CVX_DMAX, M>), grid, dim3(256), lds, st, __VA_ARGS__);                        \
     } while (0)
 
-extern "C" int mpc_cvx_traj_fwd(const float *params, const float *mask, const float *basis, float scale, float *traj,
-                                int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile, void *stream) {
-    if (!params || !mask || !basis || !traj) { mpc_set_error("%s: null argument", __func__); return MPC_E_NULL; }
-    int rc = cvx_check(__func__, B, d, T, h, w, tile);
+// the ONE copy of the host code of the three entry points; M: the element type of mask / grad_mask (dt_device.h)
+template <typename M>
+static int cvx_traj_fwd_run(const char *who, const float *params, const void *mask, const float *basis, float scale, float *traj,
+                            int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile, void *stream) {
+    if (!params || !mask || !basis || !traj) { mpc_set_error("%s: null argument", who); return MPC_E_NULL; }
+    int rc = cvx_check(who, B, d, T, h, w, tile);
     if (rc) return rc;
     const int nty = cvx_tiles(8 * h, tile), ntx = cvx_tiles(8 * w, tile), n = nty * ntx;
     const long long work = (long long)B * n;
     if (work == 0) return 0;
-    if (work > (1ll << 38)) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+    if (work > (1ll << 38)) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
     const dim3 grid((unsigned)((work + 255) / 256));
     const size_t lds = (size_t)T * d * sizeof(float);
-    CVX_DISPATCH(k_cvx_traj_fwd, grid, lds, (hipStream_t)stream, params, mask, basis, scale, traj, B, d, T, h, w, tile, ntx, n);
-    MPC_CHECK_LAUNCH();
+    CVX_DISPATCH(k_cvx_traj_fwd, M, grid, lds, (hipStream_t)stream, params, (const M *)mask, basis, scale, traj, B, d, T, h, w, tile, ntx, n);
+    MPC_CHECK_LAUNCH_WHO(who);
     return 0;
 }
 
-extern "C" int mpc_cvx_flow_fwd(const float *params, const float *mask, const float *basis, float scale, float *flows,
-                                int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream) {
-    if (!params || !mask || !basis || !flows) { mpc_set_error("%s: null argument", __func__); return MPC_E_NULL; }
-    int rc = cvx_check(__func__, B, d, T, h, w, 1);
+template <typename M>
+static int cvx_flow_fwd_run(const char *who, const float *params, const void *mask, const float *basis, float scale, float *flows,
+                            int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream) {
+    if (!params || !mask || !basis || !flows) { mpc_set_error("%s: null argument", who); return MPC_E_NULL; }
+    int rc = cvx_check(who, B, d, T, h, w, 1);
     if (rc) return rc;
     const long long work = (long long)B * 64 * h * w;
     if (work == 0) return 0;
-    if (work > (1ll << 38)) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+    if (work > (1ll << 38)) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
     const dim3 grid((unsigned)((work + 255) / 256));
     const size_t lds = (size_t)T * d * sizeof(float);
-    CVX_DISPATCH(k_cvx_flow_fwd, grid, lds, (hipStream_t)stream, params, mask, basis, scale, flows, B, d, T, h, w);
-    MPC_CHECK_LAUNCH();
+    CVX_DISPATCH(k_cvx_flow_fwd, M, grid, lds, (hipStream_t)stream, params, (const M *)mask, basis, scale, flows, B, d, T, h, w);
+    MPC_CHECK_LAUNCH_WHO(who);
     return 0;
 }
 
@@ -264,36 +274,69 @@ extern "C" int64_t mpc_cvx_traj_bwd_workspace_bytes(int32_t B, int32_t d, int32_
     return mpc_align((int64_t)B * n * (2 * d + 9) * (int64_t)sizeof(float));
 }
 
-extern "C" int mpc_cvx_traj_bwd(const float *grad_traj, const float *params, const float *mask, const float *basis, float scale,
-                                float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t T, int32_t h, int32_t w,
-                                int32_t tile, void *ws, void *stream) {
-    if (!grad_traj || !params || !mask || !basis) { mpc_set_error("%s: null argument", __func__); return MPC_E_NULL; }
-    int rc = cvx_check(__func__, B, d, T, h, w, tile);
+template <typename M>
+static int cvx_traj_bwd_run(const char *who, const float *grad_traj, const float *params, const void *mask, const float *basis, float scale,
+                            float *grad_params, void *grad_mask, int32_t B, int32_t d, int32_t T, int32_t h, int32_t w,
+                            int32_t tile, void *ws, void *stream) {
+    if (!grad_traj || !params || !mask || !basis) { mpc_set_error("%s: null argument", who); return MPC_E_NULL; }
+    int rc = cvx_check(who, B, d, T, h, w, tile);
     if (rc) return rc;
-    if (grad_params && !ws) { mpc_set_error("%s: grad_params needs the workspace", __func__); return MPC_E_NULL; }
+    if (grad_params && !ws) { mpc_set_error("%s: grad_params needs the workspace", who); return MPC_E_NULL; }
     if (!grad_params && !grad_mask) return 0;
     const long long plane = (long long)h * w;
     if ((long long)B * plane == 0) return 0;
     const int nty = cvx_tiles(8 * h, tile), ntx = cvx_tiles(8 * w, tile), n = nty * ntx;
     const long long work = (long long)B * n;
-    if (work > (1ll << 38)) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+    if (work > (1ll << 38)) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
     const int nA = (int)((work + 255) / 256);
     const int chunks = (int)((plane + CVX_FILL_ELEMS - 1) / CVX_FILL_ELEMS);
     const long long nfill = grad_mask ? (long long)B * 576 * chunks : 0;
-    if (nA + nfill > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
+    if (nA + nfill > 0x7fffffffll) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
     float *ws_dflow = grad_params ? (float *)ws : nullptr;
     float *ws_w = grad_params ? ws_dflow + (size_t)B * 2 * d * n : nullptr;
     const size_t lds = (size_t)T * d * sizeof(float);
     if (nA + nfill > 0) {
         const dim3 grid((unsigned)(nA + nfill));
-        CVX_DISPATCH(k_cvx_bwd_centres, grid, lds, (hipStream_t)stream, grad_traj, params, mask, basis, scale, grad_mask, ws_dflow, ws_w,
+        CVX_DISPATCH(k_cvx_bwd_centres, M, grid, lds, (hipStream_t)stream, grad_traj, params, (const M *)mask, basis, scale, (M *)grad_mask, ws_dflow, ws_w,
                      B, d, T, h, w, tile, ntx, n, nA, chunks);
-        MPC_CHECK_LAUNCH();
+        MPC_CHECK_LAUNCH_WHO(who);
     }
     if (grad_params) {
         const dim3 grid((unsigned)((plane + 255) / 256), (unsigned)(2 * d), (unsigned)B);
         MPC_LAUNCH(k_cvx_bwd_params, grid, dim3(256), 0, (hipStream_t)stream, ws_dflow, ws_w, grad_params, d, h, w, tile, nty, ntx, n);
-        MPC_CHECK_LAUNCH();
+        MPC_CHECK_LAUNCH_WHO(who);
     }
     return 0;
+}
+
+extern "C" int mpc_cvx_traj_fwd_dt(const float *params, const void *mask, int32_t dtype, const float *basis, float scale, float *traj,
+                                   int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile, void *stream) {
+    MPC_DT_RETURN(dtype, cvx_traj_fwd_run, params, mask, basis, scale, traj, B, d, T, h, w, tile, stream);
+}
+
+extern "C" int mpc_cvx_flow_fwd_dt(const float *params, const void *mask, int32_t dtype, const float *basis, float scale, float *flows,
+                                   int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream) {
+    MPC_DT_RETURN(dtype, cvx_flow_fwd_run, params, mask, basis, scale, flows, B, d, T, h, w, stream);
+}
+
+extern "C" int mpc_cvx_traj_bwd_dt(const float *grad_traj, const float *params, const void *mask, int32_t dtype, const float *basis, float scale,
+                                   float *grad_params, void *grad_mask, int32_t B, int32_t d, int32_t T, int32_t h, int32_t w,
+                                   int32_t tile, void *ws, void *stream) {
+    MPC_DT_RETURN(dtype, cvx_traj_bwd_run, grad_traj, params, mask, basis, scale, grad_params, grad_mask, B, d, T, h, w, tile, ws, stream);
+}
+
+extern "C" int mpc_cvx_traj_fwd(const float *params, const float *mask, const float *basis, float scale, float *traj,
+                                int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, int32_t tile, void *stream) {
+    return mpc_cvx_traj_fwd_dt(params, mask, MPC_DT_F32, basis, scale, traj, B, d, T, h, w, tile, stream);
+}
+
+extern "C" int mpc_cvx_flow_fwd(const float *params, const float *mask, const float *basis, float scale, float *flows,
+                                int32_t B, int32_t d, int32_t T, int32_t h, int32_t w, void *stream) {
+    return mpc_cvx_flow_fwd_dt(params, mask, MPC_DT_F32, basis, scale, flows, B, d, T, h, w, stream);
+}
+
+extern "C" int mpc_cvx_traj_bwd(const float *grad_traj, const float *params, const float *mask, const float *basis, float scale,
+                                float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t T, int32_t h, int32_t w,
+                                int32_t tile, void *ws, void *stream) {
+    return mpc_cvx_traj_bwd_dt(grad_traj, params, mask, MPC_DT_F32, basis, scale, grad_params, grad_mask, B, d, T, h, w, tile, ws, stream);
 }

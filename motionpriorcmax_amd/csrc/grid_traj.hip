@@ -19,6 +19,7 @@
 // Sums run in index order (over s, j, t), one rounding per multiply and per add (-ffp-contract=off).
 #include "common.h"
 #include "bounds.h"
+#include "dt_device.h"         // the element types of grid / grad_grid (mpc_ld, mpc_store_vec)
 
 #define GT_KMAX 16             // basis orders per axis
 #define GT_TC 256              // tile columns of a backward workgroup (one thread each)
@@ -37,8 +38,8 @@ __device__ __forceinline__ void gt_load_dphi(float *s_phi, const float *times, c
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(256) void k_grid_traj_fwd(const float *__restrict__ grid, const float *__restrict__ times,
+template <int K, typename T>
+__global__ __launch_bounds__(256) void k_grid_traj_fwd(const T *__restrict__ grid, const float *__restrict__ times,
                                                        const float *__restrict__ dphi, int basis, float anchor, int add_offsets,
                                                        float *__restrict__ traj, float *__restrict__ rows, int B, int S, int k, int H,
                                                        int W, int tile, int n_t, int hq, int wq) {
@@ -53,14 +54,14 @@ __global__ __launch_bounds__(256) void k_grid_traj_fwd(const float *__restrict__
     const int y = iy * tile + tile / 2, x = ix * tile + tile / 2;
     MPC_EXPECT(y < H && x < W);
     const size_t plane = (size_t)H * W;
-    const float *src = grid + (size_t)b * S * 2 * k * plane + (size_t)y * W + x;
+    const T *src = grid + (size_t)b * S * 2 * k * plane + (size_t)y * W + x;
     float cy[K], cx[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) cy[j] = cx[j] = 0.f;
     for (int s = 0; s < S; ++s) {               // neighbouring lanes: neighbouring tiles of one row of a channel plane
 #pragma unroll
         for (int j = 0; j < K; ++j)
-            if (j < k) { cy[j] += src[((size_t)s * 2 * k + j) * plane]; cx[j] += src[((size_t)s * 2 * k + k + j) * plane]; }
+            if (j < k) { cy[j] += mpc_ld(src + ((size_t)s * 2 * k + j) * plane); cx[j] += mpc_ld(src + ((size_t)s * 2 * k + k + j) * plane); }
     }
     if (rows != nullptr) {
 #pragma unroll
@@ -79,12 +80,12 @@ __global__ __launch_bounds__(256) void k_grid_traj_fwd(const float *__restrict__
 }
 
 // one workgroup per (b, pixel row y, chunk of GT_TC tile columns); `part` (learned basis only): [B*hq*nch][n_t][k]
-template <int K>
+template <int K, typename T>
 __global__ __launch_bounds__(256) void k_grid_traj_bwd(const float *__restrict__ g, const float *__restrict__ times,
                                                        const float *__restrict__ dphi, int basis, float anchor,
-                                                       const float *__restrict__ rows, float *__restrict__ ggrid,
+                                                       const float *__restrict__ rows, T *__restrict__ ggrid,
                                                        float *__restrict__ part, int B, int S, int k, int H, int W, int tile, int n_t,
-                                                       int hq, int wq, int nch, int vec4) {
+                                                       int hq, int wq, int nch, int vec) {
     extern __shared__ float s_phi[];            // [n_t][k]
     __shared__ float s_g[2 * K * GT_TC];        // [2k][GT_TC] the centre values of this row chunk
     __shared__ float s_red[4][K];
@@ -153,21 +154,23 @@ __global__ __launch_bounds__(256) void k_grid_traj_bwd(const float *__restrict__
     const int x0 = tx0 * tile;
     const int xw = min(W - x0, GT_TC * tile);
     const size_t plane = (size_t)H * W;
-    float *row = ggrid + ((size_t)b * S * c2 * H + y) * W + x0;               // + (s * c2 + c) * plane
-    if (vec4) {                                 // W % 4 == 0: 16-byte stores (x0 is a multiple of 4)
-        const int nx4 = xw >> 2;
-        for (int it = threadIdx.x; it < c2 * nx4; it += 256) {
-            const int c = it / nx4, q = it - c * nx4;
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
+    T *row = ggrid + ((size_t)b * S * c2 * H + y) * W + x0;                   // + (s * c2 + c) * plane
+    constexpr int V = MPC_VEC(T);               // elements of a 16-byte store: 4 fp32, 8 fp16 / bf16
+    if (vec) {                                  // W % V == 0 and a 16-byte aligned tensor: 16-byte stores (x0 is a multiple of 8)
+        const int nxv = xw / V;
+        for (int it = threadIdx.x; it < c2 * nxv; it += 256) {
+            const int c = it / nxv, q = it - c * nxv;
+            float v[V];
+#pragma unroll
+            for (int u = 0; u < V; ++u) v[u] = 0.f;
             if (centre) {
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int x = x0 + 4 * q + u, ix = x / tile;
+                for (int u = 0; u < V; ++u) {
+                    const int x = x0 + V * q + u, ix = x / tile;
                     if (x - ix * tile == s0 && ix < wq) v[u] = s_g[MPC_IDX(c * GT_TC + ix - tx0, 2 * K * GT_TC)];
                 }
             }
-            const float4 v4 = make_float4(v[0], v[1], v[2], v[3]);
-            for (int s = 0; s < S; ++s) *reinterpret_cast<float4 *>(row + (size_t)(s * c2 + c) * plane + 4 * q) = v4;
+            for (int s = 0; s < S; ++s) mpc_store_vec(row + (size_t)(s * c2 + c) * plane + V * q, v);
         }
     } else {
         for (int it = threadIdx.x; it < c2 * xw; it += 256) {
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(256) void k_grid_traj_bwd(const float *__restrict__
             const int x = x0 + xx, ix = x / tile;
             float v = 0.f;
             if (centre && x - ix * tile == s0 && ix < wq) v = s_g[MPC_IDX(c * GT_TC + ix - tx0, 2 * K * GT_TC)];
-            for (int s = 0; s < S; ++s) row[(size_t)(s * c2 + c) * plane + xx] = v;
+            for (int s = 0; s < S; ++s) mpc_st(row + (size_t)(s * c2 + c) * plane + xx, v);
         }
     }
 }
@@ -221,65 +224,94 @@ extern "C" int64_t mpc_grid_traj_scratch_floats(int32_t B, int32_t k, int32_t H,
     return (int64_t)B * hq * nch * n_t * k;
 }
 
-extern "C" int mpc_grid_traj_fwd(const float *grid, const float *times, const float *dphi, int32_t basis, float anchor_time,
-                                 int32_t add_offsets, float *traj, float *rows, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W,
-                                 int32_t tile, int32_t n_t, void *stream) {
-    int rc = gt_check(basis, times, dphi, B, S, k, H, W, tile, n_t, __func__);
+// the ONE copy of the host code of the two entry points; T: the element type of grid / grad_grid (dt_device.h)
+template <typename T>
+static int gt_fwd(const char *who, const void *grid_, const float *times, const float *dphi, int32_t basis, float anchor_time, int32_t add_offsets,
+                  float *traj, float *rows, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W, int32_t tile, int32_t n_t, void *stream) {
+    const T *grid = (const T *)grid_;
+    int rc = gt_check(basis, times, dphi, B, S, k, H, W, tile, n_t, who);
     if (rc) return rc;
     int hq, wq;
     gt_tiles(H, W, tile, &hq, &wq);
     const long long total = (long long)B * hq * wq;
     if (total == 0) return 0;                   // (empty tensors may come as NULL)
-    MPC_CHECK_ARG(grid && traj, MPC_E_NULL, "null argument");
+    MPC_CHECK_ARG_WHO(who, grid && traj, MPC_E_NULL, "null argument");
     const dim3 grd((unsigned)((total + 255) / 256));
     const size_t lds = (size_t)n_t * k * sizeof(float);
     hipStream_t st = (hipStream_t)stream;
-#define GT_FWD(KK) MPC_LAUNCH(k_grid_traj_fwd<KK>, grd, dim3(256), lds, st, grid, times, dphi, basis, anchor_time, add_offsets, traj, rows, B, S, k, H, W, tile, n_t, hq, wq)
+#define GT_FWD(KK) MPC_LAUNCH((k_grid_traj_fwd<KK, T>), grd, dim3(256), lds, st, grid, times, dphi, basis, anchor_time, add_offsets, traj, rows, B, S, k, H, W, tile, n_t, hq, wq)
     if (k <= 4) GT_FWD(4);
     else if (k <= 8) GT_FWD(8);
     else GT_FWD(GT_KMAX);
 #undef GT_FWD
-    MPC_CHECK_LAUNCH();
+    MPC_CHECK_LAUNCH_WHO(who);
     return 0;
 }
 
-extern "C" int mpc_grid_traj_bwd(const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time,
-                                 const float *rows, float *grad_grid, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k,
-                                 int32_t H, int32_t W, int32_t tile, int32_t n_t, void *stream) {
-    int rc = gt_check(basis, times, dphi, B, S, k, H, W, tile, n_t, __func__);
+template <typename T>
+static int gt_bwd(const char *who, const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time, const float *rows,
+                  void *grad_grid_, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W, int32_t tile,
+                  int32_t n_t, void *stream) {
+    T *grad_grid = (T *)grad_grid_;
+    int rc = gt_check(basis, times, dphi, B, S, k, H, W, tile, n_t, who);
     if (rc) return rc;
-    if (grad_dphi != nullptr) MPC_CHECK_ARG(basis == MPC_BASIS_MATRIX, MPC_E_UNSUPPORTED, "grad_dphi is only defined for MPC_BASIS_MATRIX");
+    if (grad_dphi != nullptr) MPC_CHECK_ARG_WHO(who, basis == MPC_BASIS_MATRIX, MPC_E_UNSUPPORTED, "grad_dphi is only defined for MPC_BASIS_MATRIX");
     hipStream_t st = (hipStream_t)stream;
     if (B == 0) {                               // no gradient element; grad_dphi is still an output: zeros (a sum over no partials)
         if (grad_dphi != nullptr) {
             MPC_LAUNCH(k_grid_dphi_sum, dim3((unsigned)(n_t * k)), dim3(256), 0, st, scratch, grad_dphi, 0ll, n_t * k);
-            MPC_CHECK_LAUNCH();
+            MPC_CHECK_LAUNCH_WHO(who);
         }
         return 0;
     }
     int hq, wq;
     gt_tiles(H, W, tile, &hq, &wq);
     const bool tiles = (long long)hq * wq > 0;  // (without tiles grad_traj and rows are empty: they may come as NULL, and are not read)
-    MPC_CHECK_ARG(grad_grid && (grad_traj || !tiles), MPC_E_NULL, "null argument");
-    if (grad_dphi != nullptr) MPC_CHECK_ARG(scratch && (rows || !tiles), MPC_E_NULL, "grad_dphi needs rows and scratch");
+    MPC_CHECK_ARG_WHO(who, grad_grid && (grad_traj || !tiles), MPC_E_NULL, "null argument");
+    if (grad_dphi != nullptr) MPC_CHECK_ARG_WHO(who, scratch && (rows || !tiles), MPC_E_NULL, "grad_dphi needs rows and scratch");
     const int nch = (int)(((long long)W + (long long)GT_TC * tile - 1) / ((long long)GT_TC * tile));
     const long long blocks = (long long)B * H * nch;
-    if (blocks > 0x7fffffffll) { mpc_set_error("%s: grid too large", __func__); return MPC_E_UNSUPPORTED; }
-    const int vec4 = (W & 3) == 0 && ((uintptr_t)grad_grid & 15) == 0;
+    if (blocks > 0x7fffffffll) { mpc_set_error("%s: grid too large", who); return MPC_E_UNSUPPORTED; }
+    // (every row start and every chunk start x0 = ch * GT_TC * tile is then a multiple of MPC_VEC elements from the 16-byte aligned base)
+    const int vec = W % MPC_VEC(T) == 0 && ((uintptr_t)grad_grid & 15) == 0;
     const size_t lds = (size_t)n_t * k * sizeof(float);
     float *part = grad_dphi != nullptr ? scratch : nullptr;
-#define GT_BWD(KK) MPC_LAUNCH(k_grid_traj_bwd<KK>, dim3((unsigned)blocks), dim3(256), lds, st, grad_traj, times, dphi, basis, anchor_time, rows, grad_grid, part, B, S, k, H, W, tile, n_t, hq, wq, nch, vec4)
+#define GT_BWD(KK) MPC_LAUNCH((k_grid_traj_bwd<KK, T>), dim3((unsigned)blocks), dim3(256), lds, st, grad_traj, times, dphi, basis, anchor_time, rows, grad_grid, part, B, S, k, H, W, tile, n_t, hq, wq, nch, vec)
     if (k <= 4) GT_BWD(4);
     else if (k <= 8) GT_BWD(8);
     else GT_BWD(GT_KMAX);
 #undef GT_BWD
-    MPC_CHECK_LAUNCH();
+    MPC_CHECK_LAUNCH_WHO(who);
     if (grad_dphi != nullptr) {
         const long long P = (long long)B * hq * nch;
         MPC_LAUNCH(k_grid_dphi_sum, dim3((unsigned)(n_t * k)), dim3(256), 0, st, scratch, grad_dphi, P, n_t * k);
-        MPC_CHECK_LAUNCH();
+        MPC_CHECK_LAUNCH_WHO(who);
     }
     return 0;
+}
+
+extern "C" int mpc_grid_traj_fwd_dt(const void *grid, int32_t dtype, const float *times, const float *dphi, int32_t basis, float anchor_time,
+                                    int32_t add_offsets, float *traj, float *rows, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W,
+                                    int32_t tile, int32_t n_t, void *stream) {
+    MPC_DT_RETURN(dtype, gt_fwd, grid, times, dphi, basis, anchor_time, add_offsets, traj, rows, B, S, k, H, W, tile, n_t, stream);
+}
+
+extern "C" int mpc_grid_traj_bwd_dt(const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time,
+                                    const float *rows, void *grad_grid, int32_t dtype, float *grad_dphi, float *scratch, int32_t B, int32_t S,
+                                    int32_t k, int32_t H, int32_t W, int32_t tile, int32_t n_t, void *stream) {
+    MPC_DT_RETURN(dtype, gt_bwd, grad_traj, times, dphi, basis, anchor_time, rows, grad_grid, grad_dphi, scratch, B, S, k, H, W, tile, n_t, stream);
+}
+
+extern "C" int mpc_grid_traj_fwd(const float *grid, const float *times, const float *dphi, int32_t basis, float anchor_time,
+                                 int32_t add_offsets, float *traj, float *rows, int32_t B, int32_t S, int32_t k, int32_t H, int32_t W,
+                                 int32_t tile, int32_t n_t, void *stream) {
+    return mpc_grid_traj_fwd_dt(grid, MPC_DT_F32, times, dphi, basis, anchor_time, add_offsets, traj, rows, B, S, k, H, W, tile, n_t, stream);
+}
+
+extern "C" int mpc_grid_traj_bwd(const float *grad_traj, const float *times, const float *dphi, int32_t basis, float anchor_time,
+                                 const float *rows, float *grad_grid, float *grad_dphi, float *scratch, int32_t B, int32_t S, int32_t k,
+                                 int32_t H, int32_t W, int32_t tile, int32_t n_t, void *stream) {
+    return mpc_grid_traj_bwd_dt(grad_traj, times, dphi, basis, anchor_time, rows, grad_grid, MPC_DT_F32, grad_dphi, scratch, B, S, k, H, W, tile, n_t, stream);
 }
 
 MPC_BOUNDS_UNIT("grid_traj.hip")

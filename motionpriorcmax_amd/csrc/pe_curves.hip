@@ -124,7 +124,8 @@ __device__ __forceinline__ void pec_basis(const PecBasis &pb, float t, float E[P
 }
 
 // ---- head rows ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pec_head_rows(const float *__restrict__ params, const float *__restrict__ mask, float scale, int tile,
+template <typename M>
+__global__ __launch_bounds__(256) void k_pec_head_rows(const float *__restrict__ params, const M *__restrict__ mask, float scale, int tile,
                                                        float *__restrict__ rows, int B, int d, int h, int w, int nty, int ntx) {
     const long long gi = (long long)blockIdx.x * 256 + threadIdx.x;
     const int n = nty * ntx;
@@ -481,17 +482,29 @@ extern "C" int32_t mpc_pec_supported(const mpc_shape *s, int32_t d, int32_t basi
     return r;
 }
 
-extern "C" int mpc_pec_head_rows(const float *params, const float *mask, float scale, int32_t tile, float *rows,
-                                 int32_t B, int32_t d, int32_t h, int32_t w, void *stream) {
-    MPC_CHECK_ARG(params && rows, MPC_E_NULL, "null argument");
+// the ONE copy of the host code of the two entry points; M: the element type of mask / grad_mask (dt_device.h)
+template <typename M>
+static int pec_head_rows_run(const char *who, const float *params, const void *mask, float scale, int32_t tile, float *rows,
+                             int32_t B, int32_t d, int32_t h, int32_t w, void *stream) {
+    MPC_CHECK_ARG_WHO(who, params && rows, MPC_E_NULL, "null argument");
     int nty = 0, ntx = 0;
-    int rc = pec_head_grid(__func__, B, d, h, w, tile, mask != nullptr, &nty, &ntx);
+    int rc = pec_head_grid(who, B, d, h, w, tile, mask != nullptr, &nty, &ntx);
     if (rc) return rc;
     const long long work = (long long)B * nty * ntx;
     if (work == 0) return 0;
-    MPC_LAUNCH(k_pec_head_rows, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, mask, scale, tile, rows, B, d, h, w, nty, ntx);
-    MPC_CHECK_LAUNCH();
+    MPC_LAUNCH(k_pec_head_rows<M>, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, (const M *)mask, scale, tile, rows, B, d, h, w, nty, ntx);
+    MPC_CHECK_LAUNCH_WHO(who);
     return 0;
+}
+
+extern "C" int mpc_pec_head_rows_dt(const float *params, const void *mask, int32_t dtype, float scale, int32_t tile, float *rows,
+                                    int32_t B, int32_t d, int32_t h, int32_t w, void *stream) {
+    MPC_DT_RETURN(dtype, pec_head_rows_run, params, mask, scale, tile, rows, B, d, h, w, stream);
+}
+
+extern "C" int mpc_pec_head_rows(const float *params, const float *mask, float scale, int32_t tile, float *rows,
+                                 int32_t B, int32_t d, int32_t h, int32_t w, void *stream) {
+    return mpc_pec_head_rows_dt(params, mask, MPC_DT_F32, scale, tile, rows, B, d, h, w, stream);
 }
 
 extern "C" int64_t mpc_pec_head_rows_bwd_workspace_bytes(int32_t B, int32_t d, int32_t h, int32_t w, int32_t tile) {
@@ -503,8 +516,10 @@ extern "C" int64_t mpc_pec_head_rows_bwd_workspace_bytes(int32_t B, int32_t d, i
     return mpc_align((int64_t)B * d * nty * ntx * 2 * 4) + mpc_align((int64_t)d * d * 4) + cvx;
 }
 
-extern "C" int mpc_pec_head_rows_bwd(const float *grad_rows, const float *params, const float *mask, float scale, int32_t tile,
-                                     float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream) {
+extern "C" int mpc_pec_head_rows_bwd_dt(const float *grad_rows, const float *params, const void *mask, int32_t dtype, float scale, int32_t tile,
+                                        float *grad_params, void *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream) {
+    MPC_CHECK_ARG(dtype == MPC_DT_F32 || dtype == MPC_DT_F16 || dtype == MPC_DT_BF16, MPC_E_UNSUPPORTED,
+                  "unknown dtype code (MPC_DT_F32, MPC_DT_F16 or MPC_DT_BF16)");
     MPC_CHECK_ARG(grad_rows && params && grad_params && (!mask || (grad_mask && ws)), MPC_E_NULL, "null argument");
     int nty = 0, ntx = 0;
     int rc = pec_head_grid(__func__, B, d, h, w, tile, mask != nullptr, &nty, &ntx);
@@ -525,7 +540,12 @@ extern "C" int mpc_pec_head_rows_bwd(const float *grad_rows, const float *params
     if (total < (long long)d * d) total = (long long)d * d;
     MPC_LAUNCH(k_pec_rows_to_traj, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, grad_rows, gtraj, ident, B, d, n);
     MPC_CHECK_LAUNCH();
-    return mpc_cvx_traj_bwd(gtraj, params, mask, ident, scale, grad_params, grad_mask, B, d, d, h, w, tile, cvx_ws, stream);
+    return mpc_cvx_traj_bwd_dt(gtraj, params, mask, dtype, ident, scale, grad_params, grad_mask, B, d, d, h, w, tile, cvx_ws, stream);
+}
+
+extern "C" int mpc_pec_head_rows_bwd(const float *grad_rows, const float *params, const float *mask, float scale, int32_t tile,
+                                     float *grad_params, float *grad_mask, int32_t B, int32_t d, int32_t h, int32_t w, void *ws, void *stream) {
+    return mpc_pec_head_rows_bwd_dt(grad_rows, params, mask, MPC_DT_F32, scale, tile, grad_params, grad_mask, B, d, h, w, ws, stream);
 }
 
 #define PEC_SHAPE_CHECKS()                                                                                                                   \

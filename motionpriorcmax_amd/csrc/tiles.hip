@@ -9,10 +9,12 @@
 //   k_basis_field<8>   field[(b, t)][cell][d]    = sum_j rows[(b, cell)][d][j] phim[t][j]            (pe_device.h: the curves' field is <16>)
 //   k_rows_grad_finish out[(b, cell)][d][j]      = sum_split gp[split][(b, cell)][d][j] + gout * sum_t gfield[(b, t)][cell][d] phim[t][j]
 #include "pe_device.h"
+#include "dt_device.h"         // the element types of grid / grad_grid (mpc_ld, mpc_store_vec)
 
 #define TILE_KMAX PE_KMAX      // basis orders per axis (mpc_pe_warp's register variant holds as many)
 
-__global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ grid, float *__restrict__ rows, int B, int S, int c2, int H, int W,
+template <typename T>
+__global__ __launch_bounds__(256) void k_tile_rows(const T *__restrict__ grid, float *__restrict__ rows, int B, int S, int c2, int H, int W,
                                                    int tile, int hq, int wq) {
     const long long total = (long long)B * hq * wq * c2;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -25,35 +27,40 @@ __global__ __launch_bounds__(256) void k_tile_rows(const float *__restrict__ gri
     const int y = iy * tile + tile / 2, x = ix * tile + tile / 2;
     float v = 0.f;
     if (y < H && x < W)
-        for (int s = 0; s < S; ++s) v += grid[((((size_t)b * S + s) * c2 + c) * H + y) * W + x];
+        for (int s = 0; s < S; ++s) v += mpc_ld(grid + ((((size_t)b * S + s) * c2 + c) * H + y) * W + x);
     rows[(((size_t)b * hq + iy) * wq + ix) * c2 + c] = v;
 }
 
-__global__ __launch_bounds__(256) void k_tile_rows_bwd(const float *__restrict__ grows, float *__restrict__ ggrid, int B, int S, int c2, int H, int W,
+template <typename T>
+__global__ __launch_bounds__(256) void k_tile_rows_bwd(const float *__restrict__ grows, T *__restrict__ ggrid, int B, int S, int c2, int H, int W,
                                                        int tile, int hq, int wq) {
-    // one thread per four consecutive pixels of a row (16-byte stores where W is a multiple of 4; the zero fill IS the kernel: the
-    // dense gradient is 103 MB at the DSEC batch shape)
-    const int W4 = (W + 3) >> 2;
-    const long long total = (long long)B * S * c2 * H * W4;
+    // one thread per V consecutive pixels of a row, V = 4 fp32 or 8 fp16 / bf16 elements (16-byte stores where W is a multiple of V;
+    // the zero fill IS the kernel: the dense gradient is 103 MB in fp32 at the DSEC batch shape)
+    constexpr int V = MPC_VEC(T);
+    const int WV = (W + V - 1) / V;
+    const long long total = (long long)B * S * c2 * H * WV;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-        const int x4 = (int)(i % W4);
-        long long r = i / W4;
+        const int xv = (int)(i % WV);
+        long long r = i / WV;
         const int y = (int)(r % H); r /= H;
         const int c = (int)(r % c2); r /= c2;
         const int b = (int)(r / S);
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        float v[V];
+#pragma unroll
+        for (int u = 0; u < V; ++u) v[u] = 0.f;
         const int iy = y / tile;
         if (y - iy * tile == tile / 2 && iy < hq) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int x = 4 * x4 + u, ix = x / tile;
+            for (int u = 0; u < V; ++u) {
+                const int x = V * xv + u, ix = x / tile;
                 if (x < W && x - ix * tile == tile / 2 && ix < wq) v[u] = grows[(((size_t)b * hq + iy) * wq + ix) * c2 + c];
             }
         }
-        float *dst = ggrid + (size_t)(i / W4) * W + 4 * x4;
-        if ((W & 3) == 0) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        T *dst = ggrid + (size_t)(i / WV) * W + V * xv;
+        // (fp32: torch's allocations are 16-byte aligned, as before; a 16-bit tensor may be a view at any even address)
+        if (W % V == 0 && (sizeof(T) == 4 || ((uintptr_t)dst & 15) == 0)) mpc_store_vec(dst, v);
         else
-            for (int u = 0; u < 4 && 4 * x4 + u < W; ++u) dst[u] = v[u];
+            for (int u = 0; u < V && V * xv + u < W; ++u) mpc_st(dst + u, v[u]);
     }
 }
 
@@ -99,29 +106,51 @@ static int tile_args(int B, int S, int c2, int H, int W, int tile, const char *w
     return 0;
 }
 
-extern "C" int mpc_pe_tile_rows(const float *grid, float *rows, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream) {
-    MPC_CHECK_ARG(grid && rows, MPC_E_NULL, "null argument");
-    int rc = tile_args(B, S, c2, H, W, tile, __func__);
+// the ONE copy of the host code of the two entry points; T: the element type of grid / grad_grid (dt_device.h)
+template <typename T>
+static int tile_rows_run(const char *who, const void *grid, float *rows, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream) {
+    MPC_CHECK_ARG_WHO(who, grid && rows, MPC_E_NULL, "null argument");
+    int rc = tile_args(B, S, c2, H, W, tile, who);
     if (rc) return rc;
     const int hq = (H + tile - 1) / tile, wq = (W + tile - 1) / tile;
     const long long total = (long long)B * hq * wq * c2;
     if (total == 0) return 0;
-    MPC_LAUNCH(k_tile_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, grid, rows, B, S, c2, H, W, tile, hq, wq);
-    MPC_CHECK_LAUNCH();
+    MPC_LAUNCH(k_tile_rows<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const T *)grid, rows, B, S, c2, H, W, tile, hq, wq);
+    MPC_CHECK_LAUNCH_WHO(who);
     return 0;
 }
 
-extern "C" int mpc_pe_tile_rows_bwd(const float *grad_rows, float *grad_grid, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream) {
-    MPC_CHECK_ARG(grad_rows && grad_grid, MPC_E_NULL, "null argument");
-    int rc = tile_args(B, S, c2, H, W, tile, __func__);
+template <typename T>
+static int tile_rows_bwd_run(const char *who, const float *grad_rows, void *grad_grid, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile,
+                             void *stream) {
+    MPC_CHECK_ARG_WHO(who, grad_rows && grad_grid, MPC_E_NULL, "null argument");
+    int rc = tile_args(B, S, c2, H, W, tile, who);
     if (rc) return rc;
     const int hq = (H + tile - 1) / tile, wq = (W + tile - 1) / tile;
-    const long long total = (long long)B * S * c2 * H * ((W + 3) / 4);
+    const long long total = (long long)B * S * c2 * H * ((W + MPC_VEC(T) - 1) / MPC_VEC(T));
     if (total == 0) return 0;
     const long long blocks = (total + 255) / 256;
-    MPC_LAUNCH(k_tile_rows_bwd, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, grad_rows, grad_grid, B, S, c2, H, W, tile, hq, wq);
-    MPC_CHECK_LAUNCH();
+    MPC_LAUNCH(k_tile_rows_bwd<T>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, grad_rows, (T *)grad_grid, B, S, c2, H, W, tile, hq, wq);
+    MPC_CHECK_LAUNCH_WHO(who);
     return 0;
+}
+
+extern "C" int mpc_pe_tile_rows_dt(const void *grid, int32_t dtype, float *rows, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile,
+                                   void *stream) {
+    MPC_DT_RETURN(dtype, tile_rows_run, grid, rows, B, S, c2, H, W, tile, stream);
+}
+
+extern "C" int mpc_pe_tile_rows_bwd_dt(const float *grad_rows, void *grad_grid, int32_t dtype, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W,
+                                       int32_t tile, void *stream) {
+    MPC_DT_RETURN(dtype, tile_rows_bwd_run, grad_rows, grad_grid, B, S, c2, H, W, tile, stream);
+}
+
+extern "C" int mpc_pe_tile_rows(const float *grid, float *rows, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream) {
+    return mpc_pe_tile_rows_dt(grid, MPC_DT_F32, rows, B, S, c2, H, W, tile, stream);
+}
+
+extern "C" int mpc_pe_tile_rows_bwd(const float *grad_rows, float *grad_grid, int32_t B, int32_t S, int32_t c2, int32_t H, int32_t W, int32_t tile, void *stream) {
+    return mpc_pe_tile_rows_bwd_dt(grad_rows, grad_grid, MPC_DT_F32, B, S, c2, H, W, tile, stream);
 }
 
 extern "C" int mpc_pe_basis_field(const float *rows, const float *phim, float *field, int32_t B, int32_t G, int32_t k, int32_t nb, void *stream) {

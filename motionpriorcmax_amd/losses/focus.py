@@ -229,7 +229,11 @@ class FocusLoss(base.TrajectoryLossBase):
         A tile without a centre: there are ceil(H / sp) x ceil(W / sp) cells, and where 0 < H % sp <= sp // 2 (W likewise) the
         centre sp // 2 of the last row (column) of cells lies outside the image.  Such a cell carries zero coefficients: its
         events are not warped, it enters the smoothness field with zero flow, and no element of coeff_grid receives its
-        gradient."""
+        gradient.
+
+        An fp16 / bf16 coeff_grid (a network under autocast, a .half() / .bfloat16() model) is read by the fused node as it is -- no
+        .float() copy; the conversion at the load is exact, so loss and images are those of coeff_grid.float(), bit for bit -- and
+        its gradient comes back in the grid's dtype, computed in fp32 and rounded once (round to nearest even)."""
         from ..utils import basis_values, table_basis_values
         if self.num_tref != 1:
             raise ValueError('calc_per_event_basis needs num_tref == 1')
@@ -358,7 +362,10 @@ class FocusLoss(base.TrajectoryLossBase):
         phi [B, M, d] and the rows in plain torch around the existing per-event nodes (the cross-check).  A table that trains is
         served by the fused node wherever a constant one is (mpc_pec_table_basis_grad: one more streaming pass, Q33.30 sums, bitwise
         reproducible in either event layout; |G_j| < 2^31 and a knot's sum over the batch below 2^33); elsewhere phi stays in the
-        graph and plain torch around the vote / objective kernels delivers the same three gradients.  No graph capture."""
+        graph and plain torch around the vote / objective kernels delivers the same three gradients.  No graph capture.
+        An fp16 / bf16 up_mask (a network under autocast) is read by the fused node as it is -- no .float() copy, the same loss bits
+        as for the upcast mask -- and gets its gradient in its own dtype, computed in fp32 and rounded once; params that are not
+        fp32 go through a differentiable .float()."""
         from ..utils import curve_event_basis, curve_head_rows, curve_basis, table_basis_values
         from ..utils.basis import CURVE_EVENT_TYPES, BSPLINE_MIN_DEGREE
         d, tile = self._curve_tile_grid(params, up_mask, scale)
@@ -429,6 +436,8 @@ class FocusLoss(base.TrajectoryLossBase):
             if phim.shape[0] == 0:
                 phim = None
         if fused:
+            if params.dtype != torch.float32:
+                params = params.float()           # (differentiable: autograd casts grad_params back; the mask is read in its own dtype)
             loss, focus, smooth, iwes = ops.PerEventCurvesFn.apply(params, up_mask, events, t_ref, phim, self._cfg, int(num_pos_events), offsets,
                                                                    curve_type, basis_table, float(scale), tile)
         elif trains:

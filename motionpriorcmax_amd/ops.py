@@ -155,6 +155,19 @@ def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+_DT_CODE = {torch.float32: C.DT_F32, torch.float16: C.DT_F16, torch.bfloat16: C.DT_BF16}
+
+
+def _net(t: torch.Tensor):
+    """A network tensor (the coefficient grid, the convex-upsampling mask) for a `_dt` entry point -> (the tensor's OWN contiguous
+    storage where it is fp32, fp16 or bf16 -- no upcast copy: the kernels convert at the load, exactly --, else an fp32 copy; its
+    MPC_DT_* code).  The gradient goes back in that dtype, rounded once by the kernel that computes it."""
+    t = t.detach()
+    if t.dtype not in _DT_CODE:
+        t = t.float()
+    return t.contiguous(), _DT_CODE[t.dtype]
+
+
 def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
@@ -1040,7 +1053,7 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         _require_gpu(coeff_grid, 'coeff_grid')
         B, M, Mp = _check_events(events, cfg, num_pos)
         dev = coeff_grid.device
-        cg = _f32c(coeff_grid.detach())
+        cg, cg_dt = _net(coeff_grid)                                # (fp16 / bf16 grids are read as they are: no .float() copy)
         ev = _f32c(events.detach())
         ph = _f32c(phi.detach()) if phi is not None else None       # None: the polynomial basis, worked out in the kernels
         pm = _f32c(phim.detach()) if phim is not None else None     # [nb, k]: basis(t_ref) - basis(bin mid-times), or None: no smoothness term
@@ -1059,12 +1072,12 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         if Bc != B or c2 != 2 * k or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coeff_grid {tuple(cg.shape)} / phi do not match [B, S, 2k, H, W] / [B, M, k] (k <= 8 without phi)')
         c_rows = torch.empty((B * G, 2 * k), dtype=torch.float32, device=dev)
-        _call('mpc_pe_tile_rows', dev, _ptr(cg), _ptr(c_rows), B, S, c2, H, W, tile)
+        _call('mpc_pe_tile_rows_dt', dev, _ptr(cg), cg_dt, _ptr(c_rows), B, S, c2, H, W, tile, label='mpc_pe_tile_rows')
         ws = alloc_workspace(shape, dev)
         field = ('mpc_pe_basis_field', c_rows, pm, k) if pm is not None and cfg.smooth_weight > 0 else None
         rows, blur, gimg, g_field, scal = _pe_fwd(cfg, shape, ev, c_rows, ph, k, tr, ws, need_grad, tab, field)
         offs = _pe_ordered_offsets(offsets, cfg, shape, k, dev)
-        ctx.shape, ctx.k, ctx.tile, ctx.grid_shape = shape, k, tile, (B, S, c2, H, W)
+        ctx.shape, ctx.k, ctx.tile, ctx.grid_shape, ctx.grid_dtype = shape, k, tile, (B, S, c2, H, W), cg.dtype
         ctx.has = (ph is not None, pm is not None and g_field is not None, offs is not None)
         ctx.has_tab = tab is not None
         ctx.set_materialize_grads(False)
@@ -1109,8 +1122,9 @@ class PerEventBasisCalcFn(torch.autograd.Function):
         nb = pm.shape[0] if has_smooth else 0
         _call('mpc_pe_rows_grad_finish', dev, _ptr(gp), gp.shape[0], _ptr(g_field) if has_smooth else None, _ptr(pm) if has_smooth else None,
               _ptr(go), _ptr(g_rows), B, G, k, max(nb, 1))
-        g_grid = torch.empty(ctx.grid_shape, dtype=torch.float32, device=dev)
-        _call('mpc_pe_tile_rows_bwd', dev, _ptr(g_rows), _ptr(g_grid), B, S, c2, H, W, ctx.tile)
+        g_grid = torch.empty(ctx.grid_shape, dtype=ctx.grid_dtype, device=dev)          # (in the grid's dtype; every element is written)
+        _call('mpc_pe_tile_rows_bwd_dt', dev, _ptr(g_rows), _ptr(g_grid), _DT_CODE[ctx.grid_dtype], B, S, c2, H, W, ctx.tile,
+              label='mpc_pe_tile_rows_bwd')
         return (g_grid, None, None, g_phim) + (None,) * 6 + (g_table,)
 
 
@@ -1155,10 +1169,10 @@ class PerEventCurvesFn(torch.autograd.Function):
         B, M, Mp = _check_events(events, cfg, num_pos)
         dev = params.device
         p = _f32c(params.detach())
-        m = None
+        m, m_dt = None, C.DT_F32
         if up_mask is not None:
             _require_gpu(up_mask, 'up_mask')
-            m = _f32c(up_mask.detach())
+            m, m_dt = _net(up_mask)                   # (an fp16 / bf16 mask is read as it is: no .float() copy)
         ev = _f32c(events.detach())
         pm = _f32c(phim.detach()) if phim is not None else None
         tr = _f32c(t_ref.detach().to(dev))
@@ -1183,7 +1197,7 @@ class PerEventCurvesFn(torch.autograd.Function):
         basis_trains = (tab is not None and ctx.needs_input_grad[9]) or (pm is not None and ctx.needs_input_grad[4])
         need_grad = need_grad or basis_trains
         c_rows = torch.empty((B * G, 2 * d), dtype=torch.float32, device=dev)
-        _call('mpc_pec_head_rows', dev, _ptr(p), _ptr(m), float(scale), int(tile), _ptr(c_rows), B, d, h, w)
+        _call('mpc_pec_head_rows_dt', dev, _ptr(p), _ptr(m), m_dt, float(scale), int(tile), _ptr(c_rows), B, d, h, w, label='mpc_pec_head_rows')
         ws = alloc_workspace(shape, dev)
         rows = torch.empty_like(ev)
         if B * M > 0:                                 # (an empty tensor has no pointer to hand over)
@@ -1236,10 +1250,10 @@ class PerEventCurvesFn(torch.autograd.Function):
         gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
         gm = ws = None
         if has_mask:
-            gm = torch.empty((B, 576, h, w), dtype=torch.float32, device=dev)          # (every element is written)
+            gm = torch.empty((B, 576, h, w), dtype=m.dtype, device=dev)                # (in the mask's dtype; every element is written)
             ws = torch.empty(max(_query('mpc_pec_head_rows_bwd_workspace_bytes', dev, B, d, h, w, tile), 256), dtype=torch.uint8, device=dev)
-        _call('mpc_pec_head_rows_bwd', dev, _ptr(g_rows), _ptr(p), _ptr(m) if has_mask else None, scale, tile, _ptr(gp), _ptr(gm), B, d, h, w,
-              _ptr(ws))
+        _call('mpc_pec_head_rows_bwd_dt', dev, _ptr(g_rows), _ptr(p), _ptr(m) if has_mask else None, _DT_CODE[m.dtype] if has_mask else C.DT_F32,
+              scale, tile, _ptr(gp), _ptr(gm), B, d, h, w, _ptr(ws), label='mpc_pec_head_rows_bwd')
         return (gp, gm, None, None, g_phim) + (None,) * 4 + (g_table,) + (None,) * 3
 
 
@@ -1456,14 +1470,14 @@ class CvxCurveTrajFn(torch.autograd.Function):
         d, T, tile = c2 // 2, basis.shape[0], int(tile)
         dev = params.device
         p = _f32c(params.detach())
-        m = _f32c(up_mask.detach())
+        m, m_dt = _net(up_mask)                       # (an fp16 / bf16 mask is read as it is: no .float() copy)
         bm = _f32c(basis.detach())
         s = tile // 2
         nty, ntx = ((v - s + tile - 1) // tile if v > s else 0 for v in (8 * h, 8 * w))          # (the count of the tile mask's centres)
         n = nty * ntx
         traj = torch.empty((B, T, n, 2), dtype=torch.float32, device=dev)
         if B * n > 0:                                 # (an empty tensor has no pointer to hand over: 8h or 8w within half a tile)
-            _call('mpc_cvx_traj_fwd', dev, _ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile)
+            _call('mpc_cvx_traj_fwd_dt', dev, _ptr(p), _ptr(m), m_dt, _ptr(bm), float(scale), _ptr(traj), B, d, T, h, w, tile, label='mpc_cvx_traj_fwd')
         ctx.save_for_backward(p, m, bm)
         ctx.dims = (B, d, T, h, w, tile, float(scale))
         return traj
@@ -1482,9 +1496,10 @@ class CvxCurveTrajFn(torch.autograd.Function):
             gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
             ws = torch.empty(max(_query('mpc_cvx_traj_bwd_workspace_bytes', dev, B, d, T, h, w, tile), 4) // 4, dtype=torch.float32, device=dev)
         if ctx.needs_input_grad[1]:
-            gm = torch.empty((B, 576, h, w), dtype=torch.float32, device=dev)          # (every element is written by the kernel)
+            gm = torch.empty((B, 576, h, w), dtype=m.dtype, device=dev)                # (in the mask's dtype; every element is written by the kernel)
         if gp is not None or gm is not None:
-            _call('mpc_cvx_traj_bwd', dev, _ptr(g), _ptr(p), _ptr(m), _ptr(bm), scale, _ptr(gp), _ptr(gm), B, d, T, h, w, tile, _ptr(ws))
+            _call('mpc_cvx_traj_bwd_dt', dev, _ptr(g), _ptr(p), _ptr(m), _DT_CODE[m.dtype], _ptr(bm), scale, _ptr(gp), _ptr(gm), B, d, T, h, w, tile,
+                  _ptr(ws), label='mpc_cvx_traj_bwd')
         return gp, gm, None, None, None
 
 
@@ -1496,8 +1511,8 @@ def cvx_flows(params, up_mask, basis, scale: float):
     B, c2, h, w = params.shape
     d, T, dev = c2 // 2, basis.shape[0], params.device
     flows = torch.empty((T, B, 2, 8 * h, 8 * w), dtype=torch.float32, device=dev)
-    p, m, bm = _f32c(params.detach()), _f32c(up_mask.detach()), _f32c(basis.detach())
-    _call('mpc_cvx_flow_fwd', dev, _ptr(p), _ptr(m), _ptr(bm), float(scale), _ptr(flows), B, d, T, h, w)
+    p, (m, m_dt), bm = _f32c(params.detach()), _net(up_mask), _f32c(basis.detach())
+    _call('mpc_cvx_flow_fwd_dt', dev, _ptr(p), _ptr(m), m_dt, _ptr(bm), float(scale), _ptr(flows), B, d, T, h, w, label='mpc_cvx_flow_fwd')
     return flows
 
 
@@ -1765,7 +1780,7 @@ class GridTrajFn(torch.autograd.Function):
         _require_gpu(coeff_grid, 'coeff_grid')
         B, S, c2, H, W = coeff_grid.shape
         k, dev = c2 // 2, coeff_grid.device
-        cg = _f32c(coeff_grid.detach())
+        cg, cg_dt = _net(coeff_grid)                  # (fp16 / bf16 grids are read as they are: no .float() copy)
         tm = None if times is None else _f32c(times.detach()).reshape(-1)
         dp = None if dphi is None else _f32c(dphi.detach())
         n_t = dp.shape[0] if dp is not None else tm.shape[0]
@@ -1776,10 +1791,11 @@ class GridTrajFn(torch.autograd.Function):
         rows = None
         if dp is not None and ctx.needs_input_grad[2]:        # (saved only when the basis itself is learned)
             rows = torch.empty((B * hq * wq, c2), dtype=torch.float32, device=dev)
-        _call('mpc_grid_traj_fwd', dev, _ptr(cg), _ptr(tm), _ptr(dp), int(basis), float(anchor), int(bool(add_offsets)), _ptr(traj),
-              _ptr(rows), B, S, k, H, W, int(tile), n_t)
+        _call('mpc_grid_traj_fwd_dt', dev, _ptr(cg), cg_dt, _ptr(tm), _ptr(dp), int(basis), float(anchor), int(bool(add_offsets)), _ptr(traj),
+              _ptr(rows), B, S, k, H, W, int(tile), n_t, label='mpc_grid_traj_fwd')
         ctx.save_for_backward(tm, dp, rows)
         ctx.dims = (B, S, k, H, W, int(tile), n_t, int(basis), float(anchor))
+        ctx.grid_dtype = cg.dtype
         return traj
 
     @staticmethod
@@ -1788,14 +1804,14 @@ class GridTrajFn(torch.autograd.Function):
         B, S, k, H, W, tile, n_t, basis, anchor = ctx.dims
         g = _f32c(g)
         dev = g.device
-        gg = torch.empty((B, S, 2 * k, H, W), dtype=torch.float32, device=dev)          # (every element is written by the kernel)
+        gg = torch.empty((B, S, 2 * k, H, W), dtype=ctx.grid_dtype, device=dev)         # (in the grid's dtype; every element is written by the kernel)
         gd = scratch = None
         if rows is not None:
             nsc = _query('mpc_grid_traj_scratch_floats', dev, B, k, H, W, tile, n_t)
             gd = torch.empty((n_t, k), dtype=torch.float32, device=dev)
             scratch = torch.empty(max(nsc, 1), dtype=torch.float32, device=dev)
-        _call('mpc_grid_traj_bwd', dev, _ptr(g), _ptr(tm), _ptr(dp), basis, anchor, _ptr(rows), _ptr(gg), _ptr(gd), _ptr(scratch),
-              B, S, k, H, W, tile, n_t)
+        _call('mpc_grid_traj_bwd_dt', dev, _ptr(g), _ptr(tm), _ptr(dp), basis, anchor, _ptr(rows), _ptr(gg), _DT_CODE[ctx.grid_dtype], _ptr(gd),
+              _ptr(scratch), B, S, k, H, W, tile, n_t, label='mpc_grid_traj_bwd')
         return gg, None, gd, None, None, None, None
 
 

@@ -234,6 +234,14 @@ def _tile_positions(H, W, tile_size, device, dtype):
     return ent
 
 
+def _basis_dtype(params):
+    """The dtype of the basis matrix of the curve adapters: that of `params`, except fp32 for fp16 / bf16 control points on the GPU
+    -- those run in the fused nodes, which evaluate in fp32 (a Bernstein matrix rounded to bf16 would cost the curve 8 of its 24
+    bits for nothing); where such a tensor still takes a plain-torch mirror (a shape beyond the kernels' limits), the mirror rounds
+    the matrix to the dtype of `params`, as it always did."""
+    return torch.float32 if params.is_cuda and params.dtype in (torch.float16, torch.bfloat16) else params.dtype
+
+
 def _basis_trains(bm):
     """Does autograd want the gradient of this basis matrix (the reference's curve_type LEARNED while its basis network trains)?  The
     fused nodes treat the matrix as a constant (ops.CurveTrajFn, ops.CvxCurveTrajFn, ops.CorrLookupFn return None for it), so such a
@@ -247,12 +255,16 @@ def _curve_trajectories(params, bm, tile_size, H, W, scale):
     (the host-side tests against the reference's curves) the same in plain torch."""
     B, c2, h, w = params.shape
     d = c2 // 2
+    if params.is_cuda and params.dtype in _KERNEL_DTYPES and d <= 16 and not _basis_trains(bm):
+        # (fp16 / bf16 control points go through a differentiable .float() -- autograd casts their gradient back --, and the basis
+        # matrix and the tile positions are fp32 whatever params.dtype is: the trajectories are fp32, never positions in 16 bits)
+        from .. import ops
+        pos, pos_dev = _tile_positions(H, W, tile_size, params.device, torch.float32)
+        assert pos.shape[0] == h * w, 'image shape must be a multiple of the tile size'
+        return ops.CurveTrajFn.apply(params.float(), bm.float(), pos_dev, float(scale)), pos
     pos, pos_dev = _tile_positions(H, W, tile_size, params.device, params.dtype)
     assert pos.shape[0] == h * w, 'image shape must be a multiple of the tile size'
-    if params.is_cuda and params.dtype == torch.float32 and d <= 16 and not _basis_trains(bm):
-        from .. import ops
-        return ops.CurveTrajFn.apply(params, bm, pos_dev, float(scale)), pos
-    flow = torch.einsum('bcdhw,td->btchw', params.view(B, 2, d, h, w), bm) * scale  # [B, n_t, (x, y), h, w]
+    flow = torch.einsum('bcdhw,td->btchw', params.view(B, 2, d, h, w), bm.to(params.dtype)) * scale  # [B, n_t, (x, y), h, w]
     disp = torch.stack((flow[:, :, 1], flow[:, :, 0]), dim=-1).reshape(B, bm.shape[0], h * w, 2)
     return disp + pos_dev[None, None], pos
 
@@ -273,13 +285,15 @@ def _cvx_upsample(params, up_mask):
 
 
 _CVX_KERNEL_TILES = (2, 4, 8, 16)
+_KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)          # what the fused nodes take (the mask in place: include/mpcmax.h, MPC_DT_*)
 
 
 def _cvx_kernels_serve(params, up_mask, bm):
-    """The routing rule of `_curve_trajectories`: the kernels take fp32 GPU tensors with d <= 16 and a basis matrix within their
-    48 KB LDS slice that is a constant to autograd; everything else (CPU tensors, other dtypes, d > 16, more times, a basis matrix
-    that requires grad) runs in plain torch."""
-    return (params.is_cuda and up_mask.is_cuda and params.dtype == torch.float32 and up_mask.dtype == torch.float32
+    """The routing rule of `_curve_trajectories`: the kernels take fp32, fp16 or bf16 GPU tensors (the mask is read in its own dtype,
+    the control points go through .float()) with d <= 16 and a basis matrix within their 48 KB LDS slice that is a constant to
+    autograd; everything else (CPU tensors, other dtypes, d > 16, more times, a basis matrix that requires grad) runs in plain
+    torch."""
+    return (params.is_cuda and up_mask.is_cuda and params.dtype in _KERNEL_DTYPES and up_mask.dtype in _KERNEL_DTYPES
             and params.shape[1] // 2 <= 16 and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024 and not _basis_trains(bm))
 
 
@@ -289,14 +303,16 @@ def _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale):
     d = c2 // 2
     idx = pos_dev.long()
     up = _cvx_upsample(params, up_mask)[:, :, idx[:, 0], idx[:, 1]]                     # [B, 2d, n]
-    flow = torch.einsum('bcdn,td->btcn', up.reshape(B, 2, d, -1), bm) * scale           # [B, n_t, (x, y), n]
+    flow = torch.einsum('bcdn,td->btcn', up.reshape(B, 2, d, -1), bm.to(up.dtype)) * scale           # [B, n_t, (x, y), n]
     disp = torch.stack((flow[:, :, 1], flow[:, :, 0]), dim=-1)
     return disp + pos_dev[None, None]
 
 
 def _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale):
     """`_curve_trajectories` for control points on the 1/8 grid with their convex-upsampling mask (the RAFT-spline output head):
-    on the GPU ops.CvxCurveTrajFn (csrc/cvx_curves.hip; tile sizes 2, 4, 8, 16), else the plain-torch mirror."""
+    on the GPU ops.CvxCurveTrajFn (csrc/cvx_curves.hip; tile sizes 2, 4, 8, 16), else the plain-torch mirror.  On the kernel route
+    an fp16 / bf16 mask is passed as it is and gets its gradient in its own dtype (computed in fp32, rounded once); control points
+    that are not fp32 go through a differentiable .float(); the basis matrix is fp32 and so are the trajectories."""
     B, c2, h, w = params.shape
     if up_mask.dim() != 4 or tuple(up_mask.shape) != (B, 576, h, w):
         raise ValueError(f'up_mask must be [B, 576, h, w] = {(B, 576, h, w)}, got {tuple(up_mask.shape)}')
@@ -305,7 +321,7 @@ def _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale):
     pos, pos_dev = _tile_positions(H, W, tile_size, params.device, params.dtype)
     if _cvx_kernels_serve(params, up_mask, bm) and tile_size in _CVX_KERNEL_TILES:
         from .. import ops
-        return ops.CvxCurveTrajFn.apply(params, up_mask, bm, float(scale), int(tile_size)), pos
+        return ops.CvxCurveTrajFn.apply(params.float(), up_mask, bm.float(), float(scale), int(tile_size)), pos
     return _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale), pos
 
 
@@ -317,16 +333,16 @@ def flows_from_bezier(params, times, up_mask=None, scale=1.0):
     B, c2, h, w = params.shape
     assert c2 % 2 == 0, params.shape
     d = c2 // 2
-    bm = _device_basis('bernstein', times, (int(d),), params.device, params.dtype)    # [n_t, d]
+    bm = _device_basis('bernstein', times, (int(d),), params.device, _basis_dtype(params))    # [n_t, d]
     if up_mask is not None:
         if up_mask.dim() != 4 or tuple(up_mask.shape) != (B, 576, h, w):
             raise ValueError(f'up_mask must be [B, 576, h, w] = {(B, 576, h, w)}, got {tuple(up_mask.shape)}')
         needs_grad = torch.is_grad_enabled() and (params.requires_grad or up_mask.requires_grad)
         if not needs_grad and _cvx_kernels_serve(params, up_mask, bm):
             from .. import ops
-            return ops.cvx_flows(params, up_mask, bm, float(scale))
+            return ops.cvx_flows(params, up_mask, bm, float(scale))          # (fp32 flows; a 16-bit mask is read in place)
         params = _cvx_upsample(params, up_mask)
-    return torch.einsum('bcdhw,td->tbchw', params.reshape(B, 2, d, *params.shape[-2:]), bm) * scale
+    return torch.einsum('bcdhw,td->tbchw', params.reshape(B, 2, d, *params.shape[-2:]), bm.to(params.dtype)) * scale
 
 
 def bernstein_basis(times, degree):
@@ -426,12 +442,13 @@ def _curve_matrix(params, times, curve_type, basis_network):
     """(degree, the basis matrix of `curve_basis` on the device and in the dtype of `params`) for the entry points below."""
     c2 = params.shape[1]
     assert params.dim() == 4 and c2 % 2 == 0, params.shape
-    return c2 // 2, curve_basis(curve_type, times, c2 // 2, basis_network, device=params.device).to(params.dtype)
+    return c2 // 2, curve_basis(curve_type, times, c2 // 2, basis_network, device=params.device).to(_basis_dtype(params))
 
 
 def trajectories_from_curves(params, times, tile_size, image_shape, curve_type='BEZIER', basis_network=None, scale=1.0, up_mask=None):
     """`trajectories_from_bezier` for any of the reference's curve types (`curve_basis`: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the
-    latter with its `basis_network` on the device of `params`) and for 'BSPLINE' (the bits of `trajectories_from_bspline`): the same contracts, the same routing -- fp32 GPU tensors with
+    latter with its `basis_network` on the device of `params`) and for 'BSPLINE' (the bits of `trajectories_from_bspline`): the same contracts, the same routing -- fp32, fp16 or bf16 GPU tensors (16-bit ones as `trajectories_from_bezier` says: the mask
+    read in place, fp32 trajectories) with
     d <= 16 (and, with `up_mask`, a basis matrix within 48 KB and a tile size of 2, 4, 8 or 16) run in the fused nodes
     (ops.CurveTrajFn / ops.CvxCurveTrajFn), everything else in their plain-torch mirrors -- and with 'BEZIER' the same launches
     and bits.  Times are evaluated as a LIST (no scalar-time shortcut, see `curve_basis`): a learned curve is not zero at t = 0.
@@ -460,9 +477,9 @@ def flows_from_curves(params, times, curve_type='BEZIER', basis_network=None, up
         needs_grad = torch.is_grad_enabled() and (params.requires_grad or up_mask.requires_grad)
         if not needs_grad and _cvx_kernels_serve(params, up_mask, bm):
             from .. import ops
-            return ops.cvx_flows(params, up_mask, bm, float(scale))
+            return ops.cvx_flows(params, up_mask, bm, float(scale))          # (fp32 flows; a 16-bit mask is read in place)
         params = _cvx_upsample(params, up_mask)
-    return torch.einsum('bcdhw,td->tbchw', params.reshape(B, 2, d, *params.shape[-2:]), bm) * scale
+    return torch.einsum('bcdhw,td->tbchw', params.reshape(B, 2, d, *params.shape[-2:]), bm.to(params.dtype)) * scale
 
 
 def trajectories_from_bezier(params, times, tile_size, image_shape, scale=1.0, up_mask=None):
@@ -480,12 +497,20 @@ def trajectories_from_bezier(params, times, tile_size, image_shape, scale=1.0, u
     With `up_mask` [B, 576, h, w] (the RAFT-spline output head: reference curves/base.py:35-38, raft_spline/utils.py:30-45) `params`
     are the control points on the 1/8 grid, `image_shape` must be (8h, 8w) (ValueError otherwise), and the curves are those of
     `BezierCurves(params).create_upsampled(up_mask)` sampled at the tile centres: the factor 8 of cvx_upsample is applied inside,
-    `scale` multiplies on top.  Differentiable w.r.t. `params` and `up_mask`."""
+    `scale` multiplies on top.  Differentiable w.r.t. `params` and `up_mask`.
+
+    fp16 / bf16 on the GPU (a network under autocast, a .half() / .bfloat16() model) within the kernels' limits takes the fused nodes:
+    the mask is read in its own dtype (no .float() copy; the conversion at the load is exact) and its gradient comes back in that
+    dtype, computed in fp32 and rounded once; control points that are not fp32 go through a differentiable .float(); basis matrix
+    and tile positions are fp32.  The trajectories are then fp32 -- bit for bit those of the upcast inputs -- and NOT the 16-bit
+    tensor the plain-torch mirror used to return for such inputs: displacement + pixel position in bf16 (8 significant bits) lies on
+    a 2-4 px lattice between 256 and 640 px.  `FocusLoss.calc` converts its trajectories to fp32 anyway.  CPU tensors, and shapes
+    beyond the kernels' limits, still take the mirrors in their own dtype."""
     B, c2, h, w = params.shape
     H, W = (int(v) for v in image_shape)
     assert c2 % 2 == 0 and (up_mask is not None or (h == H // tile_size and w == W // tile_size)), (params.shape, image_shape, tile_size)
     d = c2 // 2
-    bm = _device_basis('bernstein', times, (int(d),), params.device, params.dtype)    # [n_t, d]
+    bm = _device_basis('bernstein', times, (int(d),), params.device, _basis_dtype(params))    # [n_t, d]
     if up_mask is not None:
         return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale)
     return _curve_trajectories(params, bm, tile_size, H, W, scale)
@@ -537,7 +562,7 @@ def trajectories_from_bspline(params, times, tile_size, image_shape, scale=1.0, 
     H, W = (int(v) for v in image_shape)
     assert c2 % 2 == 0 and (up_mask is not None or (h == H // tile_size and w == W // tile_size)), (params.shape, image_shape, tile_size)
     d = c2 // 2
-    bm = _device_basis('bspline', times, (int(d + 1), int(degree)), params.device, params.dtype)      # [n_t, d]
+    bm = _device_basis('bspline', times, (int(d + 1), int(degree)), params.device, _basis_dtype(params))      # [n_t, d]
     if up_mask is not None:
         return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale)
     return _curve_trajectories(params, bm, tile_size, H, W, scale)

@@ -11,6 +11,7 @@ from . import flow as _flow
 _BASIS_CODE = {'polynomial': 0, 'dct': 1, 'learned': 2}          # include/mpcmax.h: MPC_BASIS_POLY / _DCT / _MATRIX
 _GRID_POS_CACHE = {}
 GRID_KMAX = 16
+GRID_DTYPES = (torch.float32, torch.float16, torch.bfloat16)          # what the kernels read in place (include/mpcmax.h: MPC_DT_*)
 GRID_PHI_FLOATS = 4096          # n_t * k limit of the kernels (csrc/grid_traj.hip: GT_PHI_BYTES, the LDS slice of the basis)
 
 
@@ -48,12 +49,16 @@ def trajectories_from_grid(coeff_grid, times, num_basis, basis_type, tile_size, 
     grid's device) -- tile centres (tile // 2 + iy * tile, tile // 2 + ix * tile), row-major.  `pixel_positions` is a cached tensor
     shared by all calls of the same (H, W, tile, device): do not modify it in place.
 
-    A CUDA fp32 grid with 1 <= k <= 16 and n_t * k <= 4096 runs one kernel forward and one backward (two for 'learned', whose
-    [n_t, k] basis difference keeps its gradient, so the MLP trains), on torch's current stream, without a host synchronisation, fp32
-    contiguous trajectories.  Anything else -- CPU tensors, fp16 / bf16, k > 16, more than 4096 basis values n_t * k -- takes the
-    plain-torch mirror (coeffs_grid_to_list + compute_basis), which
-    returns the dtype of the grid.  Object masks other than the tile mask are not served here: use coeffs_grid_to_list and
-    compute_basis with the mask, as the reference does."""
+    A CUDA grid in fp32, fp16 or bf16 with 1 <= k <= 16 and n_t * k <= 4096 runs one kernel forward and one backward (two for
+    'learned', whose [n_t, k] basis difference keeps its gradient, so the MLP trains), on torch's current stream, without a host
+    synchronisation, fp32 contiguous trajectories.  A 16-bit grid (a network under autocast, a .half() / .bfloat16() model) is read
+    as it is -- no .float() copy; the conversion at the load is exact, so the trajectories are, bit for bit, those of grid.float()
+    -- and its gradient comes back in the grid's dtype, computed in fp32 and rounded once.  The trajectories of a CUDA 16-bit grid
+    are therefore fp32, NOT the grid's dtype as they were when such a grid took the mirror: displacement + pixel position in bf16
+    (8 significant bits) puts positions between 256 and 640 px on a 2-4 px lattice, which is useless to the loss.  Anything else
+    -- CPU tensors, other dtypes, k > 16, more than 4096 basis values n_t * k -- takes the plain-torch mirror (coeffs_grid_to_list +
+    compute_basis), which returns the dtype of the grid.  Object masks other than the tile mask are not served here: use
+    coeffs_grid_to_list and compute_basis with the mask, as the reference does."""
     if coeff_grid.dim() == 4:
         coeff_grid = coeff_grid[:, None]                        # trajectory_net.py:113-114
     B, S, c2, H, W = coeff_grid.shape
@@ -64,7 +69,7 @@ def trajectories_from_grid(coeff_grid, times, num_basis, basis_type, tile_size, 
         raise ValueError(f'coeff_grid has {c2} channels, 2 * num_basis = {2 * k} expected')
     dev = coeff_grid.device
     pos = _grid_positions(H, W, tile, dev)
-    if coeff_grid.is_cuda and coeff_grid.dtype == torch.float32 and 1 <= k <= GRID_KMAX and times.numel() * k <= GRID_PHI_FLOATS:
+    if coeff_grid.is_cuda and coeff_grid.dtype in GRID_DTYPES and 1 <= k <= GRID_KMAX and times.numel() * k <= GRID_PHI_FLOATS:
         from .. import ops
         if times.device != dev:
             times = times.to(dev)

@@ -857,6 +857,31 @@ int mpc_corr_pyramid_multi_supported(const mpc_corr_desc *desc, int D, const mpc
 int mpc_corr_pyramid_multi_fwd(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream);
 int mpc_corr_pyramid_multi_bwd(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, void *ws, void *stream);
 
+/* The same four calls on feature maps of element type `dtype` (MPC_DT_*, additive, still version 107): what the RAFT-spline encoders
+ * hand over under autocast, read in place instead of the reference's `.float()` copies (raft.py:126).  fmap1 / fmap2 and grad_fmap1 /
+ * grad_fmap2 are of that type -- in the list form the pointers of mpc_corr_refs are READ AS that type, one dtype per call --; levels,
+ * cotangents and the workspace stay fp32, and the workspace and `_supported` queries are those above.  The fp32 entry points ARE
+ * these with MPC_DT_F32: the same kernels and bits as before.  Any other dtype code: MPC_E_UNSUPPORTED with an error string, no launch.
+ * With MPC_DT_F16 / MPC_DT_BF16:
+ *   level 0 of the forward runs on the 16-bit matrix cores (v_mfma_f32_32x32x16_f16 / _bf16, k_corr_pyr_gemm16): products of two
+ *     16-bit values are exact in fp32 and the accumulation is fp32, so the element is the sum the fp32 call forms on the upcast
+ *     tensors in another order (16 channels per instruction): equal where every partial sum is exact, otherwise within
+ *     gamma(D) * sum |fmap1| |fmap2| / sqrt(D), gamma(n) = (n + 8) u / (1 - (n + 8) u) with u = 2^-23 (the rounding of the
+ *     instruction's adder is not specified).  fp16 subnormal inputs are multiplied as the values they are, not flushed.
+ *   everything else -- the pools, the forward levels >= 1, both backward products, the reduce and the gather -- converts the 16-bit
+ *     element at the load (exact) and is the fp32 call's arithmetic on the upcast tensors bit for bit, on v_mfma_f32_32x32x2_f32
+ *     with the same tiling, k splits and order of partials.  The forward is two GEMM launches (level 0, then the levels above).
+ *   gradients are computed in fp32 as in the fp32 call and rounded ONCE to `dtype`, round to nearest even (as
+ *     torch.Tensor.to(dtype)); grad_fmap2 with 16-byte stores of 8 elements where w is a multiple of 8 and the tensors are 16-byte
+ *     aligned, element by element otherwise; the split-k partials and the per-level gradients in the workspace stay fp32.
+ *   16-byte loads of 8 elements at level 0 where the map is 16-byte aligned and h * w is a multiple of 8, element loads otherwise
+ *     (any 2-byte aligned view is served). */
+int mpc_corr_pyramid_fwd_dt(const mpc_corr_desc *desc, int D, const void *fmap1, const void *fmap2, int32_t dtype, void *ws, void *stream);
+int mpc_corr_pyramid_bwd_dt(const mpc_corr_desc *desc, int D, const void *fmap1, const void *fmap2, void *grad_fmap1, void *grad_fmap2,
+                            int32_t dtype, void *ws, void *stream);
+int mpc_corr_pyramid_multi_fwd_dt(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, int32_t dtype, void *ws, void *stream);
+int mpc_corr_pyramid_multi_bwd_dt(const mpc_corr_desc *desc, int D, const mpc_corr_refs *refs, int32_t dtype, void *ws, void *stream);
+
 /* ---- the ground-truth flow targets of the EVIMO2 / MultiFlow configurations (what mpc_val_metrics takes as flow_gt / flow_valid)
  * from the raw multi-step flow, as one launch.
  * Reference: src/loader/evimo2/datasubset.py:171-188 (mode 0), src/loader/multiflow/sample.py:108-139 with downsample=True (mode 1).

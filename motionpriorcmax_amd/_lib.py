@@ -225,6 +225,10 @@ SIGNATURES = {
     'mpc_corr_pyramid_multi_supported': (cint, [cdp, cint, crp]),
     'mpc_corr_pyramid_multi_fwd': (cint, [cdp, cint, crp, vp, vp]),
     'mpc_corr_pyramid_multi_bwd': (cint, [cdp, cint, crp, vp, vp]),
+    'mpc_corr_pyramid_fwd_dt': (cint, [cdp, cint, vp, vp, i32, vp, vp]),
+    'mpc_corr_pyramid_bwd_dt': (cint, [cdp, cint] + [vp] * 4 + [i32, vp, vp]),
+    'mpc_corr_pyramid_multi_fwd_dt': (cint, [cdp, cint, crp, i32, vp, vp]),
+    'mpc_corr_pyramid_multi_bwd_dt': (cint, [cdp, cint, crp, i32, vp, vp]),
     'mpc_flow_targets_supported': (cint, [tsp]),
     'mpc_flow_targets': (cint, [tsp] + [vp] * 6),
     'mpc_dsec_flow_decode': (cint, [vp, vp, vp, i32, i32, i32, vp]),

@@ -1657,10 +1657,13 @@ def _corr_pyramid_ws(desc, D, backward, dev):
 
 class CorrPyramidFn(torch.autograd.Function):
     """The RAFT-spline correlation pyramid (utils.corr_pyramid_fused; reference corr.py:235-270, 106-123): fmap1 [B, D, h, w],
-    fmap2 [T, B, D, h, w] (fp32, contiguous, on the GPU) and the host list of level counts -> the levels [n_l, B*h*w, 1, h_l, w_l] as a
-    tuple, one autograd node (csrc/corr_pyramid.hip: every level is its own fp32-MFMA GEMM against the pooled feature map, written
-    once).  The backward computes only the requested gradients, takes a missing level cotangent as zero, and every element of a
-    gradient it returns is written by a kernel (no memset).  No host synchronisation; bitwise reproducible."""
+    fmap2 [T, B, D, h, w] (both fp32, both fp16 or both bf16; contiguous, on the GPU) and the host list of level counts -> the levels
+    [n_l, B*h*w, 1, h_l, w_l], fp32 whatever the maps are, as a tuple, one autograd node (csrc/corr_pyramid.hip: every level is its
+    own fp32-MFMA GEMM against the pooled feature map, written once).  16-bit maps are read in place (no .float() copy): level 0 runs
+    on the 16-bit matrix cores -- the same sum in another order --, everything else is the fp32 arithmetic on the upcast maps bit
+    for bit, and the gradients come back in the maps' dtype, rounded once.  The backward computes only the requested gradients, takes
+    a missing level cotangent as zero, and every element of a gradient it returns is written by a kernel (no memset).  No host
+    synchronisation; bitwise reproducible."""
 
     @staticmethod
     def forward(ctx, fmap1, fmap2, num_levels_per_target):
@@ -1670,12 +1673,14 @@ class CorrPyramidFn(torch.autograd.Function):
         dev = fmap1.device
         desc, tix = corr_pyramid_desc(B, h, w, num_levels_per_target)
         levels = [torch.empty((len(ts), B * h * w, 1, h >> l, w >> l), dtype=torch.float32, device=dev) for l, ts in enumerate(tix)]
-        f1, f2 = fmap1.detach(), fmap2.detach()
+        (f1, dt), (f2, dt2) = _net(fmap1), _net(fmap2)
+        if dt != dt2:
+            raise ValueError(f'CorrPyramidFn: fmap1 is {fmap1.dtype}, fmap2 {fmap2.dtype}: one dtype per call')
         if B > 0:
             for l, lv in enumerate(levels):
                 desc.level[l] = lv.data_ptr()
             ws = _corr_pyramid_ws(desc, D, 0, dev)
-            _call('mpc_corr_pyramid_fwd', dev, ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(ws))
+            _call('mpc_corr_pyramid_fwd_dt', dev, ctypes.byref(desc), D, _ptr(f1), _ptr(f2), dt, _ptr(ws), label='mpc_corr_pyramid_fwd')
         ctx.nl = [int(v) for v in num_levels_per_target]
         ctx.set_materialize_grads(False)                              # (an unused level arrives as None, not as a volume of zeros)
         ctx.save_for_backward(f1, f2)
@@ -1689,7 +1694,7 @@ class CorrPyramidFn(torch.autograd.Function):
         want1, want2 = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not want1 and not want2:
             return None, None, None
-        g1 = torch.empty_like(f1) if want1 else None                  # (every element is written by a kernel)
+        g1 = torch.empty_like(f1) if want1 else None                  # (every element is written by a kernel; in the maps' dtype)
         g2 = torch.empty_like(f2) if want2 else None
         if B > 0:
             desc, _ = corr_pyramid_desc(B, h, w, ctx.nl)
@@ -1697,7 +1702,8 @@ class CorrPyramidFn(torch.autograd.Function):
             for l, g in enumerate(gl):
                 desc.grad_level[l] = None if g is None else g.data_ptr()
             ws = _corr_pyramid_ws(desc, D, 1, dev)
-            _call('mpc_corr_pyramid_bwd', dev, ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(g1), _ptr(g2), _ptr(ws))
+            _call('mpc_corr_pyramid_bwd_dt', dev, ctypes.byref(desc), D, _ptr(f1), _ptr(f2), _ptr(g1), _ptr(g2), _DT_CODE[f1.dtype], _ptr(ws),
+                  label='mpc_corr_pyramid_bwd')
         return g1, g2, None
 
 
@@ -1712,7 +1718,8 @@ def corr_pyramid_refs(counts):
 class CorrPyramidMultiFn(torch.autograd.Function):
     """CorrPyramidFn over several references (utils.corr_pyramid_fused in list form; reference corr.py:221-225, 246-260, 282-302:
     the events-plus-frames pyramid): `num_levels` the host list of R lists of level counts, then fmap1[0..R) [B, D, h, w] and
-    fmap2[0..R) [n_r, B, D, h, w] (fp32, contiguous, on one GPU) -> the levels of the merged target list as a tuple, one autograd
+    fmap2[0..R) [n_r, B, D, h, w] (all fp32, all fp16 or all bf16 -- as CorrPyramidFn --, contiguous, on one GPU) -> the fp32
+    levels of the merged target list as a tuple, one autograd
     node with the launches of the single-reference node (csrc/corr_pyramid.hip: a slot reads the feature maps of its reference where
     they lie).  The backward computes only the requested ones of the 2R gradients, each written straight into its own tensor, every
     element by a kernel; a missing level cotangent is zero.  Equal, bit for bit, to the R single-reference nodes."""
@@ -1727,7 +1734,9 @@ class CorrPyramidMultiFn(torch.autograd.Function):
         nl = [int(v) for ref in num_levels for v in ref]
         desc, tix = corr_pyramid_desc(B, h, w, nl)
         levels = [torch.empty((len(ts), B * h * w, 1, h >> l, w >> l), dtype=torch.float32, device=dev) for l, ts in enumerate(tix)]
-        fm = [t.detach() for t in fmaps]
+        fm = [_net(t)[0] for t in fmaps]
+        if len({t.dtype for t in fm}) != 1:
+            raise ValueError(f'CorrPyramidMultiFn: feature maps of dtypes {[str(t.dtype) for t in fmaps]}: one dtype per call')
         if B > 0:
             for l, lv in enumerate(levels):
                 desc.level[l] = lv.data_ptr()
@@ -1736,7 +1745,8 @@ class CorrPyramidMultiFn(torch.autograd.Function):
                 refs.fmap1[r], refs.fmap2[r] = fm[r].data_ptr(), fm[R + r].data_ptr()
             nws = _query('mpc_corr_pyramid_multi_workspace_bytes', dev, ctypes.byref(desc), D, ctypes.byref(refs), 0)
             ws = torch.empty((nws + 3) // 4, dtype=torch.float32, device=dev)
-            _call('mpc_corr_pyramid_multi_fwd', dev, ctypes.byref(desc), D, ctypes.byref(refs), _ptr(ws))
+            _call('mpc_corr_pyramid_multi_fwd_dt', dev, ctypes.byref(desc), D, ctypes.byref(refs), _DT_CODE[fm[0].dtype], _ptr(ws),
+                  label='mpc_corr_pyramid_multi_fwd')
         ctx.num_levels = [[int(v) for v in ref] for ref in num_levels]
         ctx.set_materialize_grads(False)                              # (an unused level arrives as None, not as a volume of zeros)
         ctx.save_for_backward(*fm)
@@ -1764,7 +1774,8 @@ class CorrPyramidMultiFn(torch.autograd.Function):
                 refs.grad_fmap2[r] = None if grads[R + r] is None else grads[R + r].data_ptr()
             nws = _query('mpc_corr_pyramid_multi_workspace_bytes', dev, ctypes.byref(desc), D, ctypes.byref(refs), 1)
             ws = torch.empty((nws + 3) // 4, dtype=torch.float32, device=dev)
-            _call('mpc_corr_pyramid_multi_bwd', dev, ctypes.byref(desc), D, ctypes.byref(refs), _ptr(ws))
+            _call('mpc_corr_pyramid_multi_bwd_dt', dev, ctypes.byref(desc), D, ctypes.byref(refs), _DT_CODE[fm[0].dtype], _ptr(ws),
+                  label='mpc_corr_pyramid_multi_bwd')
         return (None, *grads)
 
 

@@ -3,9 +3,10 @@ the loop that calls it: raft.py:165-189).
 
 `corr_pyramid` is the reference's batched matmul, division and average pools in plain torch: the mirror, the CPU path and the comparator.
 `corr_pyramid_fused` builds the same pyramid on the GPU as one autograd node (ops.CorrPyramidFn, csrc/corr_pyramid.hip): every level
-is its own fp32-MFMA GEMM against the pooled feature map, written once; inputs the kernels do not take -- CPU tensors, other dtypes,
-non-contiguous tensors, D that is no multiple of 4 or above 512, more than 16 targets or 6 levels -- go to `corr_pyramid`.  Both take
-one reference (tensors) or several (lists: the events-plus-frames pyramid of the reference's default model, ops.CorrPyramidMultiFn).
+is its own fp32-MFMA GEMM against the pooled feature map, written once; fp16 / bf16 feature maps (the encoders under autocast) are read
+in place, level 0 on the 16-bit matrix cores, and yield fp32 levels as raft.py:126 intends; inputs the kernels do not take -- CPU
+tensors, other dtypes, non-contiguous tensors, D that is no multiple of 4 or above 512, more than 16 targets or 6 levels -- go to
+`corr_pyramid`.  Both take one reference (tensors) or several (lists: the events-plus-frames pyramid of the reference's default model, ops.CorrPyramidMultiFn).
 `CorrLookup` is the network's one gather, 12 times per forward: on the GPU one kernel each way (ops.CorrLookupFn, csrc/corr_lookup.hip); everything the kernels do not take --
 CPU tensors, other dtypes, non-contiguous tensors, radius > 4, more than 16 targets or control points, more than 6 levels -- runs the
 plain-torch mirror below, which is written as the reference's own operator chain (coordinate tensor, normalisation to [-1, 1],
@@ -16,6 +17,16 @@ import torch.nn.functional as F
 from .basis import _basis_trains, _device_basis, curve_basis
 
 _KERNEL_MAX_RADIUS, _KERNEL_MAX_TARGETS, _KERNEL_MAX_D, _KERNEL_MAX_LEVELS = 4, 16, 16, 6
+_PYRAMID_DTYPES = (torch.float32, torch.float16, torch.bfloat16)         # what the pyramid kernels read in place (include/mpcmax.h: MPC_DT_*)
+
+
+def _one_dtype(tensors):
+    """The served feature maps of one call in ONE dtype: as they are where they share it (16-bit maps then go to the kernels in
+    place), else the 16-bit ones through a differentiable .float() -- a map upcast by hand beside one that is not -- for the fp32
+    node; each gradient still arrives in its input's dtype (the .float() node rounds it)."""
+    if len({t.dtype for t in tensors}) == 1:
+        return list(tensors)
+    return [t if t.dtype == torch.float32 else t.float() for t in tensors]
 
 
 def _levels_list(num_levels_per_target):
@@ -100,7 +111,7 @@ def _corr_pyramid_fused_refs(fmap1, fmap2, num_levels_per_target):
         return corr_pyramid_fused(f1s[0], f2s[0], nls[0])
     B, D, h, w = f1s[0].shape
     dev = f1s[0].device
-    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev for t in f1s + f2s):
+    if not all(t.is_cuda and t.dtype in _PYRAMID_DTYPES and t.is_contiguous() and t.device == dev for t in f1s + f2s):
         return corr_pyramid(f1s, f2s, nls)
     import ctypes
     from .. import ops, _lib as C
@@ -111,15 +122,19 @@ def _corr_pyramid_fused_refs(fmap1, fmap2, num_levels_per_target):
     refs = ops.corr_pyramid_refs([len(ref) for ref in nls])
     if C.lib().mpc_corr_pyramid_multi_supported(ctypes.byref(desc), D, ctypes.byref(refs)) != 0:
         return corr_pyramid(f1s, f2s, nls)
-    return list(ops.CorrPyramidMultiFn.apply(nls, *f1s, *f2s)), tix
+    return list(ops.CorrPyramidMultiFn.apply(nls, *_one_dtype(f1s + f2s))), tix
 
 
 def corr_pyramid_fused(fmap1, fmap2, num_levels_per_target):
     """`corr_pyramid` with the same arguments, checks, level shapes and target_indices, built on the GPU by ops.CorrPyramidFn where the
-    kernels serve the inputs (fp32, contiguous, CUDA, D a multiple of 4 up to 512, at most 16 targets and 6 levels): one autograd
-    node with gradients to fmap1 and fmap2, no host synchronisation, bitwise reproducible.  Everything else returns
-    `corr_pyramid(...)`.  The list form (several references: events plus frames) goes to ops.CorrPyramidMultiFn under the same
-    conditions on every tensor and on the merged target list, and at most 4 references (MPC_CORR_MAX_REFS): one node with the same
+    kernels serve the inputs (fp32, fp16 or bf16, contiguous, CUDA, D a multiple of 4 up to 512, at most 16 targets and 6 levels):
+    one autograd node with gradients to fmap1 and fmap2, no host synchronisation, bitwise reproducible.  Everything else returns
+    `corr_pyramid(...)`.  Served 16-bit maps yield fp32 levels (what raft.py:126 intends with its `.float()`; `corr_pyramid` itself
+    keeps the dtype of its input): where all maps of a call share one 16-bit dtype they are read in place -- level 0 on the 16-bit
+    matrix cores, the same sum as on the upcast maps in another order; the levels above and both gradients the fp32 node's on the
+    upcast maps bit for bit, the gradients rounded once to the maps' dtype --; where the dtypes are mixed the 16-bit ones go
+    through a differentiable `.float()` and the fp32 node runs.  The list form (several references: events plus frames) goes to
+    ops.CorrPyramidMultiFn under the same conditions on every tensor and on the merged target list, and at most 4 references (MPC_CORR_MAX_REFS): one node with the same
     launches, gradients to all 2R feature maps, equal bit for bit to the R single-reference nodes."""
     if isinstance(fmap1, (list, tuple)):
         return _corr_pyramid_fused_refs(fmap1, fmap2, num_levels_per_target)
@@ -130,7 +145,7 @@ def corr_pyramid_fused(fmap1, fmap2, num_levels_per_target):
     n, B, D, h, w = f2.shape
     if tuple(fmap1.shape) != (B, D, h, w) or len(nl) != n:
         raise ValueError(f'fmap1 {tuple(fmap1.shape)}, fmap2 {tuple(f2.shape)} and {len(nl)} level counts do not belong together')
-    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == fmap1.device for t in (fmap1, f2)):
+    if not all(t.is_cuda and t.dtype in _PYRAMID_DTYPES and t.is_contiguous() and t.device == fmap1.device for t in (fmap1, f2)):
         return corr_pyramid(fmap1, fmap2, nl)
     import ctypes
     from .. import ops, _lib as C
@@ -139,7 +154,7 @@ def corr_pyramid_fused(fmap1, fmap2, num_levels_per_target):
     desc, tix = ops.corr_pyramid_desc(B, h, w, nl)
     if C.lib().mpc_corr_pyramid_supported(ctypes.byref(desc), D) != 0:
         return corr_pyramid(fmap1, fmap2, nl)
-    return list(ops.CorrPyramidFn.apply(fmap1, f2, nl)), tix
+    return list(ops.CorrPyramidFn.apply(*_one_dtype([fmap1, f2]), nl)), tix
 
 
 def coords_grid(batch, ht, wd, device, dtype=torch.float32):
@@ -238,7 +253,8 @@ class CorrLookup:
         """The lookup over the pyramid of `corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)`: what raft.py:129 / :161 build
         from the two feature maps, with the pyramid as one autograd node back to the feature maps.  In list form (fmap1, fmap2 and
         num_levels_per_target lists of R entries: raft.py:131-144 with boundary images, events then frames) the lookup is over the
-        merged level counts."""
+        merged level counts.  fp16 / bf16 feature maps that the pyramid kernels serve give fp32 levels, so the lookups stay on
+        their kernels."""
         levels, _ = corr_pyramid_fused(fmap1, fmap2, num_levels_per_target)
         if isinstance(fmap1, (list, tuple)):
             num_levels_per_target = [v for ref in num_levels_per_target for v in _levels_list(ref)]

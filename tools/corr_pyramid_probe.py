@@ -60,7 +60,7 @@ def kernel_times(fn, reps):
     n = int(L.mpc_profile_stop(names, len(names), ms, cap))
     out = {}
     for nm, t in zip(names.value.decode().split('\n')[:n], ms[:n]):
-        k = nm.strip().lstrip('(').rstrip(')').strip()
+        k = nm.strip().lstrip('(').rstrip(')').strip().replace(', T>', '>').replace('<T>', '')      # (the element type of a templated kernel)
         out[k] = out.get(k, 0.0) + 1e3 * t / reps
     return out
 

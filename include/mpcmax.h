@@ -448,6 +448,33 @@ int mpc_pool2_fwd(const float *in, float *out, int32_t nimg, int32_t H, int32_t 
 int mpc_pool2_bwd_add(const float *small, const float *coef_small, float *big, const float *coef_big, int32_t nimg,
                       int32_t H, int32_t W, void *stream);
 
+/* UNPINNED EXTENSION: the IWE pyramid as one pass behind ANY forward of the library (csrc/iwe_pyramid.hip).  Every route ends
+ * its forward in the raw IWE, the unscaled adjoint image grad_iwe and `scal` with d focus / d iwe_raw = scal[MPC_SCAL_GCOEF] *
+ * grad_iwe; this pass adds the coarse levels to the latter two, so the backward of the route runs unchanged.  The definition is
+ * the one of the helpers above: level l + 1 = 2x2 average of the raw level l (0.25f * ((p[0] + p[1]) + (p[W] + p[W + 1]))), the
+ * 3x3 reflect blur and the gradient-magnitude objective on every level's own elements, focus = sum over the levels of 1 / val_l.
+ *   mpc_iwe_pyramid_supported        host only, no device: 0, or MPC_E_UNSUPPORTED (levels outside [2, 6], MPC_F_OBJ_VARIANCE,
+ *                                    T != 1), MPC_E_SHAPE (H or W not divisible by 2^(levels - 1), a coarsest level below 3x3, a
+ *                                    shape mpc_workspace_bytes refuses), MPC_E_NULL.  The other two refuse the same, before any launch.
+ *   mpc_iwe_pyramid_workspace_bytes  bytes of `pws` (host only).  Layout, part of the ABI: with want_grad the unscaled adjoint
+ *                                    images of levels 1 .. levels - 1, [nimg][H >> l][W >> l] floats each, level l at float offset
+ *                                    sum_{1 <= j < l} roundup(nimg * (H >> j) * (W >> j), 64); then the band sums.  nimg = B * P.
+ *   mpc_iwe_pyramid_fwd              iwe_raw [nimg][H][W] (16-byte aligned); grad_iwe in/out, or NULL: no gradient (two launches
+ *                                    instead of three); scal [MPC_SCAL_COUNT] in/out: FOCUS and LOSS gain the coarse levels' 1 / val_l
+ *                                    (fp32, level by level; LOSS = the new FOCUS + SMOOTH), VAL and GCOEF stay level 0's; scal_out
+ *                                    (or NULL): loss and focus once more, as mpc_focus_buffers.scal_out; level_scal (out)
+ *                                    [levels][MPC_SCAL_COUNT]: row l = the scalars of level l alone (row 0: `scal` as it came) and in
+ *                                    [MPC_SCAL_PYR_RATIO] the ratio r_l the fold used: grad_iwe[y][x] += sum_{l >= 1} r_l *
+ *                                    g_l[y >> l][x >> l], r_l = 4^-l GCOEF_l / GCOEF_0, or 0 where a coefficient of level 0 .. l is 0,
+ *                                    inf or NaN (mpc_pool2_bwd_add's rule: a flat level passes nothing on).  pws: a workspace of its
+ *                                    own -- the step's `ws` carries state to the backward and is not touched.  Kernels only, on
+ *                                    `stream`: no memset / memcpy node, no atomics, no host synchronisation; bitwise reproducible. */
+#define MPC_SCAL_PYR_RATIO 5
+int mpc_iwe_pyramid_supported(const mpc_shape *s, int32_t levels);
+int64_t mpc_iwe_pyramid_workspace_bytes(const mpc_shape *s, int32_t levels, int32_t want_grad);
+int mpc_iwe_pyramid_fwd(const mpc_shape *s, int32_t levels, const float *iwe_raw, float *grad_iwe, float *scal, float *scal_out,
+                        float *level_scal, void *pws, void *stream);
+
 /* y[i] = a[0] * x[i] (device scalar a; used to scale the smoothness gradient by grad_out). */
 int mpc_scale(const float *x, const float *a, float *y, int64_t count, void *stream);
 

@@ -27,6 +27,7 @@ E_NULL, E_SHAPE, E_UNSUPPORTED = -1, -2, -4        # include/mpcmax.h
 BASIS_POLY, BASIS_DCT, BASIS_MATRIX = 0, 1, 2
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2                   # include/mpcmax.h: MPC_DT_*, the element type of a `_dt` entry point's network tensor
 SCAL_LOSS, SCAL_FOCUS, SCAL_SMOOTH, SCAL_VAL, SCAL_GCOEF, SCAL_COUNT = 0, 1, 2, 3, 4, 8
+SCAL_PYR_RATIO = 5                                  # level_scal rows of mpc_iwe_pyramid_fwd: the fold ratio r_l
 
 class Shape(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in
@@ -177,6 +178,9 @@ SIGNATURES = {
     'mpc_event_splat_bwd_ordered': (cint, [sp] + [vp] * 11),
     'mpc_pool2_fwd': (cint, [vp, vp, i32, i32, i32, vp]),
     'mpc_pool2_bwd_add': (cint, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    'mpc_iwe_pyramid_supported': (cint, [sp, i32]),
+    'mpc_iwe_pyramid_workspace_bytes': (i64, [sp, i32, i32]),
+    'mpc_iwe_pyramid_fwd': (cint, [sp, i32] + [vp] * 7),
     'mpc_scale': (cint, [vp, vp, vp, i64, vp]),
     'mpc_voxel_workspace_bytes': (i64, [vsp]),
     'mpc_voxel_grid': (cint, [vsp] + [vp] * 5),

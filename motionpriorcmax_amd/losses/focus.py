@@ -26,8 +26,16 @@ class FocusLoss(base.TrajectoryLossBase):
         smooth_type (str): 'on_flow_to_tref' or 'on_flow_to_next'.
         loss_type (str, build-side extension): 'gradient_magnitude' (what the reference hard-codes,
             focus.py:90-91) or 'variance' (reference src/utils/loss.py:14-16).
-        pyramid_levels (int, UNPINNED extension, default 1 = the reference): IWE pyramid of that many levels (2x2 averages of the
-            raw IWE), the focus term summed over the levels (`ops.PyramidFocusFn`); BASELINE.json names one, the reference has none.
+        pyramid_levels (int, UNPINNED extension, default 1 = the reference): IWE pyramid of that many levels, 2 .. 6 -- level l + 1 is
+            the 2x2 average of the raw level l, every level goes through the reference's blur and gradient-magnitude objective on its
+            own elements, and the focus term is the sum of the levels' 1 / val; `iwes` stay the blurred level-0 images, the smoothness
+            term is untouched.  BASELINE.json names one, the reference has none.  Served on EVERY loss route -- `calc` (eager, with
+            `event_offsets`, static_shapes and the automatic capture), `calc_per_event_basis`, `calc_per_event_curves` and their
+            unfused cross-checks -- by one fused pass behind the route's forward (`ops.iwe_pyramid_pass`: three launches, two without
+            a gradient; the backward of the route is unchanged).  Refused with a ValueError: num_tref > 1, loss_type='variance', an
+            image not divisible by 2^(levels - 1) or with a coarsest level below 3x3, more than 65535 trajectories per sample.
+        pyramid_fused (bool, default True): False sends `calc` through the stage calls of `ops.PyramidFocusFn` instead (one pooling,
+            contrast and finalize launch per level, no captured form, `event_offsets` unused): the cross-check of the fused pass.
         trefs_as_samples (bool, build-side switch, default True): with num_tref > 1 the T reference times of a sample run as T samples
             of the num_tref == 1 kernels (`_calc_trefs_as_samples`); False: the general kernels (every stage in one launch for all T).
         static_shapes (bool, build-side extension, default False): capture `calc` + backward once per input shape into HIP
@@ -39,7 +47,7 @@ class FocusLoss(base.TrajectoryLossBase):
                  lut_superpixel_size, focus_loss_norm, dist_norm,
                  scale_iwe_by_dt, mask_image_border, polarity_aware_batching,
                  interpolation_scheme, smooth_type, loss_type='gradient_magnitude', profiler=None,
-                 static_shapes=False, pyramid_levels=1, auto_static_shapes=True, trefs_as_samples=True, **kwargs):
+                 static_shapes=False, pyramid_levels=1, auto_static_shapes=True, trefs_as_samples=True, pyramid_fused=True, **kwargs):
         super().__init__()
         self.image_shape = image_shape
         self.num_tref = num_tref
@@ -57,9 +65,11 @@ class FocusLoss(base.TrajectoryLossBase):
         self.loss_type = loss_type
         self.profiler = profiler
         self.static_shapes = bool(static_shapes)
-        self.pyramid_levels = int(pyramid_levels)      # UNPINNED extension (ops.PyramidFocusFn); 1 = the reference's single scale
+        self.pyramid_levels = int(pyramid_levels)      # UNPINNED extension (ops.iwe_pyramid_pass); 1 = the reference's single scale
+        self.pyramid_fused = bool(pyramid_fused)       # False: `calc` on the stage calls of ops.PyramidFocusFn (cross-check)
         if self.pyramid_levels < 1 or (self.pyramid_levels > 1 and (num_tref != 1 or loss_type != 'gradient_magnitude')):
-            raise ValueError('pyramid_levels > 1 needs num_tref == 1 and the gradient-magnitude objective')
+            raise ValueError(f"pyramid_levels > 1 needs num_tref == 1 and the gradient-magnitude objective (got num_tref={num_tref}, "
+                             f"loss_type='{loss_type}')")
         self._static_plans = {}
         # Small steps are bound by the HOST (a B = 1 step: ~13 kernel boundaries of one wave of workgroups each behind two eager
         # C-ABI calls): when the same small shape comes `AUTO_STATIC_AFTER` times in a row, calc switches to the captured
@@ -96,9 +106,11 @@ class FocusLoss(base.TrajectoryLossBase):
             scale_by_dt=bool(scale_iwe_by_dt), mask_border=bool(mask_image_border),
             polarity_split=bool(polarity_aware_batching),
             scheme_iwd=(interpolation_scheme == 'iwd'), smooth_on_next=(smooth_type == 'on_flow_to_next'),
-            variance=(loss_type == 'variance'), atomic_path=bool(kwargs.get('debug_atomic_path', False)))
+            variance=(loss_type == 'variance'), atomic_path=bool(kwargs.get('debug_atomic_path', False)),
+            pyramid_levels=self.pyramid_levels)
         import dataclasses
         self._cfg_t1 = dataclasses.replace(self._cfg, num_tref=1)
+        self._cfg_one_level = dataclasses.replace(self._cfg, pyramid_levels=1)      # what ops.PyramidFocusFn runs its level 0 on
 
     def _calc_trefs_as_samples(self, trajectories, events, t_ref, offsets):
         """num_tref = T > 1 (focus.py:53-57, 66-113) on the kernels of the shipped num_tref == 1 configurations: sample b with its T
@@ -497,8 +509,8 @@ class FocusLoss(base.TrajectoryLossBase):
         if self.num_tref > 1 and self.trefs_as_samples and not self._cfg.atomic_path and torch.is_tensor(events) and events.dim() == 3 \
                 and torch.is_tensor(trajectories) and trajectories.dim() == 4:
             out = self._calc_trefs_as_samples(trajectories, events, t_ref, offsets)
-        elif self.pyramid_levels > 1:
-            out = ops.PyramidFocusFn.apply(trajectories, events, t_ref, self._cfg, int(num_pos_events), self.pyramid_levels)
+        elif self.pyramid_levels > 1 and not self.pyramid_fused:
+            out = ops.PyramidFocusFn.apply(trajectories, events, t_ref, self._cfg_one_level, int(num_pos_events), self.pyramid_levels)
         elif self.static_shapes and ops.STAGE_TIMER is None and not torch.cuda.is_current_stream_capturing():
             out = ops.StaticFocusCalcFn.apply(trajectories, events, t_ref, self._cfg, int(num_pos_events), offsets, self._static_plans)
         elif self._auto_static(trajectories, events, num_pos_events, offsets):

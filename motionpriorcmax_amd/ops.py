@@ -32,6 +32,7 @@ class PathConfig:
     smooth_on_next: bool
     variance: bool = False
     atomic_path: bool = False
+    pyramid_levels: int = 1       # UNPINNED extension: levels of the IWE pyramid every route serves (iwe_pyramid_pass); 1 = the reference
 
     def flags(self):
         f = 0
@@ -377,6 +378,53 @@ def scale(x, a):
     return y
 
 
+# ------------------------------------------------------------------------------------------
+# the IWE pyramid as one pass behind any forward (csrc/iwe_pyramid.hip)
+# ------------------------------------------------------------------------------------------
+def _pyramid_limit(levels, what):
+    return ValueError(f'pyramid_levels={levels}: {what} (the IWE pyramid serves 2 .. 6 levels of the gradient-magnitude objective at '
+                      f'num_tref == 1, on images divisible by 2^(levels - 1) whose coarsest level is at least 3x3)')
+
+
+def iwe_pyramid_check(cfg: PathConfig, shape, dev):
+    """Raises the ValueError of a configuration the pyramid pass does not serve -- BEFORE the route launches anything; the rule
+    is the library's (mpc_iwe_pyramid_supported, host only).  Nothing to check at pyramid_levels == 1."""
+    if cfg.pyramid_levels > 1:
+        rc = _query('mpc_iwe_pyramid_supported', dev, ctypes.byref(shape), cfg.pyramid_levels, accept=(C.E_SHAPE, C.E_UNSUPPORTED))
+        if rc:
+            raise _pyramid_limit(cfg.pyramid_levels, C.lib().mpc_last_error_string().decode(errors='replace'))
+
+
+def iwe_pyramid_level_offsets(shape, levels):
+    """Float offsets of the unscaled adjoint images of levels 1 .. levels - 1 inside the pass's workspace (include/mpcmax.h:
+    the layout is part of the ABI) and their shapes [nimg, H >> l, W >> l]."""
+    nimg = shape.B * shape.T * (2 if shape.flags & C.F_POLARITY_SPLIT else 1)
+    out, off = [], 0
+    for l in range(1, levels):
+        h, w = shape.H >> l, shape.W >> l
+        out.append((off, (nimg, h, w)))
+        off += (nimg * h * w + 63) // 64 * 64
+    return out
+
+
+def iwe_pyramid_pass(shape, levels, raw, gimg, scal, scal_out=None, pws=None, level_scal=None):
+    """mpc_iwe_pyramid_fwd behind a forward that left the raw IWE `raw`, the unscaled adjoint image `gimg` (None: no gradient) and
+    `scal`: the coarse levels' focus terms go into scal (and scal_out) and their adjoint images into gimg, IN PLACE, in units of
+    level 0's coefficient -- the route's backward then runs as it is.  raw / gimg / scal: tensors, or device addresses (int) of
+    buffers inside a plan.  `pws`, `level_scal`: the caller's buffers (a captured plan), else allocated here.
+    -> (level_scal [levels, SCAL_COUNT], pws)."""
+    def addr(t):
+        return None if t is None else ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())
+    dev = (pws if pws is not None else raw).device
+    want_grad = gimg is not None
+    if pws is None:
+        pws = torch.empty(max(_query('mpc_iwe_pyramid_workspace_bytes', dev, ctypes.byref(shape), levels, int(want_grad)), 256), dtype=torch.uint8, device=dev)
+    if level_scal is None:
+        level_scal = torch.empty((levels, C.SCAL_COUNT), dtype=torch.float32, device=dev)
+    _call('mpc_iwe_pyramid_fwd', dev, ctypes.byref(shape), levels, addr(raw), addr(gimg), addr(scal), addr(scal_out), _ptr(level_scal), _ptr(pws))
+    return level_scal, pws
+
+
 FUSED_CALLS = True    # FocusCalcFn: mpc_focus_fwd / mpc_focus_bwd (two C-ABI calls per step) instead of one call per stage
 
 
@@ -396,7 +444,11 @@ class _Plan:
         self.shape = make_shape(cfg, B, M, Mp, n, extra_flags=0 if (need_grad and not has_offs) else C.F_NO_BWD_RECORDS)
         self.shape_ref = ctypes.byref(self.shape)
         self.need_grad = need_grad
+        iwe_pyramid_check(cfg, self.shape, dev)          # (a plan is built before the first launch of its shape)
         self.ws_bytes = max(_query('mpc_workspace_bytes', dev, self.shape_ref), 256)
+        self.pyr_bytes = 0
+        if cfg.pyramid_levels > 1:
+            self.pyr_bytes = max(_query('mpc_iwe_pyramid_workspace_bytes', dev, self.shape_ref, cfg.pyramid_levels, int(need_grad)), 256)
         s = self.shape
         self.P = 2 if s.flags & C.F_POLARITY_SPLIT else 1
         self.lut_shape = (B, s.nb, s.hq, s.wq, s.T, 2)
@@ -431,6 +483,13 @@ class _Plan:
     def view(self, buf, name):
         off, cnt = self.o[name]
         return buf[off:off + cnt] if cnt else None
+
+    def pyramid(self, dev, buf, out3, pws, level_scal):
+        """The pyramid pass behind mpc_focus_fwd on this plan's buffer `buf` (pyramid_levels > 1): same stream, plain launches."""
+        def at(name):
+            off, cnt = self.o[name]
+            return buf.data_ptr() + 4 * off if cnt else None
+        iwe_pyramid_pass(self.shape, self.cfg.pyramid_levels, at('raw'), at('gimg'), at('scal'), _vp(out3), pws, level_scal)
 
 
 _PLANS = {}
@@ -595,6 +654,8 @@ class FocusCalcFn(torch.autograd.Function):
         ctx.set_materialize_grads(False)      # no zero-filled [B,P,H,W] gradient for the detached outputs
 
         wide = knn_is_wide(n)
+        if wide and cfg.pyramid_levels > 1:
+            raise _wide_limit('pyramid_levels > 1', n)
         if STAGE_TIMER is None and FUSED_CALLS and not wide:
             # one C-ABI call for the whole forward (mpc_focus_fwd issues the same launches); per-shape host state is cached
             p = _plan(cfg, B, M, Mp, n, need_grad, event_offsets is not None, dev)
@@ -606,6 +667,10 @@ class FocusCalcFn(torch.autograd.Function):
             # io.scal_out -- instead of the host cloning them with a kernel of its own)
             out = torch.empty(3, dtype=torch.float32, device=dev)
             _focus_fwd_call(p, dev, traj, ev, tr, buf, blur, ws, offs, out)
+            if cfg.pyramid_levels > 1:
+                # (the pass's workspace lives for the forward only: the backward reads the folded adjoint image)
+                p.pyramid(dev, buf, out, torch.empty(p.pyr_bytes, dtype=torch.uint8, device=dev),
+                          torch.empty((cfg.pyramid_levels, C.SCAL_COUNT), dtype=torch.float32, device=dev))
             ctx.plan, ctx.ws, ctx.offs = p, ws, offs
             ctx.save_for_backward(traj, ev, tr, buf)
             loss, focus, smooth = out[C.SCAL_LOSS], out[C.SCAL_FOCUS], out[C.SCAL_SMOOTH]
@@ -619,7 +684,10 @@ class FocusCalcFn(torch.autograd.Function):
         ws = alloc_workspace(shape, dev)
         offs = _check_offsets(event_offsets, cfg, shape, dev)
         fshape = shape if offs is None else make_shape(cfg, B, M, Mp, ns, extra_flags=C.F_NO_BWD_RECORDS, K=Ks)
-        flow_lut, state, g_field, _, blur, gimg, scal = _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad, kshape)
+        iwe_pyramid_check(cfg, shape, dev)
+        flow_lut, state, g_field, raw, blur, gimg, scal = _staged_fwd(cfg, shape, fshape, traj, ev, tr, ws, need_grad, kshape)
+        if cfg.pyramid_levels > 1:
+            iwe_pyramid_pass(shape, cfg.pyramid_levels, raw, gimg, scal)
         ctx.plan = None
         ctx.shape, ctx.kshape = shape, kshape
         ctx.offs = offs
@@ -653,7 +721,8 @@ class PyramidFocusFn(torch.autograd.Function):
     configs[2] names one, the reference has none (focus.py:90-91 evaluates one scale), so this is a definition, not a port:
     level l + 1 is the 2x2 average of the RAW level-l IWE, every level goes through the reference's own blur + gradient-magnitude
     objective (mpc_contrast_fwd on a shape of that level's size), and the focus term is the sum of the levels' 1 / val.
-    Stage calls (no fused path); `iwes` are the blurred level-0 images."""
+    Stage calls (no fused path); `iwes` are the blurred level-0 images.  FocusLoss(pyramid_fused=False) runs it: the cross-check of
+    the fused pass (iwe_pyramid_pass), which serves every route by default."""
 
     @staticmethod
     def forward(ctx, trajectories, events, t_ref, cfg: PathConfig, num_pos: int, levels: int):
@@ -743,6 +812,9 @@ class StaticFocusPlan:
         self.blur = torch.empty(p.img_shape, dtype=torch.float32, device=dev)
         self.gout = torch.ones(1, dtype=torch.float32, device=dev)
         self.scratch = torch.empty(_bwd_scratch_floats(p), dtype=torch.float32, device=dev) if need_grad else None
+        # (pyramid_levels > 1: the pass is part of the captured forward, its workspace and level table belong to the plan)
+        self.pyr_ws = torch.empty(p.pyr_bytes, dtype=torch.uint8, device=dev) if p.pyr_bytes else None
+        self.pyr_scal = torch.empty((cfg.pyramid_levels, C.SCAL_COUNT), dtype=torch.float32, device=dev) if p.pyr_bytes else None
         self.g_traj = torch.empty_like(traj) if need_grad else None
         self.generation = 0
         self.pending = None              # weak reference to the marker of the latest calc that still waits for its backward (automatic mode)
@@ -771,6 +843,8 @@ class StaticFocusPlan:
 
     def _fwd(self):
         _focus_fwd_call(self.plan, self.dev, self.traj, self.ev, self.tr, self.buf, self.blur, self.ws, self.offs)
+        if self.pyr_ws is not None:
+            self.plan.pyramid(self.dev, self.buf, None, self.pyr_ws, self.pyr_scal)
 
     def _bwd(self):
         _focus_bwd_call(self.plan, self.dev, self.traj, self.ev, self.tr, self.buf, self.ws, self.offs, self.gout, self.scratch, self.g_traj)
@@ -886,9 +960,12 @@ class EventFocusFn(torch.autograd.Function):
         need_grad = flow_lut.requires_grad
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=0 if need_grad else C.F_NO_BWD_RECORDS)
         ws = alloc_workspace(shape, dev)
+        iwe_pyramid_check(cfg, shape, dev)
         raw = event_splat_fwd(shape, ev, lut, tr, ws)
         blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
         scal = finalize(shape, 0, 0, 0.0, ws, dev)
+        if cfg.pyramid_levels > 1:
+            iwe_pyramid_pass(shape, cfg.pyramid_levels, raw, gimg, scal)
         ctx.shape, ctx.ws = shape, ws
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(ev, tr, lut, gimg, scal)
@@ -924,6 +1001,7 @@ def _pe_tail(cfg, shape, rows, tr, ws, need_grad, field=None):
     raw = event_splat_fwd(shape, rows, None, tr, ws)
     blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
     g_field, s_nimg = None, 0
+    pyr = cfg.pyramid_levels > 1
     if field is not None:
         name, c_rows, pm, k = field
         nbm = pm.shape[0]
@@ -932,6 +1010,8 @@ def _pe_tail(cfg, shape, rows, tr, ws, need_grad, field=None):
         _call(name, rows.device, _ptr(c_rows), _ptr(pm), _ptr(fld), shape.B, shape.hq * shape.wq, k, nbm)
         g_field = lut_smooth(shape, fld, s_nimg, 2, cfg.smooth_weight, ws, need_grad)
     scal = finalize(shape, s_nimg, 2 if s_nimg else 0, cfg.smooth_weight if s_nimg else 0.0, ws, rows.device)
+    if pyr:
+        iwe_pyramid_pass(shape, cfg.pyramid_levels, raw, gimg, scal)
     return blur, gimg, g_field, scal
 
 
@@ -1008,6 +1088,7 @@ class PerEventBasisFocusFn(torch.autograd.Function):
         tr = _f32c(t_ref.detach().to(dev))
         need_grad = coef_rows.requires_grad
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+        iwe_pyramid_check(cfg, shape, dev)
         if tuple(cr.shape) != (B * shape.hq * shape.wq, 2 * k) or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coef_rows {tuple(cr.shape)} / phi do not match [B*hq*wq, 2k] / [B, M, k] (k <= 8 without phi)')
         ws = alloc_workspace(shape, dev)
@@ -1068,6 +1149,7 @@ class PerEventBasisCalcFn(torch.autograd.Function):
             need_grad = need_grad or table.requires_grad or (phim is not None and phim.requires_grad)
         Bc, S, c2, H, W = cg.shape
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+        iwe_pyramid_check(cfg, shape, dev)
         G = shape.hq * shape.wq
         if Bc != B or c2 != 2 * k or (ph is not None and tuple(ph.shape) != (B, M, k)) or (ph is None and k > 8):
             raise ValueError(f'coeff_grid {tuple(cg.shape)} / phi do not match [B, S, 2k, H, W] / [B, M, k] (k <= 8 without phi)')
@@ -1183,6 +1265,7 @@ class PerEventCurvesFn(torch.autograd.Function):
         Bp, c2, h, w = p.shape
         d, kind, S = c2 // 2, PEC_BASIS[curve_type], (tab.shape[0] - 1 if tab is not None else 0)
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+        iwe_pyramid_check(cfg, shape, dev)
         hq, wq = shape.hq, shape.wq
         G = hq * wq
         grid = (8 * h // tile, 8 * w // tile) if m is not None else (h, w)
@@ -1348,10 +1431,13 @@ class PrewarpedFocusFn(torch.autograd.Function):
         tr = _f32c(t_ref.detach().to(dev))
         need_grad = warped_pos.requires_grad
         shape = make_shape(cfg, B, M, Mp, 0, K=0, extra_flags=C.F_NO_WARP | C.F_NO_BWD_RECORDS)
+        iwe_pyramid_check(cfg, shape, dev)
         ws = alloc_workspace(shape, dev)
         raw = event_splat_fwd(shape, rows, None, tr, ws)
         blur, gimg = contrast_fwd(shape, raw, ws, need_grad)
         scal = finalize(shape, 0, 0, 0.0, ws, dev)
+        if cfg.pyramid_levels > 1:
+            iwe_pyramid_pass(shape, cfg.pyramid_levels, raw, gimg, scal)
         ctx.shape = shape
         ctx.set_materialize_grads(False)
         ctx.save_for_backward(rows, tr, gimg, scal)

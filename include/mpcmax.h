@@ -801,7 +801,9 @@ int mpc_val_metrics(const mpc_val_shape *s, const float *params, const float *up
  * mpc_corr_lookup_bwd: the adjoint applied to grad_out [B][E * K * K][h][w] -- grad_coords [T][B][2][h][w] (coords mode) or grad_params
  * [B][2d][h][w] (Bezier mode: the curve adjoint in the same launch), and for every level with desc->grad_level[l] != NULL the whole
  * of grad_level[l] (window cells in gather form, every other element 0: nothing to pre-zero).  A NULL gradient pointer drops its
- * part.  A query's slice is read by that query alone: no atomics, every sum in a fixed order, bitwise reproducible.  One launch
+ * part.  In the Bezier mode a non-NULL grad_coords is written too -- the coordinate gradient of every target, which the launch forms
+ * before it contracts it with the matrix (what mpc_curve_basis_grad, below, sums the matrix' own gradient from); grad_params may
+ * then be NULL.  A query's slice is read by that query alone: no atomics, every sum in a fixed order, bitwise reproducible.  One launch
  * each way; the descriptor travels by value as a kernel argument (no copy to the device).
  * MPC_CORR_F_GRAD_ACCUM (mpc_corr_lookup_bwd only): every non-NULL grad_level[l] holds a gradient already (a call without the flag
  * wrote it) and the window cells of this call are ADDED to it -- per in-slice window cell of each (slot, query) one read, one add of
@@ -830,6 +832,32 @@ int mpc_corr_lookup_fwd(const mpc_corr_desc *desc, const float *coords, const fl
                         void *stream);
 int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coords, const float *params, const float *basis,
                         const float *grad_out, float *grad_coords, float *grad_params, void *stream);
+
+/* ---- the gradient of the basis matrix of the three RAFT-spline nodes above (additive, still version 107): the reference's
+ * curve_type LEARNED while its basis network trains (src/models/raft_spline/curves/learned.py:76-77).  The curve is linear in the
+ * matrix, so one reduction serves mpc_curve_traj_bwd, mpc_cvx_traj_bwd and mpc_corr_lookup_bwd, run BEHIND them (their kernels are
+ * unchanged).  With R[b][i][c][j] the control points that site i of sample b evaluates and G[t][b][i][c] the cotangent of the
+ * displacement there (c: x, y):
+ *   grad_basis [T][d] (out, overwritten) = scale * sum over (b, i) of (G[t][b][i].x * R[b][i].x[j] + G[t][b][i].y * R[b][i].y[j])
+ *   MPC_CBG_PLAIN   the plain head:  R = params [B][2][d][sites] (x first), G = grad_traj [B][T][sites][2] ((y, x) order), sites = n
+ *   MPC_CBG_ROWS    the convex-upsampling head:  R = rows [B * sites][2][d] (y first) of mpc_pec_head_rows(_dt) called with scale 1 --
+ *                   the upsampled control points at the tile centres, in the mask's own dtype --, G = grad_traj as above
+ *   MPC_CBG_LOOKUP  the lookup in the Bezier mode:  R = params [B][2d][h][w], G = grad_coords [T][B][2][h][w] as mpc_corr_lookup_bwd
+ *                   writes it when it is given grad_coords in that mode -- beside grad_params, or alone with grad_params NULL
+ *                   (params detached); sites = h * w, scale = 1.  A call that does not ask for grad_coords there launches what it
+ *                   launched before.
+ * Two kernels: per-workgroup partials [P][T][d] over 256 consecutive (sample, site) pairs each (a butterfly over the wavefront, the
+ * waves in order), then the finishing pass of mpc_grid_traj_bwd's grad_dphi over the partials.  No float atomics, no host
+ * synchronisation, nothing allocated: bitwise reproducible, independent of the scheduling.  scratch:
+ * mpc_curve_basis_grad_scratch_floats() floats = ceil(B * sites / 256) * T * d.
+ * Limits: those of the nodes, d <= 16 and T * d * 4 <= 48 KB (else MPC_E_UNSUPPORTED, also from the size query).  B = 0 or sites = 0:
+ * grad_basis = 0 (one kernel); G, R and scratch may be NULL then. */
+#define MPC_CBG_PLAIN 0
+#define MPC_CBG_ROWS 1
+#define MPC_CBG_LOOKUP 2
+int64_t mpc_curve_basis_grad_scratch_floats(int32_t B, int32_t d, int32_t T, int32_t sites);
+int mpc_curve_basis_grad(const float *G, const float *R, int32_t layout, float scale, float *grad_basis, float *scratch,
+                         int32_t B, int32_t d, int32_t T, int32_t sites, void *stream);
 
 /* ---- the RAFT-spline correlation pyramid the lookup reads, built from the two feature maps on the fp32 matrix cores.
  * Reference: src/models/raft_spline/corr.py:235-270 (CorrComputation._corr_dot_prod_1_to_N / get_correlation_volume:

@@ -76,6 +76,7 @@ class ValShape(ctypes.Structure):
 
 CORR_MAX_LEVELS, CORR_MAX_TARGETS, CORR_MAX_RADIUS, CORR_F_LANE_PER_QUERY = 6, 16, 4, 1        # include/mpcmax.h
 CORR_F_GRAD_ACCUM = 2                                   # mpc_corr_lookup_bwd: add the window cells into grad_level (include/mpcmax.h)
+CBG_PLAIN, CBG_ROWS, CBG_LOOKUP = 0, 1, 2               # mpc_curve_basis_grad: the layouts of the three RAFT-spline nodes (include/mpcmax.h: MPC_CBG_*)
 
 
 class CorrDesc(ctypes.Structure):
@@ -221,6 +222,8 @@ SIGNATURES = {
     'mpc_corr_lookup_supported': (cint, [cdp]),
     'mpc_corr_lookup_fwd': (cint, [cdp] + [vp] * 5),
     'mpc_corr_lookup_bwd': (cint, [cdp] + [vp] * 7),
+    'mpc_curve_basis_grad_scratch_floats': (i64, [i32] * 4),
+    'mpc_curve_basis_grad': (cint, [vp, vp, i32, f32, vp, vp] + [i32] * 4 + [vp]),
     'mpc_corr_pyramid_workspace_bytes': (ctypes.c_longlong, [cdp, cint, cint]),
     'mpc_corr_pyramid_supported': (cint, [cdp, cint]),
     'mpc_corr_pyramid_fwd': (cint, [cdp, cint] + [vp] * 4),

@@ -5,7 +5,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libmpcmax.so')
-SOURCES = ['api.hip', 'contrast.hip', 'iwe_pyramid.hip', 'events.hip', 'knn.hip', 'knn_strip.hip', 'knn_wide.hip', 'voxel.hip', 'ingest.hip', 'flow.hip', 'curves.hip', 'cvx_curves.hip', 'corr_lookup.hip', 'corr_pyramid.hip', 'val_metrics.hip', 'tiles.hip', 'grid_traj.hip', 'repr.hip', 'flow_targets.hip', 'dsec_io.hip', 'pe_curves.hip', 'pe_basis.hip', 'ev_order.hip']
+SOURCES = ['api.hip', 'contrast.hip', 'iwe_pyramid.hip', 'events.hip', 'knn.hip', 'knn_strip.hip', 'knn_wide.hip', 'voxel.hip', 'ingest.hip', 'flow.hip', 'curves.hip', 'curve_basis.hip', 'cvx_curves.hip', 'corr_lookup.hip', 'corr_pyramid.hip', 'val_metrics.hip', 'tiles.hip', 'grid_traj.hip', 'repr.hip', 'flow_targets.hip', 'dsec_io.hip', 'pe_curves.hip', 'pe_basis.hip', 'ev_order.hip']
 FLAGS = ['-shared', '-fPIC', '-O3', '--offload-arch=gfx950', '-ffp-contract=off', '-std=c++17',
          '-Wall', '-Wno-unused-function']
 

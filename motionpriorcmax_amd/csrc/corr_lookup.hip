@@ -299,7 +299,10 @@ __device__ __forceinline__ void corr_bwd_accum(const mpc_corr_desc &D, const flo
             if (off[qi][p] >= 0) gs[MPC_IDX(off[qi][p], (long long)nlive * sl)] = o[qi][p] + v[qi][p];
 }
 
-template <int R, int ACC = 0>
+// GC (Bezier mode only): the coordinate gradient of every target, which the centre role forms before it contracts it with the basis
+// matrix, is ALSO written to grad_coords [T][B][2][h][w] (what the basis matrix' own gradient is summed from: curve_basis.hip), and
+// grad_params may be NULL.  A variant of its own: with GC = 0 the kernel is the code it was.
+template <int R, int ACC = 0, int GC = 0>
 __global__ __launch_bounds__(256) void k_corr_lookup_bwd(const mpc_corr_desc D, const float *__restrict__ coords,
                                                          const float *__restrict__ params, const float *__restrict__ basis,
                                                          const float *__restrict__ grad_out, float *__restrict__ grad_coords,
@@ -383,9 +386,18 @@ __global__ __launch_bounds__(256) void k_corr_lookup_bwd(const mpc_corr_desc D, 
             } else {
                 s_gc[MPC_IDX((t * 2 + 0) * 64 + lane, T * 128)] = gx;
                 s_gc[MPC_IDX((t * 2 + 1) * 64 + lane, T * 128)] = gy;
+                if constexpr (GC != 0) {
+                    if (live) {
+                        float *gc = grad_coords + ((size_t)t * D.B + b) * 2 * hw + pix;
+                        gc[0] = gx; gc[hw] = gy;
+                    }
+                }
             }
         }
         if (coords) return;
+        if constexpr (GC != 0) {
+            if (!grad_params) return;           // (uniform: params detached, the coordinate gradient alone)
+        }
         __syncthreads();
         for (int c = wv; c < 2 * d; c += 4) {
             const int axis = c / d, j = c - axis * d;
@@ -562,7 +574,9 @@ extern "C" int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coord
     if (rc) return rc;
     if (desc->B == 0) return 0;
     if (!grad_out) { mpc_set_error("%s: null argument", __func__); return MPC_E_NULL; }
-    if ((grad_coords && !coords) || (grad_params && !params)) { mpc_set_error("%s: a gradient for an input that was not given", __func__); return MPC_E_NULL; }
+    // (grad_coords in the Bezier mode: the targets' coordinate gradient beside grad_params, or alone -- the GC variant of the kernel)
+    if (grad_params && !params) { mpc_set_error("%s: a gradient for an input that was not given", __func__); return MPC_E_NULL; }
+    const bool gc = params && grad_coords;
     const long long hw = (long long)desc->h * desc->w, nq = (long long)desc->B * hw;
     const int E = corr_entries(desc);
     const int chunks = (int)((hw + 63) / 64), groups = (int)((nq + 3) / 4);
@@ -577,6 +591,23 @@ extern "C" int mpc_corr_lookup_bwd(const mpc_corr_desc *desc, const float *coord
     const size_t lds = std::max(((coords ? 0 : (size_t)desc->T * desc->d) + ((size_t)E + desc->T) * 128) * sizeof(float),
                                 4 * WN * WN * sizeof(float));                       // (the slice-fill workgroups' window gradients)
     const dim3 grid((unsigned)(nA + nfill));
+#define CORR_BWD_VARIANT(RR, AA, GG, bytes)                                                                                   \
+    MPC_LAUNCH((k_corr_lookup_bwd<RR, AA, GG>), grid, dim3(256), bytes, (hipStream_t)stream, *desc, coords, params, basis, grad_out, \
+               grad_coords, grad_params, chunks, (int)nA, E, groups)
+    if (gc) {                                   // every other call takes the launches below, as it did
+        const size_t K = 2 * (size_t)desc->radius + 1;
+        const bool acc = accum && nfill > 0;
+        const size_t bytes = acc ? std::max(lds, (K * K * CORR_TILE_LD + 256 + (size_t)desc->d) * sizeof(float)) : lds;
+        switch (desc->radius) {
+        case 1: if (acc) CORR_BWD_VARIANT(1, 1, 1, bytes); else CORR_BWD_VARIANT(1, 0, 1, bytes); break;
+        case 2: if (acc) CORR_BWD_VARIANT(2, 1, 1, bytes); else CORR_BWD_VARIANT(2, 0, 1, bytes); break;
+        case 3: if (acc) CORR_BWD_VARIANT(3, 1, 1, bytes); else CORR_BWD_VARIANT(3, 0, 1, bytes); break;
+        default: if (acc) CORR_BWD_VARIANT(4, 1, 1, bytes); else CORR_BWD_VARIANT(4, 0, 1, bytes); break;
+        }
+        MPC_CHECK_LAUNCH();
+        return 0;
+    }
+#undef CORR_BWD_VARIANT
     if (accum && nfill > 0) {
         const size_t K = 2 * (size_t)desc->radius + 1;
         const size_t lds_acc = std::max(lds, (K * K * CORR_TILE_LD + 256 + (coords ? 0 : (size_t)desc->d)) * sizeof(float));

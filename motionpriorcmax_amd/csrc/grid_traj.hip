@@ -20,6 +20,7 @@
 #include "common.h"
 #include "bounds.h"
 #include "dt_device.h"         // the element types of grid / grad_grid (mpc_ld, mpc_store_vec)
+#include "partials_device.h"   // the finishing pass of grad_dphi, shared with curve_basis.hip
 
 #define GT_KMAX 16             // basis orders per axis
 #define GT_TC 256              // tile columns of a backward workgroup (one thread each)
@@ -183,19 +184,11 @@ __global__ __launch_bounds__(256) void k_grid_traj_bwd(const float *__restrict__
     }
 }
 
-// grad_dphi[e] = sum over the P workgroup partials part[p][e], e = (t, j): one workgroup per element, a fixed order
+// grad_dphi[e] = sum over the P workgroup partials part[p][e], e = (t, j): one workgroup per element, a fixed order (partials_device.h)
 __global__ __launch_bounds__(256) void k_grid_dphi_sum(const float *__restrict__ part, float *__restrict__ grad_dphi, long long P, int ne) {
     __shared__ float s[256];
-    const int e = blockIdx.x;
-    float v = 0.f;
-    for (long long p = threadIdx.x; p < P; p += 256) v = v + part[p * ne + e];
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) grad_dphi[e] = s[0];
+    const float v = mpc_partials_sum(part, P, ne, (int)blockIdx.x, s);
+    if (threadIdx.x == 0) grad_dphi[blockIdx.x] = v;
 }
 
 static void gt_tiles(int H, int W, int tile, int *hq, int *wq) {

@@ -1510,10 +1510,23 @@ class LutSmoothFn(torch.autograd.Function):
         return scale(g, _f32c(g_out.reshape(1))), None, None
 
 
+def _curve_basis_grad(G, R, layout, scale, B, d, T, sites):
+    """grad_basis [T, d] fp32 of the three RAFT-spline nodes (csrc/curve_basis.hip: mpc_curve_basis_grad, two kernels behind the
+    node's own backward launches): G the cotangent of the displacements, R the control points the sites evaluate, in the layout
+    C.CBG_* of the node.  No host synchronisation; bitwise reproducible."""
+    dev = G.device
+    gb = torch.empty((T, d), dtype=torch.float32, device=dev)
+    scratch = torch.empty(max(_query('mpc_curve_basis_grad_scratch_floats', dev, B, d, T, sites), 1), dtype=torch.float32, device=dev)
+    _call('mpc_curve_basis_grad', dev, _ptr(G), _ptr(R), int(layout), float(scale), _ptr(gb), _ptr(scratch), B, d, T, sites)
+    return gb
+
+
 class CurveTrajFn(torch.autograd.Function):
     """Flow curves -> `trajectories` (BASELINE.json configs[3]): params [B, 2d, h, w] ((x, y) channel order,
     reference curves/polynomial.py:60-61), basis [T, d] on the device, tile centres [n, 2] (y, x) -> [B, T, n, 2], one kernel each
-    way (csrc/curves.hip) instead of the einsum / stack / add chain of plain torch and its adjoints."""
+    way (csrc/curves.hip) instead of the einsum / stack / add chain of plain torch and its adjoints.  A basis matrix that requires
+    grad (a learned basis that trains, routed here by basis_grad='fused') gets its gradient from `_curve_basis_grad` behind the
+    backward kernel; only the gradients autograd asks for are computed."""
 
     @staticmethod
     def forward(ctx, params, basis, pos, scale: float):
@@ -1526,18 +1539,22 @@ class CurveTrajFn(torch.autograd.Function):
         ps = _f32c(pos.detach())
         traj = torch.empty((B, T, n, 2), dtype=torch.float32, device=dev)
         _call('mpc_curve_traj_fwd', dev, _ptr(p), _ptr(bm), _ptr(ps), float(scale), _ptr(traj), B, d, T, n)
-        ctx.save_for_backward(bm)
+        ctx.save_for_backward(bm, p if ctx.needs_input_grad[1] else None)
         ctx.dims = (B, d, T, n, h, w, float(scale))
         return traj
 
     @staticmethod
     def backward(ctx, g):
-        (bm,) = ctx.saved_tensors
+        bm, p = ctx.saved_tensors
         B, d, T, n, h, w, scale = ctx.dims
         g = _f32c(g)
-        gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=g.device)
-        _call('mpc_curve_traj_bwd', g.device, _ptr(g), _ptr(bm), scale, _ptr(gp), B, d, T, n)
-        return gp, None, None, None
+        gp = gb = None
+        if ctx.needs_input_grad[0]:
+            gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=g.device)
+            _call('mpc_curve_traj_bwd', g.device, _ptr(g), _ptr(bm), scale, _ptr(gp), B, d, T, n)
+        if p is not None:
+            gb = _curve_basis_grad(g, p, C.CBG_PLAIN, scale, B, d, T, n)
+        return gp, gb, None, None
 
 
 class CvxCurveTrajFn(torch.autograd.Function):
@@ -1546,7 +1563,9 @@ class CvxCurveTrajFn(torch.autograd.Function):
     95-123) with basis [T, d] on the device -> [B, T, n, 2] at the tile centres of the 8h x 8w image, one kernel forward and two
     backward (csrc/cvx_curves.hip) instead of the softmax / unfold / [B, 2d, 9, 8, 8, h, w] product / sum / permute chain.  The
     backward computes only the gradients autograd asks for: without a mask gradient the dense [B, 576, h, w] tensor is neither
-    allocated nor filled.  No host synchronisation either way."""
+    allocated nor filled.  No host synchronisation either way.  A basis matrix that requires grad (basis_grad='fused') gets its
+    gradient behind those launches: the upsampled control points at the tile centres once more (mpc_pec_head_rows_dt, the mask
+    read in its own dtype), then `_curve_basis_grad`."""
 
     @staticmethod
     def forward(ctx, params, up_mask, basis, scale: float, tile: int):
@@ -1577,7 +1596,7 @@ class CvxCurveTrajFn(torch.autograd.Function):
         gp = gm = ws = None
         if g.numel() == 0:                            # no tile centre (or B = 0): no cotangent to hand over, and nothing reaches the inputs
             return (torch.zeros_like(p) if ctx.needs_input_grad[0] else None, torch.zeros_like(m) if ctx.needs_input_grad[1] else None,
-                    None, None, None)
+                    torch.zeros_like(bm) if ctx.needs_input_grad[2] else None, None, None)
         if ctx.needs_input_grad[0]:
             gp = torch.empty((B, 2 * d, h, w), dtype=torch.float32, device=dev)
             ws = torch.empty(max(_query('mpc_cvx_traj_bwd_workspace_bytes', dev, B, d, T, h, w, tile), 4) // 4, dtype=torch.float32, device=dev)
@@ -1586,7 +1605,13 @@ class CvxCurveTrajFn(torch.autograd.Function):
         if gp is not None or gm is not None:
             _call('mpc_cvx_traj_bwd_dt', dev, _ptr(g), _ptr(p), _ptr(m), _DT_CODE[m.dtype], _ptr(bm), scale, _ptr(gp), _ptr(gm), B, d, T, h, w, tile,
                   _ptr(ws), label='mpc_cvx_traj_bwd')
-        return gp, gm, None, None, None
+        gb = None
+        if ctx.needs_input_grad[2]:
+            n = g.shape[2]
+            rows = torch.empty((B * n, 2 * d), dtype=torch.float32, device=dev)        # (scale 1: the reduction applies the node's scale once)
+            _call('mpc_pec_head_rows_dt', dev, _ptr(p), _ptr(m), _DT_CODE[m.dtype], 1.0, tile, _ptr(rows), B, d, h, w, label='mpc_pec_head_rows')
+            gb = _curve_basis_grad(g, rows, C.CBG_ROWS, scale, B, d, T, n)
+        return gp, gm, gb, None, None
 
 
 def cvx_flows(params, up_mask, basis, scale: float):
@@ -1619,6 +1644,15 @@ def _corr_lookup_fwd(x, basis, lookup):
 def _corr_lookup_bwd(lookup, d, x, basis, g, want_x, grad_levels, flags=0):
     """The backward launch of both lookup nodes: the gradient of x (None unless `want_x`), and the level cotangents into the tensors of
     `grad_levels` (None: a level nobody asked for), written whole or, under MPC_CORR_F_GRAD_ACCUM in `flags`, added to."""
+    return _corr_lookup_bwd_basis(lookup, d, x, basis, g, want_x, grad_levels, flags, False)[0]
+
+
+def _corr_lookup_bwd_basis(lookup, d, x, basis, g, want_x, grad_levels, flags, want_basis):
+    """`_corr_lookup_bwd` -> (the gradient of x, None unless `want_x`; the gradient of the basis matrix, None
+    unless `want_basis`), and the level cotangents into the tensors of `grad_levels` (None: a level nobody asked for), written
+    whole or, under MPC_CORR_F_GRAD_ACCUM in `flags`, added to.  `want_basis` (Bezier mode): the same launch also writes the targets'
+    coordinate gradient [T, B, 2, h, w] -- alone, with grad_params NULL, where x is detached --, and `_curve_basis_grad` sums the
+    matrix' gradient from it."""
     g = _f32c(g)
     desc = C.CorrDesc.from_buffer_copy(lookup.descriptor(d))
     desc.flags |= flags
@@ -1626,9 +1660,11 @@ def _corr_lookup_bwd(lookup, d, x, basis, g, want_x, grad_levels, flags=0):
     for l, t in enumerate(grad_levels):
         desc.grad_level[l] = None if t is None else t.data_ptr()
     bez = basis is not None
+    gc = torch.empty((basis.shape[0], lookup.B, 2, lookup.h, lookup.w), dtype=torch.float32, device=g.device) if bez and want_basis else None
     _call('mpc_corr_lookup_bwd', g.device, ctypes.byref(desc), None if bez else _ptr(x), _ptr(x) if bez else None, _ptr(basis), _ptr(g),
-          None if bez else _ptr(gx), _ptr(gx) if bez else None)
-    return gx
+          _ptr(gc) if bez else _ptr(gx), _ptr(gx) if bez else None)
+    gb = None if gc is None else _curve_basis_grad(gc, x, C.CBG_LOOKUP, 1.0, lookup.B, d, basis.shape[0], lookup.h * lookup.w)
+    return gx, gb
 
 
 class CorrLookupFn(torch.autograd.Function):
@@ -1637,6 +1673,7 @@ class CorrLookupFn(torch.autograd.Function):
     pyramid levels of `lookup` as inputs of their own (so that autograd asks for their gradients) -> [B, E * (2r+1)^2, h, w], one
     kernel forward and one backward (csrc/corr_lookup.hip) instead of the coordinate tensor / grid_sample / cat / permute chain.
     The backward computes only what autograd asks for; every element of a gradient it returns is written by the kernel (no memset).
+    A basis matrix that requires grad (a learned basis that trains, routed here by basis_grad='fused') gets its gradient too.
     The descriptor of the pyramid travels by value with the launch: no host synchronisation and no copy either way."""
 
     @staticmethod
@@ -1649,13 +1686,13 @@ class CorrLookupFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, basis, *levels = ctx.saved_tensors
-        want_x = ctx.needs_input_grad[0]
+        want_x, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         want_l = [ctx.needs_input_grad[3 + l] for l in range(len(levels))]
-        if not want_x and not any(want_l):
+        if not want_x and not want_b and not any(want_l):
             return (None,) * (3 + len(levels))
         gl = [torch.empty_like(lv) if w else None for lv, w in zip(levels, want_l)]          # (every element is written by the kernel)
-        gx = _corr_lookup_bwd(ctx.lookup, ctx.d, x, basis, g, want_x, gl)
-        return (gx, None, None) + tuple(gl)
+        gx, gb = _corr_lookup_bwd_basis(ctx.lookup, ctx.d, x, basis, g, want_x, gl, 0, want_b)
+        return (gx, gb, None) + tuple(gl)
 
 
 class CorrGradGate:
@@ -1710,10 +1747,10 @@ class CorrLookupSharedFn(torch.autograd.Function):
     def backward(ctx, g):
         x, basis = ctx.saved_tensors
         lookup, gate = ctx.lookup, ctx.lookup._gate
-        want_x = ctx.needs_input_grad[0]
+        want_x, want_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         # needs_input_grad is fixed at the forward; whether THIS pass reaches the levels is the engine's to say
         want_l = ctx.needs_input_grad[3] and ctx.gate_node is not None and torch._C._will_engine_execute_node(ctx.gate_node)
-        if not want_x and not want_l:
+        if not want_x and not want_b and not want_l:
             return None, None, None, None
         flags = 0
         if want_l:
@@ -1721,7 +1758,8 @@ class CorrLookupSharedFn(torch.autograd.Function):
                 gate.bufs = [torch.empty_like(lv) if lv.requires_grad else None for lv in lookup.levels]
             else:
                 flags = C.CORR_F_GRAD_ACCUM
-        return _corr_lookup_bwd(lookup, ctx.d, x, basis, g, want_x, gate.bufs if want_l else (), flags), None, None, None
+        gx, gb = _corr_lookup_bwd_basis(lookup, ctx.d, x, basis, g, want_x, gate.bufs if want_l else (), flags, want_b)
+        return gx, gb, None, None
 
 
 def corr_pyramid_desc(B, h, w, num_levels_per_target):

@@ -249,13 +249,30 @@ def _basis_trains(bm):
     return torch.is_grad_enabled() and bm.requires_grad
 
 
-def _curve_trajectories(params, bm, tile_size, H, W, scale):
+BASIS_GRAD_ROUTES = ('mirror', 'fused')
+
+
+def _basis_grad_fused(basis_grad):
+    """The keyword `basis_grad` of `trajectories_from_curves` / `CorrLookup.lookup_curves` checked -> is it 'fused'."""
+    if basis_grad not in BASIS_GRAD_ROUTES:
+        raise ValueError(f'basis_grad must be one of {BASIS_GRAD_ROUTES}, got {basis_grad!r}')
+    return basis_grad == 'fused'
+
+
+def _basis_served(bm, fused):
+    """May the fused nodes take this basis matrix: a constant to autograd, or -- basis_grad='fused' -- one that trains and lies within
+    the limit of its gradient's reduction (mpc_curve_basis_grad: the nodes' own 48 KB)."""
+    return not _basis_trains(bm) or (fused and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024)
+
+
+def _curve_trajectories(params, bm, tile_size, H, W, scale, fused=False):
     """pos + scale * (basis x control points), (y, x) order: on the GPU one kernel each way (ops.CurveTrajFn, csrc/curves.hip:
     mpc_curve_traj_fwd / _bwd -- a training step calls this every iteration and a B = 1 step is bound by the host); for CPU tensors
-    (the host-side tests against the reference's curves) the same in plain torch."""
+    (the host-side tests against the reference's curves) the same in plain torch.  `fused`: a basis matrix that requires grad
+    takes the node too, which then returns its gradient (csrc/curve_basis.hip)."""
     B, c2, h, w = params.shape
     d = c2 // 2
-    if params.is_cuda and params.dtype in _KERNEL_DTYPES and d <= 16 and not _basis_trains(bm):
+    if params.is_cuda and params.dtype in _KERNEL_DTYPES and d <= 16 and _basis_served(bm, fused):
         # (fp16 / bf16 control points go through a differentiable .float() -- autograd casts their gradient back --, and the basis
         # matrix and the tile positions are fp32 whatever params.dtype is: the trajectories are fp32, never positions in 16 bits)
         from .. import ops
@@ -288,13 +305,13 @@ _CVX_KERNEL_TILES = (2, 4, 8, 16)
 _KERNEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16)          # what the fused nodes take (the mask in place: include/mpcmax.h, MPC_DT_*)
 
 
-def _cvx_kernels_serve(params, up_mask, bm):
+def _cvx_kernels_serve(params, up_mask, bm, fused=False):
     """The routing rule of `_curve_trajectories`: the kernels take fp32, fp16 or bf16 GPU tensors (the mask is read in its own dtype,
     the control points go through .float()) with d <= 16 and a basis matrix within their 48 KB LDS slice that is a constant to
     autograd; everything else (CPU tensors, other dtypes, d > 16, more times, a basis matrix that requires grad) runs in plain
-    torch."""
+    torch.  `fused` (basis_grad='fused'): a basis matrix that requires grad is served too."""
     return (params.is_cuda and up_mask.is_cuda and params.dtype in _KERNEL_DTYPES and up_mask.dtype in _KERNEL_DTYPES
-            and params.shape[1] // 2 <= 16 and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024 and not _basis_trains(bm))
+            and params.shape[1] // 2 <= 16 and bm.shape[0] * bm.shape[1] * 4 <= 48 * 1024 and _basis_served(bm, fused))
 
 
 def _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale):
@@ -308,7 +325,7 @@ def _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale):
     return disp + pos_dev[None, None]
 
 
-def _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale):
+def _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale, fused=False):
     """`_curve_trajectories` for control points on the 1/8 grid with their convex-upsampling mask (the RAFT-spline output head):
     on the GPU ops.CvxCurveTrajFn (csrc/cvx_curves.hip; tile sizes 2, 4, 8, 16), else the plain-torch mirror.  On the kernel route
     an fp16 / bf16 mask is passed as it is and gets its gradient in its own dtype (computed in fp32, rounded once); control points
@@ -319,7 +336,9 @@ def _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale):
     if (H, W) != (8 * h, 8 * w):
         raise ValueError(f'with up_mask, image_shape must be 8 x the grid of params: {(8 * h, 8 * w)}, got {(H, W)}')
     pos, pos_dev = _tile_positions(H, W, tile_size, params.device, params.dtype)
-    if _cvx_kernels_serve(params, up_mask, bm) and tile_size in _CVX_KERNEL_TILES:
+    if fused and _basis_trains(bm) and (H % tile_size or W % tile_size):
+        fused = False                            # (the matrix' gradient reads the rows of mpc_pec_head_rows: whole tiles only)
+    if _cvx_kernels_serve(params, up_mask, bm, fused) and tile_size in _CVX_KERNEL_TILES:
         from .. import ops
         return ops.CvxCurveTrajFn.apply(params.float(), up_mask, bm.float(), float(scale), int(tile_size)), pos
     return _cvx_curve_trajectories_mirror(params, up_mask, bm, pos_dev, scale), pos
@@ -445,7 +464,8 @@ def _curve_matrix(params, times, curve_type, basis_network):
     return c2 // 2, curve_basis(curve_type, times, c2 // 2, basis_network, device=params.device).to(_basis_dtype(params))
 
 
-def trajectories_from_curves(params, times, tile_size, image_shape, curve_type='BEZIER', basis_network=None, scale=1.0, up_mask=None):
+def trajectories_from_curves(params, times, tile_size, image_shape, curve_type='BEZIER', basis_network=None, scale=1.0, up_mask=None,
+                             basis_grad='mirror'):
     """`trajectories_from_bezier` for any of the reference's curve types (`curve_basis`: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the
     latter with its `basis_network` on the device of `params`) and for 'BSPLINE' (the bits of `trajectories_from_bspline`): the same contracts, the same routing -- fp32, fp16 or bf16 GPU tensors (16-bit ones as `trajectories_from_bezier` says: the mask
     read in place, fp32 trajectories) with
@@ -455,14 +475,23 @@ def trajectories_from_curves(params, times, tile_size, image_shape, curve_type='
     Differentiable w.r.t. `params`, `up_mask` and, for 'LEARNED', the parameters of `basis_network`.  The fused nodes have no
     gradient for the basis matrix: a matrix that requires grad (a basis network that trains) takes the plain-torch mirrors, where it
     is an ordinary autograd input; a polynomial curve, and a learned one whose network is frozen or evaluated under no_grad, run in
-    the fused nodes."""
+    the fused nodes.
+
+    `basis_grad` ('mirror', the default: the routing above, unchanged | 'fused'; anything else raises ValueError): with 'fused' a
+    matrix that requires grad takes the fused nodes as well -- the launches of the frozen route and the same bits for the
+    trajectories and for the gradients of `params` and `up_mask`, then the matrix' own gradient [n_t, d] in fp32 as a small
+    deterministic reduction (csrc/curve_basis.hip: two kernels, behind one kernel that evaluates the upsampled control points at
+    the tile centres with `up_mask`; no float atomics, no host synchronisation), from which autograd reaches the parameters of
+    `basis_network` as it does from the mirror.  Shapes the kernels do not serve still take the mirror, and so does an
+    `image_shape` that is no multiple of `tile_size` with `up_mask`.  With a constant matrix the keyword changes nothing."""
+    fused = _basis_grad_fused(basis_grad)
     B, c2, h, w = params.shape
     H, W = (int(v) for v in image_shape)
     assert c2 % 2 == 0 and (up_mask is not None or (h == H // tile_size and w == W // tile_size)), (params.shape, image_shape, tile_size)
     d, bm = _curve_matrix(params, times, curve_type, basis_network)
     if up_mask is not None:
-        return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale)
-    return _curve_trajectories(params, bm, tile_size, H, W, scale)
+        return _cvx_curve_trajectories(params, up_mask, bm, tile_size, H, W, scale, fused)
+    return _curve_trajectories(params, bm, tile_size, H, W, scale, fused)
 
 
 def flows_from_curves(params, times, curve_type='BEZIER', basis_network=None, up_mask=None, scale=1.0):

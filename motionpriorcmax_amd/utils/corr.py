@@ -14,7 +14,7 @@ grid_sample, cat / permute / reshape) and therefore also the comparator the prob
 import torch
 import torch.nn.functional as F
 
-from .basis import _basis_trains, _device_basis, curve_basis
+from .basis import _basis_grad_fused, _basis_served, _device_basis, curve_basis
 
 _KERNEL_MAX_RADIUS, _KERNEL_MAX_TARGETS, _KERNEL_MAX_D, _KERNEL_MAX_LEVELS = 4, 16, 16, 6
 _PYRAMID_DTYPES = (torch.float32, torch.float16, torch.bfloat16)         # what the pyramid kernels read in place (include/mpcmax.h: MPC_DT_*)
@@ -335,7 +335,7 @@ class CorrLookup:
         coords = coords_grid(self.B, self.h, self.w, params.device, params.dtype)[None] + flows
         return _lookup_mirror(self.levels, self.target_indices, self.radius, coords)
 
-    def lookup_curves(self, params, times, curve_type='BEZIER', basis_network=None):
+    def lookup_curves(self, params, times, curve_type='BEZIER', basis_network=None, basis_grad='mirror'):
         """`lookup_bezier` for any of the reference's curve types (utils.curve_basis: 'BEZIER' | 'POLYNOMIAL' | 'LEARNED', the latter
         with its `basis_network` on the device of `params`; also 'BSPLINE', the cubic B-spline): the lookup at coords0 + curve.get_flow_from_reference(times) of
         raft.py:165-180, the times evaluated as a LIST (no scalar-time shortcut).  The same routing as `lookup_bezier`, with
@@ -343,7 +343,15 @@ class CorrLookup:
         graph, and the fused node has no gradient for it: while the basis network trains (the matrix requires grad) the lookup
         runs in the plain-torch mirror, where the matrix is an ordinary autograd input -- also when `params` are detached
         (`detach_bezier`, raft.py:166-167), which is what trains the basis network through the update loop.  A frozen network, or
-        one evaluated under no_grad, runs in the fused node."""
+        one evaluated under no_grad, runs in the fused node.
+
+        `basis_grad` ('mirror', the default: the routing above, unchanged | 'fused'; anything else raises ValueError): with 'fused' a
+        matrix that requires grad takes the fused node as well, `shared_grad=True` included -- the forward and backward launches of
+        the frozen route and the same bits for the output and for the gradients of `params` and the levels; the backward launch
+        also writes the targets' coordinate gradient [T, B, 2, h, w] (alone, without the gradient of `params`, where they are
+        detached), from which two small kernels sum the matrix' gradient [T, d] in a fixed order (csrc/curve_basis.hip: no float
+        atomics, no host synchronisation).  Autograd carries it into the parameters of `basis_network`."""
+        fused = _basis_grad_fused(basis_grad)
         T = len(self.num_levels_per_target)
         if params.dim() != 4 or params.shape[1] % 2 or params.shape[1] < 2 or (params.shape[0], params.shape[2], params.shape[3]) != (self.B, self.h, self.w):
             raise ValueError(f'params must be [B, 2d, h, w] with (B, h, w) = {(self.B, self.h, self.w)}, got {tuple(params.shape)}')
@@ -354,7 +362,7 @@ class CorrLookup:
             bm = self._basis(times, d, params.device, params.dtype, 'bernstein' if curve_type == 'BEZIER' else 'polynomial')
         else:                                    # (the network's output, as it comes: the kernel reads a dense [T, d])
             bm = curve_basis(curve_type, times, d, basis_network, device=params.device).to(params.dtype).contiguous()
-        if self._kernels_serve(params, d) and not _basis_trains(bm):
+        if self._kernels_serve(params, d) and _basis_served(bm, fused):
             return self._apply(params, bm)
         flows = torch.einsum('bcdhw,td->tbchw', params.reshape(self.B, 2, d, self.h, self.w), bm)
         coords = coords_grid(self.B, self.h, self.w, params.device, params.dtype)[None] + flows
